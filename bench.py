@@ -14,6 +14,13 @@ Contract (driver): ``python bench.py --gpus N --steps K --warmup W`` ; for N>1 i
 launched by torch.distributed.run with one rank per GPU.  Clips shard data-parallel
 across ranks with no data-path collective (inference: SURVEY.md 8e "replicas only"),
 so scaling is weak: every rank runs B clips.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline.  ``--full``
+adds what the headline does not need: the library's per-stage timers in the timed
+region (stage_ms_per_step, roofline of the dominant kernel), the CPU baseline and,
+at N>1, the data-parallel probes.  ``--dump-outputs DIR`` writes what the last timed
+step computed as DIR/<name>.npy (float32); the inputs are seeded, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -43,6 +50,7 @@ HEAD_FLOPS_FRAME = 432.79e6
 C3D_FLOPS_FRAME = sum(C3D_FLOPS.values())          # 76 993.27 MFLOP
 PEAK_TFLOPS = {'bf16': 2500.0, 'f32': 157.3}       # dense MFMA peaks, MI355X_MICROARCH.md
 PMC_SUMMARY = 'profiles/r05_pmc_summary.json'      # separate rocprofv3 --pmc passes of the default command (scripts/r05_profiles.sh)
+DUMP_MAX_ELEMS = 4 << 20       # per array (16 MB of float32); no workload dumps more than three arrays of that size
 
 
 def parse():
@@ -59,11 +67,17 @@ def parse():
     ap.add_argument('--dtype', choices=['bf16', 'f32'], default='bf16')
     ap.add_argument('--c3d-chunk', type=int, default=1024, help='windows per C3D launch chain')
     ap.add_argument('--graph', action='store_true', help='train workload: replay the step as HIP graphs')
+    ap.add_argument('--full', action='store_true',
+                    help="besides the headline: per-stage timers in the timed region (stage_ms_per_step, roofline), the CPU "
+                         "baseline and, with more than one rank, the data-parallel probes")
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32; an array of more "
+                         "than %d elements as a fixed, seeded sample of them)" % DUMP_MAX_ELEMS)
     ap.add_argument('--dp-train-probe', choices=['auto', 'on', 'off'], default='auto',
                     help="after the headline timing also time BASELINE config 4's data-parallel training step (B=8 x T=35 per "
                          "GPU: fwd + bwd + bucketed RCCL all-reduce + clip + Adam) and the same step at config 3's per-GPU shape "
                          "(B=64 x T=16: full-chip persistent ConvGRU launches next to the collectives), reported under 'dp_train' / "
-                         "'dp_train_b64'; auto = when more than one rank runs, so that the driver's N>1 command exercises the "
+                         "'dp_train_b64'; auto = with --full when more than one rank runs, so that the N>1 command exercises the "
                          "collective path")
     ap.add_argument('--rehearse', action='store_true',
                     help="NOT a measurement: run the N>1 control flow on a ONE-GPU box -- gloo instead of RCCL, every rank on cuda:0, "
@@ -75,11 +89,26 @@ def parse():
     ap.add_argument('--dp-finetune-probe', choices=['auto', 'on', 'off'], default='auto',
                     help="also time BASELINE config 5's data-parallel JOINT training step at its per-GPU shape (16 clips x T=35: "
                          "C3D + cascade, the gradient leaving in nine buckets on a side stream under the backward) with and "
-                         "without the all-reduce, reported under 'dp_finetune'; auto = when more than one rank runs")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+                         "without the all-reduce, reported under 'dp_finetune'; auto = with --full when more than one rank runs")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave the CPU baseline out')
     ap.add_argument('--cpu-seconds', type=float, default=15.0, help='CPU baseline budget')
     ap.add_argument('--cpu-threads', type=int, default=16, help='host threads for the CPU baseline')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
+
+
+def dump_outputs(path, arrays):
+    """{name: device tensor} -> path/<name>.npy as float32.  An array of more than DUMP_MAX_ELEMS elements is written as
+    the same seeded sample of its flattened elements in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def cpu_baseline(args, budget_s):
@@ -213,9 +242,10 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    head.profile(True)
-    if c3d is not None:
-        c3d.profile(True)
+    if args.full:
+        head.profile(True)
+        if c3d is not None:
+            c3d.profile(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -223,17 +253,63 @@ def main():
     mine = time.perf_counter() - t0
     elapsed = rdist.max_over_ranks(dist, mine, dev)
     per_rank_ms = [round(t / args.steps * 1e3, 4) for t in rdist.gather_over_ranks(dist, mine, dev)]   # which GPU set the MAX
-    hprof = head.profile_read()
-    cprof = c3d.profile_read() if c3d is not None else {}
     if ft is not None:
         assert bool(torch.isfinite(last['loss'])) and bool(torch.isfinite(last['gnorm'])), 'non-finite training step'
     else:
         assert torch.isfinite(probs).all(), 'non-finite saliency maps'
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: the maps, or the training step's results and the
+        # parameters it updated
+        if ft is not None:
+            arrays = {'loss': last['loss'], 'gnorm': last['gnorm'], 'head_params': head.flat_params, 'c3d_params': c3d.flat_params}
+        elif args.workload == 'train':
+            arrays = {'logits': logits, 'probs': probs, 'head_params': head.flat_params}
+        else:
+            arrays = {'logits': logits, 'probs': probs}
+        dump_outputs(args.dump_outputs, arrays)
 
     out = {}
     if rank == 0:
         frames_total = world * F * args.steps
         value = frames_total / elapsed
+        flops_frame = HEAD_FLOPS_FRAME + (C3D_FLOPS_FRAME if c3d is not None else 0.0)
+        if ft is not None:
+            from recurrent_gaze_prediction_amd.finetune import flops_per_frame_train
+            flops_frame = flops_per_frame_train()
+        out = {
+            'metric': 'frames/sec (49x49 saliency maps), gaze_grcn 16-frame clips',
+            'value': round(value, 2), 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps,
+            'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 4),
+            'per_rank_ms': per_rank_ms,
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+            'dtype': args.dtype, 'data': 'synthetic',
+            'config': {'workload': ('gaze_grcn END-TO-END TRAINING step: synthetic 16x112x112x3 windows -> C3D conv1a-5b (arg-max '
+                                    'recorded) -> gaze_grcn head -> xentropy loss -> head backward -> conv-stack backward '
+                                    '(dgrad + wgrad of all 8 layers) -> gradient all-reduce -> global-norm clip + TF-Adam on '
+                                    'all 30.7 M variables; roofline = dominant FORWARD kernel of the step'
+                                    if ft is not None else
+                                    'gaze_grcn end-to-end: synthetic 16x112x112x3 windows -> C3D conv1a-5b -> '
+                                    '1024->512 proj -> ConvGRU(512->128, 7x7) -> deconv head -> 49x49 softmax maps'
+                                    if c3d is not None else
+                                    'gaze_grcn head on precomputed C3D conv5b features [B,T,1024,7,7]'
+                                    if args.workload == 'head' else
+                                    'gaze_grcn TRAINING step on precomputed features: forward + backward + gradient '
+                                    'all-reduce (mean, before the clip) + clip_by_global_norm(10) + TF-Adam'),
+                       'clips_per_gpu': B, 'n_lstm_steps': T, 'frames_per_step_per_gpu': F,
+                       'parallelism': ('dp%d (clip-sharded, one flat RCCL all-reduce of the 12 MB gradient per step)' % world
+                                       if args.workload == 'train' else
+                                       'dp%d (clip-sharded, RCCL all-reduce of the 12 MB head + 110.6 MB conv gradient buckets per step)' % world
+                                       if ft is not None else
+                                       'dp%d (clip-sharded replicas, no collective)' % world),
+                       'weights': 'random init (reference initialisers), GRU filters std 0.05'},
+            'algorithmic_tflops': round(value * flops_frame / 1e12, 2),
+        }
+        if args.rehearse:
+            out['rehearsal'] = True             # gloo, one device, per-step ConvGRU: control flow only, the numbers mean nothing
+    if args.full:
+        hprof = head.profile_read()
+        cprof = c3d.profile_read() if c3d is not None else {}
+    if args.full and rank == 0:
         # ---- roofline of the dominant kernel (HIP-event time on the launch stream, timed region)
         if c3d is not None:
             groups = {}
@@ -290,47 +366,13 @@ def main():
         if kname == 'head':
             roofline['note'] = ('algorithmic FLOPs of the three transposed convolutions + out_W (164.65 MFLOP per frame, SURVEY 8d); the '
                                 'library runs them as their exact fold, which issues 4.8 MFLOP per frame: not an MFMA utilisation')
-        flops_frame = HEAD_FLOPS_FRAME + (C3D_FLOPS_FRAME if c3d is not None else 0.0)
-        if ft is not None:
-            from recurrent_gaze_prediction_amd.finetune import flops_per_frame_train
-            flops_frame = flops_per_frame_train()
-        out = {
-            'metric': 'frames/sec (49x49 saliency maps), gaze_grcn 16-frame clips',
-            'value': round(value, 2), 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 4),
-            'per_rank_ms': per_rank_ms,
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': args.dtype, 'data': 'synthetic',
-            'config': {'workload': ('gaze_grcn END-TO-END TRAINING step: synthetic 16x112x112x3 windows -> C3D conv1a-5b (arg-max '
-                                    'recorded) -> gaze_grcn head -> xentropy loss -> head backward -> conv-stack backward '
-                                    '(dgrad + wgrad of all 8 layers) -> gradient all-reduce -> global-norm clip + TF-Adam on '
-                                    'all 30.7 M variables; roofline = dominant FORWARD kernel of the step'
-                                    if ft is not None else
-                                    'gaze_grcn end-to-end: synthetic 16x112x112x3 windows -> C3D conv1a-5b -> '
-                                    '1024->512 proj -> ConvGRU(512->128, 7x7) -> deconv head -> 49x49 softmax maps'
-                                    if c3d is not None else
-                                    'gaze_grcn head on precomputed C3D conv5b features [B,T,1024,7,7]'
-                                    if args.workload == 'head' else
-                                    'gaze_grcn TRAINING step on precomputed features: forward + backward + gradient '
-                                    'all-reduce (mean, before the clip) + clip_by_global_norm(10) + TF-Adam'),
-                       'clips_per_gpu': B, 'n_lstm_steps': T, 'frames_per_step_per_gpu': F,
-                       'parallelism': ('dp%d (clip-sharded, one flat RCCL all-reduce of the 12 MB gradient per step)' % world
-                                       if args.workload == 'train' else
-                                       'dp%d (clip-sharded, RCCL all-reduce of the 12 MB head + 110.6 MB conv gradient buckets per step)' % world
-                                       if ft is not None else
-                                       'dp%d (clip-sharded replicas, no collective)' % world),
-                       'weights': 'random init (reference initialisers), GRU filters std 0.05'},
-            'algorithmic_tflops': round(value * flops_frame / 1e12, 2),
-            'stage_ms_per_step': {k: round(v[0] / args.steps, 4) for k, v in list(cprof.items()) + list(hprof.items())},
-            'roofline': roofline,
-        }
-        if args.rehearse:
-            out['rehearsal'] = True             # gloo, one device, per-step ConvGRU: control flow only, the numbers mean nothing
+        out['stage_ms_per_step'] = {k: round(v[0] / args.steps, 4) for k, v in list(cprof.items()) + list(hprof.items())}
+        out['roofline'] = roofline
         if world == 1 and not args.no_cpu_baseline and args.workload in ('e2e', 'head'):
             out['cpu_baseline'] = cpu_baseline(args, args.cpu_seconds)
             out['speedup_vs_cpu_baseline'] = round(value / out['cpu_baseline']['value'], 1)
 
-    # ---- N > 1: the driver's one command must also exercise the collective path (inference has none).  The probes run AFTER
+    # ---- N > 1 with --full: the command also exercises the collective path (inference has none).  The probes run AFTER
     # the headline is measured and assembled, under a watchdog: whatever happens in them -- an exception on this rank, a peer
     # that died, a collective that never returns -- rank 0 still prints its ONE line (with 'dp_probe_error') and exits non-zero.
     emitted = threading.Lock()
@@ -360,8 +402,8 @@ def main():
             sys.stderr.flush()
             os._exit(3)
 
-    want_train = args.dp_train_probe == 'on' or (args.dp_train_probe == 'auto' and world > 1)
-    want_ft = args.dp_finetune_probe == 'on' or (args.dp_finetune_probe == 'auto' and world > 1)
+    want_train = args.dp_train_probe == 'on' or (args.dp_train_probe == 'auto' and args.full and world > 1)
+    want_ft = args.dp_finetune_probe == 'on' or (args.dp_finetune_probe == 'auto' and args.full and world > 1)
     if control_note is not None:
         want_train = want_ft = False
         if rank == 0:

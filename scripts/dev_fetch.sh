@@ -6,8 +6,8 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 T=${1:-cur}
 O=gpurun_out/r03fetch_$T
 mkdir -p $O
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/fetch.json 2> $O/fetch.err || exit 1
-python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null > $O/time.json
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/fetch.json 2> $O/fetch.err || exit 1
+python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null > $O/time.json
 python3 - "$O" <<'PY'
 import csv, glob, json, sys, collections
 O = sys.argv[1]

@@ -5,7 +5,7 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04/ft_$1
 mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --workload finetune --batch 16 --n-steps 16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_ft.json 2> $O/stats.err || { tail -5 $O/stats.err; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full --workload finetune --batch 16 --n-steps 16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_ft.json 2> $O/stats.err || { tail -5 $O/stats.err; exit 1; }
 f=$(find $O/stats -name "*kernel_stats.csv" | head -1)
 cp $f $O/kernel_stats.csv
 python3 - "$f" <<'PY'

@@ -9,8 +9,8 @@ O=gpurun_out/r03skew
 mkdir -p $O
 for skew in 0 8; do
   export RGP_CP_ABLATE=$((skew << 8))
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch_$skew -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/fetch_$skew.json 2> $O/fetch_$skew.err || exit 1
-  python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null > $O/time_$skew.json
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch_$skew -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/fetch_$skew.json 2> $O/fetch_$skew.err || exit 1
+  python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null > $O/time_$skew.json
   python3 - "$O" "$skew" <<'PY'
 import csv, glob, json, sys, collections
 O, skew = sys.argv[1], sys.argv[2]

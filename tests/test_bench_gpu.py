@@ -1,5 +1,6 @@
 """GPU: the driver's command line -- `python bench.py` with its defaults, shortened to 2 timed steps -- prints ONE JSON
-line that keeps the contract the driver parses (metric / value / unit / roofline / cpu_baseline) and is self-consistent."""
+line that keeps the contract the driver parses (metric / value / unit / ms_per_step) and is self-consistent; with --full the
+line also carries the roofline, the per-stage times and the CPU baseline."""
 import json
 import os
 import subprocess
@@ -14,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_default_bench_line_keeps_the_contract(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--cpu-seconds', '3'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '2', '--warmup', '1', '--cpu-seconds', '3'],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -43,13 +44,39 @@ def test_default_bench_line_keeps_the_contract(gpu):
     assert abs(sum(d['stage_ms_per_step'].values()) - d['ms_per_step']) < 0.05 * d['ms_per_step']
 
 
+def test_plain_bench_line_is_the_headline_and_dumps_the_maps(gpu, tmp_path):
+    """Without --full the line is the headline alone; --dump-outputs writes the maps of the last timed step."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1',
+                        '--dump-outputs', str(tmp_path)], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d['unit'] == 'frames/s' and d['metric'].startswith('frames/sec') and d['higher_is_better'] is True
+    assert d['n_gpus'] == 1 and d['steps'] == 3 and d['warmup'] == 1 and d['dtype'] == 'bf16'
+    assert abs(d['value'] - 1024 / (d['ms_per_step'] * 1e-3)) < 1e-3 * d['value']
+    for key in ('roofline', 'stage_ms_per_step', 'cpu_baseline', 'dp_train', 'dp_finetune'):
+        assert key not in d, key
+    assert sorted(os.listdir(tmp_path)) == ['logits.npy', 'probs.npy']
+    logits, probs = np.load(tmp_path / 'logits.npy'), np.load(tmp_path / 'probs.npy')
+    assert logits.dtype == probs.dtype == np.float32 and logits.shape == probs.shape == (64, 16, 49, 49)
+    assert np.isfinite(logits).all()
+    # probs is the per-frame softmax of logits
+    z = logits.reshape(1024, -1).astype(np.float64)
+    ref = np.exp(z - z.max(-1, keepdims=True))
+    ref /= ref.sum(-1, keepdims=True)
+    assert np.abs(probs.reshape(1024, -1) - ref).max() < 1e-5
+
+
 def _rehearse(extra_env, extra_args=(), timeout=900):
-    """`bench.py --gpus 2 --rehearse`: the driver's N > 1 control flow (spawned ranks, barrier + MAX over ranks, per-rank
+    """`bench.py --full --gpus 2 --rehearse`: the driver's N > 1 control flow (spawned ranks, barrier + MAX over ranks, per-rank
     times, the three data-parallel probes, ONE line from rank 0) with gloo and both ranks on this GPU.  Small headline shape:
     the numbers mean nothing."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
     env.update(extra_env)
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--rehearse', '--steps', '2', '--warmup', '1',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--rehearse', '--steps', '2', '--warmup', '1',
            '--batch', '4', '--n-steps', '4'] + list(extra_args)
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith('{')]
