@@ -444,6 +444,98 @@ int rgp_c3d_read_grad_image(rgp_c3d_t* plan, int layer, int n_windows, float* ds
 int rgp_c3d_profile_enable(rgp_c3d_t* plan, int enable);
 int rgp_c3d_profile_read(rgp_c3d_t* plan, double ms[RGP_C3D_STAGES], long long calls[RGP_C3D_STAGES]);
 
+/* ------------------------------------------------------------------ saliency metrics
+ * evaluation_metrics.py:15-297 scored on the device: ONE launch scores n_frames frames on every requested metric, one
+ * workgroup per frame.  The semantics are those of this package's evaluation_metrics.py (itself pinned to the
+ * reference's file by tests/golden/metrics_ref.npz) for maps of one common shape height x width, where its `resize`
+ * is the identity: pred is min-max normalised first (saliency_score_single, :239-272) and
+ *   sim (:207-218)  cc (:221-236)  AUC_Judd (:42-98)  AUC_Borji (:101-164)  AUC_shuffled (:167-204)  NSS (not in the
+ *   reference: mean z-scored saliency at the fixations)
+ * are computed in fp64 with IEEE division and no contraction, comparisons included, so every `>=` of the ROC sweeps
+ * falls as it does on the host and only the order of summation differs.  pred is fp32 unless RGP_METRICS_PRED_F64 is
+ * set; an fp32 pred is normalised in fp32 and then widened, which is what numpy does with an fp32 array, an fp64 pred
+ * in fp64.  NaN follows numpy too (np.min / np.max propagate it, sort and searchsorted place it last).
+ * Where the host raises instead of returning (a prediction without contrast or an empty negative set in AUC_Borji /
+ * AUC_shuffled) the score is NaN.
+ *
+ * scores [RGP_METRICS_COUNT, n_frames] fp64, row RGP_METRIC_ROW_* per metric; rows of metrics that were not
+ * requested are left untouched.  A frame without fixations scores NaN on NSS and the three AUCs.  The mean over
+ * frames is the caller's.
+ *
+ * Random draws, two forms:
+ *  - the caller's (default): judd_jitter [n_frames, height*width] fp64 uniform draws (NULL: AUC_Judd without jitter);
+ *    borji_neg / shuf_neg [n_frames, n_rep, neg_stride] int32 PIXEL INDICES of each repetition's negatives, of which
+ *    AUC_Borji reads the first n_fix of a row and AUC_shuffled the first shuf_cnt[frame] (= min(n_fix, size of the
+ *    frame's negative set), what `permutation(M)[:n_fix]` yields); `other` is not read;
+ *  - RGP_METRICS_DEVICE_DRAWS: the four pointers are NULL and the draws come from Philox-4x32-10 keyed by `seed`, the
+ *    counter made of (offset + frame, metric, repetition, sample): scores do not depend on the launch geometry, and
+ *    frames [a, b) of a call with offset o are frames [0, b-a) of a call with offset o+a.  AUC_Borji negatives are
+ *    uniform over the map, AUC_shuffled negatives min(n_fix, M) DISTINCT members of the frame's negative set `other`
+ *    (Floyd's subset sampling), AUC_Judd is jittered unless RGP_METRICS_NO_JITTER.  The drawn indices are left in the
+ *    workspace in the caller's-draws layout (see below), where a test can read them.
+ *
+ * fix / other: a pixel belongs to the set iff its value > 0.5.  other_stride is the distance in elements between two
+ * frames' negative maps: 0 (one map for all frames, saliency_score :275-295) or height*width (one per frame,
+ * evaluate_gaze.py:116-135).
+ *
+ * Limits: height*width <= RGP_METRICS_MAX_PIX, at most neg_stride <= RGP_METRICS_MAX_FIX fixations per frame,
+ * 1/step_size <= RGP_METRICS_MAX_THRESHOLDS.  The host refuses what it can see (RGP_EINVAL before any launch).  The
+ * number of fixations is only known on the device: a frame with more than neg_stride of them, or one whose supplied
+ * indices / counts are out of range, gets NaN in all its requested scores and is counted in the workspace's status
+ * word, which rgp_metrics_status reports.
+ *
+ * workspace (device, 8-byte aligned, rgp_metrics_workspace_bytes): bytes [0, 64) status; with
+ * RGP_METRICS_DEVICE_DRAWS then borji_neg, shuf_neg (int32 [n_frames, n_rep, neg_stride] each) and shuf_cnt
+ * (int32 [n_frames]).  rgp_saliency_scores clears the status word on the stream before its launch. */
+#define RGP_METRICS_MAX_PIX 4096
+#define RGP_METRICS_MAX_FIX 256
+#define RGP_METRICS_MAX_THRESHOLDS 1024
+#define RGP_METRICS_COUNT 6
+#define RGP_METRIC_SIM 1
+#define RGP_METRIC_CC 2
+#define RGP_METRIC_AUC_JUDD 4
+#define RGP_METRIC_AUC_BORJI 8
+#define RGP_METRIC_AUC_SHUFFLED 16
+#define RGP_METRIC_NSS 32
+#define RGP_METRIC_ALL 63
+/* row of `scores` = bit position of the metric */
+#define RGP_METRIC_ROW_SIM 0
+#define RGP_METRIC_ROW_CC 1
+#define RGP_METRIC_ROW_AUC_JUDD 2
+#define RGP_METRIC_ROW_AUC_BORJI 3
+#define RGP_METRIC_ROW_AUC_SHUFFLED 4
+#define RGP_METRIC_ROW_NSS 5
+#define RGP_METRICS_DEVICE_DRAWS 1
+#define RGP_METRICS_NO_JITTER 2
+#define RGP_METRICS_PRED_F64 4
+#define RGP_METRICS_GT_F64 8
+
+typedef struct rgp_metrics_args {
+  const void* pred;            /* [n_frames, height, width] fp32 (fp64 with RGP_METRICS_PRED_F64) */
+  const void* gt;              /* same shape, fp32 (fp64 with RGP_METRICS_GT_F64); read by sim and cc only */
+  const float* fix;            /* same shape */
+  const float* other;          /* negative set of AUC_shuffled; read with RGP_METRICS_DEVICE_DRAWS only */
+  long long other_stride;      /* 0 or height*width */
+  int n_frames, height, width;
+  unsigned metrics;            /* RGP_METRIC_* bits */
+  unsigned flags;              /* RGP_METRICS_* bits */
+  int n_rep;                   /* repetitions of AUC_Borji / AUC_shuffled (the reference: 100) */
+  int neg_stride;              /* ints per (frame, repetition) row of the negatives = fixation cap of this call */
+  double step_size;            /* threshold step of AUC_Borji / AUC_shuffled (the reference: 0.1) */
+  const double* judd_jitter;
+  const int *borji_neg, *shuf_neg, *shuf_cnt;
+  unsigned long long seed, offset;
+  void* workspace;
+  size_t workspace_bytes;
+  double* scores;              /* [RGP_METRICS_COUNT, n_frames] */
+} rgp_metrics_args;
+
+size_t rgp_metrics_workspace_bytes(int n_frames, int n_rep, int neg_stride, unsigned flags);
+int rgp_saliency_scores(const rgp_metrics_args* args, rgp_stream_t stream);
+/* Waits for `stream`, reads the status word of the last rgp_saliency_scores that used `workspace`: RGP_OK, or
+ * RGP_EINVAL with the number of refused frames in rgp_last_error(). */
+int rgp_metrics_status(const void* workspace, rgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

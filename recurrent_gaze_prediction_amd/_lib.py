@@ -22,6 +22,11 @@ RGP_C3D_SAVE_FOR_BACKWARD, RGP_C3D_KERNELS_IGEMM, RGP_C3D_KERNELS_TILE128, RGP_C
 RGP_FAULT_SEQ_LOST_MEMBER, RGP_FAULT_BPTT_LOST_MEMBER = 1, 2
 RGP_GRCN_GRADS_TOP, RGP_GRCN_GRADS_GRU, RGP_GRCN_GRADS_PROJ = 0, 1, 2
 RGP_SQNORM_PARTIALS = 256          # include/rgp.h
+# saliency metrics (include/rgp.h): caps, metric bits (row of `scores` = bit position), flags
+RGP_METRICS_MAX_PIX, RGP_METRICS_MAX_FIX, RGP_METRICS_MAX_THRESHOLDS, RGP_METRICS_COUNT = 4096, 256, 1024, 6
+METRIC_BITS = {'sim': 1, 'cc': 2, 'AUC_Judd': 4, 'AUC_Borji': 8, 'AUC_shuffled': 16, 'NSS': 32}
+METRIC_ROWS = {'sim': 0, 'cc': 1, 'AUC_Judd': 2, 'AUC_Borji': 3, 'AUC_shuffled': 4, 'NSS': 5}
+RGP_METRICS_DEVICE_DRAWS, RGP_METRICS_NO_JITTER, RGP_METRICS_PRED_F64, RGP_METRICS_GT_F64 = 1, 2, 4, 8
 DTYPES = {'f32': RGP_F32, 'fp32': RGP_F32, 'float32': RGP_F32, 'bf16': RGP_BF16, 'bfloat16': RGP_BF16}
 
 c_void_p, c_int, c_size_t, c_char_p = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_char_p
@@ -57,6 +62,16 @@ class CascadeWeights(ctypes.Structure):
 
 class C3DWeights(ctypes.Structure):
     _fields_ = [('w', c_void_p * 8), ('b', c_void_p * 8)]
+
+
+class MetricsArgs(ctypes.Structure):
+    _fields_ = [('pred', c_void_p), ('gt', c_void_p), ('fix', c_void_p), ('other', c_void_p),
+                ('other_stride', ctypes.c_longlong), ('n_frames', c_int), ('height', c_int), ('width', c_int),
+                ('metrics', ctypes.c_uint), ('flags', ctypes.c_uint), ('n_rep', c_int), ('neg_stride', c_int),
+                ('step_size', ctypes.c_double), ('judd_jitter', c_void_p), ('borji_neg', c_void_p),
+                ('shuf_neg', c_void_p), ('shuf_cnt', c_void_p), ('seed', ctypes.c_ulonglong),
+                ('offset', ctypes.c_ulonglong), ('workspace', c_void_p), ('workspace_bytes', c_size_t),
+                ('scores', c_void_p)]
 
 
 # name -> (restype, argtypes); every symbol include/rgp.h declares
@@ -144,6 +159,9 @@ SIGNATURES = {
                                       c_void_p, c_void_p]),
     'rgp_l2_loss_fwd': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p]),
     'rgp_dropout_mask': (c_int, [c_void_p, ctypes.c_longlong, ctypes.c_float, ctypes.c_ulonglong, ctypes.c_ulonglong, c_void_p]),
+    'rgp_metrics_workspace_bytes': (c_size_t, [c_int, c_int, c_int, ctypes.c_uint]),
+    'rgp_saliency_scores': (c_int, [ctypes.POINTER(MetricsArgs), c_void_p]),
+    'rgp_metrics_status': (c_int, [c_void_p, c_void_p]),
     'rgp_dropout_apply': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_float, c_void_p]),
     'rgp_fcgru_set_dropout': (c_int, [c_void_p, ctypes.c_float, c_void_p]),
     'rgp_cascade_set_dropout': (c_int, [c_void_p, ctypes.c_float, c_void_p]),

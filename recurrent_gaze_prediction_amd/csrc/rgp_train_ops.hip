@@ -12,22 +12,11 @@
 
 #include "rgp_host.h"
 #include "bwd_kernels.hip.h"
+#include "philox.hip.h"
 
 using namespace rgp;
 
 namespace {
-
-// Philox-4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0,k1) -> 4 x 32 random bits.
-__device__ __forceinline__ void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
 
 // mask[i] = floor(keep + u_i), u_i uniform in [0,1) with 24 random bits (tf.nn.dropout's own rule:
 // random_tensor = keep_prob + random_uniform; binary_tensor = floor(random_tensor)).

@@ -1,0 +1,287 @@
+"""Saliency metrics scored on the GPU: all frames and all requested metrics in one launch.
+
+Device-side counterpart of ``evaluation_metrics`` (the host module, pinned to the reference's
+evaluation_metrics.py by tests/golden/metrics_ref.npz) for the case every caller of this package has:
+prediction, ground truth and fixation maps of one common shape of at most 4096 pixels.  The kernel
+(csrc/rgp_metrics.hip, ``rgp_saliency_scores`` in include/rgp.h) follows the host module statement for
+statement in fp64, so with the host's own random draws it returns the host's scores to summation order
+(about 1e-12); the averaging over frames stays here (``np.mean``).
+
+Random draws come in two forms:
+
+* ``draws='reference'``: :func:`draw_reference_samples` consumes numpy's global RNG exactly as the host
+  functions do and hands the draws to the kernel -- same seed, same scores as the host module;
+* ``draws='device'``: the kernel draws with Philox-4x32-10 keyed by ``seed`` -- nothing but the launch.
+
+What the kernel does not cover -- maps and fixation maps of different shapes (the host's spline
+``resize``), more than 4096 pixels, more than 256 fixations in a frame -- raises ``ValueError``; there is
+no silent fallback: use ``evaluation_metrics`` for those.
+"""
+import ctypes
+
+import numpy as np
+import numpy.random as random
+import scipy.sparse
+import torch
+
+from . import _lib
+
+METRICS = ('sim', 'cc', 'AUC_Judd', 'AUC_Borji', 'AUC_shuffled', 'NSS')       # rows of the kernel's score table
+FRAME_METRICS = ('sim', 'cc', 'AUC_Borji', 'AUC_Judd', 'AUC_shuffled')        # evaluate_gaze.py:135
+MAX_PIX, MAX_FIX = _lib.RGP_METRICS_MAX_PIX, _lib.RGP_METRICS_MAX_FIX
+_HOST = 'recurrent_gaze_prediction_amd.evaluation_metrics (the host module) scores such input'
+
+
+def _dense(m):
+    return m.toarray() if scipy.sparse.issparse(m) else m
+
+
+def _is_tensor(x):
+    return isinstance(x, torch.Tensor)
+
+
+def stack_maps(maps, what):
+    """A [N,H,W] array (or the tensor itself) from an array, a tensor or a list of (sparse) maps."""
+    if _is_tensor(maps):
+        out = maps
+    elif isinstance(maps, np.ndarray) and maps.dtype != object:
+        out = maps
+    else:
+        maps = [np.asarray(_dense(m)) for m in maps]
+        if len({m.shape for m in maps}) > 1:
+            raise ValueError('%s: frames of different shapes; %s' % (what, _HOST))
+        out = np.stack(maps)
+    if out.ndim != 3:
+        raise ValueError('%s: expected [N,H,W], got shape %s' % (what, tuple(out.shape)))
+    return out
+
+
+def _check_metrics(metrics):
+    metrics = (metrics,) if isinstance(metrics, str) else tuple(metrics)
+    for m in metrics:
+        if m not in _lib.METRIC_BITS:
+            raise ValueError(m)
+    if not metrics:
+        raise ValueError('no metric requested')
+    return metrics
+
+
+def draw_reference_samples(fixation_maps, other_union, metrics, n_rep=100, order='metric', jitter=True):
+    """The random draws of the host metrics, taken from numpy's GLOBAL RNG in the host's order, packed for the kernel.
+
+    Per frame that has a fixation (the host functions return NaN before drawing otherwise) AUC_Judd consumes
+    ``rand(H, W)``, AUC_Borji ``randint(0, n_pix, [n_fix, n_rep])`` and AUC_shuffled ``n_rep`` calls of
+    ``permutation(M)`` (M = size of the negative set), of which the first n_fix entries are used.
+    ``order='metric'``: all frames of the first metric of ``metrics``, then the next -- what ``saliency_score`` called
+    once per metric consumes.  ``order='frame'``: per frame the requested metrics in ``FRAME_METRICS`` order -- what
+    ``evaluate_gaze.handle_frame`` consumes.  ``other_union``: one [H,W] map for all frames or [N,H,W], one per frame;
+    only AUC_shuffled reads it.
+
+    Returns a dict: ``judd_jitter`` f64 [N, n_pix] (None when AUC_Judd is not requested or ``jitter`` is off),
+    ``borji_neg`` / ``shuf_neg`` int32 [N, n_rep, neg_stride] pixel indices (None when not requested), ``shuf_cnt``
+    int32 [N] = min(n_fix, M), ``n_fix`` int32 [N] and ``neg_stride`` = the largest n_fix (at least 1)."""
+    metrics = _check_metrics(metrics)
+    if order not in ('metric', 'frame'):
+        raise ValueError(order)
+    fix = np.asarray(stack_maps(fixation_maps, 'fixation_maps')) > 0.5
+    N, H, W = fix.shape
+    n_pix = H * W
+    fix = fix.reshape(N, n_pix)
+    n_fix = fix.sum(1).astype(np.int32)
+    if n_fix.max(initial=0) > MAX_FIX:
+        raise ValueError('a frame has %d fixations, more than RGP_METRICS_MAX_FIX = %d; %s' % (n_fix.max(), MAX_FIX, _HOST))
+    stride = max(1, int(n_fix.max(initial=0)))
+    out = {'judd_jitter': None, 'borji_neg': None, 'shuf_neg': None, 'shuf_cnt': None, 'n_fix': n_fix, 'neg_stride': stride}
+    if 'AUC_Judd' in metrics and jitter:
+        out['judd_jitter'] = np.zeros((N, n_pix), np.float64)
+    if 'AUC_Borji' in metrics:
+        out['borji_neg'] = np.zeros((N, n_rep, stride), np.int32)
+    if 'AUC_shuffled' in metrics:
+        if other_union is None:
+            raise ValueError('other_map_union required')
+        other = np.asarray(_dense(other_union)) > 0.5
+        if other.shape not in ((H, W), (N, H, W)):
+            raise ValueError('other_map.shape != fixation_map.shape')
+        other = other.reshape(-1, n_pix)
+        negatives = [np.nonzero(o)[0] for o in other]
+        out['shuf_neg'] = np.zeros((N, n_rep, stride), np.int32)
+        out['shuf_cnt'] = np.zeros(N, np.int32)
+
+    def draw(metric, i):
+        k = int(n_fix[i])
+        if k == 0:
+            return
+        if metric == 'AUC_Judd' and jitter:
+            out['judd_jitter'][i] = random.rand(H, W).ravel()
+        elif metric == 'AUC_Borji':
+            out['borji_neg'][i, :, :k] = random.randint(0, n_pix, [k, n_rep]).T
+        elif metric == 'AUC_shuffled':
+            members = negatives[i if len(negatives) > 1 else 0]
+            idx = np.stack([random.permutation(len(members))[:k] for _ in range(n_rep)])      # [n_rep, min(k, M)]
+            out['shuf_cnt'][i] = idx.shape[1]
+            out['shuf_neg'][i, :, :idx.shape[1]] = members[idx]
+
+    if order == 'metric':
+        for metric in metrics:
+            for i in range(N):
+                draw(metric, i)
+    else:
+        for i in range(N):
+            for metric in FRAME_METRICS:
+                if metric in metrics:
+                    draw(metric, i)
+    return out
+
+
+def _device_maps(x, what, dev, binary=False):
+    """-> contiguous device tensor the kernel reads: fp32 / fp64 maps as they are, anything else as numpy would treat
+    it (fp64); ``binary`` maps as fp32 0 / 1 of ``x > 0.5`` unless already fp32 on the device."""
+    if _is_tensor(x):
+        t = x.to(dev)
+    else:
+        a = np.asarray(x)
+        if binary:
+            a = (a > 0.5).astype(np.float32)
+        elif a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    if binary:
+        if t.dtype != torch.float32:
+            t = (t > 0.5).to(torch.float32)
+    elif t.dtype not in (torch.float32, torch.float64):
+        t = t.to(torch.float64)
+    return t.contiguous()
+
+
+def saliency_scores_single(pred, gt, fix, other, metrics, draws='device', seed=0, offset=0, n_rep=100, step_size=0.1,
+                           jitter=True, max_fix=None, device=None, return_draws=False):
+    """Per-frame scores {metric: f64 [N]} of N frames in one launch (``evaluation_metrics.saliency_score_single`` for
+    every frame and every metric of ``metrics``).
+
+    pred, gt, fix: [N,H,W], torch device tensors (fp32 / fp64 ones are read in place) or numpy arrays / lists of maps
+    (uploaded).  other: the AUC_shuffled negative set, [H,W] (one for all frames) or [N,H,W]; None if AUC_shuffled is
+    not requested.  ``draws='reference'`` takes the draws from numpy's global RNG as the host does, metric after
+    metric in the order of ``metrics`` (:func:`draw_reference_samples`, or pass its result as ``draws``);
+    ``draws='device'`` draws on the device from (seed, offset + frame): frames a..b of one call equal a call on those
+    frames alone with ``offset=a``.  ``max_fix``: upper bound of the fixations per frame if known (device draws size
+    their index buffers by it; by default it is counted).  ``return_draws`` adds the indices the kernel used under
+    the key ``'draws'``.  Raises ValueError for what the kernel does not cover, naming the host module."""
+    metrics = _check_metrics(metrics)
+    pred, gt, fix = stack_maps(pred, 'pred'), stack_maps(gt, 'gt'), stack_maps(fix, 'fix')
+    if not (tuple(pred.shape) == tuple(gt.shape) == tuple(fix.shape)):
+        raise ValueError('pred %s, gt %s and fixation maps %s differ in shape; %s'
+                         % (tuple(pred.shape), tuple(gt.shape), tuple(fix.shape), _HOST))
+    N, H, W = (int(v) for v in pred.shape)
+    if N < 1:
+        raise ValueError('no frames')
+    if H * W > MAX_PIX:
+        raise ValueError('maps of %d x %d pixels, more than RGP_METRICS_MAX_PIX = %d; %s' % (H, W, MAX_PIX, _HOST))
+    if device is None:
+        device = next((t.device for t in (pred, gt, fix) if _is_tensor(t) and t.is_cuda), torch.device('cuda:0'))
+    dev = torch.device(device)
+
+    flags, packed = 0, None
+    if isinstance(draws, dict) or draws == 'reference':
+        if not isinstance(draws, dict):
+            host_fix = fix.cpu().numpy() if _is_tensor(fix) else fix
+            host_other = other.cpu().numpy() if _is_tensor(other) else other
+            draws = draw_reference_samples(host_fix, host_other, metrics, n_rep=n_rep, jitter=jitter)
+        packed = draws
+        stride = int(packed['neg_stride'])
+    elif draws == 'device':
+        flags |= _lib.RGP_METRICS_DEVICE_DRAWS | (0 if jitter else _lib.RGP_METRICS_NO_JITTER)
+        if 'AUC_shuffled' in metrics and other is None:
+            raise ValueError('other_map_union required')
+    else:
+        raise ValueError("draws must be 'device', 'reference' or the result of draw_reference_samples")
+
+    if packed is None and max_fix is None and not _is_tensor(fix):
+        max_fix = int((np.asarray(fix) > 0.5).reshape(N, -1).sum(1).max())
+    if max_fix is not None and max_fix > MAX_FIX:
+        raise ValueError('a frame has %d fixations, more than RGP_METRICS_MAX_FIX = %d; %s' % (max_fix, MAX_FIX, _HOST))
+    d_pred, d_gt = _device_maps(pred, 'pred', dev), _device_maps(gt, 'gt', dev)
+    d_fix = _device_maps(fix, 'fix', dev, binary=True)
+    flags |= _lib.RGP_METRICS_PRED_F64 if d_pred.dtype == torch.float64 else 0
+    flags |= _lib.RGP_METRICS_GT_F64 if d_gt.dtype == torch.float64 else 0
+    d_other, other_stride = None, 0
+    if packed is None:
+        if max_fix is None:
+            max_fix = int((d_fix > 0.5).reshape(N, -1).sum(1).max().item())
+        if max_fix > MAX_FIX:
+            raise ValueError('a frame has %d fixations, more than RGP_METRICS_MAX_FIX = %d; %s' % (max_fix, MAX_FIX, _HOST))
+        stride = max(1, int(max_fix))
+        if 'AUC_shuffled' in metrics:
+            d_other = _device_maps(_dense(other), 'other', dev, binary=True)
+            if tuple(d_other.shape) == (N, H, W):
+                other_stride = H * W
+            elif tuple(d_other.shape) != (H, W):
+                raise ValueError('other_map.shape != fixation_map.shape')
+
+    def up(key, dtype):
+        a = packed.get(key) if packed is not None else None
+        return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype)).to(dev)
+    d_jit, d_borji = up('judd_jitter', np.float64), up('borji_neg', np.int32)
+    d_shuf, d_cnt = up('shuf_neg', np.int32), up('shuf_cnt', np.int32)
+
+    lib = _lib.load()
+    bits = 0
+    for m in metrics:
+        bits |= _lib.METRIC_BITS[m]
+    ws_bytes = int(lib.rgp_metrics_workspace_bytes(N, n_rep, stride, flags))
+    ws = torch.empty(max(ws_bytes, 64), dtype=torch.uint8, device=dev)
+    scores = torch.full((_lib.RGP_METRICS_COUNT, N), float('nan'), dtype=torch.float64, device=dev)
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+    args = _lib.MetricsArgs(pred=ptr(d_pred), gt=ptr(d_gt), fix=ptr(d_fix), other=ptr(d_other), other_stride=other_stride,
+                            n_frames=N, height=H, width=W, metrics=bits, flags=flags, n_rep=int(n_rep), neg_stride=stride,
+                            step_size=float(step_size), judd_jitter=ptr(d_jit), borji_neg=ptr(d_borji), shuf_neg=ptr(d_shuf),
+                            shuf_cnt=ptr(d_cnt), seed=int(seed) & (2 ** 64 - 1), offset=int(offset), workspace=ws.data_ptr(),
+                            workspace_bytes=ws.numel(), scores=scores.data_ptr())
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.rgp_saliency_scores(ctypes.byref(args), stream)
+        if rc == 0:
+            rc = lib.rgp_metrics_status(ws.data_ptr(), stream)
+    if rc == -1:
+        raise ValueError('%s; %s' % (lib.rgp_last_error().decode(), _HOST))
+    _lib.check(rc)
+    host_scores = scores.cpu().numpy()
+    out = {m: host_scores[_lib.METRIC_ROWS[m]].copy() for m in metrics}
+    if return_draws:
+        if packed is not None:
+            out['draws'] = packed
+        else:
+            e = N * int(n_rep) * stride
+            ints = ws[64:64 + (2 * e + N) * 4].view(torch.int32).cpu().numpy()
+            out['draws'] = {'borji_neg': ints[:e].reshape(N, n_rep, stride), 'shuf_neg': ints[e:2 * e].reshape(N, n_rep, stride),
+                            'shuf_cnt': ints[2 * e:], 'neg_stride': stride,
+                            'n_fix': (d_fix > 0.5).reshape(N, -1).sum(1).to(torch.int32).cpu().numpy()}
+    return out
+
+
+def union_of_ten(fixation_maps, rng=random):
+    """The AUC_shuffled negative set of ``saliency_score`` (evaluation_metrics.py:275-295): the sum of ``> 0`` of ten
+    fixation maps drawn without replacement from ``rng`` (numpy's global RNG by default)."""
+    n = len(fixation_maps)
+    assert n >= 10
+    union = None
+    for i in rng.choice(range(n), 10, replace=False):
+        fm = fixation_maps[int(i)]
+        fm = (fm > 0).to(torch.float32) if _is_tensor(fm) else (np.asarray(_dense(fm)) > 0).astype(np.float32)
+        union = fm if union is None else union + fm
+    return union
+
+
+def saliency_score(metric, pred_maps, gt_maps, fixation_maps, draws='device', seed=0):
+    """``evaluation_metrics.saliency_score`` with the frames scored on the device: the mean over the frames of
+    ``metric``, AUC_shuffled's negatives from the union of ten fixation maps chosen with numpy's global RNG (both
+    forms of ``draws`` consume that ``choice``).  With ``draws='reference'`` the result is the host function's for the
+    same global RNG state."""
+    assert len(gt_maps) == len(pred_maps) == len(fixation_maps)
+    union = union_of_ten(fixation_maps)
+    scores = saliency_scores_single(pred_maps, gt_maps, fixation_maps, union, (metric,), draws=draws, seed=seed)
+    return np.mean(scores[metric])
+
+
+__all__ = ['METRICS', 'FRAME_METRICS', 'stack_maps', 'draw_reference_samples', 'saliency_scores_single', 'saliency_score', 'union_of_ten']

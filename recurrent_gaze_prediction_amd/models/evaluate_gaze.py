@@ -19,6 +19,27 @@ def _dense(m):
     return m.toarray() if scipy.sparse.issparse(m) else np.asarray(m)
 
 
+def _write_frame(i, n_images, image, pred_gazemap, gt_gazemap, scores, out_dir, dump_images):
+    """evaluate_gaze.py:137-158: the per-frame dumps."""
+    if dump_images:
+        try:
+            from PIL import Image
+
+            def save(name, arr):
+                a = np.asarray(arr, np.float64)
+                a = (a - a.min()) / max(a.max() - a.min(), 1e-12)
+                Image.fromarray((a * 255).astype(np.uint8)).save(os.path.join(out_dir, name))
+            save('%05d.frame.jpg' % i, image)
+            save('%05d.gaze_pred.jpg' % i, pred_gazemap)
+            save('%05d.gaze_gt.jpg' % i, gt_gazemap)
+        except ImportError:
+            pass
+    with open(os.path.join(out_dir, '%05d.scores.txt' % i), 'w') as fp:
+        fp.write('%d / %d\n' % (i, n_images))
+        for k, v in scores.items():
+            fp.write('%s : %.4f\n' % (k, v))
+
+
 def handle_frame(i, n_images, image, pred_gazemap, gt_gazemap, fixationmap, out_dir, fixationmaps_all, rng,
                  dump_images=True):
     """evaluate_gaze.py:116-158: union of 10 random other fixation maps, 5 metrics, dumps."""
@@ -34,29 +55,36 @@ def handle_frame(i, n_images, image, pred_gazemap, gt_gazemap, fixationmap, out_
         scores[metric] = saliency_score_single(metric, pred_map=pred_gazemap, gt_map=gt_gazemap,
                                                fixation_map=fixationmap, other_map_union=other_map_union)
     if out_dir is not None:
-        if dump_images:
-            try:
-                from PIL import Image
-
-                def save(name, arr):
-                    a = np.asarray(arr, np.float64)
-                    a = (a - a.min()) / max(a.max() - a.min(), 1e-12)
-                    Image.fromarray((a * 255).astype(np.uint8)).save(os.path.join(out_dir, name))
-                save('%05d.frame.jpg' % i, image)
-                save('%05d.gaze_pred.jpg' % i, pred_gazemap)
-                save('%05d.gaze_gt.jpg' % i, gt_gazemap)
-            except ImportError:
-                pass
-        with open(os.path.join(out_dir, '%05d.scores.txt' % i), 'w') as fp:
-            fp.write('%d / %d\n' % (i, n_images))
-            for k, v in scores.items():
-                fp.write('%s : %.4f\n' % (k, v))
+        _write_frame(i, n_images, image, pred_gazemap, gt_gazemap, scores, out_dir, dump_images)
     return scores
 
 
-def run_evaluation(model, data_sets, out_dir, num_frames=1000, seed=0, dump_images=False):
-    """evaluate_gaze.py:172-227 -> {metric: mean}; writes <out_dir>/overall.txt in the reference's format."""
+def _device_frame_scores(pred, gt, fix, rng, scorer, seed):
+    """All frames in one launch of the HIP metrics kernel (evaluation_metrics_gpu): per frame the union of 10 random
+    other fixation maps drawn from ``rng`` as handle_frame draws them, then the five FRAME_METRICS.  'device-reference'
+    feeds the kernel the draws the host loop would take from numpy's global RNG (frame after frame, FRAME_METRICS
+    order); 'device' lets the kernel draw from ``seed``."""
+    from .. import evaluation_metrics_gpu as emg
+    fix = np.asarray(emg.stack_maps(fix, 'fixationmap_list'))
+    if fix.shape != pred.shape:
+        raise ValueError('fixation maps %s and predicted maps %s differ in shape; %s' % (fix.shape, pred.shape, emg._HOST))
+    positive = (fix > 0).astype(np.uint8)
+    unions = np.stack([positive[rng.choice(range(len(fix)), 10, replace=False)].sum(0, dtype=np.uint8) for _ in range(len(fix))])
+    draws = 'device'
+    if scorer == 'device-reference':
+        draws = emg.draw_reference_samples(fix, unions, FRAME_METRICS, order='frame')
+    return emg.saliency_scores_single(pred, gt, fix, unions, FRAME_METRICS, draws=draws, seed=seed)
+
+
+def run_evaluation(model, data_sets, out_dir, num_frames=1000, seed=0, dump_images=False, scorer='host'):
+    """evaluate_gaze.py:172-227 -> {metric: mean}; writes <out_dir>/overall.txt in the reference's format.
+
+    ``scorer``: 'host' (default) scores frame by frame with evaluation_metrics; 'device-reference' and 'device' score all
+    frames in one launch on the GPU (see _device_frame_scores), the former with the host's own draws -- same numbers, same
+    files -- the latter with draws made on the device from ``seed``.  Both need fixation maps of the maps' shape."""
     assert out_dir is not None
+    if scorer not in ('host', 'device', 'device-reference'):
+        raise ValueError("scorer must be 'host', 'device' or 'device-reference', got %r" % (scorer,))
     os.makedirs(out_dir, exist_ok=True)
     T = model.n_lstm_steps
     ret = model.generate(data_sets.valid, max_instances=int(np.divide(num_frames, T, dtype=float) + 1))
@@ -69,10 +97,18 @@ def run_evaluation(model, data_sets, out_dir, num_frames=1000, seed=0, dump_imag
     np.random.seed(seed)                       # AUC_Judd / AUC_Borji draw from the global RNG (9-Q11)
     try:
         aggregated = defaultdict(list)
-        for i in range(n_images):
-            scores = handle_frame(i, n_images, images[i], pred[i], gt[i], fix[i], out_dir, fix, rng, dump_images)
-            for metric, score in scores.items():
-                aggregated[metric].append(score)
+        if scorer == 'host':
+            for i in range(n_images):
+                scores = handle_frame(i, n_images, images[i], pred[i], gt[i], fix[i], out_dir, fix, rng, dump_images)
+                for metric, score in scores.items():
+                    aggregated[metric].append(score)
+        else:
+            per_frame = _device_frame_scores(pred, gt, fix, rng, scorer, seed)
+            for metric in FRAME_METRICS:
+                aggregated[metric] = [float(v) for v in per_frame[metric]]
+            for i in range(n_images):
+                scores = OrderedDict((metric, aggregated[metric][i]) for metric in FRAME_METRICS)
+                _write_frame(i, n_images, images[i], pred[i], gt[i], scores, out_dir, dump_images)
     finally:
         np.random.set_state(state)
     overall = OrderedDict()

@@ -7,6 +7,7 @@ BASELINE config 2) runs forward AND backward on the HIP path (rgp_fcgru_*), incl
 training-time dropout on its projected features."""
 import logging
 import time
+from functools import partial
 from types import SimpleNamespace
 
 import numpy as np
@@ -377,22 +378,40 @@ class GazePredictionGRU(ModelBase):
         out['fixationmap_list'] = fixations
         return out
 
-    def evaluate(self, pred_gazemap_list, gt_gazemap_list, fixationmap_list, images_list, **_ignored):
+    def evaluate(self, pred_gazemap_list, gt_gazemap_list, fixationmap_list, images_list, scorer='host', seed=0, **_ignored):
         """gaze_rnn.py:653-674.  Extra keys of generate()'s dictionary are accepted and ignored
-        (the reference raises TypeError there)."""
+        (the reference raises TypeError there).
+
+        ``scorer``: 'host' (default) scores with evaluation_metrics, frame by frame on the CPU; 'device' scores all
+        frames of a metric in one launch of the HIP metrics kernel with draws made on the device from ``seed``
+        (evaluation_metrics_gpu); 'device-reference' the same kernel fed with the host's own draws from numpy's global
+        RNG, which reproduces the host's scores for the same RNG state.  The device scorers need maps and fixation maps
+        of one shape and raise ValueError otherwise."""
         assert len(pred_gazemap_list) == len(gt_gazemap_list) == len(fixationmap_list) == len(images_list), \
             "Length mismatch: %d %d %d %d" % (len(pred_gazemap_list), len(gt_gazemap_list),
                                               len(fixationmap_list), len(images_list))
+        if scorer == 'host':
+            score = saliency_score
+        elif scorer in ('device', 'device-reference'):
+            from .. import evaluation_metrics_gpu as emg
+            if scorer == 'device':      # one upload for the four metrics
+                dev = self.session.device
+                pred_gazemap_list, gt_gazemap_list, fixationmap_list = (
+                    torch.as_tensor(np.asarray(emg.stack_maps(m, name))).to(dev)
+                    for m, name in ((pred_gazemap_list, 'pred'), (gt_gazemap_list, 'gt'), (fixationmap_list, 'fix')))
+            score = partial(emg.saliency_score, draws='device' if scorer == 'device' else 'reference', seed=seed)
+        else:
+            raise ValueError("scorer must be 'host', 'device' or 'device-reference', got %r" % (scorer,))
         batch_scores = {}
         for metric in AVAILABLE_METRICS:
-            batch_scores[metric] = saliency_score(metric, pred_gazemap_list, gt_gazemap_list, fixationmap_list)
+            batch_scores[metric] = score(metric, pred_gazemap_list, gt_gazemap_list, fixationmap_list)
             log.info('Saliency %s : %f', metric, batch_scores[metric])
         self.report_evaluate_summary(batch_scores)
         return batch_scores
 
-    def generate_and_evaluate(self, dataset, max_instances=50):
+    def generate_and_evaluate(self, dataset, max_instances=50, scorer='host'):
         ret = self.generate(dataset, max_instances)
-        return ret, self.evaluate(**ret)
+        return ret, self.evaluate(scorer=scorer, **ret)
 
 
 __all__ = ['CONSTANTS', 'GRUModelConfig', 'GazePredictionGRU', 'evaluation_metrics']
