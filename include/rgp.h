@@ -413,9 +413,9 @@ int rgp_c3d_create_ex(rgp_c3d_t** plan, int max_windows, int dtype, int flags);
  *                             implementation of those layers (tile chosen by problem size: 256x256 / 512x128 /
  *                             staggered 256x128 / 128x128), kept for cross-checking the default path.
  *  RGP_C3D_KERNELS_TILE128    with RGP_C3D_KERNELS_IGEMM: every implicit GEMM of the plan on the 128x128 tile loop.
- *  RGP_C3D_CONV2A_ROWWISE     inference plans on the patch kernels: conv2a + pool2 through the row-wise fetch of
- *                             conv_patch.hip.h (what training plans run) instead of the plane-slab fetch of
- *                             conv_patch_slab.hip.h; bit-identical results (a cross-check and A/B switch). */
+ *  RGP_C3D_CONV2A_ROWWISE     inference plans on the patch kernels: conv2a + pool2 through conv_patch_bf16_kernel of
+ *                             conv_patch.hip.h instead of conv_patch_slab_bf16_kernel of conv_patch_slab.hip.h (both
+ *                             skip the halo-plane tap groups); bit-identical results (a cross-check and A/B switch). */
 #define RGP_C3D_SAVE_FOR_BACKWARD 1
 #define RGP_C3D_KERNELS_IGEMM 2
 #define RGP_C3D_KERNELS_TILE128 4

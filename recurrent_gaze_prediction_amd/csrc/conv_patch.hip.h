@@ -45,8 +45,9 @@
 //    fragment address is one register per dz set + immediates (256 bytes per column pair, ky pitch + 64 kx per tap).
 //  * output plane z = 0 multiplies its kz = 0 taps with the zero halo plane z = -1, and z = DEPTH - 1 its kz = 2 taps with
 //    the halo plane z = DEPTH: in the tiles of the first / last pooled plane the dz = 0 / dz = 1 fragments skip that tap
-//    group (12 or 16 MFMAs per wave and step instead of 28): 2 of the 4 pooled planes of conv3a / conv3b.  conv2a (2 of 8)
-//    measured no gain and runs every tap group; so does conv3b's training forward (register pressure, see the kernel).
+//    group (12 or 16 MFMAs per wave and step instead of 28): 2 of the 4 pooled planes of conv3a / conv3b (1/12 of the
+//    MFMAs), 2 of the 8 of conv2a's inference forward (1/24; on a tile order of its own, see decode(): -0.3 ms per 1024
+//    windows).  conv2a's training forward and conv3b's (register pressure, see the kernel) run every tap group.
 //  * pooling: max over (dy, dx) in the lane's registers, over dz between two accumulator slots of the wave; column pair 3
 //    has its two planes in different waves, which exchange fp32 maxima through the filter-ring slot that is idle during
 //    the epilogue (conv_patch14.hip.h).
@@ -56,7 +57,10 @@
 #include "igemm.hip.h"
 
 #ifndef RGP_MMA_ORDER
-#define RGP_MMA_ORDER 1     // 1: filter fragment outermost in a step (7 consecutive MFMAs share it; 0: the activation fragment, 4): -0.5 % wall
+#define RGP_MMA_ORDER 2     // filter fragment outermost in a step (7 consecutive MFMAs share it: -0.5 % wall against the activation
+                            // fragment outermost); 2: boustrophedon, odd filter fragments walk the slots downwards, so exactly one
+                            // operand changes per MFMA (29 changes per 28 MFMAs against 32 with 1): same-box A/B conv2a -0.08 ms,
+                            // conv3a -0.04, conv3b -0.07 per 1024 windows (profiles/conv2a_halo_skip_ab.txt)
 #endif
 #ifndef RGP_CP_CHUNK56
 #define RGP_CP_CHUNK56 1     // clip windows per tile-order chunk, 56 x 56 planes (see decode() in the kernel)
@@ -153,8 +157,9 @@ static __device__ __forceinline__ f32x4 cp_lds_read128(unsigned addr) {
 // the rotated, in/out-swapped one of the backward plan): no bias, no ReLU, the result masked by the forward activation.
 // DENSE (DGRAD only): the output is the dense, un-masked [n][D*HW*HW][NOUT] image the un-pool kernel consumes (gradient
 // w.r.t. a pooled layer's output).
-template <int CIN, int NOUT, int HW, int DEPTH, bool POOL, bool ARGMAX = false, bool DGRAD = false, bool DENSE = false>
-static __global__ __launch_bounds__(512) void conv_patch_bf16_kernel(const ConvPatchParams p) {
+// (The body is a device function: conv_patch_slab.hip.h instantiates it under a second kernel name.)
+template <int CIN, int NOUT, int HW, int DEPTH, bool POOL, bool ARGMAX, bool DGRAD, bool DENSE>
+static __device__ __forceinline__ void conv_patch_body(const ConvPatchParams& p) {
   static_assert(!DENSE || DGRAD, "dense output: input gradients only");
   static_assert(POOL || !ARGMAX, "arg-max codes belong to the pooled layers");
   static_assert(!POOL || !DGRAD, "the input gradient is an un-pooled convolution");
@@ -180,12 +185,27 @@ static __global__ __launch_bounds__(512) void conv_patch_bf16_kernel(const ConvP
   };
   int t_seq = blockIdx.x;
   if (t_seq >= nt) return;
+  constexpr bool ROT56 = HW == 56 && POOL && !ARGMAX;        // the tile order of conv2a's inference forward, see decode()
   // tile -> (clip window, pooled plane zp, tile row yp).  Tiles are numbered (chunk of RGP_CP_CHUNK56 / 28 windows, zp, window, yp):
   // runs of CHUNK x YT tiles of ONE pooled plane follow each other, so the CUs of an XCD work on tiles of equal length at
   // any time -- the tiles of the first / last pooled plane skip tap groups and are ~7 % shorter; mixed with the others
   // they let the CUs drift apart, which costs the L2 sharing of halo rows and planes between neighbouring tiles
   // (conv3b's traffic beyond L2 went 9.4 -> 18 GB with the (window, zp, yp) order)
+  // conv2a's inference forward (ROT56; 8 pooled planes, 2 of them short): tiles are numbered (window, yp, zp + rotation),
+  // the 8 pooled planes of a row pair adjacent -- they share planes, and the next row pair its halo rows, inside one
+  // lockstep round of an XCD (32 consecutive tiles) -- and zp is rotated by the index of the tile's block of 32: CU i of the
+  // XCD meets tile i + 32 k of its range in round k, so it walks through all 8 pooled planes in any 8 consecutive rounds
+  // and every CU gets its two short tiles at the same rate: the drift between CUs is bounded by one short tile's saving.
+  // (A block of 32 holds whole groups of 8, so the rotation permutes zp inside a group: every tile exactly once, any n.)
   auto decode = [&](int tile, int& tn, int& zp, int& yp) {
+    if constexpr (ROT56) {
+      static_assert(!ROT56 || (C::TILES_PER_WINDOW % 8 == 0 && DEPTH == 16), "groups of 8 pooled planes");
+      tn = tile / C::TILES_PER_WINDOW;
+      const int r = tile - tn * C::TILES_PER_WINDOW;
+      yp = r >> 3;
+      zp = ((r & 7) + (tile >> 5)) & 7;
+      return;
+    }
     constexpr int NW = HW == 56 ? RGP_CP_CHUNK56 : RGP_CP_CHUNK28, TPW = C::TILES_PER_WINDOW;
     const int c = tile / (NW * TPW), r = tile - c * (NW * TPW);
     const int cw = min(NW, p.n_windows - c * NW);              // windows of this chunk (the last one may be short)
@@ -373,7 +393,11 @@ static __global__ __launch_bounds__(512) void conv_patch_bf16_kernel(const ConvP
 #pragma unroll
         for (int j = 0; j < NI; ++j)
 #pragma unroll
-          for (int i = I0; i < I1; ++i) Mma<bf16_t>::step(acc[i][j], af[i], bf[j]);
+          for (int i = I0; i < I1; ++i) {
+            // RGP_MMA_ORDER 2: every accumulator still receives its MFMAs in the same K order
+            const int ii = RGP_MMA_ORDER == 2 && (j & 1) ? I0 + I1 - 1 - i : i;
+            Mma<bf16_t>::step(acc[ii][j], af[ii], bf[j]);
+          }
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -397,9 +421,10 @@ static __global__ __launch_bounds__(512) void conv_patch_bf16_kernel(const ConvP
     // conv3b's training forward (arg-max codes): with the three loop variants the register allocator spills a fragment
     // inside the COMPUTE phases (scripts/check_isa_waits.py); it runs all seven slots in every tap group
     if constexpr (ARGMAX && CIN == 256) mode_k0 = mode_k2 = 0;
-    // conv2a (56 x 56 planes, 2 of its 8 pooled planes could skip): measured, skipping gains it nothing (14.10 vs 14.20 ms,
-    // both -0.4 % against the round-2 layout) and the unequal tiles let the CUs drift apart: 2 x FETCH 8.2 -> 17.5 GB
-    if constexpr (HW == 56) mode_k0 = mode_k2 = 0;
+    // conv2a (56 x 56 planes, 2 of its 8 pooled planes skip: 1/24 of the MFMAs): the inference forward skips, on the tile
+    // order of decode() -- with the (window, zp, yp) order the unequal tiles let the CUs drift apart (round 3: 14.10 vs
+    // 14.20 ms, 2 x FETCH 8.2 -> 17.5 GB).  The training forward and the input gradient keep every tap group.
+    if constexpr (HW == 56 && !ROT56) mode_k0 = mode_k2 = 0;
 #pragma clang loop unroll(disable)
     for (int cc = 0; cc < C::NCC; ++cc) {
       // the sweep after this one: the next channel slice of this tile, or the first one of the next tile
@@ -586,6 +611,11 @@ static __global__ __launch_bounds__(512) void conv_patch_bf16_kernel(const ConvP
     }
     t_seq = t_next;                                            // (the K loop's barriers separate this tile's staging reads from the next one's writes)
   }
+}
+
+template <int CIN, int NOUT, int HW, int DEPTH, bool POOL, bool ARGMAX = false, bool DGRAD = false, bool DENSE = false>
+static __global__ __launch_bounds__(512) void conv_patch_bf16_kernel(const ConvPatchParams p) {
+  conv_patch_body<CIN, NOUT, HW, DEPTH, POOL, ARGMAX, DGRAD, DENSE>(p);
 }
 
 }  // namespace rgp

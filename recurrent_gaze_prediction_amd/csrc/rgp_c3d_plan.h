@@ -32,10 +32,10 @@ struct rgp_c3d {
   int kernels = 0;               // 0: patch kernels for conv2a..conv4b (bf16); RGP_C3D_KERNELS_IGEMM / _TILE128 bits otherwise
   bool use_patch() const { return dtype == RGP_BF16 && !(kernels & RGP_C3D_KERNELS_IGEMM); }
   bool tile128() const { return (kernels & RGP_C3D_KERNELS_TILE128) != 0; }
-  // conv2a's INFERENCE forward on the plane-slab variant of the patch kernel (conv_patch_slab.hip.h) instead of the row-wise
-  // one (conv_patch.hip.h): same operands, bit-identical results; chosen by a same-box A/B (profiles/r05_ab_conv2a_slab.txt) and
-  // switched off per plan by RGP_C3D_CONV2A_ROWWISE.  Training plans (arg-max codes recorded) stay on the row-wise kernel:
-  // the slab variant's training forward measured 4 % slower.
+  // conv2a's INFERENCE forward under the kernel name conv_patch_slab_bf16_kernel (conv_patch_slab.hip.h; since the layer
+  // skips its halo-plane tap groups: the body of conv_patch.hip.h, see that file) instead of conv_patch_bf16_kernel: same
+  // operands, bit-identical results; switched off per plan by RGP_C3D_CONV2A_ROWWISE.  Training plans (arg-max codes
+  // recorded) run conv_patch_bf16_kernel<..., ARGMAX>.
   bool conv2a_slab() const { return use_patch() && !save && !(kernels & RGP_C3D_CONV2A_ROWWISE) && rgp::dev_knob("RGP_C2A_SLAB", 1) != 0; }
   rgp::ConvDesc L[8];
   size_t act_off[9] = {0};       // act[i] = halo-padded input of layer i; act[8] = conv5b rows

@@ -31,9 +31,9 @@ static int run_conv_patch(rgp_c3d* c, int layer, int n, hipStream_t s) {
   return RGP_OK;
 }
 
-// conv2a + pool2 on the plane-slab variant (conv_patch_slab.hip.h): inference plans
+// conv2a + pool2 under the kernel name of conv_patch_slab.hip.h: inference plans
 static int run_conv2a_slab(rgp_c3d* c, int n, hipStream_t s) {
-  using Cfg = PatchSlabCfg<64, 128, 56, 16>;
+  using Cfg = PatchCfg<64, 128, 56, 16, true>;
   ConvPatchParams p;
   p.in = (const bf16_t*)(c->ws + c->act_off[1]);
   p.wp = (const bf16_t*)(c->ws + c->L[1].w_off);

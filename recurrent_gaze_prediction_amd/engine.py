@@ -685,8 +685,8 @@ class C3DEngine(object):
     def __init__(self, max_windows, dtype='bf16', device='cuda:0', save_for_backward=False, kernels='patch'):
         """kernels: 'patch' (default: the layer-specific kernels for conv2a..conv4b), 'igemm' (the general
         implicit-GEMM / filter-gradient kernels for every layer, tile by problem size) or 'igemm128' (the same on
-        the 128x128 tile loop only), 'patch-rowwise' (the patch kernels with conv2a's inference forward on the row-wise
-        fetch instead of the plane-slab one: RGP_C3D_CONV2A_ROWWISE) -- rgp_c3d_create_ex flags; the alternatives exist
+        the 128x128 tile loop only), 'patch-rowwise' (the patch kernels with conv2a's inference forward on
+        conv_patch_bf16_kernel instead of conv_patch_slab_bf16_kernel: RGP_C3D_CONV2A_ROWWISE) -- rgp_c3d_create_ex flags; the alternatives exist
         for cross-checks."""
         self.lib = _lib.load()
         self.device = _require_gpu(device)
