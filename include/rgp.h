@@ -288,6 +288,52 @@ int rgp_fcgru_backward(rgp_fcgru_t* plan, const float* logits, const float* prob
  * by every following forward AND backward until changed; keep_prob = 1 or mask = NULL switches the site off
  * (inference, the default). */
 int rgp_fcgru_set_dropout(rgp_fcgru_t* plan, float keep_prob, const unsigned char* mask);
+/* ------------------------------------------------------------------ gaze_c3d_conv (the no-recurrence baseline) */
+typedef struct rgp_c3dconv rgp_c3dconv_t;
+
+/* GazePredictionConv.create_gazeprediction_network (models/gaze_c3d_conv.py:105-218): gaze_grcn's projection and
+ * three-stage up-sampling head with the ConvGRU taken out; no batch-norm, no state, both dropout sites inert.  fp32
+ * device pointers (proj_c3d_W 16-byte aligned): proj_c3d_W [1024,P] proj_c3d_b [P] (:124-125); up_weight1 [5,5,64,P]
+ * up_weight2 [5,5,32,64] up_weight3 [7,7,12,32] out_W [12,1] out_b [1] (:153-173).  The graph is linear per frame:
+ * set_weights folds it, in fp32 with sums in a fixed order (equal weights give equal bits), into one 1024 -> 384 filter
+ * and a 49x49 bias plane (csrc/c3dconv_fused.hip.h). */
+typedef struct rgp_c3dconv_weights {
+  const float *proj_c3d_W, *proj_c3d_b, *up_weight1, *up_weight2, *up_weight3, *out_W, *out_b;
+} rgp_c3dconv_weights;
+
+/* flags: 0 = the library's choice (bf16 inference plans: the fused kernel -- rows to logits and softmax in one launch;
+ * everything else: the staged path -- projection GEMM, folded head GEMM, col2im, softmax).  RGP_C3DCONV_STAGED forces
+ * the staged path, RGP_C3DCONV_FUSED the fused kernel (bf16 without SAVE_FOR_BACKWARD only, RGP_EINVAL otherwise).
+ * RGP_C3DCONV_SAVE_FOR_BACKWARD: a training plan, keeps the input rows and the projected features.
+ * dim_proj: a multiple of 64 (the reference: 512). */
+#define RGP_C3DCONV_SAVE_FOR_BACKWARD 1
+#define RGP_C3DCONV_STAGED 2
+#define RGP_C3DCONV_FUSED 4
+int rgp_c3dconv_create(rgp_c3dconv_t** plan, int batch, int n_steps, int dim_proj, int dtype, int flags);
+int rgp_c3dconv_destroy(rgp_c3dconv_t* plan);
+size_t rgp_c3dconv_workspace_bytes(const rgp_c3dconv_t* plan);
+int rgp_c3dconv_bind_workspace(rgp_c3dconv_t* plan, void* workspace, size_t bytes, rgp_stream_t stream);
+int rgp_c3dconv_set_weights(rgp_c3dconv_t* plan, const rgp_c3dconv_weights* w, rgp_stream_t stream);
+/* c3d_input [B,T,1024,7,7] fp32 (the placeholder layout) -> logits [B,T,49,49]; probs (optional) = per-frame softmax.
+ * No atomics on either path: two calls on the same input give the same bits. */
+int rgp_c3dconv_forward(rgp_c3dconv_t* plan, const float* c3d_input, float* logits, float* probs, rgp_stream_t stream);
+/* c3d_rows: [B*T*49, 1024] in the plan's operand dtype, column d*512+c, 16-byte aligned (what rgp_c3d_forward writes) */
+int rgp_c3dconv_forward_rows(rgp_c3dconv_t* plan, const void* c3d_rows, float* logits, float* probs, rgp_stream_t stream);
+/* Training plans, after a forward: gradients of the loss of gaze_rnn.py:363-408 (loss_type 0 xentropy: probs and labels
+ * are read; 1 l2: logits and labels) w.r.t. the seven variables (grads: arrays shaped like the weights, fully
+ * overwritten).  No float atomics: every reduction runs in a fixed order, two calls on the same inputs give the same bits. */
+int rgp_c3dconv_backward(rgp_c3dconv_t* plan, const float* logits, const float* probs, const float* labels,
+                         const rgp_c3dconv_weights* grads, int loss_type, rgp_stream_t stream);
+/* After rgp_c3dconv_backward: d loss / d input as conv5b rows [B*T*49, 1024] fp32 (column d*512+c), the gradient
+ * rgp_c3d_backward consumes when the conv stack is fine-tuned beneath this model. */
+int rgp_c3dconv_backward_input(rgp_c3dconv_t* plan, float* d_rows, rgp_stream_t stream);
+/* fp32 copies of "c3d_embedded" [B*T*49, P] (staged plans, after a forward), "folded_filter" [384, 1024] (row = tap
+ * (r+3)*19+t+3 of the 19x19 stride-6 filter, rows 361..383 zero; column = placeholder channel) and "bias_plane" [49,49]
+ * (both after set_weights, inference plans).  buffer_elems: the element count, 0 = this plan has no such buffer. */
+int rgp_c3dconv_read_buffer(rgp_c3dconv_t* plan, const char* name, float* dst, rgp_stream_t stream);
+size_t rgp_c3dconv_buffer_elems(const rgp_c3dconv_t* plan, const char* name);
+/* "fused" or "staged": what forward will run */
+const char* rgp_c3dconv_path(const rgp_c3dconv_t* plan);
 /* ------------------------------------------------------------------ frame-wise ShallowNet */
 typedef struct rgp_shallownet rgp_shallownet_t;
 

@@ -25,6 +25,8 @@ The other three graphs of the gaze family (``model=`` of import_tf_variables / e
   'shallownet'  (saliency_shallownet.py:92-185, tf.contrib.layers scopes; what
       initialize_pretrained_shallownet copies from a separate checkpoint, gaze_rnn.py:412-433):
       ShallowNet/conv{1,2,3}/{weights,biases}, ShallowNet/fc{1,2}/{weights,biases} -> conv1_w, conv1_b, ... fc2_b
+  'gaze_c3d_conv'  (gaze_c3d_conv.py:105-173; scope "RGP", no recurrence, no batch-norm):
+      RGP/proj_c3d_W, RGP/proj_c3d_b, RGP/Upsampling/weight{1,2,3}, RGP/out_W, RGP/out_b -> as gaze_grcn's
   'gaze_grcn_cascade'  (gaze_grcn_cascade.py:267-423):
       proj_c3d_W, proj_c3d_b; RCNBottom/GRU_Conv_*; Upsampling/weight; RCNGaze/GRU_Conv_*;
       RCNGaze/LastProjection/fc{1,2}/{weights,biases|bias}    -> LastProjection/fc{1,2}_{w,b}
@@ -201,9 +203,30 @@ def export_cascade_variables(state):
     return out
 
 
-_IMPORTERS = {'gaze_rnn': import_fcgru_variables, 'shallownet': import_shallownet_variables,
+def import_c3d_conv_variables(tf_vars):
+    """gaze_c3d_conv (gaze_c3d_conv.py:105,124-125,153-173): the seven variables of _SIMPLE, with or without the RGP/
+    scope and the ':0' suffix (RGP/Upsampling/weight1:0, Upsampling/weight1, ...)."""
+    src = {_strip(k): np.asarray(v) for k, v in dict(tf_vars).items() if not _skip(_strip(k))}
+    out = {}
+    for tf_name, key in _SIMPLE.items():
+        for name in (tf_name, tf_name[len('RGP/'):]):
+            if name in src and key not in out:
+                out[key] = src[name].astype(np.float32)
+    missing = sorted(set(_SIMPLE.values()) - set(out))
+    if missing:
+        raise KeyError('TF checkpoint lacks gaze_c3d_conv variables for: %s' % ', '.join(missing))
+    return out
+
+
+def export_c3d_conv_variables(state):
+    """state dict -> TF names under the RGP/ scope."""
+    inv = {v: k for k, v in _SIMPLE.items()}
+    return {inv[k]: np.asarray(v) for k, v in state.items() if k in inv}
+
+
+_IMPORTERS = {'gaze_c3d_conv': import_c3d_conv_variables, 'gaze_rnn': import_fcgru_variables, 'shallownet': import_shallownet_variables,
               'gaze_framewise_shallownet': import_shallownet_variables, 'gaze_grcn_cascade': import_cascade_variables}
-_EXPORTERS = {'gaze_rnn': export_fcgru_variables, 'shallownet': export_shallownet_variables,
+_EXPORTERS = {'gaze_c3d_conv': export_c3d_conv_variables, 'gaze_rnn': export_fcgru_variables, 'shallownet': export_shallownet_variables,
               'gaze_framewise_shallownet': export_shallownet_variables, 'gaze_grcn_cascade': export_cascade_variables}
 
 

@@ -366,6 +366,147 @@ class GrcnEngine(object):
         return {k: (ms[i], calls[i]) for i, k in enumerate(_lib.GRCN_STAGES)}
 
 
+C3DCONV_PARAM_TO_FIELD = {   # reference TF variable name (without scope) -> rgp_c3dconv_weights field
+    'proj_c3d_W': 'proj_c3d_W', 'proj_c3d_b': 'proj_c3d_b',
+    'weight1': 'up_weight1', 'weight2': 'up_weight2', 'weight3': 'up_weight3', 'out_W': 'out_W', 'out_b': 'out_b',
+}
+
+
+class C3dConvEngine(object):
+    """gaze_c3d_conv graph (models/gaze_c3d_conv.py:105-218), the no-recurrence baseline, at fixed (B, T, P, dtype).
+
+    path=None: the library's choice (bf16 inference plans: the fused kernel, one launch from rows to softmax; everything
+    else the staged path); 'fused' / 'staged' force one (RGP_C3DCONV_FUSED / RGP_C3DCONV_STAGED).  Training plans
+    (save_for_backward=True) run the staged path; their backward uses no float atomics (bit-reproducible gradients)."""
+
+    def __init__(self, batch, n_steps, dim_proj=512, dtype='bf16', save_for_backward=False, device='cuda:0', path=None):
+        self.lib = _lib.load()
+        self.device = _require_gpu(device)
+        self.B, self.T, self.P = int(batch), int(n_steps), int(dim_proj)
+        self.dtype = dtype
+        self.save_for_backward = bool(save_for_backward)
+        self.torch_dtype = torch.bfloat16 if _lib.DTYPES[dtype] == _lib.RGP_BF16 else torch.float32
+        flags = {None: 0, 'staged': _lib.RGP_C3DCONV_STAGED, 'fused': _lib.RGP_C3DCONV_FUSED}[path]
+        flags |= _lib.RGP_C3DCONV_SAVE_FOR_BACKWARD if save_for_backward else 0
+        self.flat_params = self.flat_grads = self.grads = None
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_c3dconv_create(ctypes.byref(self._h), self.B, self.T, self.P, _lib.DTYPES[dtype], flags))
+            nbytes = self.lib.rgp_c3dconv_workspace_bytes(self._h)
+            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.rgp_c3dconv_bind_workspace(self._h, _ptr(self.workspace), nbytes, _stream_ptr(self.device)))
+        self.path = self.lib.rgp_c3dconv_path(self._h).decode()
+        self.weights = None
+
+    def __del__(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h:
+            self.lib.rgp_c3dconv_destroy(h)
+
+    def _flat_views(self, like):
+        sizes = [(k, tuple(like[k].shape)) for k in C3DCONV_PARAM_TO_FIELD]
+        flat = torch.zeros(sum(int(np.prod(s)) for _, s in sizes), dtype=torch.float32, device=self.device)
+        views, off = {}, 0
+        for k, shp in sizes:
+            n = int(np.prod(shp))
+            views[k] = flat[off:off + n].view(shp)
+            off += n
+        return flat, views
+
+    def _struct(self, views):
+        st = _lib.C3dConvWeights()
+        for k, f in C3DCONV_PARAM_TO_FIELD.items():
+            setattr(st, f, views[k].data_ptr())
+        return st
+
+    def set_weights(self, params):
+        """params: dict keyed by the reference's TF variable names (scope stripped) -> array/tensor (fp32); copied into
+        the engine's flat fp32 master buffer, then folded (repack)."""
+        src = {k: _as_dev_f32(params[k], self.device) for k in C3DCONV_PARAM_TO_FIELD}
+        assert tuple(src['proj_c3d_W'].shape) == (1024, self.P) and tuple(src['weight1'].shape) == (5, 5, 64, self.P)
+        if self.weights is None:
+            self.flat_params, self.weights = self._flat_views(src)
+        for k in C3DCONV_PARAM_TO_FIELD:
+            self.weights[k].copy_(src[k])
+        self.repack()
+
+    def repack(self):
+        """Fold the master weights into the 1024 -> 384 filter and the bias plane (and the staged path's operands)."""
+        st = self._struct(self.weights)     # the plan keeps raw pointers to the biases: views stay alive
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_c3dconv_set_weights(self._h, ctypes.byref(st), _stream_ptr(self.device)))
+
+    def backward(self, logits, probs, labels, loss_type='xentropy'):
+        """Gradients of the reference loss (gaze_rnn.py:363-408) w.r.t. the seven variables, after a forward() on the same
+        inputs.  labels: normalised gt maps [B,T,49,49] fp32 device tensor.  Returns {TF variable name: fp32 gradient
+        view}; the flat buffer is self.flat_grads (fully overwritten)."""
+        assert self.save_for_backward, 'create the engine with save_for_backward=True'
+        assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
+        if self.grads is None:
+            self.flat_grads, self.grads = self._flat_views(self.weights)
+        st = self._struct(self.grads)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_c3dconv_backward(self._h, _ptr(logits), _ptr(probs), _ptr(labels), ctypes.byref(st),
+                                                     {'xentropy': 0, 'l2': 1}[loss_type], _stream_ptr(self.device)))
+        return self.grads
+
+    def grad_buckets(self):
+        """[(slice of flat_grads, ready)]: one bucket, complete when backward() returns on the launch stream."""
+        return [(self.flat_grads, lambda stream: stream.wait_stream(torch.cuda.current_stream(self.device)))]
+
+    def backward_input(self, out=None):
+        """After backward(): d loss / d input as conv5b rows [B*T*49, 1024] fp32 (column d*512+c), the gradient
+        C3DEngine.backward(d_rows=...) consumes when the conv stack is fine-tuned."""
+        d = out if out is not None else torch.empty(self.B * self.T * 49, 1024, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_c3dconv_backward_input(self._h, _ptr(d), _stream_ptr(self.device)))
+        return d
+
+    def adam_step(self, step, lr, max_grad_norm=10.0, method='adam'):
+        """clip_by_global_norm + the chosen optimizer of base.py:268-273 on the flat buffers, then repack (re-fold)."""
+        return clip_step_multi([self], step, lr, max_grad_norm, method)
+
+    def _outputs(self, want_probs, out_logits, out_probs):
+        logits = out_logits if out_logits is not None else torch.empty(self.B, self.T, 49, 49, device=self.device)
+        probs = None
+        if want_probs:
+            probs = out_probs if out_probs is not None else torch.empty_like(logits)
+        return logits, probs
+
+    def forward(self, c3d_input, want_probs=True, out_logits=None, out_probs=None):
+        """c3d_input [B,T,1024,7,7] fp32 device tensor -> (logits, probs) [B,T,49,49]."""
+        x = c3d_input
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        assert tuple(x.shape) == (self.B, self.T, 1024, 7, 7), tuple(x.shape)
+        logits, probs = self._outputs(want_probs, out_logits, out_probs)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_c3dconv_forward(self._h, _ptr(x), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
+        return logits, probs
+
+    def forward_rows(self, rows, want_probs=True, out_logits=None, out_probs=None):
+        """rows: conv5b rows from C3DEngine.forward (operand dtype, [B*T*49, 1024], column d*512+c)."""
+        assert rows.is_cuda and rows.dtype == self.torch_dtype and rows.is_contiguous()
+        assert rows.numel() == self.B * self.T * 49 * 1024
+        logits, probs = self._outputs(want_probs, out_logits, out_probs)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_c3dconv_forward_rows(self._h, _ptr(rows), _ptr(logits), _ptr(probs),
+                                                         _stream_ptr(self.device)))
+        return logits, probs
+
+    def read_buffer_elems(self, name):
+        return int(self.lib.rgp_c3dconv_buffer_elems(self._h, name.encode()))
+
+    def read_buffer(self, name):
+        """'c3d_embedded' [B*T*49, P] (staged plans), 'folded_filter' [384, 1024], 'bias_plane' [49, 49] as fp32."""
+        n = self.read_buffer_elems(name)
+        if n == 0:
+            raise _lib.RgpError('unknown intermediate %r' % name)
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_c3dconv_read_buffer(self._h, name.encode(), _ptr(out), _stream_ptr(self.device)))
+        return out
+
+
 def softmax_xent(logits, labels=None, want_probs=True):
     """Per-frame softmax / cross entropy (model_util.py:61-72; gaze_rnn.py:390-407).
     logits [..., H, W] fp32 device tensor -> (probs, frame_loss, loss)."""

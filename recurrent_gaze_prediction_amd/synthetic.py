@@ -67,6 +67,20 @@ def grcn_params(seed, n_steps, dim_proj=512, dim_state=128, gru_std=0.05, random
     return p
 
 
+def c3d_conv_params(seed, dim_proj=512):
+    """Weights of GazePredictionConv (gaze_c3d_conv.py:124-125 U(-0.1, 0.1); :153-173 Xavier-uniform / U(-0.1, 0.1)),
+    keyed as grcn_params keys the same variables."""
+    rs = np.random.RandomState(seed)
+    u = lambda *s: rs.uniform(-0.1, 0.1, size=s).astype(np.float32)
+    return {
+        'proj_c3d_W': u(1024, dim_proj), 'proj_c3d_b': u(dim_proj),
+        'weight1': _xavier_conv(rs, (5, 5, 64, dim_proj)),
+        'weight2': _xavier_conv(rs, (5, 5, 32, 64)),
+        'weight3': _xavier_conv(rs, (7, 7, 12, 32)),
+        'out_W': u(12, 1), 'out_b': u(1),
+    }
+
+
 def fcgru_params(seed, gh=49, gw=49, dim_proj=32):
     """Weights of GazePredictionGRU (gaze_rnn.py:294-320; TF GRUCell: gate bias 1)."""
     rs = np.random.RandomState(seed)
