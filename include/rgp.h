@@ -334,6 +334,67 @@ int rgp_c3dconv_read_buffer(rgp_c3dconv_t* plan, const char* name, float* dst, r
 size_t rgp_c3dconv_buffer_elems(const rgp_c3dconv_t* plan, const char* name);
 /* "fused" or "staged": what forward will run */
 const char* rgp_c3dconv_path(const rgp_c3dconv_t* plan);
+/* ------------------------------------------------------------------ gaze_lstm (the ConvLSTM model) */
+typedef struct rgp_lstm rgp_lstm_t;
+
+/* GazePredictionLSTM.create_gazeprediction_network (models/gaze_lstm.py:178-353): projection 1024 -> 512, LSTM_RCN_Cell
+ * (:48-148; 128 state channels, 3x3 SAME on 7x7, zero state for c and h, no batch-norm), gaze_grcn's up-sampling head
+ * on h_t.  The cell as the reference writes it (:114-131):
+ *   i = sigmoid(W_xi*x + W_hi*h + W_ci.c)   f = sigmoid(W_xf*x + W_hf*h + W_cf.c)   g = tanh(W_xc*x + W_hi*h)
+ *   c' = f.c + i.g   o = sigmoid(W_xo*x + W_ho*h + W_co.c)   h' = tanh(c').o
+ * -- g reuses W_hi, o reads the OLD c, and W_hc [3,3,128,128] is a variable nothing reads: it is carried (checkpoints),
+ * its gradient is written as zeros, and the optimizer must leave it out (tf.gradients gives None for it).
+ * All fp32 device pointers: W_x* [3,3,512,128], W_h* [3,3,128,128], peepholes W_c* [7,7,128] (per position);
+ * the others as in rgp_grcn_weights. */
+typedef struct rgp_lstm_weights {
+  const float *proj_c3d_W, *proj_c3d_b;
+  const float *W_xi, *W_hi, *W_ci, *W_xf, *W_hf, *W_cf, *W_xc, *W_hc, *W_xo, *W_ho, *W_co;
+  const float *up_weight1, *up_weight2, *up_weight3, *out_W, *out_b;
+} rgp_lstm_weights;
+
+/* flags: RGP_LSTM_SAVE_FOR_BACKWARD  training plan (gates, states and operand images kept for rgp_lstm_backward);
+ *        RGP_LSTM_PER_STEP           run the recurrence as one launch per timestep even where the persistent kernel
+ *                                    applies: the library's second implementation, always used by f32 plans and by
+ *                                    plans with more than 64 clips;
+ *        RGP_LSTM_PERSISTENT         ask for the persistent kernel (all T steps in one launch, csrc/convlstm_seq.hip.h):
+ *                                    bf16 plans of at most 64 clips, RGP_EINVAL otherwise.  On a device with fewer
+ *                                    than 8 CUs per group the plan still runs per step
+ *                                    (rgp_lstm_persistent_workgroups tells).
+ *        0                           the library's choice for plans both paths can run: the persistent kernel,
+ *                                    measured faster than per-step launches at both benchmark shapes. */
+#define RGP_LSTM_SAVE_FOR_BACKWARD 1
+#define RGP_LSTM_PER_STEP 2
+#define RGP_LSTM_PERSISTENT 4
+int rgp_lstm_create(rgp_lstm_t** plan, int batch, int n_steps, int dtype, int flags);
+int rgp_lstm_destroy(rgp_lstm_t* plan);
+size_t rgp_lstm_workspace_bytes(const rgp_lstm_t* plan);
+int rgp_lstm_bind_workspace(rgp_lstm_t* plan, void* workspace, size_t bytes, rgp_stream_t stream);
+int rgp_lstm_set_weights(rgp_lstm_t* plan, const rgp_lstm_weights* w, rgp_stream_t stream);
+/* c3d_input [B,T,1024,7,7] fp32 -> logits [B,T,49,49]; probs (optional) = per-frame softmax.  No float atomics: two
+ * calls on the same input give the same bits.  The persistent recurrence kernel computes a clip with the same bits
+ * whatever its group slot and the batch size; for the whole forward that also needs the GEMMs around it to pick tiles
+ * with one accumulation order, which is tested for clips of a 64 x 16 call against 2 x 16 calls only. */
+int rgp_lstm_forward(rgp_lstm_t* plan, const float* c3d_input, float* logits, float* probs, rgp_stream_t stream);
+/* c3d_rows: [B*T*49, 1024] in the plan's operand dtype, column d*512+c, 16-byte aligned (what rgp_c3d_forward writes) */
+int rgp_lstm_forward_rows(rgp_lstm_t* plan, const void* c3d_rows, float* logits, float* probs, rgp_stream_t stream);
+/* Training plans, after a forward: gradients of the loss of gaze_rnn.py:363-408 (loss_type 0 xentropy, 1 l2) w.r.t. the
+ * 18 variables (grads: arrays shaped like the weights).  BPTT runs as per-timestep launches; grads->W_hc is zeroed. */
+int rgp_lstm_backward(rgp_lstm_t* plan, const float* logits, const float* probs, const float* labels,
+                      const rgp_lstm_weights* grads, int loss_type, rgp_stream_t stream);
+/* After rgp_lstm_backward: d loss / d input as conv5b rows [B*T*49, 1024] fp32 (column d*512+c) */
+int rgp_lstm_backward_input(rgp_lstm_t* plan, float* d_rows, rgp_stream_t stream);
+/* The persistent kernel fails as the ConvGRU kernels do (rgp_grcn_status): a group that misses a member gives up after
+ * about a second, NaN-poisons its clips and raises the plan's error state -- the next call on the plan and
+ * rgp_lstm_status (which first waits for `stream`) return RGP_ETIMEOUT once.  rgp_lstm_inject_fault
+ * (RGP_FAULT_SEQ_LOST_MEMBER): test hook, the next persistent launch runs without one member of its first group. */
+int rgp_lstm_status(rgp_lstm_t* plan, rgp_stream_t stream);
+int rgp_lstm_inject_fault(rgp_lstm_t* plan, int kind);
+/* Workgroups (= CUs) a persistent launch of this plan occupies on the current device; 0 = per-timestep launches */
+int rgp_lstm_persistent_workgroups(const rgp_lstm_t* plan);
+/* fp32 copies of "h", "c" (and, training plans, the gates "i", "f", "g", "o") as [B,T,7,7,128], and of "emb", the
+ * projected features [B*T*49, 512], after a forward.  buffer_elems: the element count, 0 = no such buffer. */
+int rgp_lstm_read_buffer(rgp_lstm_t* plan, const char* name, float* dst, rgp_stream_t stream);
+size_t rgp_lstm_buffer_elems(const rgp_lstm_t* plan, const char* name);
 /* ------------------------------------------------------------------ frame-wise ShallowNet */
 typedef struct rgp_shallownet rgp_shallownet_t;
 

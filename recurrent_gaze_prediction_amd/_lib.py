@@ -20,6 +20,7 @@ RGP_ETIMEOUT = -5
 RGP_GRCN_SAVE_FOR_BACKWARD, RGP_GRCN_PER_STEP, RGP_GRCN_UNFOLDED_HEAD = 1, 2, 4
 RGP_C3D_SAVE_FOR_BACKWARD, RGP_C3D_KERNELS_IGEMM, RGP_C3D_KERNELS_TILE128, RGP_C3D_CONV2A_ROWWISE = 1, 2, 4, 8
 RGP_C3DCONV_SAVE_FOR_BACKWARD, RGP_C3DCONV_STAGED, RGP_C3DCONV_FUSED = 1, 2, 4
+RGP_LSTM_SAVE_FOR_BACKWARD, RGP_LSTM_PER_STEP, RGP_LSTM_PERSISTENT = 1, 2, 4
 RGP_FAULT_SEQ_LOST_MEMBER, RGP_FAULT_BPTT_LOST_MEMBER = 1, 2
 RGP_GRCN_GRADS_TOP, RGP_GRCN_GRADS_GRU, RGP_GRCN_GRADS_PROJ = 0, 1, 2
 RGP_SQNORM_PARTIALS = 256          # include/rgp.h
@@ -51,6 +52,12 @@ class FcGruWeights(ctypes.Structure):
 
 class C3dConvWeights(ctypes.Structure):
     FIELDS = ('proj_c3d_W', 'proj_c3d_b', 'up_weight1', 'up_weight2', 'up_weight3', 'out_W', 'out_b')
+    _fields_ = [(n, c_void_p) for n in FIELDS]
+
+
+class LstmWeights(ctypes.Structure):
+    FIELDS = ('proj_c3d_W', 'proj_c3d_b', 'W_xi', 'W_hi', 'W_ci', 'W_xf', 'W_hf', 'W_cf', 'W_xc', 'W_hc', 'W_xo', 'W_ho', 'W_co',
+              'up_weight1', 'up_weight2', 'up_weight3', 'out_W', 'out_b')
     _fields_ = [(n, c_void_p) for n in FIELDS]
 
 
@@ -124,6 +131,20 @@ SIGNATURES = {
     'rgp_c3dconv_read_buffer': (c_int, [c_void_p, c_char_p, c_void_p, c_void_p]),
     'rgp_c3dconv_buffer_elems': (c_size_t, [c_void_p, c_char_p]),
     'rgp_c3dconv_path': (c_char_p, [c_void_p]),
+    'rgp_lstm_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int]),
+    'rgp_lstm_destroy': (c_int, [c_void_p]),
+    'rgp_lstm_workspace_bytes': (c_size_t, [c_void_p]),
+    'rgp_lstm_bind_workspace': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    'rgp_lstm_set_weights': (c_int, [c_void_p, ctypes.POINTER(LstmWeights), c_void_p]),
+    'rgp_lstm_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rgp_lstm_forward_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rgp_lstm_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(LstmWeights), c_int, c_void_p]),
+    'rgp_lstm_backward_input': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'rgp_lstm_status': (c_int, [c_void_p, c_void_p]),
+    'rgp_lstm_inject_fault': (c_int, [c_void_p, c_int]),
+    'rgp_lstm_persistent_workgroups': (c_int, [c_void_p]),
+    'rgp_lstm_read_buffer': (c_int, [c_void_p, c_char_p, c_void_p, c_void_p]),
+    'rgp_lstm_buffer_elems': (c_size_t, [c_void_p, c_char_p]),
     'rgp_shallownet_create_ex': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int]),
     'rgp_shallownet_backward': (c_int, [c_void_p, c_int, c_void_p, ctypes.POINTER(ShallowNetWeights), c_void_p]),
     'rgp_shallownet_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),

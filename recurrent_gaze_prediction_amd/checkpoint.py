@@ -27,6 +27,11 @@ The other three graphs of the gaze family (``model=`` of import_tf_variables / e
       ShallowNet/conv{1,2,3}/{weights,biases}, ShallowNet/fc{1,2}/{weights,biases} -> conv1_w, conv1_b, ... fc2_b
   'gaze_c3d_conv'  (gaze_c3d_conv.py:105-173; scope "RGP", no recurrence, no batch-norm):
       RGP/proj_c3d_W, RGP/proj_c3d_b, RGP/Upsampling/weight{1,2,3}, RGP/out_W, RGP/out_b -> as gaze_grcn's
+  'gaze_lstm'  (gaze_lstm.py:219,238-239,260-261,64-87,291-308; cell variables under RGP/RCNBottom/, unpinned: TF's
+      unique-name rule restated, no TF at hand -- the repeated name= arguments get the suffix _1):
+      RGP/RCNBottom/ConvLSTM_{Wxi,Wxi_1,Wci,Wxf,Wxf_1,Wcf,Wxc,Whc,Wxo,Wxo_1,Wco} -> same names without the scopes
+        (Wxi_1 = W_hi, Wxf_1 = W_hf, Wxo_1 = W_ho; Whc is carried although nothing reads it)
+      RGP/proj_c3d_W, RGP/proj_c3d_b, RGP/Upsampling/weight{1,2,3}, RGP/out_W, RGP/out_b -> as gaze_grcn's
   'gaze_grcn_cascade'  (gaze_grcn_cascade.py:267-423):
       proj_c3d_W, proj_c3d_b; RCNBottom/GRU_Conv_*; Upsampling/weight; RCNGaze/GRU_Conv_*;
       RCNGaze/LastProjection/fc{1,2}/{weights,biases|bias}    -> LastProjection/fc{1,2}_{w,b}
@@ -224,9 +229,34 @@ def export_c3d_conv_variables(state):
     return {inv[k]: np.asarray(v) for k, v in state.items() if k in inv}
 
 
-_IMPORTERS = {'gaze_c3d_conv': import_c3d_conv_variables, 'gaze_rnn': import_fcgru_variables, 'shallownet': import_shallownet_variables,
+_LSTM_CELL = ('ConvLSTM_Wxi', 'ConvLSTM_Wxi_1', 'ConvLSTM_Wci', 'ConvLSTM_Wxf', 'ConvLSTM_Wxf_1', 'ConvLSTM_Wcf',
+              'ConvLSTM_Wxc', 'ConvLSTM_Whc', 'ConvLSTM_Wxo', 'ConvLSTM_Wxo_1', 'ConvLSTM_Wco')
+_LSTM = dict(_SIMPLE, **{'RGP/RCNBottom/' + k: k for k in _LSTM_CELL})
+
+
+def import_lstm_variables(tf_vars):
+    """gaze_lstm: the 18 variables of _LSTM, with or without the RGP/ scope and the ':0' suffix."""
+    src = {_strip(k): np.asarray(v) for k, v in dict(tf_vars).items() if not _skip(_strip(k))}
+    out = {}
+    for tf_name, key in _LSTM.items():
+        for name in (tf_name, tf_name[len('RGP/'):]):
+            if name in src and key not in out:
+                out[key] = src[name].astype(np.float32)
+    missing = sorted(set(_LSTM.values()) - set(out))
+    if missing:
+        raise KeyError('TF checkpoint lacks gaze_lstm variables for: %s' % ', '.join(missing))
+    return out
+
+
+def export_lstm_variables(state):
+    """state dict -> TF names under RGP/ (cell variables under RGP/RCNBottom/)."""
+    inv = {v: k for k, v in _LSTM.items()}
+    return {inv[k]: np.asarray(v) for k, v in state.items() if k in inv}
+
+
+_IMPORTERS = {'gaze_lstm': import_lstm_variables, 'gaze_c3d_conv': import_c3d_conv_variables, 'gaze_rnn': import_fcgru_variables, 'shallownet': import_shallownet_variables,
               'gaze_framewise_shallownet': import_shallownet_variables, 'gaze_grcn_cascade': import_cascade_variables}
-_EXPORTERS = {'gaze_c3d_conv': export_c3d_conv_variables, 'gaze_rnn': export_fcgru_variables, 'shallownet': export_shallownet_variables,
+_EXPORTERS = {'gaze_lstm': export_lstm_variables, 'gaze_c3d_conv': export_c3d_conv_variables, 'gaze_rnn': export_fcgru_variables, 'shallownet': export_shallownet_variables,
               'gaze_framewise_shallownet': export_shallownet_variables, 'gaze_grcn_cascade': export_cascade_variables}
 
 

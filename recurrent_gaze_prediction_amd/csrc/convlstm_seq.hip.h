@@ -1,0 +1,279 @@
+// Persistent ConvLSTM sequence kernel (gfx950, bf16 operands): ALL T steps of LSTM_RCN_Cell.__call__
+// (/root/reference/models/gaze_lstm.py:103-133, unrolled at :270-286) in ONE launch.  The scheme is convgru_seq.hip.h's
+// (read that header first: decomposition, exchange protocol, time-out), with the cell's own shape:
+//
+//   i = sigmoid(W_xi*x + W_hi*h + W_ci.c)     f = sigmoid(W_xf*x + W_hf*h + W_cf.c)
+//   g = tanh(W_xc*x + W_hi*h)                  (:125 reuses W_hi; W_hc is never read)
+//   c' = f.c + i.g       o = sigmoid(W_xo*x + W_ho*h + W_co.c)   (:130 the OLD c)      h' = tanh(c').o
+//
+// All four gates read h_{t-1} only, so a step has ONE group hand-off (h'), where the ConvGRU has two (r.h, h').  There are
+// three distinct recurrent filters (W_hi, W_hf, W_ho): member j of a group of 8 workgroups keeps their columns of state
+// channels [16j, 16j+16) in registers -- 3 x 16 columns x K = 1152, 108 VGPRs per lane, the ConvGRU's z / r / c budget --
+// split over its 4 waves as K quarters, plus its slice of the three peephole planes [7,7,128] (24 VGPRs: a lane's 8 rows
+// x 3 planes).  c of a tile lives in fp32 in the registers of the wave that finalises it for the whole sequence; h is
+// needed only as the bf16 operand image (LDS), which is what the exchange delivers.
+// LDS: one 9x9 operand image pair (50 592 B) + 4 waves x 7 fragments x 3 gates partial tiles (84 KiB) + staging = 138 672 B.
+//
+// The h' exchange image is double-buffered by step parity: with one hand-off per step nothing else separates a fast
+// member's stores of step t+1 from a slow member's loads of step t.  (A member can be at most one step ahead: its
+// wait for step t+1 needs everybody's arrival, which follows everybody's loads of step t.)
+// No float atomics; a clip's bits depend on neither its group slot nor the batch size (NF only pads with zero rows).
+#pragma once
+#include "convgru_seq.hip.h"
+
+namespace rgp {
+
+struct LstmSeqParams {
+  const bf16_t* w_rec;       // packed [512][K]: row 4 c + q, q = 0 W_hi, 1 W_hf, 3 W_ho (2 stays zero); K = tap*128 + channel
+  const float* xpre;         // [B][T][49][512] hoisted x parts, column 4 c + q, q = i, f, g, o
+  const float* peep;         // [3][49][128] W_ci, W_cf, W_co
+  float* hall;               // [T+1][B][49][128] fp32 h (slot 0 = zero state, pre-zeroed)
+  float* call;               // [T+1][B][49][128] fp32 c
+  float* gates;              // optional (training): [4][T][B][49][128] i, f, g, o
+  bf16_t* hseq;              // [B][T+1][81][128] halo-padded h_t at slot t+1 (slot 0 zero): the head's input
+  bf16_t* xch;               // [2][ngroups][98][128] exchange images of h' (step parity)
+  unsigned* cnt;             // [ngroups][T] phase counters, zeroed before the launch
+  unsigned* err;             // host-visible error word of the plan
+  int B, T, NC, ngroups, K;
+  int skip_member;           // fault injection: this member of group 0 leaves at once; -1 = none
+};
+
+constexpr int LSQ_RED_OFF = SEQ_IMG;                   // 4 waves x 7 fragments x 3 gates partial tiles of 1 KiB
+constexpr int LSQ_STAGE_OFF = LSQ_RED_OFF + 84 * 1024;
+constexpr int LSQ_FLAG_OFF = LSQ_STAGE_OFF + 4 * 512;
+constexpr int LSQ_SMEM = LSQ_FLAG_OFF + 16;
+static_assert(LSQ_SMEM <= 160 * 1024, "LDS budget");
+
+template <int NF>
+static __global__ __launch_bounds__(SEQ_NT) void convlstm_seq_kernel(const LstmSeqParams p) {
+  extern __shared__ __attribute__((aligned(16))) char lq_smem[];
+  char* img_h = lq_smem;
+  char* red = lq_smem + LSQ_RED_OFF;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int kq = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave = K quarter
+  char* stage = lq_smem + LSQ_STAGE_OFF + kq * 512;
+
+  int group, j;
+  {
+    const int b = blockIdx.x;
+    if ((p.ngroups & 7) == 0) { const int slot = b >> 3; group = (slot >> 3) * 8 + (b & 7); j = slot & 7; }
+    else { group = b >> 3; j = b & 7; }
+  }
+  if (group == 0 && j == p.skip_member) return;           // fault injection: a member that never arrives
+  const int clip0 = group * p.NC;
+  const int nclip = min(p.NC, p.B - clip0);
+  const int rows = nclip * 49;
+  const int S = 128, T_ = p.T;
+  const long long st = (long long)p.B * 49 * S;
+
+  for (int i = tid; i < SEQ_IMG / 16; i += SEQ_NT) ((u32x4*)lq_smem)[i] = (u32x4){0u, 0u, 0u, 0u};
+
+  // ---- resident filter fragments: k-steps [9 kq, 9 kq + 9) of the W_hi, W_hf, W_ho columns of channels 16 j .. 16 j + 15
+  const int frow = lane & 15, fk = lane >> 4;
+  const int ch = 16 * j + frow;                          // this lane's state channel
+  f32x4 bi[9], bf[9], bo[9];
+  {
+    const bf16_t* wi = p.w_rec + (long long)(4 * ch + 0) * p.K;
+    const bf16_t* wf = p.w_rec + (long long)(4 * ch + 1) * p.K;
+    const bf16_t* wo = p.w_rec + (long long)(4 * ch + 3) * p.K;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      const int k = (kq * 9 + i) * 32 + fk * 8;
+      bi[i] = *(const f32x4*)(wi + k);
+      bf[i] = *(const f32x4*)(wf + k);
+      bo[i] = *(const f32x4*)(wo + k);
+    }
+  }
+  int abase[NF];
+#pragma unroll
+  for (int f = 0; f < NF; ++f) {
+    const int m = f * 16 + frow;
+    int pix = 2 * 81;
+    if (m < rows) { const int c = m / 49, q = m - c * 49; pix = c * 81 + (q / 7) * 9 + (q % 7); }
+    abase[f] = pix * SEQ_PIXB + fk * 16;
+  }
+  // this wave finalises fragments kq and kq + 4 (accumulator layout: row 4 (lane >> 4) + r, column lane & 15)
+  // per owned row, resolved once: xo = element of (clip, step 0, position, channel) in xpre, so = in a state snapshot,
+  // po = in slot 0 of the clip's padded h images; -1 = a padding row.  (Per-lane integers: the row -> (clip, position)
+  // arithmetic is not redone per step, and the loop keeps no scalar state per row.)
+  int xo[2][4], so_[2][4], po[2][4];
+  float wci[2][4], wcf[2][4], wco[2][4];
+#pragma unroll
+  for (int o = 0; o < 2; ++o)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = (kq + 4 * o) * 16 + fk * 4 + r;
+      const int c = row / 49, r49 = row - c * 49;
+      const bool ok = row < rows;
+      xo[o][r] = ok ? (((clip0 + c) * T_) * 49 + r49) * (4 * S) + 4 * ch : -1;
+      so_[o][r] = (clip0 * 49 + row) * S + ch;
+      po[o][r] = (((clip0 + c) * (T_ + 1)) * 81 + (r49 / 7 + 1) * 9 + (r49 % 7 + 1)) * S + ch;
+      wci[o][r] = p.peep[(0 * 49 + r49) * S + ch];
+      wcf[o][r] = p.peep[(1 * 49 + r49) * S + ch];
+      wco[o][r] = p.peep[(2 * 49 + r49) * S + ch];
+    }
+  float c_prev[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  const unsigned xbytes = 2u * (unsigned)p.ngroups * 98u * 256u;
+  unsigned* cnt = p.cnt + (long long)group * T_;
+  int& s_timeout = *(int*)(lq_smem + LSQ_FLAG_OFF);
+  if (tid == 0) s_timeout = 0;
+  __syncthreads();
+
+  auto a_frags = [&](int i, f32x4 (&a)[NF]) {
+    const int ks = kq * 9 + i, tap = ks >> 2, cb = ks & 3;
+    const int toff = ((tap / 3) * 9 + tap % 3) * SEQ_PIXB + cb * 64;
+#pragma unroll
+    for (int f = 0; f < NF; ++f) a[f] = *(const f32x4*)(img_h + abase[f] + toff);
+  };
+  auto mma = [&](const f32x4 (&a)[NF], const f32x4& b, f32x4 (&acc)[NF]) {
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+      acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(s16x8, a[f]), __builtin_bit_cast(s16x8, b), acc[f], 0, 0, 0);
+  };
+  // publish an owned 16 x 16 tile (bf16) as 16-byte rows into exchange image `par`, write-through
+  auto publish_tile = [&](int par, int f, const float (&v)[4]) {
+    bf16_t* sg = (bf16_t*)stage;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sg[(fk * 4 + r) * 16 + frow] = f2bf(v[r]);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" ::: "memory");
+    if (lane < 32) {
+      const int row = f * 16 + (lane >> 1);
+      if (row < rows) {
+        const u32x4 q = *(const u32x4*)(stage + lane * 16);
+        seq_st_sc1(p.xch, xbytes, (unsigned)((((par * p.ngroups + group) * 98 + row) * 128 + 16 * j + (lane & 1) * 8) * 2), q);
+      }
+    }
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" ::: "memory");
+  };
+  auto arrive = [&](int ph) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its write-through stores
+    __syncthreads();
+    if (tid == 0) __hip_atomic_fetch_add(cnt + ph, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  auto wait_load = [&](int ph, int par) {
+    if (tid == 0) {
+      if (!s_timeout && !seq_wait_phase(cnt + ph)) s_timeout = 1;
+    }
+    __syncthreads();
+    for (int i = tid; i < rows * 16; i += SEQ_NT) {
+      const int row = i >> 4, c16 = i & 15;
+      const u32x4 q = seq_ld_sc1(p.xch, xbytes, (unsigned)((((par * p.ngroups + group) * 98 + row) * 128 + c16 * 8) * 2));
+      const int c = row / 49, r49 = row - c * 49;
+      const int pix = c * 81 + (r49 / 7 + 1) * 9 + (r49 % 7 + 1);
+      *(u32x4*)(img_h + pix * SEQ_PIXB + c16 * 16) = q;
+    }
+    __syncthreads();
+  };
+
+  for (int t = 0; t < T_; ++t) {
+    // hoisted input parts of this lane's rows: one 16-byte load per row (i, f, g, o of its channel), in flight during the MFMAs
+    f32x4 xv[2][4];
+    const float* xpre_t = p.xpre + (long long)t * (49 * 4 * S);
+#pragma unroll
+    for (int o = 0; o < 2; ++o)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        xv[o][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (xo[o][r] >= 0) xv[o][r] = *(const f32x4*)(xpre_t + xo[o][r]);
+      }
+    // ---- the three recurrent convolutions on h_{t-1}: partial sums of this wave's K quarter, reduced through LDS
+    if (t > 0) {
+      f32x4 ai[NF], af[NF], ao[NF];
+#pragma unroll
+      for (int f = 0; f < NF; ++f) { ai[f] = (f32x4){0.f, 0.f, 0.f, 0.f}; af[f] = ai[f]; ao[f] = ai[f]; }
+      f32x4 a0[NF], a1[NF];                              // two k-steps of A fragments in flight (software pipeline)
+      a_frags(0, a0);
+#pragma unroll
+      for (int i = 0; i < 9; i += 2) {
+        if (i + 1 < 9) a_frags(i + 1, a1);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(a0, bi[i], ai); mma(a0, bf[i], af); mma(a0, bo[i], ao);
+        if (i + 2 < 9) a_frags(i + 2, a0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (i + 1 < 9) { mma(a1, bi[i + 1], ai); mma(a1, bf[i + 1], af); mma(a1, bo[i + 1], ao); }
+      }
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        *(f32x4*)(red + (((kq * NF + f) * 3 + 0) << 10) + lane * 16) = ai[f];
+        *(f32x4*)(red + (((kq * NF + f) * 3 + 1) << 10) + lane * 16) = af[f];
+        *(f32x4*)(red + (((kq * NF + f) * 3 + 2) << 10) + lane * 16) = ao[f];
+      }
+    }
+    __syncthreads();
+    float ig[2][4], fg[2][4], gg[2][4], og[2][4], cn[2][4], hn[2][4];
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+      const int f = kq + 4 * o;
+      f32x4 si = (f32x4){0.f, 0.f, 0.f, 0.f}, sf = si, so = si;
+      if (f < NF && t > 0) {                              // (step 0: h_0 = 0, the sums are exact zeros)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          si += *(const f32x4*)(red + (((q * NF + f) * 3 + 0) << 10) + lane * 16);
+          sf += *(const f32x4*)(red + (((q * NF + f) * 3 + 1) << 10) + lane * 16);
+          so += *(const f32x4*)(red + (((q * NF + f) * 3 + 2) << 10) + lane * 16);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float cp = c_prev[o][r];
+        ig[o][r] = sigmoidf_(si[r] + xv[o][r][0] + wci[o][r] * cp);
+        fg[o][r] = sigmoidf_(sf[r] + xv[o][r][1] + wcf[o][r] * cp);
+        gg[o][r] = tanhf_(si[r] + xv[o][r][2]);
+        og[o][r] = sigmoidf_(so[r] + xv[o][r][3] + wco[o][r] * cp);
+        cn[o][r] = fg[o][r] * cp + ig[o][r] * gg[o][r];
+        hn[o][r] = tanhf_(cn[o][r]) * og[o][r];
+        c_prev[o][r] = cn[o][r];
+      }
+    }
+    if (t + 1 < T_) {
+#pragma unroll
+      for (int o = 0; o < 2; ++o)
+        if (kq + 4 * o < NF) publish_tile(t & 1, kq + 4 * o, hn[o]);
+      arrive(t);
+      wait_load(t, t & 1);
+    }
+    // the step's plain outputs go out BEHIND the hand-off (convgru_seq.hip.h: in front of it they sit in the queue that
+    // arrive() drains); they drain under the next step's MFMAs
+    {
+      float* hall_t = p.hall + (long long)(t + 1) * st;
+      float* call_t = p.call + (long long)(t + 1) * st;
+      float* gates_t = p.gates ? p.gates + (long long)t * st : nullptr;
+      bf16_t* hseq_t = p.hseq + (long long)(t + 1) * (81 * S);
+      const long long gs = (long long)T_ * st;
+#pragma unroll
+      for (int o = 0; o < 2; ++o)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (xo[o][r] >= 0) {
+            hall_t[so_[o][r]] = hn[o][r];
+            call_t[so_[o][r]] = cn[o][r];
+            if (gates_t) {
+              float* gp = gates_t + so_[o][r];
+              gp[0] = ig[o][r]; gp[gs] = fg[o][r]; gp[2 * gs] = gg[o][r]; gp[3 * gs] = og[o][r];
+            }
+            hseq_t[po[o][r]] = f2bf(hn[o][r]);
+          }
+    }
+  }
+  // a group that timed out must not look like a result: the head reads hseq, the tests and the backward hall / call
+  if (s_timeout) {
+    if (tid == 0 && p.err) { *(volatile unsigned*)p.err = 1u; __threadfence_system(); }
+#pragma unroll
+    for (int o = 0; o < 2; ++o)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (xo[o][r] >= 0) {
+          for (int t = 0; t < T_; ++t) {
+            p.hseq[(long long)(t + 1) * (81 * S) + po[o][r]] = (bf16_t)0x7FC0;     // bf16 NaN
+            p.hall[(long long)(t + 1) * st + so_[o][r]] = __builtin_nanf("");
+            p.call[(long long)(t + 1) * st + so_[o][r]] = __builtin_nanf("");
+          }
+        }
+  }
+}
+
+}  // namespace rgp

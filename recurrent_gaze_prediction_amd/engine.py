@@ -507,6 +507,176 @@ class C3dConvEngine(object):
         return out
 
 
+LSTM_PARAM_TO_FIELD = {   # TF variable name under RGP/ and RGP/RCNBottom/ (scope stripped) -> rgp_lstm_weights field.  TF
+    # uniquifies the repeated name= of gaze_lstm.py:64-87: the second 'ConvLSTM_Wxi' is W_hi, and so on (unpinned: no TF here)
+    'proj_c3d_W': 'proj_c3d_W', 'proj_c3d_b': 'proj_c3d_b',
+    'ConvLSTM_Wxi': 'W_xi', 'ConvLSTM_Wxi_1': 'W_hi', 'ConvLSTM_Wci': 'W_ci',
+    'ConvLSTM_Wxf': 'W_xf', 'ConvLSTM_Wxf_1': 'W_hf', 'ConvLSTM_Wcf': 'W_cf',
+    'ConvLSTM_Wxc': 'W_xc', 'ConvLSTM_Whc': 'W_hc',
+    'ConvLSTM_Wxo': 'W_xo', 'ConvLSTM_Wxo_1': 'W_ho', 'ConvLSTM_Wco': 'W_co',
+    'weight1': 'up_weight1', 'weight2': 'up_weight2', 'weight3': 'up_weight3', 'out_W': 'out_W', 'out_b': 'out_b',
+}
+# gaze_lstm.py:80: W_hc is a graph variable with no path to the loss.  tf.gradients gives None for it, and
+# clip_by_global_norm / apply_gradients (base.py:278-297) skip None: it is in checkpoints, never in the norm or the update.
+LSTM_UNTRAINED = ('ConvLSTM_Whc',)
+
+
+def lstm_flat_layout(shapes):
+    """[(name, offset, numel)] of the flat fp32 buffer the clip norm and the optimizer see: every variable of
+    LSTM_PARAM_TO_FIELD in order EXCEPT LSTM_UNTRAINED.  shapes: {name: shape}.  Host logic only."""
+    out, off = [], 0
+    for k in LSTM_PARAM_TO_FIELD:
+        if k in LSTM_UNTRAINED:
+            continue
+        n = int(np.prod(shapes[k]))
+        out.append((k, off, n))
+        off += n
+    return out
+
+
+class LstmEngine(object):
+    """gaze_lstm graph (models/gaze_lstm.py:178-353) at fixed (B, T, dtype): projection, ConvLSTM, up-sampling head.
+
+    per_step=True: the recurrence as one launch per timestep (RGP_LSTM_PER_STEP), the library's second implementation;
+    otherwise bf16 plans of at most 64 clips run all T steps in one persistent launch (csrc/convlstm_seq.hip.h).
+    flat_params / flat_grads hold the 17 trained variables; W_hc (LSTM_UNTRAINED) lives outside them."""
+
+    def __init__(self, batch, n_steps, dtype='bf16', save_for_backward=False, device='cuda:0', per_step=False, persistent=False):
+        """persistent=True asks for the persistent kernel by name (RGP_LSTM_PERSISTENT: refused for plans it cannot run);
+        with both False the library chooses."""
+        self.lib = _lib.load()
+        self.device = _require_gpu(device)
+        self.B, self.T, self.P, self.S = int(batch), int(n_steps), 512, 128
+        self.dtype = dtype
+        self.per_step, self.save_for_backward = bool(per_step), bool(save_for_backward)
+        self.torch_dtype = torch.bfloat16 if _lib.DTYPES[dtype] == _lib.RGP_BF16 else torch.float32
+        flags = (_lib.RGP_LSTM_SAVE_FOR_BACKWARD if save_for_backward else 0) | (_lib.RGP_LSTM_PER_STEP if per_step else 0) | \
+            (_lib.RGP_LSTM_PERSISTENT if persistent else 0)
+        self.flat_params = self.flat_grads = self.grads = self.weights = None
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_lstm_create(ctypes.byref(self._h), self.B, self.T, _lib.DTYPES[dtype], flags))
+            nbytes = self.lib.rgp_lstm_workspace_bytes(self._h)
+            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.rgp_lstm_bind_workspace(self._h, _ptr(self.workspace), nbytes, _stream_ptr(self.device)))
+
+    def __del__(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h:
+            self.lib.rgp_lstm_destroy(h)
+
+    def _flat_views(self, like):
+        shapes = {k: tuple(like[k].shape) for k in LSTM_PARAM_TO_FIELD}
+        layout = lstm_flat_layout(shapes)
+        flat = torch.zeros(sum(n for _, _, n in layout), dtype=torch.float32, device=self.device)
+        views = {k: flat[off:off + n].view(shapes[k]) for k, off, n in layout}
+        for k in LSTM_UNTRAINED:
+            views[k] = torch.zeros(shapes[k], dtype=torch.float32, device=self.device)
+        return flat, {k: views[k] for k in LSTM_PARAM_TO_FIELD}
+
+    def _struct(self, views):
+        st = _lib.LstmWeights()
+        for k, f in LSTM_PARAM_TO_FIELD.items():
+            setattr(st, f, views[k].data_ptr())
+        return st
+
+    def set_weights(self, params):
+        src = {k: _as_dev_f32(params[k], self.device) for k in LSTM_PARAM_TO_FIELD}
+        assert tuple(src['ConvLSTM_Wxi'].shape) == (3, 3, self.P, self.S) and tuple(src['ConvLSTM_Wci'].shape) == (7, 7, self.S)
+        if self.weights is None:
+            self.flat_params, self.weights = self._flat_views(src)
+        for k in LSTM_PARAM_TO_FIELD:
+            self.weights[k].copy_(src[k])
+        self.repack()
+
+    def repack(self):
+        st = self._struct(self.weights)     # the plan keeps raw pointers to the biases: views stay alive
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_lstm_set_weights(self._h, ctypes.byref(st), _stream_ptr(self.device)))
+
+    def backward(self, logits, probs, labels, loss_type='xentropy'):
+        """Gradients of the reference loss w.r.t. every variable, after a forward() on the same inputs.  Returns
+        {TF variable name: fp32 gradient}; W_hc's is zeros and is not part of self.flat_grads."""
+        assert self.save_for_backward, 'create the engine with save_for_backward=True'
+        assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
+        if self.grads is None:
+            self.flat_grads, self.grads = self._flat_views(self.weights)
+        st = self._struct(self.grads)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_lstm_backward(self._h, _ptr(logits), _ptr(probs), _ptr(labels), ctypes.byref(st),
+                                                  {'xentropy': 0, 'l2': 1}[loss_type], _stream_ptr(self.device)))
+        return self.grads
+
+    def grad_buckets(self):
+        return [(self.flat_grads, lambda stream: stream.wait_stream(torch.cuda.current_stream(self.device)))]
+
+    def backward_input(self, out=None):
+        d = out if out is not None else torch.empty(self.B * self.T * 49, 1024, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_lstm_backward_input(self._h, _ptr(d), _stream_ptr(self.device)))
+        return d
+
+    def adam_step(self, step, lr, max_grad_norm=10.0, method='adam'):
+        """clip_by_global_norm + the chosen optimizer on the flat buffers (the trained variables only), then repack."""
+        return clip_step_multi([self], step, lr, max_grad_norm, method)
+
+    def _outputs(self, want_probs, out_logits, out_probs):
+        logits = out_logits if out_logits is not None else torch.empty(self.B, self.T, 49, 49, device=self.device)
+        probs = None
+        if want_probs:
+            probs = out_probs if out_probs is not None else torch.empty_like(logits)
+        return logits, probs
+
+    def forward(self, c3d_input, want_probs=True, out_logits=None, out_probs=None):
+        """c3d_input [B,T,1024,7,7] fp32 device tensor -> (logits, probs) [B,T,49,49]."""
+        x = c3d_input
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        assert tuple(x.shape) == (self.B, self.T, 1024, 7, 7), tuple(x.shape)
+        logits, probs = self._outputs(want_probs, out_logits, out_probs)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_lstm_forward(self._h, _ptr(x), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
+        return logits, probs
+
+    def forward_rows(self, rows, want_probs=True, out_logits=None, out_probs=None):
+        assert rows.is_cuda and rows.dtype == self.torch_dtype and rows.is_contiguous()
+        assert rows.numel() == self.B * self.T * 49 * 1024
+        logits, probs = self._outputs(want_probs, out_logits, out_probs)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_lstm_forward_rows(self._h, _ptr(rows), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
+        return logits, probs
+
+    def status(self):
+        """Wait for the current stream; raises RgpError (RGP_ETIMEOUT) if a persistent launch lost a group member."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_lstm_status(self._h, _stream_ptr(self.device)))
+
+    @property
+    def persistent_workgroups(self):
+        with torch.cuda.device(self.device):
+            return int(self.lib.rgp_lstm_persistent_workgroups(self._h))
+
+    @property
+    def persistent(self):
+        return self.persistent_workgroups > 0
+
+    def inject_fault(self, kind='seq'):
+        assert kind == 'seq'
+        _lib.check(self.lib.rgp_lstm_inject_fault(self._h, _lib.RGP_FAULT_SEQ_LOST_MEMBER))
+
+    def read_buffer_elems(self, name):
+        return int(self.lib.rgp_lstm_buffer_elems(self._h, name.encode()))
+
+    def read_buffer(self, name):
+        """'h', 'c' (training plans also 'i', 'f', 'g', 'o') [B,T,7,7,128]; 'emb' [B*T*49, 512]; fp32."""
+        n = self.read_buffer_elems(name)
+        if n == 0:
+            raise _lib.RgpError('unknown intermediate %r' % name)
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_lstm_read_buffer(self._h, name.encode(), _ptr(out), _stream_ptr(self.device)))
+        return out
+
+
 def softmax_xent(logits, labels=None, want_probs=True):
     """Per-frame softmax / cross entropy (model_util.py:61-72; gaze_rnn.py:390-407).
     logits [..., H, W] fp32 device tensor -> (probs, frame_loss, loss)."""

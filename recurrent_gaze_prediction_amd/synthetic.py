@@ -81,6 +81,29 @@ def c3d_conv_params(seed, dim_proj=512):
     }
 
 
+def lstm_params(seed, lstm_std=0.02, peephole_std=0.3):
+    """Weights of GazePredictionLSTM keyed by the TF variable names (scopes stripped; TF uniquifies the repeated name= of
+    gaze_lstm.py:64-87, so 'ConvLSTM_Wxi_1' is W_hi, '..Wxf_1' W_hf, '..Wxo_1' W_ho).  The reference draws all eleven cell
+    variables with stddev 1e-4, which leaves every gate at 0.5 and tests nothing: parity runs use lstm_std 0.02 for the
+    filters and peephole_std 0.3 for the [7,7,128] peephole planes (gate pre-activations of std ~1.4 on c3d_features)."""
+    rs = np.random.RandomState(seed)
+    u = lambda *s: rs.uniform(-0.1, 0.1, size=s).astype(np.float32)
+    P, S = 512, 128
+    wx = lambda: _trunc_normal(rs, (3, 3, P, S), lstm_std)
+    wh = lambda: _trunc_normal(rs, (3, 3, S, S), lstm_std)
+    wc = lambda: _trunc_normal(rs, (7, 7, S), peephole_std)
+    p = {'proj_c3d_W': u(1024, P), 'proj_c3d_b': u(P)}
+    p['ConvLSTM_Wxi'], p['ConvLSTM_Wxi_1'], p['ConvLSTM_Wci'] = wx(), wh(), wc()      # gaze_lstm.py:64-69
+    p['ConvLSTM_Wxf'], p['ConvLSTM_Wxf_1'], p['ConvLSTM_Wcf'] = wx(), wh(), wc()      # :71-76
+    p['ConvLSTM_Wxc'], p['ConvLSTM_Whc'] = wx(), wh()                                 # :78-81 (W_hc: never read)
+    p['ConvLSTM_Wxo'], p['ConvLSTM_Wxo_1'], p['ConvLSTM_Wco'] = wx(), wh(), wc()      # :83-88
+    p['weight1'] = _xavier_conv(rs, (5, 5, 64, S))
+    p['weight2'] = _xavier_conv(rs, (5, 5, 32, 64))
+    p['weight3'] = _xavier_conv(rs, (7, 7, 12, 32))
+    p['out_W'], p['out_b'] = u(12, 1), u(1)
+    return p
+
+
 def fcgru_params(seed, gh=49, gw=49, dim_proj=32):
     """Weights of GazePredictionGRU (gaze_rnn.py:294-320; TF GRUCell: gate bias 1)."""
     rs = np.random.RandomState(seed)
