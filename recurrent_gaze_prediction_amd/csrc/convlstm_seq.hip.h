@@ -1,6 +1,6 @@
 // Persistent ConvLSTM sequence kernel (gfx950, bf16 operands): ALL T steps of LSTM_RCN_Cell.__call__
-// (/root/reference/models/gaze_lstm.py:103-133, unrolled at :270-286) in ONE launch.  The scheme is convgru_seq.hip.h's
-// (read that header first: decomposition, exchange protocol, time-out), with the cell's own shape:
+// (/root/reference/models/gaze_lstm.py:103-133, unrolled at :270-286) in ONE launch, on the group scheme of
+// seq_group.hip.h (decomposition, exchange protocol, time-out), with the cell's own shape:
 //
 //   i = sigmoid(W_xi*x + W_hi*h + W_ci.c)     f = sigmoid(W_xf*x + W_hf*h + W_cf.c)
 //   g = tanh(W_xc*x + W_hi*h)                  (:125 reuses W_hi; W_hc is never read)
@@ -19,7 +19,7 @@
 // wait for step t+1 needs everybody's arrival, which follows everybody's loads of step t.)
 // No float atomics; a clip's bits depend on neither its group slot nor the batch size (NF only pads with zero rows).
 #pragma once
-#include "convgru_seq.hip.h"
+#include "seq_group.hip.h"
 
 namespace rgp {
 
@@ -32,10 +32,8 @@ struct LstmSeqParams {
   float* gates;              // optional (training): [4][T][B][49][128] i, f, g, o
   bf16_t* hseq;              // [B][T+1][81][128] halo-padded h_t at slot t+1 (slot 0 zero): the head's input
   bf16_t* xch;               // [2][ngroups][98][128] exchange images of h' (step parity)
-  unsigned* cnt;             // [ngroups][T] phase counters, zeroed before the launch
-  unsigned* err;             // host-visible error word of the plan
-  int B, T, NC, ngroups, K;
-  int skip_member;           // fault injection: this member of group 0 leaves at once; -1 = none
+  SeqGroupArgs g;            // T phase counters per group
+  int T, K;
 };
 
 constexpr int LSQ_RED_OFF = SEQ_IMG;                   // 4 waves x 7 fragments x 3 gates partial tiles of 1 KiB
@@ -49,28 +47,14 @@ static __global__ __launch_bounds__(SEQ_NT) void convlstm_seq_kernel(const LstmS
   extern __shared__ __attribute__((aligned(16))) char lq_smem[];
   char* img_h = lq_smem;
   char* red = lq_smem + LSQ_RED_OFF;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int kq = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave = K quarter
-  char* stage = lq_smem + LSQ_STAGE_OFF + kq * 512;
-
-  int group, j;
-  {
-    const int b = blockIdx.x;
-    if ((p.ngroups & 7) == 0) { const int slot = b >> 3; group = (slot >> 3) * 8 + (b & 7); j = slot & 7; }
-    else { group = b >> 3; j = b & 7; }
-  }
-  if (group == 0 && j == p.skip_member) return;           // fault injection: a member that never arrives
-  const int clip0 = group * p.NC;
-  const int nclip = min(p.NC, p.B - clip0);
-  const int rows = nclip * 49;
+  SeqGroup<NF> g;
+  if (!g.init(lq_smem, SEQ_IMG, LSQ_STAGE_OFF, LSQ_FLAG_OFF, p.g, p.T)) return;
+  const int kq = g.kq, ch = g.ch, clip0 = g.clip0;
   const int S = 128, T_ = p.T;
-  const long long st = (long long)p.B * 49 * S;
-
-  for (int i = tid; i < SEQ_IMG / 16; i += SEQ_NT) ((u32x4*)lq_smem)[i] = (u32x4){0u, 0u, 0u, 0u};
+  const long long st = (long long)p.g.B * 49 * S;
+  const unsigned xbytes = 2u * (unsigned)p.g.ngroups * 98u * 256u;
 
   // ---- resident filter fragments: k-steps [9 kq, 9 kq + 9) of the W_hi, W_hf, W_ho columns of channels 16 j .. 16 j + 15
-  const int frow = lane & 15, fk = lane >> 4;
-  const int ch = 16 * j + frow;                          // this lane's state channel
   f32x4 bi[9], bf[9], bo[9];
   {
     const bf16_t* wi = p.w_rec + (long long)(4 * ch + 0) * p.K;
@@ -78,23 +62,14 @@ static __global__ __launch_bounds__(SEQ_NT) void convlstm_seq_kernel(const LstmS
     const bf16_t* wo = p.w_rec + (long long)(4 * ch + 3) * p.K;
 #pragma unroll
     for (int i = 0; i < 9; ++i) {
-      const int k = (kq * 9 + i) * 32 + fk * 8;
+      const int k = (kq * 9 + i) * 32 + g.fk * 8;
       bi[i] = *(const f32x4*)(wi + k);
       bf[i] = *(const f32x4*)(wf + k);
       bo[i] = *(const f32x4*)(wo + k);
     }
   }
-  int abase[NF];
-#pragma unroll
-  for (int f = 0; f < NF; ++f) {
-    const int m = f * 16 + frow;
-    int pix = 2 * 81;
-    if (m < rows) { const int c = m / 49, q = m - c * 49; pix = c * 81 + (q / 7) * 9 + (q % 7); }
-    abase[f] = pix * SEQ_PIXB + fk * 16;
-  }
-  // this wave finalises fragments kq and kq + 4 (accumulator layout: row 4 (lane >> 4) + r, column lane & 15)
   // per owned row, resolved once: xo = element of (clip, step 0, position, channel) in xpre, so = in a state snapshot,
-  // po = in slot 0 of the clip's padded h images; -1 = a padding row.  (Per-lane integers: the row -> (clip, position)
+  // po = in slot 0 of the clip's padded h images; xo = -1: a padding row.  (Per-lane integers: the row -> (clip, position)
   // arithmetic is not redone per step, and the loop keeps no scalar state per row.)
   int xo[2][4], so_[2][4], po[2][4];
   float wci[2][4], wcf[2][4], wco[2][4];
@@ -102,72 +77,18 @@ static __global__ __launch_bounds__(SEQ_NT) void convlstm_seq_kernel(const LstmS
   for (int o = 0; o < 2; ++o)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int row = (kq + 4 * o) * 16 + fk * 4 + r;
+      const int row = g.own_row(o, r);
       const int c = row / 49, r49 = row - c * 49;
-      const bool ok = row < rows;
+      const bool ok = g.own_valid(o, r);
       xo[o][r] = ok ? (((clip0 + c) * T_) * 49 + r49) * (4 * S) + 4 * ch : -1;
       so_[o][r] = (clip0 * 49 + row) * S + ch;
-      po[o][r] = (((clip0 + c) * (T_ + 1)) * 81 + (r49 / 7 + 1) * 9 + (r49 % 7 + 1)) * S + ch;
+      po[o][r] = (((clip0 + c) * (T_ + 1)) * 81 + seq_pad_pix(r49)) * S + ch;
       wci[o][r] = p.peep[(0 * 49 + r49) * S + ch];
       wcf[o][r] = p.peep[(1 * 49 + r49) * S + ch];
       wco[o][r] = p.peep[(2 * 49 + r49) * S + ch];
     }
   float c_prev[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-  const unsigned xbytes = 2u * (unsigned)p.ngroups * 98u * 256u;
-  unsigned* cnt = p.cnt + (long long)group * T_;
-  int& s_timeout = *(int*)(lq_smem + LSQ_FLAG_OFF);
-  if (tid == 0) s_timeout = 0;
-  __syncthreads();
-
-  auto a_frags = [&](int i, f32x4 (&a)[NF]) {
-    const int ks = kq * 9 + i, tap = ks >> 2, cb = ks & 3;
-    const int toff = ((tap / 3) * 9 + tap % 3) * SEQ_PIXB + cb * 64;
-#pragma unroll
-    for (int f = 0; f < NF; ++f) a[f] = *(const f32x4*)(img_h + abase[f] + toff);
-  };
-  auto mma = [&](const f32x4 (&a)[NF], const f32x4& b, f32x4 (&acc)[NF]) {
-#pragma unroll
-    for (int f = 0; f < NF; ++f)
-      acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(s16x8, a[f]), __builtin_bit_cast(s16x8, b), acc[f], 0, 0, 0);
-  };
-  // publish an owned 16 x 16 tile (bf16) as 16-byte rows into exchange image `par`, write-through
-  auto publish_tile = [&](int par, int f, const float (&v)[4]) {
-    bf16_t* sg = (bf16_t*)stage;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sg[(fk * 4 + r) * 16 + frow] = f2bf(v[r]);
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-    if (lane < 32) {
-      const int row = f * 16 + (lane >> 1);
-      if (row < rows) {
-        const u32x4 q = *(const u32x4*)(stage + lane * 16);
-        seq_st_sc1(p.xch, xbytes, (unsigned)((((par * p.ngroups + group) * 98 + row) * 128 + 16 * j + (lane & 1) * 8) * 2), q);
-      }
-    }
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-  };
-  auto arrive = [&](int ph) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its write-through stores
-    __syncthreads();
-    if (tid == 0) __hip_atomic_fetch_add(cnt + ph, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  auto wait_load = [&](int ph, int par) {
-    if (tid == 0) {
-      if (!s_timeout && !seq_wait_phase(cnt + ph)) s_timeout = 1;
-    }
-    __syncthreads();
-    for (int i = tid; i < rows * 16; i += SEQ_NT) {
-      const int row = i >> 4, c16 = i & 15;
-      const u32x4 q = seq_ld_sc1(p.xch, xbytes, (unsigned)((((par * p.ngroups + group) * 98 + row) * 128 + c16 * 8) * 2));
-      const int c = row / 49, r49 = row - c * 49;
-      const int pix = c * 81 + (r49 / 7 + 1) * 9 + (r49 % 7 + 1);
-      *(u32x4*)(img_h + pix * SEQ_PIXB + c16 * 16) = q;
-    }
-    __syncthreads();
-  };
+  __syncthreads();                                       // image zeroed, flag cleared (init)
 
   for (int t = 0; t < T_; ++t) {
     // hoisted input parts of this lane's rows: one 16-byte load per row (i, f, g, o of its channel), in flight during the MFMAs
@@ -186,22 +107,19 @@ static __global__ __launch_bounds__(SEQ_NT) void convlstm_seq_kernel(const LstmS
 #pragma unroll
       for (int f = 0; f < NF; ++f) { ai[f] = (f32x4){0.f, 0.f, 0.f, 0.f}; af[f] = ai[f]; ao[f] = ai[f]; }
       f32x4 a0[NF], a1[NF];                              // two k-steps of A fragments in flight (software pipeline)
-      a_frags(0, a0);
+      g.a_frags(img_h, 0, a0);
 #pragma unroll
       for (int i = 0; i < 9; i += 2) {
-        if (i + 1 < 9) a_frags(i + 1, a1);
+        if (i + 1 < 9) g.a_frags(img_h, i + 1, a1);
         __builtin_amdgcn_sched_barrier(0);
-        mma(a0, bi[i], ai); mma(a0, bf[i], af); mma(a0, bo[i], ao);
-        if (i + 2 < 9) a_frags(i + 2, a0);
+        g.mma(a0, bi[i], ai); g.mma(a0, bf[i], af); g.mma(a0, bo[i], ao);
+        if (i + 2 < 9) g.a_frags(img_h, i + 2, a0);
         __builtin_amdgcn_sched_barrier(0);
-        if (i + 1 < 9) { mma(a1, bi[i + 1], ai); mma(a1, bf[i + 1], af); mma(a1, bo[i + 1], ao); }
+        if (i + 1 < 9) { g.mma(a1, bi[i + 1], ai); g.mma(a1, bf[i + 1], af); g.mma(a1, bo[i + 1], ao); }
       }
-#pragma unroll
-      for (int f = 0; f < NF; ++f) {
-        *(f32x4*)(red + (((kq * NF + f) * 3 + 0) << 10) + lane * 16) = ai[f];
-        *(f32x4*)(red + (((kq * NF + f) * 3 + 1) << 10) + lane * 16) = af[f];
-        *(f32x4*)(red + (((kq * NF + f) * 3 + 2) << 10) + lane * 16) = ao[f];
-      }
+      g.template store_partials<3>(red, 0, ai);
+      g.template store_partials<3>(red, 1, af);
+      g.template store_partials<3>(red, 2, ao);
     }
     __syncthreads();
     float ig[2][4], fg[2][4], gg[2][4], og[2][4], cn[2][4], hn[2][4];
@@ -210,12 +128,9 @@ static __global__ __launch_bounds__(SEQ_NT) void convlstm_seq_kernel(const LstmS
       const int f = kq + 4 * o;
       f32x4 si = (f32x4){0.f, 0.f, 0.f, 0.f}, sf = si, so = si;
       if (f < NF && t > 0) {                              // (step 0: h_0 = 0, the sums are exact zeros)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          si += *(const f32x4*)(red + (((q * NF + f) * 3 + 0) << 10) + lane * 16);
-          sf += *(const f32x4*)(red + (((q * NF + f) * 3 + 1) << 10) + lane * 16);
-          so += *(const f32x4*)(red + (((q * NF + f) * 3 + 2) << 10) + lane * 16);
-        }
+        si = g.template reduce_tile<3>(red, 0, f);
+        sf = g.template reduce_tile<3>(red, 1, f);
+        so = g.template reduce_tile<3>(red, 2, f);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -230,11 +145,15 @@ static __global__ __launch_bounds__(SEQ_NT) void convlstm_seq_kernel(const LstmS
       }
     }
     if (t + 1 < T_) {
+      const int par = (t & 1) * p.g.ngroups + g.group;   // exchange image of this step's parity
 #pragma unroll
       for (int o = 0; o < 2; ++o)
-        if (kq + 4 * o < NF) publish_tile(t & 1, kq + 4 * o, hn[o]);
-      arrive(t);
-      wait_load(t, t & 1);
+        if (kq + 4 * o < NF) g.publish_tile(p.xch, xbytes, par, kq + 4 * o, hn[o]);
+      g.arrive(t);
+      g.wait(t);
+      __syncthreads();
+      g.load_image(p.xch, xbytes, par, img_h);
+      __syncthreads();
     }
     // the step's plain outputs go out BEHIND the hand-off (convgru_seq.hip.h: in front of it they sit in the queue that
     // arrive() drains); they drain under the next step's MFMAs
@@ -260,8 +179,7 @@ static __global__ __launch_bounds__(SEQ_NT) void convlstm_seq_kernel(const LstmS
     }
   }
   // a group that timed out must not look like a result: the head reads hseq, the tests and the backward hall / call
-  if (s_timeout) {
-    if (tid == 0 && p.err) { *(volatile unsigned*)p.err = 1u; __threadfence_system(); }
+  if (g.timed_out()) {
 #pragma unroll
     for (int o = 0; o < 2; ++o)
 #pragma unroll

@@ -173,7 +173,7 @@ int forward_impl(rgp_cascade* g, const float* frames, const float* c3d_input, fl
   hipStream_t sc = s, st2 = s;
   RGP_TRY(g->fork(s, 0, &sc));
   // (the per-step events exist only where the bottom recurrence is per-step launches: S = 256 always is)
-  const bool pipe = sc != s && dev_knob("RGP_CASCADE_PIPE", 1) && g->bottom->seq_groups <= 0 && g->pipe_ok(s, T_);
+  const bool pipe = sc != s && dev_knob("RGP_CASCADE_PIPE", 1) && g->bottom->sg.groups <= 0 && g->pipe_ok(s, T_);
   if (pipe) {
     st2 = g->side2;
     RGP_HIP(hipStreamWaitEvent(st2, g->ev[0], 0));            // behind everything queued on s, as sc

@@ -183,7 +183,7 @@ int backward_impl(rgp_cascade* g, const float* maps, const float* gt, const rgp_
 
   // ---- top cell BPTT -> input gradient -> stride-7 transposed convolution -> bottom cell BPTT.  Three chains one time step
   // apart (rgp_cascade_plan.h) when the plan has its streams: each chain is per-step launches on a fraction of the CUs.
-  const bool pipe = sw != s && dev_knob("RGP_CASCADE_PIPE", 1) && g->bottom->seq_groups <= 0 && g->pipe_ok(s, T_);
+  const bool pipe = sw != s && dev_knob("RGP_CASCADE_PIPE", 1) && g->bottom->sg.groups <= 0 && g->pipe_ok(s, T_);
   hipStream_t sa = s, sb = s;                                   // top cell BPTT / its input gradient down to the bottom states
   if (pipe) {
     sa = g->side2; sb = g->side3;

@@ -128,18 +128,10 @@ int xconv_impl(rgp_grcn* g, hipStream_t s) {
 
 }  // namespace
 
-// The persistent ConvGRU kernels need all their workgroups (8 per group, one per CU) resident together.
-bool seq_persistent_ok(const rgp_grcn* g) {
-  int n_cu = 0;
-  return g->seq_groups > 0 && device_cu_count(&n_cu) == RGP_OK && g->seq_groups * 8 <= n_cu;
-}
-
 // Whether the TOP gradient group may be released (its all-reduce started on another stream) BEFORE the persistent BPTT
 // launch: only when that launch leaves at least RGP_RCCL_CU_RESERVE CUs to the collective's workgroups.
 bool grads_top_early(const rgp_grcn* g) {
-  int n_cu = 0;
-  if (g->seq_groups <= 0 || device_cu_count(&n_cu) != RGP_OK) return true;      // per-step plans: nothing needs co-residency
-  return g->seq_groups * 8 <= n_cu - RGP_RCCL_CU_RESERVE;
+  return g->sg.resident(RGP_RCCL_CU_RESERVE, true);       // (per-step plans: nothing needs co-residency)
 }
 
 namespace {
@@ -168,29 +160,16 @@ int seq_persistent(rgp_grcn* g, hipStream_t s) {
   p.bn_inv_std = 1.0f / sqrtf(1.0f + 1e-3f);   // moving mean 0 / var 1, eps 1e-3
   p.xch_h = (bf16_t*)(g->ws + g->xch_h.off);
   p.xch_rh = (bf16_t*)(g->ws + g->xch_rh.off);
-  p.cnt = (unsigned*)(g->ws + g->seq_cnt.off);
-  p.B = B; p.T = T_; p.NC = g->seq_nc; p.ngroups = g->seq_groups; p.K = g->gzr.K;
-  p.err = g->err_host;
-  p.skip_member = (g->fault & 1) ? 7 : -1;
-  g->fault &= ~1;
+  p.g = g->sg.args(B, (unsigned*)(g->ws + g->seq_cnt.off), RGP_FAULT_SEQ_LOST_MEMBER);
+  p.T = T_; p.K = g->gzr.K;
   RGP_REQUIRE(g->gzr.K == 9 * S && g->gc.K == 9 * S && g->gzr.chunk_major == 0, "convgru_seq: unexpected filter packing");
-  PersistentLaunch guard(s);
-  RGP_TRY(guard.status());
-  if (g->seq_nc == 1) {
-    RGP_TRY(ensure_dyn_smem((const void*)convgru_seq_kernel<4>, SEQ_SMEM));
-    convgru_seq_kernel<4><<<g->seq_groups * 8, SEQ_NT, SEQ_SMEM, s>>>(p);
-  } else {
-    RGP_TRY(ensure_dyn_smem((const void*)convgru_seq_kernel<7>, SEQ_SMEM));
-    convgru_seq_kernel<7><<<g->seq_groups * 8, SEQ_NT, SEQ_SMEM, s>>>(p);
-  }
-  RGP_HIP(hipGetLastError());
-  return guard.commit();
+  return launch_seq_group(g->sg, convgru_seq_kernel<4>, convgru_seq_kernel<7>, p, SEQ_SMEM, s);
 }
 
 template <typename T>
 int seq_impl(rgp_grcn* g, hipStream_t s) {
   const int B = g->B, T_ = g->T, S = g->S;
-  if (sizeof(T) == 2 && seq_persistent_ok(g) && dev_knob("RGP_SEQ", 1)) return seq_persistent(g, s);
+  if (sizeof(T) == 2 && g->sg.resident() && dev_knob("RGP_SEQ", 1)) return seq_persistent(g, s);
   const size_t st = (size_t)B * 49 * S;  // fp32 elements per state snapshot
   RGP_HIP(hipMemsetAsync(g->ws + g->hp.off, 0, g->hp.bytes, s));      // h_0 = 0 (gaze_grcn.py:262)
   RGP_HIP(hipMemsetAsync(g->ws + g->hall.off, 0, st * 4, s));
@@ -319,12 +298,8 @@ int check_ready(rgp_grcn* g) {
 }  // namespace
 
 int grcn_check_error(rgp_grcn* g) {
-  if (g->err_host && *(volatile unsigned*)g->err_host) {
-    *(volatile unsigned*)g->err_host = 0u;
-    return set_err(RGP_ETIMEOUT, "rgp_grcn: a persistent ConvGRU launch of this plan lost a group member (another launch was "
-                   "resident on the device?): its outputs were NaN-poisoned");
-  }
-  return RGP_OK;
+  return g->sg.check_err("rgp_grcn: a persistent ConvGRU launch of this plan lost a group member (another launch was "
+                         "resident on the device?): its outputs were NaN-poisoned");
 }
 
 extern "C" {
@@ -465,11 +440,10 @@ int rgp_grcn_create(rgp_grcn_t** plan, int batch, int n_steps, int dim_proj, int
   // persistent sequence kernel (convgru_seq.hip.h): the reference cell (128 state channels on 7x7), bf16 operands,
   // up to 2 clips per group of 8 workgroups and at most 32 groups (= the 256 CUs)
   if (dtype == RGP_BF16 && S == 128 && batch <= 64 && !(flags & RGP_GRCN_PER_STEP)) {
-    g->seq_nc = (batch + 31) / 32;
-    g->seq_groups = (batch + g->seq_nc - 1) / g->seq_nc;
-    g->xch_h = take(a, (size_t)g->seq_groups * 98 * 128 * 2);
-    g->xch_rh = take(a, (size_t)g->seq_groups * 98 * 128 * 2);
-    g->seq_cnt = take(a, (size_t)g->seq_groups * 2 * n_steps * 4);
+    g->sg.size(batch);
+    g->xch_h = take(a, (size_t)g->sg.groups * 98 * 128 * 2);
+    g->xch_rh = take(a, (size_t)g->sg.groups * 98 * 128 * 2);
+    g->seq_cnt = take(a, (size_t)g->sg.groups * 2 * n_steps * 4);
   }
   if (g->save) {
     const int rc = grcn_bwd_plan(g, a);
@@ -482,7 +456,7 @@ int rgp_grcn_create(rgp_grcn_t** plan, int batch, int n_steps, int dim_proj, int
 
 int rgp_grcn_destroy(rgp_grcn_t* plan) {
   if (plan) grcn_bwd_destroy(plan);
-  if (plan && plan->err_host) (void)hipHostFree(plan->err_host);
+  if (plan) plan->sg.free_err();
   delete plan;
   return RGP_OK;
 }
@@ -495,8 +469,8 @@ int rgp_grcn_status(rgp_grcn_t* g, rgp_stream_t stream) {
 
 int rgp_grcn_inject_fault(rgp_grcn_t* g, int kind) {
   RGP_REQUIRE(g && (kind == RGP_FAULT_SEQ_LOST_MEMBER || kind == RGP_FAULT_BPTT_LOST_MEMBER), "rgp_grcn_inject_fault: bad arguments");
-  if (!seq_persistent_ok(g)) return set_err(RGP_ESTATE, "rgp_grcn_inject_fault: the plan does not use the persistent ConvGRU kernels");
-  g->fault |= kind;
+  if (!g->sg.resident()) return set_err(RGP_ESTATE, "rgp_grcn_inject_fault: the plan does not use the persistent ConvGRU kernels");
+  g->sg.fault |= kind;
   return RGP_OK;
 }
 
@@ -507,14 +481,7 @@ int rgp_grcn_bind_workspace(rgp_grcn_t* g, void* workspace, size_t bytes, rgp_st
   if (bytes < g->ws_bytes) return set_err(RGP_EWORKSPACE, "workspace %zu < required %zu bytes", bytes, g->ws_bytes);
   RGP_REQUIRE(((size_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  if (g->seq_groups > 0 && !g->err_host) {
-    // error word of the persistent kernels: pinned host memory the device writes directly, so the host can test it at
-    // the start of any later call without a synchronisation (host memory, not device memory: header conventions)
-    void* e = nullptr;
-    RGP_HIP(hipHostMalloc(&e, 64, hipHostMallocMapped));
-    g->err_host = (unsigned*)e;
-    *(volatile unsigned*)g->err_host = 0u;
-  }
+  RGP_TRY(g->sg.alloc_err());
   g->ws = (char*)workspace;
   g->weights_set = false;
   // zero everything once: halos of E / Hp / RHp / Hbn / D1 / D2 stay zero because

@@ -134,7 +134,7 @@ int backward_impl(rgp_grcn* g, const float* probs, const float* logits, const fl
   const bool mark = !(hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone);
   // the folded head's chain rule on the plan's side stream.  While `s` is being captured the same fork / join is recorded into
   // the graph (two parallel branches) -- provided the side stream exists already: streams are not created during a capture
-  const bool persistent = sizeof(T) == 2 && seq_persistent_ok(g) && dev_knob("RGP_SEQ", 1);
+  const bool persistent = sizeof(T) == 2 && g->sg.resident() && dev_knob("RGP_SEQ", 1);
   const bool stepwise = ext_dy && g->bwd_step_ev && !persistent && mark;
   RGP_TRY(make_side_stream(b, mark));
   const bool side_ok = b->side != nullptr && dev_knob("RGP_BWD_FORK", 1);
@@ -328,23 +328,10 @@ int backward_impl(rgp_grcn* g, const float* probs, const float* logits, const fl
     q.dh_head = Fp(b->dh_head); q.hall = Fp(g->hall); q.uall = Fp(g->uall); q.rall = Fp(g->rall); q.call = Fp(g->call);
     q.dxpre = Fp(b->dxpre);
     q.xch_c = (bf16_t*)(ws + b->xch_c.off); q.xch_z = (bf16_t*)(ws + b->xch_z.off); q.xch_r = (bf16_t*)(ws + b->xch_r.off);
-    q.cnt = (unsigned*)(ws + b->bptt_cnt.off);
-    q.B = B; q.T = T_; q.NC = g->seq_nc; q.ngroups = g->seq_groups;
-    q.err = g->err_host;
-    q.skip_member = (g->fault & 2) ? 7 : -1;
-    g->fault &= ~2;
+    q.g = g->sg.args(B, (unsigned*)(ws + b->bptt_cnt.off), RGP_FAULT_BPTT_LOST_MEMBER);
+    q.T = T_;
     RGP_REQUIRE(b->b_c.K == 9 * S && b->b_zr.K == 18 * S, "convgru_bptt: unexpected filter packing");
-    PersistentLaunch guard(s);
-    RGP_TRY(guard.status());
-    if (g->seq_nc == 1) {
-      RGP_TRY(ensure_dyn_smem((const void*)convgru_bptt_kernel<4>, SEQ_SMEM));
-      convgru_bptt_kernel<4><<<g->seq_groups * 8, SEQ_NT, SEQ_SMEM, s>>>(q);
-    } else {
-      RGP_TRY(ensure_dyn_smem((const void*)convgru_bptt_kernel<7>, SEQ_SMEM));
-      convgru_bptt_kernel<7><<<g->seq_groups * 8, SEQ_NT, SEQ_SMEM, s>>>(q);
-    }
-    RGP_HIP(hipGetLastError());
-    RGP_TRY(guard.commit());
+    RGP_TRY(launch_seq_group(g->sg, convgru_bptt_kernel<4>, convgru_bptt_kernel<7>, q, BPTT_SMEM, s));
   }
   if (fork) RGP_HIP(hipStreamWaitEvent(s, b->ev_join, 0));              // the chain has ended (it had the whole BPTT launch to do so)
   if (mark && !top_early && !stepwise) RGP_HIP(hipEventRecord(b->grad_ev[0], s));     // full-chip launch: the TOP group leaves behind it
@@ -592,11 +579,11 @@ int grcn_bwd_plan(rgp_grcn* g, Arena& a) {
   b->dxpre = take(a, (size_t)F * 49 * 3 * S * 4);
   b->dxpre_pad = take(a, (size_t)F * 81 * 3 * S * es);
   b->dE = take(a, (size_t)(b->M + 1) * P * es);        // + a leading zero row
-  if (g->seq_groups > 0) {
-    b->xch_c = take(a, (size_t)g->seq_groups * 98 * 128 * 2);
-    b->xch_z = take(a, (size_t)g->seq_groups * 98 * 128 * 2);
-    b->xch_r = take(a, (size_t)g->seq_groups * 98 * 128 * 2);
-    b->bptt_cnt = take(a, (size_t)g->seq_groups * 2 * T_ * 4);
+  if (g->sg.groups > 0) {
+    b->xch_c = take(a, (size_t)g->sg.groups * 98 * 128 * 2);
+    b->xch_z = take(a, (size_t)g->sg.groups * 98 * 128 * 2);
+    b->xch_r = take(a, (size_t)g->sg.groups * 98 * 128 * 2);
+    b->bptt_cnt = take(a, (size_t)g->sg.groups * 2 * T_ * 4);
   }
   if (!g->fold_head) {
     b->dzb = take(a, ((size_t)F * 49 * 64 + 256) * es);
@@ -689,7 +676,7 @@ int rgp_grcn_backward_from_states(rgp_grcn_t* g, const float* d_states, const rg
 }
 
 int rgp_grcn_persistent_workgroups(const rgp_grcn_t* g) {
-  return (g && g->dtype == RGP_BF16 && seq_persistent_ok(g) && dev_knob("RGP_SEQ", 1)) ? g->seq_groups * 8 : 0;
+  return (g && g->dtype == RGP_BF16 && g->sg.resident() && dev_knob("RGP_SEQ", 1)) ? g->sg.groups * 8 : 0;
 }
 
 int rgp_grcn_grads_top_early(const rgp_grcn_t* g) {

@@ -58,9 +58,7 @@ struct rgp_grcn {
   Buf hf_part;                     // the five partial sums of K (summed in a fixed order)
   Buf hf_h, hf_k, hf_z;            // H [11,11,64], K [361][S] fp32; Z [F*49][384] fp32 (the GEMM's output, gathered by col2im)
   Buf xch_h, xch_rh, seq_cnt;   // persistent ConvGRU sequence kernel: exchange images [groups][98][128] + phase counters
-  int seq_nc = 0, seq_groups = 0;   // clips per group / groups (0 = the per-step path)
-  unsigned* err_host = nullptr;     // pinned, device-visible error word: a persistent launch that timed out sets it
-  int fault = 0;                    // rgp_grcn_inject_fault: bit 0 next sequence launch, bit 1 next BPTT launch lose a member
+  rgp::SeqGroupPlan sg;             // ... its groups, error word and fault bits (rgp_grcn_inject_fault: bit 0 the next sequence launch, bit 1 the next BPTT launch)
   size_t ws_bytes = 0;
   char* ws = nullptr;
   bool weights_set = false;
@@ -77,9 +75,7 @@ inline Buf take(rgp::Arena& a, size_t bytes) {
   return b;
 }
 
-// rgp_grcn.hip: the persistent ConvGRU kernels apply to this plan on the current device
-bool seq_persistent_ok(const rgp_grcn* g);
-// ... and its persistent BPTT launch leaves RGP_RCCL_CU_RESERVE CUs free (the TOP gradient group may leave before it)
+// rgp_grcn.hip: the plan's persistent BPTT launch leaves RGP_RCCL_CU_RESERVE CUs free (the TOP gradient group may leave before it)
 bool grads_top_early(const rgp_grcn* g);
 // rgp_grcn_bwd.hip
 // returns RGP_ETIMEOUT (and clears the word) if a persistent launch of this plan reported a lost group member

@@ -15,6 +15,7 @@
 #include "kernels_misc.hip.h"
 #include "igemm_stagger.hip.h"
 #include "igemm_wide.hip.h"
+#include "seq_group.hip.h"
 
 namespace rgp {
 
@@ -53,7 +54,7 @@ constexpr int dev_knob(const char*, int dflt) { return dflt; }
 int ensure_dyn_smem(const void* kernel, int bytes);
 int device_cu_count(int* n_cu);
 
-// The persistent ConvGRU kernels (convgru_seq.hip.h, convgru_bptt.hip.h) need every workgroup of a launch resident at
+// The persistent recurrence kernels (seq_group.hip.h) need every workgroup of a launch resident at
 // once: two such launches must never share the device.  Within one process that is enforced here: a launch on stream s
 // is made inside the life of a PersistentLaunch object, which takes a process-wide lock, makes s wait for the previous
 // persistent launch of the process on the current device (whatever stream, plan or host THREAD issued it), and --
@@ -75,6 +76,55 @@ class PersistentLaunch {
   bool locked_;
   int rc_;
 };
+
+// Host side of the persistent recurrence kernels (seq_group.hip.h), one per plan: up to 2 clips per group of 8 workgroups
+// and at most 32 groups (= the 256 CUs of the chip), i.e. plans of up to 64 clips.
+struct SeqGroupPlan {
+  int nc = 0, groups = 0;           // clips per group / groups (0 = the per-step path)
+  unsigned* err_host = nullptr;     // pinned, device-visible error word: a persistent launch that timed out sets it
+  int fault = 0;                    // fault injection: the next launch that owns a set bit loses a member of group 0
+  void size(int batch) { nc = (batch + 31) / 32; groups = (batch + nc - 1) / nc; }
+  // All workgroups (8 per group, one per CU) fit on the current device together, `reserve` CUs left over.  A plan without
+  // groups, or an unknown CU count: `if_none`.
+  bool resident(int reserve = 0, bool if_none = false) const {
+    int n_cu = 0;
+    if (groups <= 0 || device_cu_count(&n_cu) != RGP_OK) return if_none;
+    return groups * 8 <= n_cu - reserve;
+  }
+  // The error word is pinned host memory the device writes directly, so the host can test it at the start of any later
+  // call without a synchronisation.
+  int alloc_err() {
+    if (groups <= 0 || err_host) return RGP_OK;
+    void* e = nullptr;
+    RGP_HIP(hipHostMalloc(&e, 64, hipHostMallocMapped));
+    err_host = (unsigned*)e;
+    *(volatile unsigned*)err_host = 0u;
+    return RGP_OK;
+  }
+  void free_err() { if (err_host) (void)hipHostFree(err_host); err_host = nullptr; }
+  int check_err(const char* msg) {                    // RGP_ETIMEOUT with `msg` (and clears the word) if a launch lost a member
+    if (!err_host || !*(volatile unsigned*)err_host) return RGP_OK;
+    *(volatile unsigned*)err_host = 0u;
+    return set_err(RGP_ETIMEOUT, "%s", msg);
+  }
+  SeqGroupArgs args(int batch, unsigned* cnt, int fault_bit) {    // of the next launch; consumes its fault bit
+    SeqGroupArgs a{cnt, err_host, batch, nc, groups, (fault & fault_bit) ? 7 : -1};
+    fault &= ~fault_bit;
+    return a;
+  }
+};
+
+// One persistent launch: the kernel for one clip per group (4 row fragments) or two (7), under the PersistentLaunch guard.
+template <typename P>
+int launch_seq_group(const SeqGroupPlan& sg, void (*k4)(P), void (*k7)(P), const P& p, int smem, hipStream_t s) {
+  void (*kern)(P) = sg.nc == 1 ? k4 : k7;
+  PersistentLaunch guard(s);
+  RGP_TRY(guard.status());
+  RGP_TRY(ensure_dyn_smem((const void*)kern, smem));
+  kern<<<sg.groups * 8, SEQ_NT, smem, s>>>(p);
+  RGP_HIP(hipGetLastError());
+  return guard.commit();
+}
 
 // Row tables of the filter-gradient kernel (wgrad.hip.h): byte offset of row m = (z*H + y)*W + x of a D x H x W grid
 // from its image in X (z*x_sz + y*x_sy + x*x_sx elements) and in dY (y_org + z*y_sz + y*y_sy + x*y_sx), entries

@@ -29,9 +29,7 @@ struct rgp_lstm {
   ConvDesc proj, proj_rows, xconv, grec, hfold;
   Buf xt, E, xpre, hall, call, gates, hseq, peep, gfold, hf_h, hf_k, hf_z, hf_part;
   Buf xch, seq_cnt;
-  int seq_nc = 0, seq_groups = 0;          // clips per group / groups of the persistent kernel (0 = per-step launches)
-  unsigned* err_host = nullptr;
-  int fault = 0;
+  SeqGroupPlan sg;                         // groups of the persistent kernel (none = per-step launches), error word, fault bit
   size_t ws_bytes = 0;
   char* ws = nullptr;
   const float *proj_b = nullptr, *out_b = nullptr;
@@ -58,18 +56,9 @@ std::vector<int> pad_tab9(int C) {
   return t;
 }
 
-bool persistent_ok(const rgp_lstm* g) {
-  int n_cu = 0;
-  return g->seq_groups > 0 && device_cu_count(&n_cu) == RGP_OK && g->seq_groups * 8 <= n_cu;
-}
-
 int lstm_check_error(rgp_lstm* g) {
-  if (g->err_host && *(volatile unsigned*)g->err_host) {
-    *(volatile unsigned*)g->err_host = 0u;
-    return set_err(RGP_ETIMEOUT, "rgp_lstm: a persistent ConvLSTM launch of this plan lost a group member (another launch was "
-                   "resident on the device?): its outputs were NaN-poisoned");
-  }
-  return RGP_OK;
+  return g->sg.check_err("rgp_lstm: a persistent ConvLSTM launch of this plan lost a group member (another launch was "
+                         "resident on the device?): its outputs were NaN-poisoned");
 }
 
 int check_ready(rgp_lstm* g) {
@@ -147,23 +136,10 @@ int seq_persistent(rgp_lstm* g, hipStream_t s) {
   p.gates = g->save ? (float*)(ws + g->gates.off) : nullptr;
   p.hseq = (bf16_t*)(ws + g->hseq.off);
   p.xch = (bf16_t*)(ws + g->xch.off);
-  p.cnt = (unsigned*)(ws + g->seq_cnt.off);
-  p.err = g->err_host;
-  p.B = g->B; p.T = g->T; p.NC = g->seq_nc; p.ngroups = g->seq_groups; p.K = g->grec.K;
-  p.skip_member = (g->fault & 1) ? 7 : -1;
-  g->fault &= ~1;
+  p.g = g->sg.args(g->B, (unsigned*)(ws + g->seq_cnt.off), RGP_FAULT_SEQ_LOST_MEMBER);
+  p.T = g->T; p.K = g->grec.K;
   RGP_REQUIRE(g->grec.K == 9 * g->S && g->grec.chunk_major == 0, "convlstm_seq: unexpected filter packing");
-  PersistentLaunch guard(s);
-  RGP_TRY(guard.status());
-  if (g->seq_nc == 1) {
-    RGP_TRY(ensure_dyn_smem((const void*)convlstm_seq_kernel<4>, LSQ_SMEM));
-    convlstm_seq_kernel<4><<<g->seq_groups * 8, SEQ_NT, LSQ_SMEM, s>>>(p);
-  } else {
-    RGP_TRY(ensure_dyn_smem((const void*)convlstm_seq_kernel<7>, LSQ_SMEM));
-    convlstm_seq_kernel<7><<<g->seq_groups * 8, SEQ_NT, LSQ_SMEM, s>>>(p);
-  }
-  RGP_HIP(hipGetLastError());
-  return guard.commit();
+  return launch_seq_group(g->sg, convlstm_seq_kernel<4>, convlstm_seq_kernel<7>, p, LSQ_SMEM, s);
 }
 
 template <typename T>
@@ -171,7 +147,7 @@ int seq_impl(rgp_lstm* g, hipStream_t s) {
   char* ws = g->ws;
   const int B = g->B, T_ = g->T, S = g->S;
   if constexpr (sizeof(T) == 2) {
-    if (persistent_ok(g)) return seq_persistent(g, s);
+    if (g->sg.resident()) return seq_persistent(g, s);
   }
   const size_t st = (size_t)B * 49 * S;
   float* hall = (float*)(ws + g->hall.off);
@@ -452,10 +428,9 @@ int rgp_lstm_create(rgp_lstm_t** plan, int batch, int n_steps, int dtype, int fl
   // persistent sequence kernel: bf16 operands, up to 2 clips per group of 8 workgroups, at most 32 groups
   const bool eligible = dtype == RGP_BF16 && batch <= 64;
   if (eligible && ((flags & RGP_LSTM_PERSISTENT) || (LSTM_DEFAULT_PERSISTENT && !(flags & RGP_LSTM_PER_STEP)))) {
-    g->seq_nc = (batch + 31) / 32;
-    g->seq_groups = (batch + g->seq_nc - 1) / g->seq_nc;
-    g->xch = take(a, (size_t)2 * g->seq_groups * 98 * 128 * 2);
-    g->seq_cnt = take(a, (size_t)g->seq_groups * T_ * 4);
+    g->sg.size(batch);
+    g->xch = take(a, (size_t)2 * g->sg.groups * 98 * 128 * 2);
+    g->seq_cnt = take(a, (size_t)g->sg.groups * T_ * 4);
   }
   if (g->save) {
     g->M = (long long)F * 49;
@@ -520,7 +495,7 @@ int rgp_lstm_create(rgp_lstm_t** plan, int batch, int n_steps, int dtype, int fl
 }
 
 int rgp_lstm_destroy(rgp_lstm_t* plan) {
-  if (plan && plan->err_host) (void)hipHostFree(plan->err_host);
+  if (plan) plan->sg.free_err();
   delete plan;
   return RGP_OK;
 }
@@ -532,12 +507,7 @@ int rgp_lstm_bind_workspace(rgp_lstm_t* g, void* workspace, size_t bytes, rgp_st
   if (bytes < g->ws_bytes) return set_err(RGP_EWORKSPACE, "workspace %zu < required %zu bytes", bytes, g->ws_bytes);
   RGP_REQUIRE(((size_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  if (g->seq_groups > 0 && !g->err_host) {                     // error word of the persistent kernel (rgp_grcn.hip: pinned host memory)
-    void* e = nullptr;
-    RGP_HIP(hipHostMalloc(&e, 64, hipHostMallocMapped));
-    g->err_host = (unsigned*)e;
-    *(volatile unsigned*)g->err_host = 0u;
-  }
+  RGP_TRY(g->sg.alloc_err());
   g->ws = (char*)workspace;
   g->weights_set = false;
   // zero everything once: the halos of E / h images / dpre, slot 0 of the states and the unused filter rows stay zero,
@@ -611,13 +581,13 @@ int rgp_lstm_status(rgp_lstm_t* g, rgp_stream_t stream) {
 
 int rgp_lstm_inject_fault(rgp_lstm_t* g, int kind) {
   RGP_REQUIRE(g && kind == RGP_FAULT_SEQ_LOST_MEMBER, "rgp_lstm_inject_fault: bad arguments");
-  if (g->dtype != RGP_BF16 || !persistent_ok(g)) return set_err(RGP_ESTATE, "rgp_lstm_inject_fault: the plan does not use the persistent ConvLSTM kernel");
-  g->fault |= kind;
+  if (g->dtype != RGP_BF16 || !g->sg.resident()) return set_err(RGP_ESTATE, "rgp_lstm_inject_fault: the plan does not use the persistent ConvLSTM kernel");
+  g->sg.fault |= kind;
   return RGP_OK;
 }
 
 int rgp_lstm_persistent_workgroups(const rgp_lstm_t* g) {
-  return (g && g->dtype == RGP_BF16 && persistent_ok(g)) ? g->seq_groups * 8 : 0;
+  return (g && g->dtype == RGP_BF16 && g->sg.resident()) ? g->sg.groups * 8 : 0;
 }
 
 size_t rgp_lstm_buffer_elems(const rgp_lstm_t* g, const char* name) {

@@ -111,6 +111,26 @@ def test_persistent_sequence_kernel_group_shapes(gpu, B, T):
     assert torch.equal(logits, logits2)
 
 
+def test_persistent_states_are_independent_of_the_batch(gpu):
+    """A clip's ConvGRU states depend on neither its group slot nor the batch size, bit for bit: B = 33 (two clips per
+    group, 7 row fragments, a ragged last group) against a B = 2 plan (one clip per group, 4 row fragments) that holds
+    the clip in slot 0.  States only: the projection and head GEMMs may pick other tiles at another M."""
+    from recurrent_gaze_prediction_amd.engine import GrcnEngine
+    B, T = 33, 3
+    p = syn.grcn_params(41, T, gru_std=0.05, random_bn=True)
+    xd = torch.tensor(syn.c3d_features(42, B, T), device=gpu)
+    eng = GrcnEngine(B, T, dtype='bf16', device=gpu)
+    eng.set_weights(p)
+    eng.forward(xd)
+    h = eng.read_buffer('rcn_outputs').clone().reshape(B, -1)
+    assert torch.isfinite(h).all() and float(h.abs().max()) > 0.1
+    two = GrcnEngine(2, T, dtype='bf16', device=gpu)
+    two.set_weights(p)
+    for k in (0, 1, 16, 32):                                   # both slots of a group, the middle, the ragged last group
+        two.forward(torch.stack([xd[k], xd[(k + 5) % B]]).contiguous())
+        assert torch.equal(two.read_buffer('rcn_outputs').reshape(2, -1)[0], h[k]), k
+
+
 @pytest.mark.parametrize('B,T', [(2, 6), (33, 3)])
 def test_per_step_recurrence_agrees_with_persistent_kernels(gpu, B, T):
     """RGP_GRCN_PER_STEP: the same bf16 plan with the recurrence (and its BPTT) as per-timestep launches -- the path
