@@ -360,11 +360,18 @@ typedef struct rgp_lstm_weights {
  *                                    bf16 plans of at most 64 clips, RGP_EINVAL otherwise.  On a device with fewer
  *                                    than 8 CUs per group the plan still runs per step
  *                                    (rgp_lstm_persistent_workgroups tells).
- *        0                           the library's choice for plans both paths can run: the persistent kernel,
- *                                    measured faster than per-step launches at both benchmark shapes. */
+ *        RGP_LSTM_BPTT_PERSISTENT    run the backward-through-time pass of rgp_lstm_backward as one persistent launch
+ *                                    (csrc/convlstm_bptt.hip.h) instead of two launches per timestep: only together with
+ *                                    RGP_LSTM_SAVE_FOR_BACKWARD, on bf16 plans of at most 64 clips, RGP_EINVAL otherwise.
+ *                                    Independent of the two flags of the forward; on a device with too few CUs the plan
+ *                                    still runs per step (rgp_lstm_bptt_persistent_workgroups tells).
+ *        0                           the library's choice for plans both paths can run: the persistent kernel for the
+ *                                    forward, measured faster than per-step launches at both benchmark shapes
+ *                                    (DESIGN.md); per-step launches for the BPTT. */
 #define RGP_LSTM_SAVE_FOR_BACKWARD 1
 #define RGP_LSTM_PER_STEP 2
 #define RGP_LSTM_PERSISTENT 4
+#define RGP_LSTM_BPTT_PERSISTENT 8
 int rgp_lstm_create(rgp_lstm_t** plan, int batch, int n_steps, int dtype, int flags);
 int rgp_lstm_destroy(rgp_lstm_t* plan);
 size_t rgp_lstm_workspace_bytes(const rgp_lstm_t* plan);
@@ -378,21 +385,28 @@ int rgp_lstm_forward(rgp_lstm_t* plan, const float* c3d_input, float* logits, fl
 /* c3d_rows: [B*T*49, 1024] in the plan's operand dtype, column d*512+c, 16-byte aligned (what rgp_c3d_forward writes) */
 int rgp_lstm_forward_rows(rgp_lstm_t* plan, const void* c3d_rows, float* logits, float* probs, rgp_stream_t stream);
 /* Training plans, after a forward: gradients of the loss of gaze_rnn.py:363-408 (loss_type 0 xentropy, 1 l2) w.r.t. the
- * 18 variables (grads: arrays shaped like the weights).  BPTT runs as per-timestep launches; grads->W_hc is zeroed. */
+ * 18 variables (grads: arrays shaped like the weights).  BPTT runs as per-timestep launches, or as one persistent launch
+ * on plans created with RGP_LSTM_BPTT_PERSISTENT; grads->W_hc is zeroed. */
 int rgp_lstm_backward(rgp_lstm_t* plan, const float* logits, const float* probs, const float* labels,
                       const rgp_lstm_weights* grads, int loss_type, rgp_stream_t stream);
 /* After rgp_lstm_backward: d loss / d input as conv5b rows [B*T*49, 1024] fp32 (column d*512+c) */
 int rgp_lstm_backward_input(rgp_lstm_t* plan, float* d_rows, rgp_stream_t stream);
 /* The persistent kernel fails as the ConvGRU kernels do (rgp_grcn_status): a group that misses a member gives up after
  * about a second, NaN-poisons its clips and raises the plan's error state -- the next call on the plan and
- * rgp_lstm_status (which first waits for `stream`) return RGP_ETIMEOUT once.  rgp_lstm_inject_fault
- * (RGP_FAULT_SEQ_LOST_MEMBER): test hook, the next persistent launch runs without one member of its first group. */
+ * rgp_lstm_status (which first waits for `stream`) return RGP_ETIMEOUT once.  The persistent BPTT poisons the
+ * pre-activation gradients of step 0 of its clips, and with them every gradient of the call.  rgp_lstm_inject_fault
+ * (RGP_FAULT_SEQ_LOST_MEMBER: the forward's kernel, RGP_FAULT_BPTT_LOST_MEMBER: the BPTT's): test hook, the next such
+ * launch runs without one member of its first group; RGP_ESTATE on a plan that does not run that kernel. */
 int rgp_lstm_status(rgp_lstm_t* plan, rgp_stream_t stream);
 int rgp_lstm_inject_fault(rgp_lstm_t* plan, int kind);
 /* Workgroups (= CUs) a persistent launch of this plan occupies on the current device; 0 = per-timestep launches */
 int rgp_lstm_persistent_workgroups(const rgp_lstm_t* plan);
+/* The same for the persistent BPTT launch of rgp_lstm_backward; 0 = the per-timestep loop */
+int rgp_lstm_bptt_persistent_workgroups(const rgp_lstm_t* plan);
 /* fp32 copies of "h", "c" (and, training plans, the gates "i", "f", "g", "o") as [B,T,7,7,128], and of "emb", the
- * projected features [B*T*49, 512], after a forward.  buffer_elems: the element count, 0 = no such buffer. */
+ * projected features [B*T*49, 512], after a forward; training plans, after a backward: "d_i", "d_f", "d_g", "d_o", the
+ * gradients of the gates' pre-activations [B,T,7,7,128] as the BPTT (either path) left them in the operand dtype.
+ * buffer_elems: the element count, 0 = no such buffer. */
 int rgp_lstm_read_buffer(rgp_lstm_t* plan, const char* name, float* dst, rgp_stream_t stream);
 size_t rgp_lstm_buffer_elems(const rgp_lstm_t* plan, const char* name);
 /* ------------------------------------------------------------------ frame-wise ShallowNet */

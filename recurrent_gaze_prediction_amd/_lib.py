@@ -20,7 +20,7 @@ RGP_ETIMEOUT = -5
 RGP_GRCN_SAVE_FOR_BACKWARD, RGP_GRCN_PER_STEP, RGP_GRCN_UNFOLDED_HEAD = 1, 2, 4
 RGP_C3D_SAVE_FOR_BACKWARD, RGP_C3D_KERNELS_IGEMM, RGP_C3D_KERNELS_TILE128, RGP_C3D_CONV2A_ROWWISE = 1, 2, 4, 8
 RGP_C3DCONV_SAVE_FOR_BACKWARD, RGP_C3DCONV_STAGED, RGP_C3DCONV_FUSED = 1, 2, 4
-RGP_LSTM_SAVE_FOR_BACKWARD, RGP_LSTM_PER_STEP, RGP_LSTM_PERSISTENT = 1, 2, 4
+RGP_LSTM_SAVE_FOR_BACKWARD, RGP_LSTM_PER_STEP, RGP_LSTM_PERSISTENT, RGP_LSTM_BPTT_PERSISTENT = 1, 2, 4, 8
 RGP_FAULT_SEQ_LOST_MEMBER, RGP_FAULT_BPTT_LOST_MEMBER = 1, 2
 RGP_GRCN_GRADS_TOP, RGP_GRCN_GRADS_GRU, RGP_GRCN_GRADS_PROJ = 0, 1, 2
 RGP_SQNORM_PARTIALS = 256          # include/rgp.h
@@ -143,6 +143,7 @@ SIGNATURES = {
     'rgp_lstm_status': (c_int, [c_void_p, c_void_p]),
     'rgp_lstm_inject_fault': (c_int, [c_void_p, c_int]),
     'rgp_lstm_persistent_workgroups': (c_int, [c_void_p]),
+    'rgp_lstm_bptt_persistent_workgroups': (c_int, [c_void_p]),
     'rgp_lstm_read_buffer': (c_int, [c_void_p, c_char_p, c_void_p, c_void_p]),
     'rgp_lstm_buffer_elems': (c_size_t, [c_void_p, c_char_p]),
     'rgp_shallownet_create_ex': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int]),

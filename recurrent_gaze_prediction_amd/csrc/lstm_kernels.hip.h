@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const float* __restr
 
 // Peephole gradients d W_c{i,f,o}[pos, ch] = sum over frames of d{i,f,o}_pre . c_{t-1}: one thread per element, a chain
 // over the steps of a clip inside a chain over the clips -- a fixed order, no atomics.  B * T dependent strided loads
-// per thread (1024 at 64 x 16) on 18 816 threads: its cost has not been measured on its own.
+// per thread (1024 at 64 x 16) on 18 816 threads: 313 us at 64 x 16, 76 us at 8 x 35 ("gaze_lstm").
 template <typename T>
 __global__ __launch_bounds__(256) void lstm_peephole_grad_kernel(const T* __restrict__ dpre, const float* __restrict__ call,
                                                                  float* __restrict__ d_ci, float* __restrict__ d_cf,
@@ -102,6 +102,17 @@ __global__ __launch_bounds__(256) void lstm_peephole_grad_kernel(const T* __rest
     acc += a;
   }
   (plane == 0 ? d_ci : plane == 1 ? d_cf : d_co)[pos * S + ch] = acc;
+}
+
+// Column block `blk` of dpre [frame][81][5 S], un-padded, as fp32 [frame][49][S] (read_buffer)
+template <typename T>
+__global__ __launch_bounds__(256) void lstm_dpre_block_kernel(const T* __restrict__ dpre, float* __restrict__ dst, int blk, int S,
+                                                              long long total) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int ch = (int)(i % S), pos = (int)((i / S) % 49);
+    const long long frame = i / (49LL * S);
+    dst[i] = Elem<T>::from(dpre[((frame * 81 + (pos / 7 + 1) * 9 + pos % 7 + 1) * 5 + blk) * S + ch]);
+  }
 }
 
 // [T,B,49,S] -> [B,T,49,S] (read_buffer)

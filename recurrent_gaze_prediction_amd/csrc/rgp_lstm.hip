@@ -1,6 +1,7 @@
 // librgp_hip.so: gaze_lstm, the ConvLSTM member of the gaze family -- plan object, forward (persistent sequence kernel or
-// per-timestep launches) and the per-step backward.  Reference graph: /root/reference/models/gaze_lstm.py:178-353, cell
-// :103-133 (three quirks kept as written: g reuses W_hi, o reads the OLD c, W_hc is a variable nothing reads).
+// per-timestep launches) and the backward (BPTT as one persistent launch or as per-timestep launches).
+// Reference graph: /root/reference/models/gaze_lstm.py:178-353, cell :103-133 (three quirks kept as written: g reuses
+// W_hi, o reads the OLD c, W_hc is a variable nothing reads).
 //
 //   [nchw_to_rows] -> projection GEMM (+ bias) -> E (halo-padded) -> hoisted x convolution, ONE GEMM with N = 512
 //   (column 4 c + {i, f, g, o}) -> recurrence -> h_t images -> folded head GEMM (head_fold.hip.h, identity batch-norm)
@@ -8,6 +9,9 @@
 // recurrence, two implementations:
 //   persistent (bf16, <= 64 clips, enough CUs): convlstm_seq.hip.h, all T steps in one launch
 //   per step   (any plan; RGP_LSTM_PER_STEP):   one igemm launch per step on h_{t-1} with the EpiLstm epilogue
+// BPTT, two implementations (the rest of the backward is common to both and reads the same dpre image):
+//   persistent (RGP_LSTM_BPTT_PERSISTENT; bf16 training plans, <= 64 clips, enough CUs): convlstm_bptt.hip.h, one launch
+//   per step   (every other plan):                 lstm_bwd_step_kernel + the step's input-gradient GEMM, 2 T - 1 launches
 // h_t lives as halo-padded operand images [B][T+1][81][S] (slot 0 = the zero state): step t's GEMM reads slot t and writes
 // slot t+1, the head reads slots 1..T (its GEMM "image" is a clip), and the backward's filter gradients read slots 0..T-1.
 #include <algorithm>
@@ -17,6 +21,7 @@
 #include "rgp_grcn_plan.h"
 #include "wgrad_launch.h"
 #include "convlstm_seq.hip.h"
+#include "convlstm_bptt.hip.h"
 #include "lstm_kernels.hip.h"
 #include "head_fold.hip.h"
 #include "c3dconv_bwd.hip.h"
@@ -28,8 +33,10 @@ struct rgp_lstm {
   bool save = false, fwd_done = false, bwd_done = false, weights_set = false;
   ConvDesc proj, proj_rows, xconv, grec, hfold;
   Buf xt, E, xpre, hall, call, gates, hseq, peep, gfold, hf_h, hf_k, hf_z, hf_part;
-  Buf xch, seq_cnt;
-  SeqGroupPlan sg;                         // groups of the persistent kernel (none = per-step launches), error word, fault bit
+  Buf xch, seq_cnt, bptt_xch, bptt_cnt;
+  SeqGroupPlan sg;                         // groups of the persistent kernels (none = per-step launches), error word, fault bits
+  bool fwd_persistent = false;             // the plan selected convlstm_seq_kernel ...
+  bool bptt_persistent = false;            // ... convlstm_bptt_kernel (each runs only where sg.resident() holds)
   size_t ws_bytes = 0;
   char* ws = nullptr;
   const float *proj_b = nullptr, *out_b = nullptr;
@@ -48,6 +55,10 @@ namespace {
 // What flags = 0 selects for plans the persistent kernel can run (bf16, <= 64 clips).  The rule ("gaze_lstm"): the
 // persistent kernel only if scripts/bench_lstm.py measures it faster than the per-step path at both of its shapes on one box.
 constexpr bool LSTM_DEFAULT_PERSISTENT = true;
+// The same for the BPTT of training plans without RGP_LSTM_BPTT_PERSISTENT, by the same rule: the persistent BPTT only if
+// scripts/bench_lstm.py measures it faster than the per-step loop at both of its shapes on one box.  (Flipping it changes
+// which path the gradient tests of tests/test_lstm_gpu.py cover: a change of its own.)
+constexpr bool LSTM_DEFAULT_BPTT_PERSISTENT = false;
 
 std::vector<int> pad_tab9(int C) {
   std::vector<int> t;
@@ -147,7 +158,7 @@ int seq_impl(rgp_lstm* g, hipStream_t s) {
   char* ws = g->ws;
   const int B = g->B, T_ = g->T, S = g->S;
   if constexpr (sizeof(T) == 2) {
-    if (g->sg.resident()) return seq_persistent(g, s);
+    if (g->fwd_persistent && g->sg.resident()) return seq_persistent(g, s);
   }
   const size_t st = (size_t)B * 49 * S;
   float* hall = (float*)(ws + g->hall.off);
@@ -170,6 +181,24 @@ int seq_impl(rgp_lstm* g, hipStream_t s) {
     RGP_TRY((launch_igemm<T, 1, 1, EpiLstm<T>>(p, e, s)));
   }
   return RGP_OK;
+}
+
+// All T backward steps in one persistent launch (convlstm_bptt.hip.h)
+int bptt_persistent(rgp_lstm* g, hipStream_t s) {
+  char* ws = g->ws;
+  RGP_HIP(hipMemsetAsync(ws + g->bptt_cnt.off, 0, g->bptt_cnt.bytes, s));     // phase counters: zeroed EVERY call
+  LstmBpttParams p;
+  p.w_rec = (const bf16_t*)(ws + g->b_rec.w_off);
+  p.dh_head = (const float*)(ws + g->dy.off);
+  p.gates = (const float*)(ws + g->gates.off);
+  p.call = (const float*)(ws + g->call.off);
+  p.peep = (const float*)(ws + g->peep.off);
+  p.dpre = (bf16_t*)(ws + g->dpre.off);
+  p.xch = (bf16_t*)(ws + g->bptt_xch.off);
+  p.g = g->sg.args(g->B, (unsigned*)(ws + g->bptt_cnt.off), RGP_FAULT_BPTT_LOST_MEMBER);
+  p.T = g->T; p.K = g->b_rec.K;
+  RGP_REQUIRE(g->b_rec.K == 27 * g->S && g->b_rec.chunk_major == 0, "convlstm_bptt: unexpected filter packing");
+  return launch_seq_group(g->sg, convlstm_bptt_kernel<4>, convlstm_bptt_kernel<7>, p, LBP_SMEM, s);
 }
 
 template <typename T>
@@ -277,8 +306,15 @@ int backward_impl(rgp_lstm* g, const float* logits, const float* probs, const fl
     RGP_TRY((launch_igemm<T, 1, 1, EpiStore<float, false, false>>(p, e, s)));
   }
   // 3. BPTT, t = T-1 .. 0: element-wise step, then dh_{t-1} = rotated [W_hi | W_hf | W_ho] on [d(i+g) | df | do]
+  bool bptt_one_launch = false;
+  if constexpr (sizeof(T) == 2) {
+    if (g->bptt_persistent && g->sg.resident()) {
+      RGP_TRY(bptt_persistent(g, s));
+      bptt_one_launch = true;
+    }
+  }
   const int ew_blocks = (int)std::min<size_t>((st + 255) / 256, 4096);
-  for (int t = T_ - 1; t >= 0; --t) {
+  for (int t = T_ - 1; t >= 0 && !bptt_one_launch; --t) {
     lstm_bwd_step_kernel<T><<<ew_blocks, 256, 0, s>>>(Fp(g->dy), Fp(g->dh_carry), Fp(g->dc_carry), Fp(g->gates), Fp(g->call),
                                                       Fp(g->peep), Tp(g->dpre), B, T_, t, S, t == T_ - 1);
     RGP_HIP(hipGetLastError());
@@ -338,7 +374,8 @@ int backward_impl(rgp_lstm* g, const float* logits, const float* probs, const fl
   return RGP_OK;
 }
 
-struct View { size_t off; int kind; size_t elems; };   // kind 0: [T][B] fp32 states -> [B][T]; 1: E (padded, operand dtype)
+// kind 0: [T][B] fp32 states -> [B][T]; 1: E (padded, operand dtype); 2: column block `off` of dpre (padded, operand dtype)
+struct View { size_t off; int kind; size_t elems; };
 
 bool find_view(const rgp_lstm* g, const char* name, View& v) {
   const std::string n(name ? name : "");
@@ -348,6 +385,8 @@ bool find_view(const rgp_lstm* g, const char* name, View& v) {
   else if (n == "emb") v = {g->E.off, 1, (size_t)g->F * 49 * g->P};
   else if (g->save && (n == "i" || n == "f" || n == "g" || n == "o"))
     v = {g->gates.off + (n == "i" ? 0 : n == "f" ? 1 : n == "g" ? 2 : 3) * all * 4, 0, all};
+  else if (g->save && (n == "d_i" || n == "d_f" || n == "d_g" || n == "d_o"))
+    v = {(size_t)(n == "d_i" ? LSTM_DI : n == "d_f" ? LSTM_DF : n == "d_g" ? LSTM_DG : LSTM_DO), 2, all};
   else return false;
   return true;
 }
@@ -358,7 +397,8 @@ extern "C" {
 
 int rgp_lstm_create(rgp_lstm_t** plan, int batch, int n_steps, int dtype, int flags) {
   RGP_REQUIRE(plan, "rgp_lstm_create: null out pointer");
-  RGP_REQUIRE((flags & ~(RGP_LSTM_SAVE_FOR_BACKWARD | RGP_LSTM_PER_STEP | RGP_LSTM_PERSISTENT)) == 0, "rgp_lstm_create: unknown flags 0x%x", flags);
+  RGP_REQUIRE((flags & ~(RGP_LSTM_SAVE_FOR_BACKWARD | RGP_LSTM_PER_STEP | RGP_LSTM_PERSISTENT | RGP_LSTM_BPTT_PERSISTENT)) == 0,
+              "rgp_lstm_create: unknown flags 0x%x", flags);
   RGP_REQUIRE((flags & (RGP_LSTM_PER_STEP | RGP_LSTM_PERSISTENT)) != (RGP_LSTM_PER_STEP | RGP_LSTM_PERSISTENT),
               "rgp_lstm_create: flags name both recurrence paths");
   RGP_REQUIRE(batch > 0 && n_steps > 0, "rgp_lstm_create: batch=%d n_steps=%d", batch, n_steps);
@@ -367,6 +407,10 @@ int rgp_lstm_create(rgp_lstm_t** plan, int batch, int n_steps, int dtype, int fl
               "rgp_lstm_create: B*T too large");
   RGP_REQUIRE(!(flags & RGP_LSTM_PERSISTENT) || (dtype == RGP_BF16 && batch <= 64),
               "rgp_lstm_create: the persistent kernel (flags) takes bf16 plans of at most 64 clips");
+  RGP_REQUIRE(!(flags & RGP_LSTM_BPTT_PERSISTENT) || (flags & RGP_LSTM_SAVE_FOR_BACKWARD),
+              "rgp_lstm_create: flags name RGP_LSTM_BPTT_PERSISTENT without RGP_LSTM_SAVE_FOR_BACKWARD (the persistent BPTT needs a training plan)");
+  RGP_REQUIRE(!(flags & RGP_LSTM_BPTT_PERSISTENT) || (dtype == RGP_BF16 && batch <= 64),
+              "rgp_lstm_create: the persistent BPTT kernel (flags) takes bf16 plans of at most 64 clips");
   rgp_lstm* g = new rgp_lstm();
   g->B = batch; g->T = n_steps; g->dtype = dtype; g->F = batch * n_steps;
   g->save = (flags & RGP_LSTM_SAVE_FOR_BACKWARD) != 0;
@@ -425,12 +469,19 @@ int rgp_lstm_create(rgp_lstm_t** plan, int batch, int n_steps, int dtype, int fl
   g->hf_k = take(a, (size_t)HF_PK * S * 4);
   g->hf_z = take(a, (size_t)F * 49 * HF_PK * 4);
   g->hf_part = take(a, (size_t)5 * HF_KP * HF_KP * S * 4);
-  // persistent sequence kernel: bf16 operands, up to 2 clips per group of 8 workgroups, at most 32 groups
+  // persistent kernels: bf16 operands, up to 2 clips per group of 8 workgroups, at most 32 groups.  The forward's flags and
+  // the BPTT's are independent of each other; the groups are sized if either kernel is selected.
   const bool eligible = dtype == RGP_BF16 && batch <= 64;
-  if (eligible && ((flags & RGP_LSTM_PERSISTENT) || (LSTM_DEFAULT_PERSISTENT && !(flags & RGP_LSTM_PER_STEP)))) {
-    g->sg.size(batch);
+  g->fwd_persistent = eligible && ((flags & RGP_LSTM_PERSISTENT) || (LSTM_DEFAULT_PERSISTENT && !(flags & RGP_LSTM_PER_STEP)));
+  g->bptt_persistent = eligible && g->save && ((flags & RGP_LSTM_BPTT_PERSISTENT) || LSTM_DEFAULT_BPTT_PERSISTENT);
+  if (g->fwd_persistent || g->bptt_persistent) g->sg.size(batch);
+  if (g->fwd_persistent) {
     g->xch = take(a, (size_t)2 * g->sg.groups * 98 * 128 * 2);
     g->seq_cnt = take(a, (size_t)g->sg.groups * T_ * 4);
+  }
+  if (g->bptt_persistent) {
+    g->bptt_xch = take(a, (size_t)2 * 3 * g->sg.groups * 98 * 128 * 2);
+    g->bptt_cnt = take(a, (size_t)g->sg.groups * T_ * 4);
   }
   if (g->save) {
     g->M = (long long)F * 49;
@@ -580,14 +631,21 @@ int rgp_lstm_status(rgp_lstm_t* g, rgp_stream_t stream) {
 }
 
 int rgp_lstm_inject_fault(rgp_lstm_t* g, int kind) {
-  RGP_REQUIRE(g && kind == RGP_FAULT_SEQ_LOST_MEMBER, "rgp_lstm_inject_fault: bad arguments");
-  if (g->dtype != RGP_BF16 || !g->sg.resident()) return set_err(RGP_ESTATE, "rgp_lstm_inject_fault: the plan does not use the persistent ConvLSTM kernel");
+  RGP_REQUIRE(g && (kind == RGP_FAULT_SEQ_LOST_MEMBER || kind == RGP_FAULT_BPTT_LOST_MEMBER), "rgp_lstm_inject_fault: bad arguments");
+  const bool selected = kind == RGP_FAULT_SEQ_LOST_MEMBER ? g->fwd_persistent : g->bptt_persistent;
+  if (g->dtype != RGP_BF16 || !selected || !g->sg.resident())
+    return set_err(RGP_ESTATE, "rgp_lstm_inject_fault: the plan does not use the persistent ConvLSTM %s kernel",
+                   kind == RGP_FAULT_SEQ_LOST_MEMBER ? "sequence" : "BPTT");
   g->sg.fault |= kind;
   return RGP_OK;
 }
 
 int rgp_lstm_persistent_workgroups(const rgp_lstm_t* g) {
-  return (g && g->dtype == RGP_BF16 && g->sg.resident()) ? g->sg.groups * 8 : 0;
+  return (g && g->dtype == RGP_BF16 && g->fwd_persistent && g->sg.resident()) ? g->sg.groups * 8 : 0;
+}
+
+int rgp_lstm_bptt_persistent_workgroups(const rgp_lstm_t* g) {
+  return (g && g->dtype == RGP_BF16 && g->bptt_persistent && g->sg.resident()) ? g->sg.groups * 8 : 0;
 }
 
 size_t rgp_lstm_buffer_elems(const rgp_lstm_t* g, const char* name) {
@@ -602,6 +660,11 @@ int rgp_lstm_read_buffer(rgp_lstm_t* g, const char* name, float* dst, rgp_stream
   hipStream_t s = (hipStream_t)stream;
   if (v.kind == 0) {
     lstm_tb_to_bt_kernel<<<1024, 256, 0, s>>>((const float*)(g->ws + v.off), dst, g->T, g->B, 49LL * g->S);
+  } else if (v.kind == 2) {
+    const long long total = (long long)v.elems;
+    const int blocks = (int)std::min<long long>((total + 255) / 256, 8192);
+    if (g->dtype == RGP_BF16) lstm_dpre_block_kernel<bf16_t><<<blocks, 256, 0, s>>>((const bf16_t*)(g->ws + g->dpre.off), dst, (int)v.off, g->S, total);
+    else lstm_dpre_block_kernel<float><<<blocks, 256, 0, s>>>((const float*)(g->ws + g->dpre.off), dst, (int)v.off, g->S, total);
   } else {
     const long long total = (long long)v.elems;
     const int blocks = (int)std::min<long long>((total + 255) / 256, 8192);

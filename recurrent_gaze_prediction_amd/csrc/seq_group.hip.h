@@ -1,6 +1,7 @@
 // The group-exchange layer of the persistent recurrence kernels (convgru_seq.hip.h, convgru_bptt.hip.h,
-// convlstm_seq.hip.h; gfx950, bf16 operands): what a kernel that runs a whole recurrence in ONE launch shares with the
-// others.  Each kernel keeps its resident filters, its K-loop schedule, its gate math and its output stores.
+// convlstm_seq.hip.h, convlstm_bptt.hip.h; gfx950, bf16 operands): what a kernel that runs a whole recurrence in ONE
+// launch shares with the others.  Each kernel keeps its resident filters, its K-loop schedule, its gate math and its
+// output stores.
 //
 // Decomposition.  A recurrent 3x3 convolution on a 7x7 state of 128 channels is K = 1152 deep against a few hundred KB of
 // bf16 filters: re-streaming the filters per step costs 12.6 us per CU at the measured 66-73 GB/s L2 -> LDS ingest,
@@ -15,7 +16,7 @@
 // rows, every storing wave drains (`s_waitcnt vmcnt(0)`), the workgroup barriers, ONE lane adds to the group's monotonic
 // phase counter; consumers poll that counter with sc1 loads from one lane (bounded, with s_sleep), barrier, and read the
 // payload with sc1 loads only.  Counters are zeroed ahead of the launch.  All 8 x ngroups <= 256 workgroups (256
-// threads, 135 - 157 KB of LDS: one per CU) must be resident together; the host checks the CU count and falls back to
+// threads, 129 - 157 KB of LDS: one per CU) must be resident together; the host checks the CU count and falls back to
 // per-step launches otherwise.  A member that never arrives (e.g. two such launches interleaved on one device from
 // different processes: keep ONE in flight per device) makes its group time out after ~1 s, NaN-poison its results and
 // leave -- a loud failure, never a hang.
@@ -191,6 +192,27 @@ struct SeqGroup {
       const u32x4 q = seq_ld_sc1(xch, xbytes, (unsigned)(((image * 98 + row) * 128 + c16 * 8) * 2));
       const int c = row / 49;
       *(u32x4*)(img + (c * 81 + seq_pad_pix(row - c * 49)) * SEQ_PIXB + c16 * 16) = q;
+    }
+  }
+  // load_image in two halves, for a kernel that has MFMAs to run between the loads and the LDS stores (convlstm_bptt.hip.h):
+  // the rows of the image in this thread's registers, then into the 9x9 images
+  static constexpr int IMG_IT = ((NF == 4 ? 49 : 98) * 16 + SEQ_NT - 1) / SEQ_NT;
+  __device__ __forceinline__ void fetch_image(const bf16_t* xch, unsigned xbytes, int image, u32x4 (&q)[IMG_IT]) const {
+#pragma unroll
+    for (int k = 0; k < IMG_IT; ++k) {
+      const int i = tid + k * SEQ_NT;
+      q[k] = (u32x4){0u, 0u, 0u, 0u};
+      if (i < rows * 16) q[k] = seq_ld_sc1(xch, xbytes, (unsigned)(((image * 98 + (i >> 4)) * 128 + (i & 15) * 8) * 2));
+    }
+  }
+  __device__ __forceinline__ void put_image(char* img, const u32x4 (&q)[IMG_IT]) const {
+#pragma unroll
+    for (int k = 0; k < IMG_IT; ++k) {
+      const int i = tid + k * SEQ_NT;
+      if (i < rows * 16) {
+        const int row = i >> 4, c = row / 49;
+        *(u32x4*)(img + (c * 81 + seq_pad_pix(row - c * 49)) * SEQ_PIXB + (i & 15) * 16) = q[k];
+      }
     }
   }
   // Epilogue: a group that timed out must not look like a result.  true = it did: the plan's error word is set, and the

@@ -539,11 +539,14 @@ class LstmEngine(object):
 
     per_step=True: the recurrence as one launch per timestep (RGP_LSTM_PER_STEP), the library's second implementation;
     otherwise bf16 plans of at most 64 clips run all T steps in one persistent launch (csrc/convlstm_seq.hip.h).
+    bptt_persistent=True: the backward-through-time pass of backward() as one persistent launch as well
+    (RGP_LSTM_BPTT_PERSISTENT, csrc/convlstm_bptt.hip.h; bf16 training plans of at most 64 clips), whatever the forward runs.
     flat_params / flat_grads hold the 17 trained variables; W_hc (LSTM_UNTRAINED) lives outside them."""
 
-    def __init__(self, batch, n_steps, dtype='bf16', save_for_backward=False, device='cuda:0', per_step=False, persistent=False):
+    def __init__(self, batch, n_steps, dtype='bf16', save_for_backward=False, device='cuda:0', per_step=False, persistent=False,
+                 bptt_persistent=False):
         """persistent=True asks for the persistent kernel by name (RGP_LSTM_PERSISTENT: refused for plans it cannot run);
-        with both False the library chooses."""
+        with both False the library chooses.  bptt_persistent=False is the library's choice for the BPTT (per step)."""
         self.lib = _lib.load()
         self.device = _require_gpu(device)
         self.B, self.T, self.P, self.S = int(batch), int(n_steps), 512, 128
@@ -551,7 +554,7 @@ class LstmEngine(object):
         self.per_step, self.save_for_backward = bool(per_step), bool(save_for_backward)
         self.torch_dtype = torch.bfloat16 if _lib.DTYPES[dtype] == _lib.RGP_BF16 else torch.float32
         flags = (_lib.RGP_LSTM_SAVE_FOR_BACKWARD if save_for_backward else 0) | (_lib.RGP_LSTM_PER_STEP if per_step else 0) | \
-            (_lib.RGP_LSTM_PERSISTENT if persistent else 0)
+            (_lib.RGP_LSTM_PERSISTENT if persistent else 0) | (_lib.RGP_LSTM_BPTT_PERSISTENT if bptt_persistent else 0)
         self.flat_params = self.flat_grads = self.grads = self.weights = None
         self._h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
@@ -659,15 +662,27 @@ class LstmEngine(object):
     def persistent(self):
         return self.persistent_workgroups > 0
 
+    @property
+    def bptt_persistent_workgroups(self):
+        with torch.cuda.device(self.device):
+            return int(self.lib.rgp_lstm_bptt_persistent_workgroups(self._h))
+
+    @property
+    def bptt_persistent(self):
+        return self.bptt_persistent_workgroups > 0
+
     def inject_fault(self, kind='seq'):
-        assert kind == 'seq'
-        _lib.check(self.lib.rgp_lstm_inject_fault(self._h, _lib.RGP_FAULT_SEQ_LOST_MEMBER))
+        """The next persistent launch of the forward ('seq') or of the BPTT ('bptt') loses a group member (test hook)."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_lstm_inject_fault(self._h, {'seq': _lib.RGP_FAULT_SEQ_LOST_MEMBER,
+                                                                'bptt': _lib.RGP_FAULT_BPTT_LOST_MEMBER}[kind]))
 
     def read_buffer_elems(self, name):
         return int(self.lib.rgp_lstm_buffer_elems(self._h, name.encode()))
 
     def read_buffer(self, name):
-        """'h', 'c' (training plans also 'i', 'f', 'g', 'o') [B,T,7,7,128]; 'emb' [B*T*49, 512]; fp32."""
+        """'h', 'c' (training plans also 'i', 'f', 'g', 'o' and, after a backward, 'd_i', 'd_f', 'd_g', 'd_o')
+        [B,T,7,7,128]; 'emb' [B*T*49, 512]; fp32."""
         n = self.read_buffer_elems(name)
         if n == 0:
             raise _lib.RgpError('unknown intermediate %r' % name)

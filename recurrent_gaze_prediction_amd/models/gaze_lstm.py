@@ -63,15 +63,19 @@ class GazePredictionLSTM(GazePredictionGRU):
         frame_images is only shape-checked by the reference.  Both tf.nn.dropout sites (:246-247, :342) are inert there:
         __init__ (:161-175) builds the graph through the parent on placeholder_with_default(1.0) and rebinds
         self.dropout_keep_prob to an orphan placeholder afterwards, so no dropout is built here.
-        config.convlstm_path ('persistent' / 'per_step', default None = the library's choice) selects the recurrence path."""
+        config.convlstm_path ('persistent' / 'per_step', default None = the library's choice) selects the recurrence path,
+        config.convlstm_bptt_path (the same values; the library's choice is per step) that of the backward-through-time pass."""
         assert model is not None, 'pass the owning model (B, T, dtype, device come from its config)'
         if net is None:
             net = {}
         path = getattr(model.config, 'convlstm_path', None)
         assert path in (None, 'persistent', 'per_step'), path
+        bptt_path = getattr(model.config, 'convlstm_bptt_path', None)
+        assert bptt_path in (None, 'persistent', 'per_step'), bptt_path
         engine = LstmEngine(model.batch_size, model.n_lstm_steps, dtype=getattr(model.config, 'compute_dtype', 'bf16'),
                             save_for_backward=getattr(model.config, 'trainable', True), device=model.session.device,
-                            per_step=path == 'per_step', persistent=path == 'persistent')
+                            per_step=path == 'per_step', persistent=path == 'persistent',
+                            bptt_persistent=bptt_path == 'persistent')
         model.variables = synthetic.lstm_params(getattr(model.config, 'init_seed', 0), lstm_std=1e-4, peephole_std=1e-4)
         engine.set_weights(model.variables)
         net['variables'] = model.variables
@@ -81,22 +85,24 @@ class GazePredictionLSTM(GazePredictionGRU):
         return False
 
     def _recover_from_timeout(self):
-        """A persistent ConvLSTM launch lost a group member (include/rgp.h): continue on a plan that runs the recurrence
-        as per-timestep launches (RGP_LSTM_PER_STEP).  A new engine object in this process; master weights and optimizer
+        """A persistent ConvLSTM launch (forward or BPTT) lost a group member (include/rgp.h): continue on a plan that runs
+        the recurrence and its BPTT as per-timestep launches (RGP_LSTM_PER_STEP, no RGP_LSTM_BPTT_PERSISTENT).  A new engine object in this process; master weights and optimizer
         slots move over device to device; the caller recomputes the poisoned batch.  (models/gaze_grcn.py does the same.)"""
         from ..engine import OPT_STATE_KEYS
         old = self.engine
-        if getattr(old, 'per_step', False):
+        if getattr(old, 'per_step', False) and not getattr(old, 'bptt_persistent', False):
             return False
         log = __import__('logging').getLogger('rgp')
         log.warning('persistent ConvLSTM launch timed out (RGP_ETIMEOUT): switching this model to per-timestep launches')
-        new = LstmEngine(old.B, old.T, dtype=old.dtype, save_for_backward=old.save_for_backward, device=old.device, per_step=True)
+        new = LstmEngine(old.B, old.T, dtype=old.dtype, save_for_backward=old.save_for_backward, device=old.device, per_step=True,
+                         bptt_persistent=False)
         new.set_weights(old.weights)
         for k in OPT_STATE_KEYS:
             if getattr(old, k, None) is not None:
                 setattr(new, k, getattr(old, k).clone())
         self.engine = new
         self.config.convlstm_path = 'per_step'
+        self.config.convlstm_bptt_path = 'per_step'
         return True
 
     # ---- variables (TF names without the RGP/ and RCNBottom/ scopes), for checkpoints and exported weights ----------

@@ -190,7 +190,8 @@ class GazePredictionGRU(ModelBase):
         # plans with persistent ConvGRU launches can fail asynchronously (RGP_ETIMEOUT): the ranks then agree on the outcome
         # of every backward before they enter the collectives.  Decided ONCE, from the plan every rank was built with (a rank
         # that later falls back to per-step launches keeps answering), so the ranks' collective sequences stay the same.
-        self._dp_agree = dist is not None and bool(getattr(self.engine, 'persistent', False))
+        self._dp_agree = dist is not None and bool(getattr(self.engine, 'persistent', False) or
+                                                   getattr(self.engine, 'bptt_persistent', False))
 
     def _train_op(self, logits, probs, labels_dev):
         loss_type = 'l2' if self.config.loss_type == 'l2' else 'xentropy'
@@ -269,7 +270,7 @@ class GazePredictionGRU(ModelBase):
         status = getattr(self.engine, 'status', None)
         if not callable(status):
             return False
-        if not getattr(self.engine, 'persistent', True):
+        if not getattr(self.engine, 'persistent', True) and not getattr(self.engine, 'bptt_persistent', False):
             return False          # per-timestep launches cannot time out: no host wait for the stream either
         from .. import _lib
         try:

@@ -7,10 +7,14 @@ window is --calls calls of one path between two device synchronisations (host cl
 figure is the median window divided by the calls, the spread is (max - min) / median of the windows.  The forward is timed
 on the placeholder layout (fp32 [B,T,1024,7,7]).  gaze_grcn's inference forward (GrcnEngine, bf16, its persistent ConvGRU
 kernel) is timed in the same alternation at the same shapes.  The training step (forward + backward + clipped Adam +
-re-pack on a bf16 training plan; BPTT per step) is timed the same way.
+re-pack) is timed the same way on two bf16 training plans per shape that alternate: 'train_step' with the flags of today
+(BPTT per step) and 'train_step_bptt_persistent' (RGP_LSTM_BPTT_PERSISTENT); 'backward' / 'backward_bptt_persistent' are
+windows of backward calls alone on the same two plans, so the BPTT's share is visible.
 
 The rule for the default of eligible plans (bf16, <= 64 clips): the persistent kernel only if it is faster than the
-per-step path at both shapes; the JSON records the verdict next to what the library does.
+per-step path at both shapes (every window, not just the medians); the JSON records the verdict next to what the library
+does, for the forward (persistent_faster_at_both_shapes) and for the BPTT (bptt_persistent_faster_at_both_shapes, on the
+training step).
 --trace-only: a short run of every path for a profiler (rocprofv3 --kernel-trace --stats); no timing, no file.
 Writes one JSON document (--out) and prints it.
 """
@@ -81,13 +85,13 @@ def main():
     sync()
     for (B, T), (x, out, engs) in plans.items():
         engs['persistent'].status()
-    if a.trace_only:
-        return
 
     result = {'device': torch.cuda.get_device_name(0), 'calls_per_window': a.calls, 'windows': a.windows, 'dtype': 'bf16',
               'method': 'host clock around windows of calls between device synchronisations; paths alternate; median window / calls',
               'shapes': {}}
     for (B, T), (x, out, engs) in plans.items():
+        if a.trace_only:
+            break
         ms = {p: [] for p in PATHS}
         for _ in range(a.windows):
             for path in PATHS:
@@ -97,30 +101,54 @@ def main():
         entry['forward']['persistent_over_per_step'] = f['ms_median'] / s['ms_median']
         entry['forward']['persistent_faster'] = bool(f['ms_max'] < s['ms_min'])      # every window, not just the medians
         result['shapes']['%dx%d' % (B, T)] = entry
-    result['persistent_faster_at_both_shapes'] = all(e['forward']['persistent_faster'] for e in result['shapes'].values())
-    result['default_of_eligible_plans'] = 'persistent' if LstmEngine(2, 2, dtype='bf16', device=dev).persistent else 'per_step'
     del plans
     for B, T in SHAPES:
-        eng = LstmEngine(B, T, dtype='bf16', save_for_backward=True, device=dev)
-        eng.set_weights(params)
+        engs = {'': LstmEngine(B, T, dtype='bf16', save_for_backward=True, device=dev),
+                '_bptt_persistent': LstmEngine(B, T, dtype='bf16', save_for_backward=True, device=dev, bptt_persistent=True)}
+        assert engs['_bptt_persistent'].bptt_persistent and not engs[''].bptt_persistent
         x = torch.tensor(syn.c3d_features(1, B, T), device=dev)
         g = syn.gaze_maps(2, B, T)[0]
         labels = torch.tensor(g / g.reshape(B, T, -1).sum(-1)[..., None, None], device=dev).contiguous()
         step = [0]
+        fwd = {}
 
-        def train():
+        def train(eng):
             logits, probs = eng.forward(x)
             eng.backward(logits, probs, labels)
             eng.adam_step(step[0], 1e-4)
             step[0] += 1
-        for _ in range(3):
-            train()
-        ms = [window(train, a.train_calls, sync) for _ in range(a.windows)]
-        result['shapes']['%dx%d' % (B, T)]['train_step'] = summarise(ms)
-        del eng
+        for k, eng in engs.items():
+            eng.set_weights(params)
+            for _ in range(3):
+                train(eng)
+            fwd[k] = eng.forward(x)
+            eng.backward(fwd[k][0], fwd[k][1], labels)
+        sync()
+        for eng in engs.values():
+            eng.status()
+        if a.trace_only:
+            continue
+        ms = {kind + k: [] for kind in ('train_step', 'backward') for k in engs}
+        for _ in range(a.windows):
+            for k, eng in engs.items():
+                ms['train_step' + k].append(window(lambda: train(eng), a.train_calls, sync))
+            for k, eng in engs.items():
+                eng.forward(x, out_logits=fwd[k][0], out_probs=fwd[k][1])
+                ms['backward' + k].append(window(lambda: eng.backward(fwd[k][0], fwd[k][1], labels), a.train_calls, sync))
+        entry = result['shapes']['%dx%d' % (B, T)]
+        entry.update({k: summarise(v) for k, v in ms.items()})
+        entry['bptt_persistent_faster'] = bool(entry['train_step_bptt_persistent']['ms_max'] < entry['train_step']['ms_min'])
+        del engs
+    if a.trace_only:
+        return
+    result['persistent_faster_at_both_shapes'] = all(e['forward']['persistent_faster'] for e in result['shapes'].values())
+    result['bptt_persistent_faster_at_both_shapes'] = all(e['bptt_persistent_faster'] for e in result['shapes'].values())
+    result['default_of_eligible_plans'] = 'persistent' if LstmEngine(2, 2, dtype='bf16', device=dev).persistent else 'per_step'
+    result['default_bptt_of_eligible_plans'] = 'persistent' if LstmEngine(2, 2, dtype='bf16', save_for_backward=True,
+                                                                          device=dev).bptt_persistent else 'per_step'
     if a.trace and os.path.exists(a.trace):
         rows_ = [l.rstrip('\n') for l in open(a.trace)]
-        result['kernel_trace_stats'] = {'header': rows_[0], 'rows': [r for r in rows_[1:] if 'lstm' in r.lower() or 'igemm' in r or
+        result['kernel_trace_stats'] = {'header': rows_[0], 'rows': [r for r in rows_[1:] if 'lstm' in r.lower() or 'igemm' in r or 'wgrad' in r or
                                                                      'col2im' in r or 'softmax' in r or 'nchw_to_rows' in r]}
     text = json.dumps(result, indent=1, sort_keys=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
