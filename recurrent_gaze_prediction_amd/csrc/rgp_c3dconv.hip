@@ -6,35 +6,34 @@
 //   fused  (bf16 plans): [nchw_to_rows] -> c3dconv_fused_kernel: rows -> logits (+ softmax), Z never leaves the CU
 //   staged (any dtype):  [nchw_to_rows] -> projection GEMM (+ bias) -> E -> folded head GEMM E x K^T -> Z -> head_col2im
 //                        (+ out_b) -> rgp_softmax_xent_fwd: existing kernels only, the one the tests compare the fused with
-// Training plans (RGP_C3DCONV_SAVE_FOR_BACKWARD) run the staged path and keep X and E; their backward is c3dconv_bwd.hip.h.
+// Training plans (RGP_C3DCONV_SAVE_FOR_BACKWARD) run the staged path and keep X and E.  Their backward is the chain rule
+// head_fold.hip.h documents with y := E, with NO float atomics: both filter gradients are GEMM-form (gaze_stages.h),
+//   dK[(r,t),s] = sum_m Pm[m,(r,t)] E[m,s]    d proj_c3d_W[k,s] = sum_m X[m,k] dE[m,s]    d proj_c3d_b = colsum(dE)
+// The projection, the folded head and their backward are the gaze family's shared stages (gaze_stages.h).
 #include <algorithm>
 #include <string>
 
-#include "bwd_kernels.hip.h"
-#include "rgp_grcn_plan.h"
+#include "gaze_stages.h"
 #include "c3dconv_fused.hip.h"
-#include "c3dconv_bwd.hip.h"
 
 using namespace rgp;
 
 struct rgp_c3dconv {
   int B = 0, T = 0, P = 0, dtype = RGP_BF16, F = 0;
   bool fused = false, save = false, fwd_done = false, bwd_done = false;
-  ConvDesc proj, proj_rows, hfold;         // staged path: E = X W (+ b), Z = E K^T
-  Buf xt, E, hf_z;                         // transposed placeholder input; staged intermediates
-  Buf gfold, hf_h, hf_k, hf_part;          // the head's fold (head_fold.hip.h): G, H, K [361][P] and K's five partial sums, fp32
+  Projection pj;                           // staged path: E = X W (+ b) ...
+  FoldedHead head;                         // ... Z = E K^T; the head's fold
+  Buf E;
   Buf m2n, m2r, beta, plane;               // the network's fold: M2 in both K orders (operand dtype), bias row, bias plane
   size_t ws_bytes = 0;
   char* ws = nullptr;
   bool weights_set = false;
   const float *proj_b = nullptr, *out_b = nullptr;
-  // ---- training plans (c3dconv_bwd.hip.h)
-  long long M = 0, Mp = 0;                 // rows = frames x 49, rounded up to 64
-  int ksplit = 1;
-  ConvDesc b_hf, b_px;                     // dE = Pm K; d rows = dE W^T
-  ConvDesc wg_k, wg_w;                     // the filter gradients as GEMMs over the rows: dK = PmT ET^T, dW = XT dET^T; their
-                                           // "filter" areas hold ET / dET [P padded to 128][Mp]
-  Buf dz, frame_sum, pm, pmT, xT, dE, part, dkf, dhf, dhp, dgp;
+  // ---- training plans
+  FoldedHeadBwd hb;                        // dE = Pm K
+  ProjectionBwd pb;                        // d rows = dE W^T; dW = XT dET^T
+  ConvDesc wg_k;                           // dK = PmT ET^T as a GEMM over the rows: its "filter" area holds ET [P padded to 128][Mp]
+  Buf pmT, dE;
   rgp_c3dconv_weights w;                   // forward weights (device fp32) as last set
 };
 
@@ -49,16 +48,9 @@ template <typename T>
 int set_weights_impl(rgp_c3dconv* g, const rgp_c3dconv_weights* w, hipStream_t s) {
   char* ws = g->ws;
   const int P = g->P;
-  float* gf = (float*)(ws + g->gfold.off);
-  float* hf = (float*)(ws + g->hf_h.off);
-  float* kf = (float*)(ws + g->hf_k.off);
-  float* part = (float*)(ws + g->hf_part.off);
-  // the head as one 19x19 stride-6 transposed convolution on E: G = weight3 o out_W -> H = G o weight2 -> K = H o weight1
-  fold_head_filter_kernel<<<(49 * 32 + 255) / 256, 256, 0, s>>>(w->up_weight3, w->out_W, gf, 49, 12, 32);
-  head_fold_h_kernel<<<(HF_HP * HF_HP * 64 + 255) / 256, 256, 0, s>>>(gf, w->up_weight2, hf);
-  head_fold_k_kernel<<<dim3(HF_KP * HF_KP, 5), 128, 0, s>>>(hf, w->up_weight1, part, P);
-  head_fold_sum_kernel<<<(HF_KP * HF_KP * P + 255) / 256, 256, 0, s>>>(part, kf, HF_KP * HF_KP * P, 5);
-  RGP_HIP(hipGetLastError());
+  const float* kf = g->head.k(ws);
+  // the head as one 19x19 stride-6 transposed convolution on E
+  RGP_TRY(g->head.fold(ws, w->up_weight3, w->out_W, w->up_weight2, w->up_weight1, s));
   // ... and the projection folded in: M2 = K W^T (both K orders), beta = K b, the bias plane (inference plans: a
   // training plan re-folds after every optimizer step and runs the staged path, which reads none of the three)
   if (!g->save) {
@@ -69,16 +61,14 @@ int set_weights_impl(rgp_c3dconv* g, const rgp_c3dconv_weights* w, hipStream_t s
   RGP_HIP(hipGetLastError());
   if (!g->fused) {
     PackBatch<T> pk(ws, s);
-    RGP_TRY(pk.add(g->proj, w->proj_c3d_W, P, 0));
-    RGP_TRY(pk.add(g->proj_rows, w->proj_c3d_W, P, 0));
-    RGP_TRY(pk.add(g->hfold, kf, HF_KP * HF_KP, 0));           // GEMM filter [(r,t)][s]; rows 361 .. 383 stay zero
+    RGP_TRY(g->pj.pack(pk, w->proj_c3d_W));
+    RGP_TRY(g->head.pack(pk));
     RGP_TRY(pk.flush());
   }
   if (g->save) {
     PackBatch<T> pk(ws, s);
-    RGP_TRY(pk.add(g->b_px, w->proj_c3d_W, 512, 0));            // d = 0: feature channels 0, 2, 4, ...
-    RGP_TRY(pk.add(g->b_px, w->proj_c3d_W + P, 512, 512));      // d = 1: feature channels 1, 3, 5, ...
-    RGP_TRY(pk.add(g->b_hf, kf, P, 0));
+    RGP_TRY(g->pb.pack(pk, w->proj_c3d_W));
+    RGP_TRY(g->hb.pack(pk, kf));
     RGP_TRY(pk.flush());
     g->w = *w;
   }
@@ -92,19 +82,14 @@ int set_weights_impl(rgp_c3dconv* g, const rgp_c3dconv_weights* w, hipStream_t s
 template <typename T>
 int forward_impl(rgp_c3dconv* g, const float* c3d_input, const void* rows, float* logits, float* probs, hipStream_t s) {
   char* ws = g->ws;
-  const void* A = rows;
-  if (!rows) {
-    nchw_to_rows_kernel<T><<<dim3(1024 / 64, g->F), 256, 0, s>>>(c3d_input, (T*)(ws + g->xt.off), 1024);
-    RGP_HIP(hipGetLastError());
-    A = ws + g->xt.off;
-  } else if (g->save) {
-    // the backward's projection filter gradient reads X in the reference's channel order c*2+d (gaze_rnn.py:494-497)
-    const long long total = (long long)g->F * 49 * 1024;
-    rows_to_xt_kernel<T><<<(int)std::min<long long>((total + 255) / 256, 8192), 256, 0, s>>>((const T*)rows, (T*)(ws + g->xt.off), total);
-    RGP_HIP(hipGetLastError());
-  }
   if constexpr (sizeof(T) == 2) {
     if (g->fused) {
+      const void* A = rows;
+      if (!rows) {
+        nchw_to_rows_kernel<T><<<dim3(1024 / 64, g->F), 256, 0, s>>>(c3d_input, (T*)(ws + g->pj.xt.off), 1024);
+        RGP_HIP(hipGetLastError());
+        A = ws + g->pj.xt.off;
+      }
       RGP_TRY(ensure_dyn_smem((const void*)c3dconv_fused_kernel, CF_SMEM));
       c3dconv_fused_kernel<<<(g->F + 1) / 2, CF_NT, CF_SMEM, s>>>((const bf16_t*)A, (const bf16_t*)(ws + (rows ? g->m2r.off : g->m2n.off)),
                                                                  (const float*)(ws + g->plane.off), logits, probs, g->F);
@@ -112,39 +97,11 @@ int forward_impl(rgp_c3dconv* g, const float* c3d_input, const void* rows, float
       return RGP_OK;
     }
   }
-  {
-    const ConvDesc& d = rows ? g->proj_rows : g->proj;
-    IgemmParams p = make_params(d, A, ws, g->F);
-    EpiParams e = make_epi(d, ws + g->E.off, ws);
-    e.bias = g->proj_b;
-    RGP_TRY((launch_igemm<T, 1, 1, EpiStore<T, true, false>>(p, e, s)));
-  }
-  {
-    IgemmParams p = make_params(g->hfold, ws + g->E.off, ws, g->F);
-    EpiParams e = make_epi(g->hfold, ws + g->hf_z.off, ws);
-    RGP_TRY((launch_igemm<T, 1, 1, EpiStore<float, false, false>>(p, e, s)));
-  }
-  const long long total = (long long)g->F * 2401;
-  head_col2im_kernel<<<(int)std::min<long long>((total + 255) / 256, 8192), 256, 0, s>>>((const float*)(ws + g->hf_z.off), g->out_b, logits, total);
-  RGP_HIP(hipGetLastError());
+  RGP_TRY(g->pj.forward<T>(ws, c3d_input, rows, g->save, g->F, ws + g->E.off, g->proj_b, s));
+  RGP_TRY(g->head.forward<T>(ws, ws + g->E.off, g->F, g->out_b, logits, g->F, s));
   if (probs) RGP_TRY(rgp_softmax_xent_fwd(logits, nullptr, probs, nullptr, nullptr, g->F, 2401, (rgp_stream_t)s));
   g->fwd_done = true;
   g->bwd_done = false;
-  return RGP_OK;
-}
-
-// one filter gradient: out[r][n] = sum_m AT[r][m] BT[n][m] (BT = the desc's filter area), K = Mp split ksplit ways into
-// g->part, summed in a fixed order
-template <typename T>
-int wgrad_gemm(rgp_c3dconv* g, const ConvDesc& d, const void* AT, float* out, hipStream_t s) {
-  char* ws = g->ws;
-  IgemmParams p = make_params(d, AT, ws, 1);
-  EpiParams e = make_epi(d, ws + g->part.off, ws);
-  const long long n = (long long)d.Mw * g->P;
-  e.xpre_img_stride = n;
-  RGP_TRY((launch_igemm<T, 1, 1, EpiStoreSplitF32>(p, e, s, g->ksplit)));
-  head_fold_sum_kernel<<<(int)((n + 255) / 256), 256, 0, s>>>((const float*)(ws + g->part.off), out, (int)n, g->ksplit);
-  RGP_HIP(hipGetLastError());
   return RGP_OK;
 }
 
@@ -153,54 +110,29 @@ int backward_impl(rgp_c3dconv* g, const float* logits, const float* probs, const
                   int loss_l2, hipStream_t s) {
   char* ws = g->ws;
   const int P = g->P, F = g->F;
-  const long long M = g->M, Mp = g->Mp;
+  const long long M = g->pb.M, Mp = g->pb.Mp;
   auto Fp = [&](const Buf& x) { return (float*)(ws + x.off); };
   auto Tp = [&](const Buf& x) { return (T*)(ws + x.off); };
-  T* eT = (T*)(ws + g->wg_k.w_off);
-  T* deT = (T*)(ws + g->wg_w.w_off);
   // 1. d loss / d logits, d out_b
-  dlogits_kernel<<<F, 256, 0, s>>>(loss_l2 ? logits : probs, labels, Fp(g->dz), Fp(g->frame_sum), 2401, 1.0f / (float)F, loss_l2);
-  sum_kernel<<<1, 256, 0, s>>>(Fp(g->frame_sum), (float*)gr->out_b, F, 1.0f);
+  RGP_TRY(g->hb.loss_grad(ws, logits, probs, labels, loss_l2, F, (float*)gr->out_b, s));
   // 2. patches of dz; dK = Pm^T E
-  const long long tot = M * HF_PK;
-  head_fold_patches_kernel<T><<<(int)std::min<long long>((tot + 255) / 256, 8192), 256, 0, s>>>(Fp(g->dz), Tp(g->pm), M);
-  c3dconv_transpose_kernel<T><<<dim3((unsigned)(Mp / 64), HF_PK / 64), 256, 0, s>>>(Tp(g->pm), Tp(g->pmT), M, HF_PK, Mp);
-  c3dconv_transpose_kernel<T><<<dim3((unsigned)(Mp / 64), P / 64), 256, 0, s>>>(Tp(g->E), eT, M, P, Mp);
+  RGP_TRY(g->hb.patches<T>(ws, F, s));
+  transpose_pad<T>(Tp(g->hb.pm), Tp(g->pmT), M, HF_PK, Mp, s);
+  transpose_pad<T>(Tp(g->E), (T*)(ws + g->wg_k.w_off), M, P, Mp, s);
   RGP_HIP(hipGetLastError());
-  RGP_TRY(wgrad_gemm<T>(g, g->wg_k, Tp(g->pmT), Fp(g->dkf), s));
-  // 3. the chain rule through the fold (head_fold.hip.h): d weight1, dH -> d weight2, dG -> d weight3, d out_W
-  const float* hf = (const float*)(ws + g->hf_h.off);
-  const float* gf = (const float*)(ws + g->gfold.off);
-  head_unfold_f1_kernel<<<(25 * 64 * P + 255) / 256, 256, 0, s>>>(Fp(g->dkf), hf, (float*)gr->up_weight1, P);
-  head_unfold_h_kernel<<<dim3(HF_HP * HF_HP, 25), 256, 0, s>>>(Fp(g->dkf), g->w.up_weight1, Fp(g->dhp), P);
-  head_fold_sum_kernel<<<(HF_HP * HF_HP * 64 + 255) / 256, 256, 0, s>>>(Fp(g->dhp), Fp(g->dhf), HF_HP * HF_HP * 64, 25);
-  head_unfold_f2_kernel<<<(25 * 32 * 64 + 255) / 256, 256, 0, s>>>(Fp(g->dhf), gf, (float*)gr->up_weight2);
-  head_unfold_g_kernel<<<49, 256, 0, s>>>(Fp(g->dhf), g->w.up_weight2, Fp(g->dgp));
-  head_unfold_grads_kernel<<<1, 256, 0, s>>>(Fp(g->dgp), g->w.up_weight3, g->w.out_W, (float*)gr->up_weight3, (float*)gr->out_W);
-  RGP_HIP(hipGetLastError());
+  RGP_TRY(wgrad_gemm<T>(ws, g->wg_k, Tp(g->pmT), g->pb.part, g->pb.ksplit, Fp(g->hb.dkf), s));
+  // 3. the chain rule through the fold
+  RGP_TRY(g->hb.unfold_chain(ws, g->head, g->w.up_weight1, g->w.up_weight2, g->w.up_weight3, g->w.out_W, (float*)gr->up_weight1,
+                             (float*)gr->up_weight2, (float*)gr->up_weight3, (float*)gr->out_W, s));
   // 4. dE = Pm K
-  {
-    IgemmParams p = make_params(g->b_hf, Tp(g->pm), ws, F);
-    EpiParams e = make_epi(g->b_hf, Tp(g->dE), ws);
-    RGP_TRY((launch_igemm<T, 1, 1, EpiStore<T, false, false>>(p, e, s)));
-  }
-  // 5. d proj_c3d_W = X^T dE, d proj_c3d_b = column sums of dE (= row sums of dE^T: one block per column, fixed tree)
-  c3dconv_transpose_kernel<T><<<dim3((unsigned)(Mp / 64), P / 64), 256, 0, s>>>(Tp(g->dE), deT, M, P, Mp);
-  c3dconv_transpose_kernel<T><<<dim3((unsigned)(Mp / 64), 1024 / 64), 256, 0, s>>>(Tp(g->xt), Tp(g->xT), M, 1024, Mp);
-  RGP_HIP(hipGetLastError());
-  RGP_TRY(wgrad_gemm<T>(g, g->wg_w, Tp(g->xT), (float*)gr->proj_c3d_W, s));
-  rowsum_kernel<T><<<P, 256, 0, s>>>(deT, (float*)gr->proj_c3d_b, Mp, M);
-  RGP_HIP(hipGetLastError());
+  RGP_TRY((g->hb.dgrad<T, T>(ws, F, Tp(g->dE), s)));
+  // 5. d proj_c3d_W = X^T dE, d proj_c3d_b = column sums of dE
+  RGP_TRY(g->pb.weight_grads<T>(ws, Tp(g->pj.xt), Tp(g->dE), (float*)gr->proj_c3d_W, (float*)gr->proj_c3d_b, s));
   g->bwd_done = true;
   return RGP_OK;
 }
 
-int check_ready(rgp_c3dconv* g) {
-  if (!g) return set_err(RGP_EINVAL, "null plan");
-  if (!g->ws) return set_err(RGP_EWORKSPACE, "rgp_c3dconv: workspace not bound");
-  if (!g->weights_set) return set_err(RGP_ESTATE, "rgp_c3dconv: weights not set");
-  return RGP_OK;
-}
+int check_ready(rgp_c3dconv* g) { return check_bound_and_set(g, "rgp_c3dconv"); }
 
 // fp32 elements of a named buffer; *off / *operand: where it lives and whether it is stored in the operand dtype
 size_t find_buffer(const rgp_c3dconv* g, const char* name, size_t* off, bool* operand) {
@@ -237,78 +169,47 @@ int rgp_c3dconv_create(rgp_c3dconv_t** plan, int batch, int n_steps, int dim_pro
   const int P = g->P, F = g->F, es = esize(dtype);
   Arena a;
   if (!g->fused) {
-    bool ok = true;
-    for (ConvDesc* d : {&g->proj, &g->proj_rows}) {            // E = X W + b (gaze_c3d_conv.py:124-138), rows [F*49][P]
-      d->Mw = 49; d->N = P;
-      d->in_img_stride = 49LL * 1024; d->out_img_stride = 49LL * P;
-      for (int p = 0; p < 49; ++p) { d->in_tab.push_back(p * 1024); d->out_tab.push_back(p * P); }
-    }
-    ok &= build_k_schedule(g->proj, {0}, {0}, 1024, dtype);
-    g->proj.s_tap = 0; g->proj.s_n = 1; g->proj.s_c = P;
-    // rows from C3D carry K order d*512+c; reference channel = c*2+d
-    ok &= build_k_schedule(g->proj_rows, {0, 512}, {0, 1}, 512, dtype);
-    g->proj_rows.s_tap = P; g->proj_rows.s_n = 1; g->proj_rows.s_c = 2LL * P;
+    std::vector<int> rows49, z49;
+    for (int p = 0; p < 49; ++p) { rows49.push_back(p * P); z49.push_back(p * HF_PK); }
+    bool ok = g->pj.plan(P, dtype, rows49, 49LL * P);           // E = X W + b (gaze_c3d_conv.py:124-138), rows [F*49][P]
     {
-      ConvDesc& d = g->hfold;                                  // the folded head on E: K = P, N = the 19x19 taps
-      d.Mw = 49; d.N = HF_PK; d.in_img_stride = 49LL * P; d.out_img_stride = 49LL * HF_PK;
-      for (int p = 0; p < 49; ++p) { d.in_tab.push_back(p * P); d.out_tab.push_back(p * HF_PK); }
-      ok &= build_k_schedule(d, {0}, {0}, P, dtype);
-      d.s_tap = 0; d.s_n = P; d.s_c = 1;                       // source K [(r,t)][s]
+      ConvDesc& d = g->head.hfold;                             // the folded head on E: a GEMM image is a frame's 49 rows
+      d.Mw = 49; d.in_img_stride = 49LL * P; d.out_img_stride = 49LL * HF_PK;
+      d.in_tab = rows49; d.out_tab = z49;
     }
+    ok &= g->head.plan(P, dtype);
     if (!ok) { delete g; return set_err(RGP_EINVAL, "rgp_c3dconv_create: unsupported channel geometry P=%d", P); }
-    for (ConvDesc* d : {&g->proj, &g->proj_rows, &g->hfold}) d->reserve(a, dtype);
+    for (ConvDesc* d : {&g->pj.proj, &g->pj.proj_rows, &g->head.hfold}) d->reserve(a, dtype);
     g->E = take(a, (size_t)F * 49 * P * es);
-    g->hf_z = take(a, (size_t)F * 49 * HF_PK * 4);
+    g->head.hf_z = take(a, FoldedHead::z_bytes(F));
   }
-  g->xt = take(a, (size_t)F * 49 * 1024 * es);
-  g->gfold = take(a, 50 * 32 * 4);
-  g->hf_h = take(a, (size_t)HF_HP * HF_HP * 64 * 4);
-  g->hf_k = take(a, (size_t)HF_PK * P * 4);                    // (rows 361 .. 383 stay zero)
-  g->hf_part = take(a, (size_t)5 * HF_KP * HF_KP * P * 4);
+  g->head.C = P;                                               // (fused plans fold the head too)
+  g->pj.xt = take(a, (size_t)F * 49 * 1024 * es);
+  g->head.gfold = take(a, FoldedHead::G_BYTES);
+  g->head.hf_h = take(a, FoldedHead::H_BYTES);
+  g->head.hf_k = take(a, g->head.k_bytes(HF_PK));
+  g->head.hf_part = take(a, g->head.part_bytes());
   g->m2n = take(a, (size_t)HF_PK * 1024 * es);
   g->m2r = take(a, (size_t)HF_PK * 1024 * es);
   g->beta = take(a, (size_t)HF_PK * 4);
   g->plane = take(a, 2401 * 4);
   if (g->save) {
-    g->M = (long long)F * 49;
-    g->Mp = (g->M + 63) / 64 * 64;
-    const int nk = (int)(g->Mp / bke(dtype));
-    g->ksplit = std::min(16, nk);
-    bool ok = g->Mp * 1024 < (1LL << 31);
-    {  // d rows[m][d*512+c] = sum_p dE[m][p] W[c*2+d][p]   (rows order of rgp_c3d_forward)
-      ConvDesc& d = g->b_px;
-      d.Mw = 1; d.N = 1024; d.in_img_stride = P; d.out_img_stride = 1024; d.in_tab = {0}; d.out_tab = {0};
-      ok &= build_k_schedule(d, {0}, {0}, P, dtype);
-      d.s_tap = 0; d.s_n = 2LL * P; d.s_c = 1;
-    }
-    {  // dE[(f,m,n), s] = sum_k Pm[(f,m,n), k] K[k, s]   (K [361][P] fp32, rows 361..383 zero)
-      ConvDesc& d = g->b_hf;
-      d.Mw = 49; d.N = P; d.in_img_stride = 49LL * HF_PK; d.out_img_stride = 49LL * P;
-      for (int pos = 0; pos < 49; ++pos) { d.in_tab.push_back(pos * HF_PK); d.out_tab.push_back(pos * P); }
-      ok &= build_k_schedule(d, {0}, {0}, HF_PK, dtype);
-      d.cin_src = HF_KP * HF_KP;
-      d.s_tap = 0; d.s_n = 1; d.s_c = P;
-    }
-    auto wgrad_desc = [&](ConvDesc& d, int rows) {               // out [rows][P] = AT [rows][Mp] x BT [P][Mp]^T
-      d.Mw = rows; d.N = P; d.in_img_stride = 0; d.out_img_stride = 0;
-      for (int r = 0; r < rows; ++r) { d.in_tab.push_back((int)(r * g->Mp)); d.out_tab.push_back(r * P); }
-      return build_k_schedule(d, {0}, {0}, (int)g->Mp, dtype);
-    };
-    if (ok) ok &= wgrad_desc(g->wg_k, HF_PK);
-    if (ok) ok &= wgrad_desc(g->wg_w, 1024);
+    bool ok = g->pb.plan(P, dtype);
+    ok &= g->hb.plan(P, dtype);
+    ok = ok && g->pb.plan_wgrad(F, dtype) && wgrad_gemm_desc(g->wg_k, HF_PK, P, g->pb.Mp, dtype);
     if (!ok) { delete g; return set_err(RGP_EINVAL, "rgp_c3dconv_create: B*T too large for the backward plan"); }
-    for (ConvDesc* d : {&g->b_px, &g->b_hf, &g->wg_k, &g->wg_w}) d->reserve(a, dtype);
-    g->dz = take(a, (size_t)F * 2401 * 4);
-    g->frame_sum = take(a, (size_t)F * 4);
-    g->pm = take(a, (size_t)g->M * HF_PK * es);
-    g->pmT = take(a, (size_t)HF_PK * g->Mp * es);
-    g->xT = take(a, (size_t)1024 * g->Mp * es);
-    g->dE = take(a, (size_t)g->M * P * es);
-    g->part = take(a, (size_t)g->ksplit * 1024 * P * 4);
-    g->dkf = take(a, (size_t)HF_PK * P * 4);
-    g->dhf = take(a, (size_t)HF_HP * HF_HP * 64 * 4);
-    g->dhp = take(a, (size_t)25 * HF_HP * HF_HP * 64 * 4);
-    g->dgp = take(a, 50 * 32 * 4);
+    for (ConvDesc* d : {&g->pb.b_px, &g->hb.b_hf, &g->wg_k, &g->pb.wg_w}) d->reserve(a, dtype);
+    g->hb.dz = take(a, FoldedHeadBwd::dz_bytes(F));
+    g->hb.frame_sum = take(a, (size_t)F * 4);
+    g->hb.pm = take(a, FoldedHeadBwd::pm_bytes(F, dtype));
+    g->pmT = take(a, (size_t)HF_PK * g->pb.Mp * es);
+    g->pb.xT = take(a, g->pb.xT_bytes(dtype));
+    g->dE = take(a, (size_t)g->pb.M * P * es);
+    g->pb.part = take(a, g->pb.part_bytes());
+    g->hb.dkf = take(a, FoldedHeadBwd::dk_bytes(P));
+    g->hb.dhf = take(a, FoldedHeadBwd::DH_BYTES);
+    g->hb.dhp = take(a, FoldedHeadBwd::DHP_BYTES);
+    g->hb.dgp = take(a, FoldedHeadBwd::DG_BYTES);
   }
   g->ws_bytes = a.off;
   *plan = g;
@@ -325,46 +226,37 @@ size_t rgp_c3dconv_workspace_bytes(const rgp_c3dconv_t* plan) { return plan ? pl
 const char* rgp_c3dconv_path(const rgp_c3dconv_t* plan) { return plan ? (plan->fused ? "fused" : "staged") : ""; }
 
 int rgp_c3dconv_bind_workspace(rgp_c3dconv_t* g, void* workspace, size_t bytes, rgp_stream_t stream) {
-  RGP_REQUIRE(g && workspace, "rgp_c3dconv_bind_workspace: null argument");
-  if (bytes < g->ws_bytes) return set_err(RGP_EWORKSPACE, "workspace %zu < required %zu bytes", bytes, g->ws_bytes);
-  RGP_REQUIRE(((size_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+  RGP_TRY(check_bind("rgp_c3dconv_bind_workspace", g, workspace, bytes));
   hipStream_t s = (hipStream_t)stream;
   g->ws = (char*)workspace;
   g->weights_set = false;
   RGP_HIP(hipMemsetAsync(g->ws, 0, g->ws_bytes, s));           // (packed-filter padding stays zero: a pack writes the same positions every time)
   if (!g->fused)
-    for (ConvDesc* d : {&g->proj, &g->proj_rows, &g->hfold}) RGP_TRY(upload_desc(*d, g->ws, s));
+    for (ConvDesc* d : {&g->pj.proj, &g->pj.proj_rows, &g->head.hfold}) RGP_TRY(upload_desc(*d, g->ws, s));
   if (g->save)
-    for (ConvDesc* d : {&g->b_px, &g->b_hf, &g->wg_k, &g->wg_w}) RGP_TRY(upload_desc(*d, g->ws, s));
+    for (ConvDesc* d : {&g->pb.b_px, &g->hb.b_hf, &g->wg_k, &g->pb.wg_w}) RGP_TRY(upload_desc(*d, g->ws, s));
   return RGP_OK;
 }
 
 int rgp_c3dconv_set_weights(rgp_c3dconv_t* g, const rgp_c3dconv_weights* w, rgp_stream_t stream) {
   RGP_REQUIRE(g && w, "rgp_c3dconv_set_weights: null argument");
   if (!g->ws) return set_err(RGP_EWORKSPACE, "rgp_c3dconv: workspace not bound");
-  const float* const* ptrs = (const float* const*)w;
-  for (size_t i = 0; i < sizeof(rgp_c3dconv_weights) / sizeof(float*); ++i)
-    RGP_REQUIRE(ptrs[i], "rgp_c3dconv_set_weights: weight pointer %zu is null", i);
+  RGP_TRY(require_pointers(w, "rgp_c3dconv_set_weights", "weight"));
   RGP_REQUIRE(((size_t)w->proj_c3d_W & 15) == 0, "rgp_c3dconv_set_weights: proj_c3d_W must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  return g->dtype == RGP_BF16 ? set_weights_impl<bf16_t>(g, w, s) : set_weights_impl<float>(g, w, s);
+  return RGP_BY_DTYPE(g->dtype, set_weights_impl, g, w, (hipStream_t)stream);
 }
 
 int rgp_c3dconv_forward(rgp_c3dconv_t* g, const float* c3d_input, float* logits, float* probs, rgp_stream_t stream) {
   RGP_TRY(check_ready(g));
   RGP_REQUIRE(c3d_input && logits, "rgp_c3dconv_forward: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  return g->dtype == RGP_BF16 ? forward_impl<bf16_t>(g, c3d_input, nullptr, logits, probs, s)
-                              : forward_impl<float>(g, c3d_input, nullptr, logits, probs, s);
+  return RGP_BY_DTYPE(g->dtype, forward_impl, g, c3d_input, nullptr, logits, probs, (hipStream_t)stream);
 }
 
 int rgp_c3dconv_forward_rows(rgp_c3dconv_t* g, const void* c3d_rows, float* logits, float* probs, rgp_stream_t stream) {
   RGP_TRY(check_ready(g));
   RGP_REQUIRE(c3d_rows && logits, "rgp_c3dconv_forward_rows: null argument");
   RGP_REQUIRE(((size_t)c3d_rows & 15) == 0, "rgp_c3dconv_forward_rows: rows must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  return g->dtype == RGP_BF16 ? forward_impl<bf16_t>(g, nullptr, c3d_rows, logits, probs, s)
-                              : forward_impl<float>(g, nullptr, c3d_rows, logits, probs, s);
+  return RGP_BY_DTYPE(g->dtype, forward_impl, g, nullptr, c3d_rows, logits, probs, (hipStream_t)stream);
 }
 
 int rgp_c3dconv_backward(rgp_c3dconv_t* g, const float* logits, const float* probs, const float* labels,
@@ -374,22 +266,14 @@ int rgp_c3dconv_backward(rgp_c3dconv_t* g, const float* logits, const float* pro
   RGP_REQUIRE(loss_type == 1 ? logits != nullptr : probs != nullptr, "rgp_c3dconv_backward: the loss needs %s", loss_type == 1 ? "logits" : "probs");
   if (!g->save) return set_err(RGP_ESTATE, "rgp_c3dconv_backward: the plan was not created with RGP_C3DCONV_SAVE_FOR_BACKWARD");
   if (!g->fwd_done) return set_err(RGP_ESTATE, "rgp_c3dconv_backward: no forward since the weights were set");
-  const float* const* ptrs = (const float* const*)grads;
-  for (size_t i = 0; i < sizeof(rgp_c3dconv_weights) / sizeof(float*); ++i)
-    RGP_REQUIRE(ptrs[i], "rgp_c3dconv_backward: gradient pointer %zu is null", i);
-  hipStream_t s = (hipStream_t)stream;
-  return g->dtype == RGP_BF16 ? backward_impl<bf16_t>(g, logits, probs, labels, grads, loss_type, s)
-                              : backward_impl<float>(g, logits, probs, labels, grads, loss_type, s);
+  RGP_TRY(require_pointers(grads, "rgp_c3dconv_backward", "gradient"));
+  return RGP_BY_DTYPE(g->dtype, backward_impl, g, logits, probs, labels, grads, loss_type, (hipStream_t)stream);
 }
 
 int rgp_c3dconv_backward_input(rgp_c3dconv_t* g, float* d_rows, rgp_stream_t stream) {
   RGP_REQUIRE(g && d_rows, "rgp_c3dconv_backward_input: null argument");
   if (!g->ws || !g->save || !g->weights_set || !g->bwd_done) return set_err(RGP_ESTATE, "rgp_c3dconv_backward_input: call after rgp_c3dconv_backward");
-  hipStream_t s = (hipStream_t)stream;
-  IgemmParams p = make_params(g->b_px, g->ws + g->dE.off, g->ws, (int)g->M);
-  EpiParams e = make_epi(g->b_px, d_rows, g->ws);
-  return g->dtype == RGP_BF16 ? launch_igemm<bf16_t, 1, 1, EpiStore<float, false, false>>(p, e, s)
-                              : launch_igemm<float, 1, 1, EpiStore<float, false, false>>(p, e, s);
+  return g->pb.backward_input(g->ws, g->dtype, g->ws + g->dE.off, g->pb.M, d_rows, (hipStream_t)stream);
 }
 
 size_t rgp_c3dconv_buffer_elems(const rgp_c3dconv_t* g, const char* name) {

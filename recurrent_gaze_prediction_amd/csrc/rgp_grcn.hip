@@ -7,7 +7,6 @@
 #include "rgp_grcn_plan.h"
 #include "convgru_seq.hip.h"
 #include "head_logits.hip.h"
-#include "head_fold.hip.h"
 
 using namespace rgp;
 
@@ -101,22 +100,7 @@ int run_d3(rgp_grcn* g, float* logits, hipStream_t s) {
 
 template <typename T>
 int proj_impl(rgp_grcn* g, const float* c3d_input, const void* rows, hipStream_t s) {
-  const ConvDesc& d = rows ? g->proj_rows : g->proj;
-  const void* A = rows;
-  if (!rows) {
-    nchw_to_rows_kernel<T><<<dim3(1024 / 64, g->F), 256, 0, s>>>(c3d_input, (T*)(g->ws + g->xt.off), 1024);
-    RGP_HIP(hipGetLastError());
-    A = g->ws + g->xt.off;
-  } else if (g->save) {
-    // the backward's projection wgrad reads xt in the reference's channel order c*2+d (gaze_rnn.py:494-497)
-    const long long total = (long long)g->F * 49 * 1024;
-    rows_to_xt_kernel<T><<<(int)std::min<long long>((total + 255) / 256, 8192), 256, 0, s>>>((const T*)rows, (T*)(g->ws + g->xt.off), total);
-    RGP_HIP(hipGetLastError());
-  }
-  IgemmParams p = make_params(d, A, g->ws, g->F);
-  EpiParams e = make_epi(d, g->ws + g->E.off, g->ws);
-  e.bias = g->proj_b;
-  return launch_igemm<T, 1, 1, EpiStore<T, true, false>>(p, e, s);
+  return g->pj.forward<T>(g->ws, c3d_input, rows, g->save != 0, g->F, g->ws + g->E.off, g->proj_b, s);
 }
 
 template <typename T>
@@ -214,16 +198,8 @@ int seq_impl(rgp_grcn* g, hipStream_t s) {
 
 template <typename T>
 int head_impl(rgp_grcn* g, float* logits, hipStream_t s) {
-  if (g->fold_head) {                                          // head_fold.hip.h: Z = BN(h) x K^T, then col2im (+ out_b)
-    IgemmParams p = make_params(g->hfold, g->ws + g->hbn.off, g->ws, g->F);
-    EpiParams e = make_epi(g->hfold, g->ws + g->hf_z.off, g->ws);
-    RGP_TRY((launch_igemm<T, 1, 1, EpiStore<float, false, false>>(p, e, s)));
-    const long long total = (long long)g->F * 2401;
-    head_col2im_kernel<<<(int)std::min<long long>((total + 255) / 256, 8192), 256, 0, s>>>((const float*)(g->ws + g->hf_z.off), g->out_b,
-                                                                                        logits, total);
-    RGP_HIP(hipGetLastError());
-    return RGP_OK;
-  }
+  // head_fold.hip.h: Z = BN(h) x K^T, then col2im (+ out_b)
+  if (g->fold_head) return g->head.forward<T>(g->ws, g->ws + g->hbn.off, g->F, g->out_b, logits, g->F, s);
   for (const ConvDesc& d : g->d1) {
     IgemmParams p = make_params(d, g->ws + g->hbn.off, g->ws, g->F);
     EpiParams e = make_epi(d, g->ws + g->D1.off, g->ws);
@@ -241,23 +217,21 @@ int head_impl(rgp_grcn* g, float* logits, hipStream_t s) {
 template <typename T>
 int set_weights_impl(rgp_grcn* g, const rgp_grcn_weights* w, hipStream_t s, hipStream_t sc) {
   char* ws = g->ws;
-  const int S = g->S, P = g->P;
+  const int S = g->S;
   PackBatch<T> pk(ws, s);       // every pack of this call in one launch, behind the fold / Toeplitz kernels it reads from
   // (the packed-filter areas were zeroed with the workspace at bind time and a pack writes the same positions every
   // time: their channel / row padding stays zero without a memset per call -- 17 launches per optimizer step)
-  RGP_TRY(pk.add(g->proj, w->proj_c3d_W, P, 0));
-  RGP_TRY(pk.add(g->proj_rows, w->proj_c3d_W, P, 0));
+  RGP_TRY(g->pj.pack(pk, w->proj_c3d_W));
   RGP_TRY(pk.add(g->xconv, w->gru_Wz, S, 0));
   RGP_TRY(pk.add(g->xconv, w->gru_Wr, S, S));
   RGP_TRY(pk.add(g->xconv, w->gru_W, S, 2 * S));
   RGP_TRY(pk.add(g->gzr, w->gru_Uz, S, 0));
   RGP_TRY(pk.add(g->gzr, w->gru_Ur, S, S));
   RGP_TRY(pk.add(g->gc, w->gru_U, S, 0));
-  // sc: the stream of the head's fold and the pack that reads it (= s, or a training plan's side stream: rgp_grcn_set_weights)
-  float* gf = (float*)(ws + g->gfold.off);
-  fold_head_filter_kernel<<<(49 * 32 + 255) / 256, 256, 0, g->fold_head ? sc : s>>>(w->up_weight3, w->out_W, gf, 49, 12, 32);
-  RGP_HIP(hipGetLastError());
   if (!g->fold_head) {                                         // the three-stage head's operand filters
+    float* gf = (float*)(ws + g->head.gfold.off);
+    fold_head_filter_kernel<<<(49 * 32 + 255) / 256, 256, 0, s>>>(w->up_weight3, w->out_W, gf, 49, 12, 32);
+    RGP_HIP(hipGetLastError());
     for (size_t i = 0; i < g->d1_pack.size(); ++i) RGP_TRY(pk.add(g->d1_pack[i], w->up_weight1, 64, (int)(i % 3) * 64));   // column phase px = i % 3
     for (size_t i = 0; i < g->d2_pack.size(); ++i) RGP_TRY(pk.add(g->d2_pack[i], w->up_weight2, 32, (int)(i % 2) * 32));
     RGP_TRY(pk.add(g->d3, gf, 1, 0));
@@ -267,16 +241,11 @@ int set_weights_impl(rgp_grcn* g, const rgp_grcn_weights* w, hipStream_t s, hipS
     RGP_TRY(pk.add(g->d3t, (const float*)(ws + g->gtoep.off), 16, 0));
   }
   if (g->fold_head) {
-    // the head as one 19x19 stride-6 transposed convolution (head_fold.hip.h): G (above) -> H = G o weight2 -> K = H o weight1
-    float* hf = (float*)(ws + g->hf_h.off);
-    float* kf = (float*)(ws + g->hf_k.off);
-    head_fold_h_kernel<<<(HF_HP * HF_HP * 64 + 255) / 256, 256, 0, sc>>>(gf, w->up_weight2, hf);
-    float* part = (float*)(ws + g->hf_part.off);
-    head_fold_k_kernel<<<dim3(HF_KP * HF_KP, 5), 128, 0, sc>>>(hf, w->up_weight1, part, S);
-    head_fold_sum_kernel<<<(HF_KP * HF_KP * S + 255) / 256, 256, 0, sc>>>(part, kf, HF_KP * HF_KP * S, 5);
-    RGP_HIP(hipGetLastError());
+    // the head as one 19x19 stride-6 transposed convolution, on sc: the stream of the head's fold and the pack that reads
+    // it (= s, or a training plan's side stream: rgp_grcn_set_weights)
+    RGP_TRY(g->head.fold(ws, w->up_weight3, w->out_W, w->up_weight2, w->up_weight1, sc));
     PackBatch<T> pk2(ws, sc);
-    RGP_TRY(pk2.add(g->hfold, kf, HF_KP * HF_KP, 0));         // GEMM filter [(r,t)][s]; rows 361 .. 383 stay zero
+    RGP_TRY(g->head.pack(pk2));
     RGP_TRY(pk2.flush());
   }
   RGP_TRY(pk.flush());
@@ -289,9 +258,7 @@ int set_weights_impl(rgp_grcn* g, const rgp_grcn_weights* w, hipStream_t s, hipS
 }
 
 int check_ready(rgp_grcn* g) {
-  if (!g) return set_err(RGP_EINVAL, "null plan");
-  if (!g->ws) return set_err(RGP_EWORKSPACE, "rgp_grcn: workspace not bound");
-  if (!g->weights_set) return set_err(RGP_ESTATE, "rgp_grcn: weights not set");
+  RGP_TRY(check_bound_and_set(g, "rgp_grcn"));
   return grcn_check_error(g);
 }
 
@@ -325,17 +292,7 @@ int rgp_grcn_create(rgp_grcn_t** plan, int batch, int n_steps, int dim_proj, int
   bool ok = true;
 
   // projection  E = X W + b  (gaze_grcn.py:239-242), output halo-padded 9x9xP
-  for (ConvDesc* d : {&g->proj, &g->proj_rows}) {
-    d->Mw = 49; d->N = P;
-    d->in_img_stride = 49LL * 1024; d->out_img_stride = 81LL * P;
-    for (int p = 0; p < 49; ++p) d->in_tab.push_back(p * 1024);
-    d->out_tab = pad_tab(7, 1, P);
-  }
-  ok &= build_k_schedule(g->proj, {0}, {0}, 1024, dtype);
-  g->proj.s_tap = 0; g->proj.s_n = 1; g->proj.s_c = P;
-  // rows from C3D carry K order d*512+c; reference channel = c*2+d
-  ok &= build_k_schedule(g->proj_rows, {0, 512}, {0, 1}, 512, dtype);
-  g->proj_rows.s_tap = P; g->proj_rows.s_n = 1; g->proj_rows.s_c = 2LL * P;
+  ok &= g->pj.plan(P, dtype, pad_tab(7, 1, P), 81LL * P);
 
   // 3x3 SAME convs on the padded 7x7 maps
   auto conv3x3 = [&](ConvDesc& d, int Cin, int N) {
@@ -381,17 +338,16 @@ int rgp_grcn_create(rgp_grcn_t** plan, int batch, int n_steps, int dim_proj, int
   }
   if (g->fold_head) {
     // the folded head (head_fold.hip.h): GEMM rows = the 7x7 positions of the padded BN(h) image, K = S, N = the 19x19 taps
-    ConvDesc& d = g->hfold;
-    d.Mw = 49; d.N = HF_PK; d.in_img_stride = 81LL * S; d.out_img_stride = 49LL * HF_PK;
+    ConvDesc& d = g->head.hfold;
+    d.Mw = 49; d.in_img_stride = 81LL * S; d.out_img_stride = 49LL * HF_PK;
     for (int m = 0; m < 7; ++m) for (int n = 0; n < 7; ++n) { d.in_tab.push_back(((m + 1) * 9 + n + 1) * S); d.out_tab.push_back((m * 7 + n) * HF_PK); }
-    ok &= build_k_schedule(d, {0}, {0}, S, dtype);
-    d.s_tap = 0; d.s_n = S; d.s_c = 1;                          // source K [(r,t)][s]
+    ok &= g->head.plan(S, dtype);
   }
   if (!ok) { delete g; return set_err(RGP_EINVAL, "rgp_grcn_create: unsupported channel geometry P=%d S=%d", P, S); }
 
   Arena a;
-  if (g->fold_head) g->hfold.reserve(a, dtype);
-  for (ConvDesc* d : {&g->proj, &g->proj_rows, &g->xconv, &g->gzr, &g->gc, &g->d3, &g->d3t}) d->reserve(a, dtype);
+  if (g->fold_head) g->head.hfold.reserve(a, dtype);
+  for (ConvDesc* d : {&g->pj.proj, &g->pj.proj_rows, &g->xconv, &g->gzr, &g->gc, &g->d3, &g->d3t}) d->reserve(a, dtype);
   for (ConvDesc& d : g->d1) d.reserve(a, dtype);
   for (ConvDesc& d : g->d2) d.reserve(a, dtype);
   // packing aliases: a tap table of their own, the packed filter of the problem they belong to
@@ -415,7 +371,7 @@ int rgp_grcn_create(rgp_grcn_t** plan, int batch, int n_steps, int dim_proj, int
   g->o_lin49_3S = put_tab(a, g->tab_lin49_3S); g->o_lin49_S = put_tab(a, g->tab_lin49_S);
 
   const size_t st = (size_t)batch * 49 * S * 4;
-  g->xt = take(a, (size_t)F * 49 * 1024 * es);
+  g->pj.xt = take(a, (size_t)F * 49 * 1024 * es);
   g->E = take(a, (size_t)F * 81 * P * es);
   g->xpre = take(a, (size_t)F * 49 * 3 * S * 4);
   g->hall = take(a, st * (n_steps + 1));
@@ -425,15 +381,15 @@ int rgp_grcn_create(rgp_grcn_t** plan, int batch, int n_steps, int dim_proj, int
   g->rhp = take(a, (size_t)batch * 81 * S * es);
   g->hbn = take(a, (size_t)F * 81 * S * es);
   if (g->fold_head) {                                      // no intermediate maps: the fold's small fp32 work areas instead
-    g->hf_h = take(a, (size_t)HF_HP * HF_HP * 64 * 4);
-    g->hf_k = take(a, (size_t)HF_KP * HF_KP * S * 4);
-    g->hf_z = take(a, (size_t)F * 49 * HF_PK * 4);
-    g->hf_part = take(a, (size_t)5 * HF_KP * HF_KP * S * 4);
+    g->head.hf_h = take(a, FoldedHead::H_BYTES);
+    g->head.hf_k = take(a, g->head.k_bytes(HF_KP * HF_KP));
+    g->head.hf_z = take(a, FoldedHead::z_bytes(F));
+    g->head.hf_part = take(a, g->head.part_bytes());
   } else {
     g->D1 = take(a, (size_t)F * 27 * 27 * 64 * es);
     g->D2 = take(a, (size_t)F * 55 * 55 * 32 * es + 4096);   // slack: the Toeplitz filter-gradient rows of pixel block 3 read past the last row
   }
-  g->gfold = take(a, 50 * 32 * 4);
+  g->head.gfold = take(a, FoldedHead::G_BYTES);
   g->gtoep = take(a, (size_t)7 * 16 * 704 * 4);
   g->bias16 = take(a, 16 * 4);
   g->frame_loss = take(a, (size_t)F * 4);
@@ -477,9 +433,7 @@ int rgp_grcn_inject_fault(rgp_grcn_t* g, int kind) {
 size_t rgp_grcn_workspace_bytes(const rgp_grcn_t* plan) { return plan ? plan->ws_bytes : 0; }
 
 int rgp_grcn_bind_workspace(rgp_grcn_t* g, void* workspace, size_t bytes, rgp_stream_t stream) {
-  RGP_REQUIRE(g && workspace, "rgp_grcn_bind_workspace: null argument");
-  if (bytes < g->ws_bytes) return set_err(RGP_EWORKSPACE, "workspace %zu < required %zu bytes", bytes, g->ws_bytes);
-  RGP_REQUIRE(((size_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+  RGP_TRY(check_bind("rgp_grcn_bind_workspace", g, workspace, bytes));
   hipStream_t s = (hipStream_t)stream;
   RGP_TRY(g->sg.alloc_err());
   g->ws = (char*)workspace;
@@ -487,8 +441,8 @@ int rgp_grcn_bind_workspace(rgp_grcn_t* g, void* workspace, size_t bytes, rgp_st
   // zero everything once: halos of E / Hp / RHp / Hbn / D1 / D2 stay zero because
   // epilogues only ever write interiors.
   RGP_HIP(hipMemsetAsync(g->ws, 0, g->ws_bytes, s));
-  for (ConvDesc* d : {&g->proj, &g->proj_rows, &g->xconv, &g->gzr, &g->gc, &g->d3, &g->d3t}) RGP_TRY(upload_desc(*d, g->ws, s));
-  if (g->fold_head) RGP_TRY(upload_desc(g->hfold, g->ws, s));
+  for (ConvDesc* d : {&g->pj.proj, &g->pj.proj_rows, &g->xconv, &g->gzr, &g->gc, &g->d3, &g->d3t}) RGP_TRY(upload_desc(*d, g->ws, s));
+  if (g->fold_head) RGP_TRY(upload_desc(g->head.hfold, g->ws, s));
   for (ConvDesc& d : g->d1) RGP_TRY(upload_desc(d, g->ws, s));
   for (ConvDesc& d : g->d2) RGP_TRY(upload_desc(d, g->ws, s));
   for (ConvDesc& d : g->d1_pack) RGP_TRY(upload_desc(d, g->ws, s));
@@ -507,13 +461,11 @@ int rgp_grcn_bind_workspace(rgp_grcn_t* g, void* workspace, size_t bytes, rgp_st
 int rgp_grcn_set_weights(rgp_grcn_t* g, const rgp_grcn_weights* w, rgp_stream_t stream) {
   RGP_REQUIRE(g && w, "rgp_grcn_set_weights: null argument");
   if (!g->ws) return set_err(RGP_EWORKSPACE, "rgp_grcn: workspace not bound");
-  const float* const* ptrs = (const float* const*)w;
-  for (size_t i = 0; i < sizeof(rgp_grcn_weights) / sizeof(float*); ++i)
-    RGP_REQUIRE(ptrs[i], "rgp_grcn_set_weights: weight pointer %zu is null", i);
+  RGP_TRY(require_pointers(w, "rgp_grcn_set_weights", "weight"));
   hipStream_t s = (hipStream_t)stream;
   hipStream_t sc = s;
   if (g->save) RGP_TRY(grcn_bwd_fork_fold(g, s, &sc));
-  RGP_TRY(g->dtype == RGP_BF16 ? set_weights_impl<bf16_t>(g, w, s, sc) : set_weights_impl<float>(g, w, s, sc));
+  RGP_TRY(RGP_BY_DTYPE(g->dtype, set_weights_impl, g, w, s, sc));
   if (g->save) RGP_TRY(grcn_bwd_pack(g, w, s, sc));
   if (sc != s) RGP_TRY(grcn_bwd_join_fold(g, s));
   return RGP_OK;
@@ -524,7 +476,7 @@ int rgp_proj_fwd(rgp_grcn_t* g, const float* c3d_input, rgp_stream_t stream) {
   RGP_REQUIRE(c3d_input, "rgp_proj_fwd: null input");
   hipStream_t s = (hipStream_t)stream;
   const int pid = g->prof.begin(0, s);
-  const int rc = g->dtype == RGP_BF16 ? proj_impl<bf16_t>(g, c3d_input, nullptr, s) : proj_impl<float>(g, c3d_input, nullptr, s);
+  const int rc = RGP_BY_DTYPE(g->dtype, proj_impl, g, c3d_input, nullptr, s);
   g->prof.end(pid, s);
   return rc;
 }
@@ -533,7 +485,7 @@ int rgp_convgru_xconv_fwd(rgp_grcn_t* g, rgp_stream_t stream) {
   RGP_TRY(check_ready(g));
   hipStream_t s = (hipStream_t)stream;
   const int pid = g->prof.begin(1, s);
-  const int rc = g->dtype == RGP_BF16 ? xconv_impl<bf16_t>(g, s) : xconv_impl<float>(g, s);
+  const int rc = RGP_BY_DTYPE(g->dtype, xconv_impl, g, s);
   g->prof.end(pid, s);
   return rc;
 }
@@ -542,7 +494,7 @@ int rgp_convgru_seq_fwd(rgp_grcn_t* g, rgp_stream_t stream) {
   RGP_TRY(check_ready(g));
   hipStream_t s = (hipStream_t)stream;
   const int pid = g->prof.begin(2, s);
-  const int rc = g->dtype == RGP_BF16 ? seq_impl<bf16_t>(g, s) : seq_impl<float>(g, s);
+  const int rc = RGP_BY_DTYPE(g->dtype, seq_impl, g, s);
   g->prof.end(pid, s);
   return rc;
 }
@@ -552,7 +504,7 @@ int rgp_head_fwd(rgp_grcn_t* g, float* logits, rgp_stream_t stream) {
   RGP_REQUIRE(logits, "rgp_head_fwd: null logits");
   hipStream_t s = (hipStream_t)stream;
   const int pid = g->prof.begin(3, s);
-  const int rc = g->dtype == RGP_BF16 ? head_impl<bf16_t>(g, logits, s) : head_impl<float>(g, logits, s);
+  const int rc = RGP_BY_DTYPE(g->dtype, head_impl, g, logits, s);
   g->prof.end(pid, s);
   return rc;
 }
@@ -579,7 +531,7 @@ int rgp_grcn_forward_rows(rgp_grcn_t* g, const void* c3d_rows, float* logits, fl
   RGP_REQUIRE(c3d_rows && logits, "rgp_grcn_forward_rows: null argument");
   hipStream_t s = (hipStream_t)stream;
   const int pid = g->prof.begin(0, s);
-  RGP_TRY(g->dtype == RGP_BF16 ? proj_impl<bf16_t>(g, nullptr, c3d_rows, s) : proj_impl<float>(g, nullptr, c3d_rows, s));
+  RGP_TRY(RGP_BY_DTYPE(g->dtype, proj_impl, g, nullptr, c3d_rows, s));
   g->prof.end(pid, s);
   return grcn_tail(g, logits, probs, stream);
 }

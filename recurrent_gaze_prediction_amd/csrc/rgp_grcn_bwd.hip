@@ -12,24 +12,21 @@
 #include <algorithm>
 #include <cstring>
 
-#include "bwd_kernels.hip.h"
 #include "rgp_grcn_plan.h"
 #include "wgrad_launch.h"
 #include "convgru_bptt.hip.h"
-#include "head_fold.hip.h"
 
 using namespace rgp;
 
 struct GrcnBwd {
   ConvDesc b_d2, b_d1, b_c, b_zr, b_x;     // dgrad convolutions
-  ConvDesc b_px;                           // projection input gradient: d rows = dE x W^T
-  ConvDesc b_hf;                           // folded head (head_fold.hip.h): dy = Pm x K, rows = (frame, 7x7 position), K = 384
-  Buf pm, dkf, dhf, dhp;                   // its patches [F*49][384] T, dK [384][S], dH [11,11,64] and dH's 25 partial sums, fp32
+  ProjectionBwd pb;                        // projection input gradient: d rows = dE x W^T (gaze_stages.h; its b_px only)
+  FoldedHeadBwd hb;                        // folded head: dy = Pm x K (unfolded plans: its dz, frame_sum and dgp only)
   // gather tables [ntaps][Mw] (element offsets, -1 = zero) + offsets in the workspace
   std::vector<int> t_y, t_pad3S, t_pad2S, koff_c;
   size_t o_y = 0, o_pad3S = 0, o_pad2S = 0, o_koff_c = 0;
   long long M = 0, M2 = 0, Mp = 0, M2p = 0;
-  Buf dz, frame_sum, dgp, gp, dd2, dd1, dy, dh_head, dh_carry, drh, dcp_pad, dzr_pad, dxpre, dxpre_pad, dE;
+  Buf gp, dd2, dd1, dy, dh_head, dh_carry, drh, dcp_pad, dzr_pad, dxpre, dxpre_pad, dE;
   Buf xch_c, xch_z, xch_r, bptt_cnt;       // persistent BPTT kernel (convgru_bptt.hip.h): exchange images + phase counters
   Buf hp_all, rhp_all, dzb, ptoep, sq_partial;   // dzb / ptoep: blocked dz and the Toeplitz partial sums of the head filter gradient     // halo-padded h_{t-1} and r.h_{t-1} of every step, [t][b][9][9][S] (wgrad operands)
   rgp_grcn_weights w;   // forward weights (device fp32) as last set
@@ -170,9 +167,9 @@ int backward_impl(rgp_grcn* g, const float* probs, const float* logits, const fl
     }
   }
   RGP_TRY(zb.add(ws + b->dE.off, (size_t)P * sizeof(T)));                                  // dE's zero row
-  if (!g->fold_head) RGP_TRY(zb.add(ws + b->dgp.off, b->dgp.bytes));                     // (the folded path overwrites dgp)
+  if (!g->fold_head) RGP_TRY(zb.add(ws + b->hb.dgp.off, b->hb.dgp.bytes));               // (the folded path overwrites dgp)
   // (buffers that only one later kernel of this call adds into: cleared here with the rest, in the one launch)
-  if (g->fold_head && !ext_dy) RGP_TRY(zb.add(ws + b->dkf.off, b->dkf.bytes));           // dK: the wgrad's atomics
+  if (g->fold_head && !ext_dy) RGP_TRY(zb.add(ws + b->hb.dkf.off, b->hb.dkf.bytes));     // dK: the wgrad's atomics
   if (persistent) RGP_TRY(zb.add(ws + b->bptt_cnt.off, b->bptt_cnt.bytes));             // phase counters: zeroed EVERY call
   if (ext_dy) {                                                                          // (the unused head's gradients)
     RGP_TRY(zb.add((void*)gr->up_weight3, (size_t)49 * 12 * 32 * 4));
@@ -188,48 +185,34 @@ int backward_impl(rgp_grcn* g, const float* probs, const float* logits, const fl
     if (!stepwise) RGP_HIP(hipMemcpyAsync(Fp(b->dy), ext_dy, (size_t)M * S * 4, hipMemcpyDeviceToDevice, s));
   } else {
   // 1. d loss / d logits, d out_b
-  dlogits_kernel<<<F, 256, 0, s>>>(loss_l2 ? logits : probs, labels, Fp(b->dz), Fp(b->frame_sum), 2401, 1.0f / (float)F, loss_l2);
-  sum_kernel<<<1, 256, 0, s>>>(Fp(b->frame_sum), (float*)gr->out_b, F, 1.0f);
+  RGP_TRY(b->hb.loss_grad(ws, logits, probs, labels, loss_l2, F, (float*)gr->out_b, s));
   if (g->fold_head) {
     // 2'-4'. the folded head (head_fold.hip.h): patches of dz -> dK (one wgrad launch: rows = the 7x7 positions, X = the
     // patches, dY = the padded BN(h) image, as deconv1's filter gradient) -> chain rule through the fold -> dy = Pm x K
-    const long long tot = M * HF_PK;
-    head_fold_patches_kernel<T><<<(int)std::min<long long>((tot + 255) / 256, 8192), 256, 0, s>>>(Fp(b->dz), Tp(b->pm), M);
-    RGP_HIP(hipGetLastError());
+    RGP_TRY(b->hb.patches<T>(ws, F, s));
     {
       WgradParams p = wg_params();
-      p.X = Tp(b->pm); p.dY = Tp(g->hbn); p.dW = Fp(b->dkf);
+      p.X = Tp(b->hb.pm); p.dY = Tp(g->hbn); p.dW = Fp(b->hb.dkf);
       wgrad_grid(p, 1, 7, 7);
       p.x_sx = HF_PK; p.x_sy = 7 * HF_PK; p.x_img_stride = 49LL * HF_PK;
       p.y_sx = S; p.y_sy = 9 * S; p.y_org = 10 * S; p.y_img_stride = 81LL * S;
       p.koff = I(b->o_koff_c); p.M = M; p.N = S; p.nk = HF_PK / Elem<T>::BKE; p.ldw = S; p.k_valid = HF_PK;
       RGP_TRY((launch_wgrad<T, 1>(p, s)));
     }
-    const float* hf = (const float*)(ws + g->hf_h.off);
-    const float* gf = (const float*)(ws + g->gfold.off);
     hipStream_t sc = s;                                          // the chain's stream
     if (fork) {
       RGP_HIP(hipEventRecord(b->ev_fork, s));                    // dK is complete, the gradient buffers are zeroed
       RGP_HIP(hipStreamWaitEvent(b->side, b->ev_fork, 0));
       sc = b->side;
     }
-    head_unfold_f1_kernel<<<(25 * 64 * S + 255) / 256, 256, 0, sc>>>(Fp(b->dkf), hf, (float*)gr->up_weight1, S);
-    head_unfold_h_kernel<<<dim3(HF_HP * HF_HP, 25), 256, 0, sc>>>(Fp(b->dkf), b->w.up_weight1, Fp(b->dhp), S);
-    head_fold_sum_kernel<<<(HF_HP * HF_HP * 64 + 255) / 256, 256, 0, sc>>>(Fp(b->dhp), Fp(b->dhf), HF_HP * HF_HP * 64, 25);
-    head_unfold_f2_kernel<<<(25 * 32 * 64 + 255) / 256, 256, 0, sc>>>(Fp(b->dhf), gf, (float*)gr->up_weight2);
-    head_unfold_g_kernel<<<49, 256, 0, sc>>>(Fp(b->dhf), b->w.up_weight2, Fp(b->dgp));
-    head_unfold_grads_kernel<<<1, 256, 0, sc>>>(Fp(b->dgp), b->w.up_weight3, b->w.out_W, (float*)gr->up_weight3, (float*)gr->out_W);
-    RGP_HIP(hipGetLastError());
-    {
-      IgemmParams p = make_params(b->b_hf, Tp(b->pm), ws, F);
-      EpiParams e = make_epi(b->b_hf, Fp(b->dy), ws);
-      RGP_TRY((launch_igemm<T, 1, 1, EpiStore<float, false, false>>(p, e, s)));
-    }
+    RGP_TRY(b->hb.unfold_chain(ws, g->head, b->w.up_weight1, b->w.up_weight2, b->w.up_weight3, b->w.out_W, (float*)gr->up_weight1,
+                               (float*)gr->up_weight2, (float*)gr->up_weight3, (float*)gr->out_W, sc));
+    RGP_TRY((b->hb.dgrad<T, float>(ws, F, Fp(b->dy), s)));
   } else {
   // 2. folded 7x7 filter: wgrad -> dF3, d out_W ; dgrad -> dd2
   {
     const long long tot = (long long)F * 49 * 64;
-    dz_block_kernel<T><<<(int)std::min<long long>((tot + 255) / 256, 4096), 256, 0, s>>>(Fp(b->dz), Tp(b->dzb), tot);
+    dz_block_kernel<T><<<(int)std::min<long long>((tot + 255) / 256, 4096), 256, 0, s>>>(Fp(b->hb.dz), Tp(b->dzb), tot);
     RGP_HIP(hipGetLastError());
     RGP_HIP(hipMemsetAsync(ws + b->ptoep.off, 0, (size_t)7 * 16 * 704 * 4, s));
     WgradParams p = wg_params();
@@ -244,11 +227,11 @@ int backward_impl(rgp_grcn* g, const float* probs, const float* logits, const fl
     p.nz = 7;
     for (int u = 0; u < 7; ++u) { p.zy[u] = (long long)u * 55 * 32 * sizeof(T); p.zw[u] = (long long)u * 16 * 704; }
     RGP_TRY((launch_wgrad<T, 1>(p, s)));
-    head_fold_toeplitz_kernel<<<(49 * 32 + 255) / 256, 256, 0, s>>>(Fp(b->ptoep), Fp(b->dgp));
+    head_fold_toeplitz_kernel<<<(49 * 32 + 255) / 256, 256, 0, s>>>(Fp(b->ptoep), Fp(b->hb.dgp));
     RGP_HIP(hipGetLastError());
   }
-  head_unfold_grads_kernel<<<1, 256, 0, s>>>(Fp(b->dgp), b->w.up_weight3, b->w.out_W, (float*)gr->up_weight3, (float*)gr->out_W);
-  head_fold_dgrad_kernel<T><<<dim3(7, F), 256, 0, s>>>(Fp(b->dz), Fp(b->gp), Tp(b->dd2));
+  head_unfold_grads_kernel<<<1, 256, 0, s>>>(Fp(b->hb.dgp), b->w.up_weight3, b->w.out_W, (float*)gr->up_weight3, (float*)gr->out_W);
+  head_fold_dgrad_kernel<T><<<dim3(7, F), 256, 0, s>>>(Fp(b->hb.dz), Fp(b->gp), Tp(b->dd2));
   RGP_HIP(hipGetLastError());
   // 3. deconv2: wgrad (dF2[a,b,o,c] = sum dd2[2i+a,2j+b,o] d1[i,j,c]) and dgrad
   {  // rows = the 23x23 positions of d1; X = dd2 at the stride-2 row origins (taps of b_d2), dY = the padded d1 image
@@ -426,7 +409,7 @@ int backward_impl(rgp_grcn* g, const float* probs, const float* logits, const fl
   }
   {
     WgradParams p = wg_params();
-    p.X = Tp(g->xt); p.dY = Tp(b->dE); p.dW = (float*)gr->proj_c3d_W;
+    p.X = Tp(g->pj.xt); p.dY = Tp(b->dE); p.dW = (float*)gr->proj_c3d_W;
     wgrad_grid(p, 1, 1, (int)M);
     p.x_sx = 1024; p.y_sx = P; p.y_org = P;
     p.koff = I(b->o_koff_c); p.M = M; p.N = P; p.nk = 1024 / Elem<T>::BKE; p.ldw = P; p.k_valid = 1024;
@@ -453,8 +436,7 @@ int pack_impl(rgp_grcn* g, const rgp_grcn_weights* w, hipStream_t s, hipStream_t
   const int S = g->S, P = g->P;
   PackBatch<T> pk(ws, s);                                                     // one launch for the ten packs
   // (no memset: the areas are zero from bind time outside the positions a pack writes, rgp_grcn.hip set_weights_impl)
-  RGP_TRY(pk.add(b->b_px, w->proj_c3d_W, 512, 0));            // d = 0: feature channels 0, 2, 4, ...
-  RGP_TRY(pk.add(b->b_px, w->proj_c3d_W + P, 512, 512));      // d = 1: feature channels 1, 3, 5, ...
+  RGP_TRY(b->pb.pack(pk, w->proj_c3d_W));
   if (!g->fold_head) {
     RGP_TRY(pk.add(b->b_d2, w->up_weight2, 64, 0));
     RGP_TRY(pk.add(b->b_d1, w->up_weight1, S, 0));
@@ -468,10 +450,10 @@ int pack_impl(rgp_grcn* g, const rgp_grcn_weights* w, hipStream_t s, hipStream_t
   RGP_TRY(pk.flush());
   if (g->fold_head) {                                          // K of the folded head: set_weights_impl built it on stream sc
     PackBatch<T> pk2(ws, sc);
-    RGP_TRY(pk2.add(b->b_hf, (const float*)(ws + g->hf_k.off), S, 0));
+    RGP_TRY(b->hb.pack(pk2, g->head.k(ws)));
     RGP_TRY(pk2.flush());
   }
-  // Gp[u,v,c] = G[6-u,6-v,c] in fp32 for the folded-filter dgrad (G itself is in g->gfold)
+  // Gp[u,v,c] = G[6-u,6-v,c] in fp32 for the folded-filter dgrad (G itself is in g->head.gfold)
   // (49*32 elements; reuse the pack kernel with T=float semantics is overkill: tiny copy kernel)
   return RGP_OK;
 }
@@ -529,22 +511,10 @@ int grcn_bwd_plan(rgp_grcn* g, Arena& a) {
   ok &= dgrad3x3(b->b_c, S, S, S, S);
   ok &= dgrad3x3(b->b_zr, 2 * S, S, S, S);
   ok &= dgrad3x3(b->b_x, 3 * S, P, P, P);
-  {  // d rows[m][d*512+c] = sum_p dE[m][p] W[c*2+d][p]   (gaze_grcn.py:225-254; rows order of rgp_c3d_forward)
-    ConvDesc& d = b->b_px;
-    d.Mw = 1; d.N = 1024; d.in_img_stride = P; d.out_img_stride = 1024; d.in_tab = {0}; d.out_tab = {0};
-    ok &= build_k_schedule(d, {0}, {0}, P, dtype);
-    d.s_tap = 0; d.s_n = 2LL * P; d.s_c = 1;
-  }
-  {  // folded head: dy[(f,m,n), s] = sum_k Pm[(f,m,n), k] K[k, s]   (head_fold.hip.h; K [361][S] fp32, rows 361..383 zero)
-    ConvDesc& d = b->b_hf;
-    d.Mw = 49; d.N = S; d.in_img_stride = 49LL * HF_PK; d.out_img_stride = 49LL * S;
-    for (int pos = 0; pos < 49; ++pos) { d.in_tab.push_back(pos * HF_PK); d.out_tab.push_back(pos * S); }
-    ok &= build_k_schedule(d, {0}, {0}, HF_PK, dtype);
-    d.cin_src = HF_KP * HF_KP;
-    d.s_tap = 0; d.s_n = 1; d.s_c = S;
-  }
+  ok &= b->pb.plan(P, dtype);                // (gaze_grcn.py:225-254)
+  ok &= b->hb.plan(S, dtype);
   if (!ok) return set_err(RGP_EINVAL, "rgp_grcn_create: backward K schedule failed");
-  for (ConvDesc* d : {&b->b_d2, &b->b_d1, &b->b_c, &b->b_zr, &b->b_x, &b->b_px, &b->b_hf}) d->reserve(a, dtype);
+  for (ConvDesc* d : {&b->b_d2, &b->b_d1, &b->b_c, &b->b_zr, &b->b_x, &b->pb.b_px, &b->hb.b_hf}) d->reserve(a, dtype);
 
   // ---- small tables
   for (int y = 0; y < 7; ++y) for (int x = 0; x < 7; ++x) {
@@ -557,15 +527,15 @@ int grcn_bwd_plan(rgp_grcn* g, Arena& a) {
 
   // ---- buffers
   const size_t st = (size_t)B * 49 * S * 4;
-  b->dz = take(a, (size_t)F * 2401 * 4);
-  b->frame_sum = take(a, (size_t)F * 4);
-  b->dgp = take(a, 50 * 32 * 4);
+  b->hb.dz = take(a, FoldedHeadBwd::dz_bytes(F));
+  b->hb.frame_sum = take(a, (size_t)F * 4);
+  b->hb.dgp = take(a, FoldedHeadBwd::DG_BYTES);
   b->gp = take(a, 50 * 32 * 4);
   if (g->fold_head) {
-    b->pm = take(a, (size_t)F * 49 * HF_PK * es);
-    b->dkf = take(a, (size_t)HF_PK * S * 4);
-    b->dhf = take(a, (size_t)HF_HP * HF_HP * 64 * 4);
-    b->dhp = take(a, (size_t)25 * HF_HP * HF_HP * 64 * 4);
+    b->hb.pm = take(a, FoldedHeadBwd::pm_bytes(F, dtype));
+    b->hb.dkf = take(a, FoldedHeadBwd::dk_bytes(S));
+    b->hb.dhf = take(a, FoldedHeadBwd::DH_BYTES);
+    b->hb.dhp = take(a, FoldedHeadBwd::DHP_BYTES);
   } else {
     b->dd2 = take(a, (size_t)F * 2401 * 32 * es + 4096);
     b->dd1 = take(a, (size_t)F * 529 * 64 * es + 4096);
@@ -597,7 +567,7 @@ int grcn_bwd_plan(rgp_grcn* g, Arena& a) {
 
 int grcn_bwd_upload(rgp_grcn* g, hipStream_t s) {
   GrcnBwd* b = g->bwd;
-  for (ConvDesc* d : {&b->b_d2, &b->b_d1, &b->b_c, &b->b_zr, &b->b_x, &b->b_px, &b->b_hf}) RGP_TRY(upload_desc(*d, g->ws, s));
+  for (ConvDesc* d : {&b->b_d2, &b->b_d1, &b->b_c, &b->b_zr, &b->b_x, &b->pb.b_px, &b->hb.b_hf}) RGP_TRY(upload_desc(*d, g->ws, s));
   auto up = [&](const std::vector<int>& t, size_t off) -> int {
     RGP_HIP(hipMemcpyAsync(g->ws + off, t.data(), t.size() * 4, hipMemcpyHostToDevice, s));
     return RGP_OK;
@@ -609,8 +579,8 @@ int grcn_bwd_upload(rgp_grcn* g, hipStream_t s) {
 
 int grcn_bwd_pack(rgp_grcn* g, const rgp_grcn_weights* w, hipStream_t s, hipStream_t sc) {
   g->bwd->w = *w;
-  RGP_TRY(g->dtype == RGP_BF16 ? pack_impl<bf16_t>(g, w, s, sc) : pack_impl<float>(g, w, s, sc));
-  flip_fold_kernel<<<(49 * 32 + 255) / 256, 256, 0, sc>>>((const float*)(g->ws + g->gfold.off), (float*)(g->ws + g->bwd->gp.off));
+  RGP_TRY(RGP_BY_DTYPE(g->dtype, pack_impl, g, w, s, sc));
+  flip_fold_kernel<<<(49 * 32 + 255) / 256, 256, 0, sc>>>((const float*)(g->ws + g->head.gfold.off), (float*)(g->ws + g->bwd->gp.off));
   RGP_HIP(hipGetLastError());
   return RGP_OK;
 }
@@ -655,24 +625,16 @@ int rgp_grcn_backward(rgp_grcn_t* g, const float* logits, const float* probs, co
   RGP_TRY(grcn_check_error(g));
   RGP_REQUIRE(loss_type == 0 || loss_type == 1, "rgp_grcn_backward: loss_type %d (0 xentropy, 1 l2)", loss_type);
   RGP_REQUIRE(loss_type == 1 || probs, "rgp_grcn_backward: xentropy needs the softmax maps");
-  const float* const* ptrs = (const float* const*)grads;
-  for (size_t i = 0; i < sizeof(rgp_grcn_weights) / sizeof(float*); ++i)
-    RGP_REQUIRE(ptrs[i], "rgp_grcn_backward: gradient pointer %zu is null", i);
-  hipStream_t s = (hipStream_t)stream;
-  return g->dtype == RGP_BF16 ? backward_impl<bf16_t>(g, probs, logits, labels, grads, loss_type, s)
-                              : backward_impl<float>(g, probs, logits, labels, grads, loss_type, s);
+  RGP_TRY(require_pointers(grads, "rgp_grcn_backward", "gradient"));
+  return RGP_BY_DTYPE(g->dtype, backward_impl, g, probs, logits, labels, grads, loss_type, (hipStream_t)stream);
 }
 
 int rgp_grcn_backward_from_states(rgp_grcn_t* g, const float* d_states, const rgp_grcn_weights* grads, rgp_stream_t stream) {
   RGP_REQUIRE(g && d_states && grads, "rgp_grcn_backward_from_states: null argument");
   if (!g->ws || !g->save || !g->bwd || !g->weights_set)
     return set_err(RGP_ESTATE, "rgp_grcn_backward_from_states: needs a save_for_backward plan with weights and a forward");
-  const float* const* ptrs = (const float* const*)grads;
-  for (size_t i = 0; i < sizeof(rgp_grcn_weights) / sizeof(float*); ++i)
-    RGP_REQUIRE(ptrs[i], "rgp_grcn_backward_from_states: gradient pointer %zu is null", i);
-  hipStream_t s = (hipStream_t)stream;
-  return g->dtype == RGP_BF16 ? backward_impl<bf16_t>(g, nullptr, nullptr, nullptr, grads, 0, s, d_states)
-                              : backward_impl<float>(g, nullptr, nullptr, nullptr, grads, 0, s, d_states);
+  RGP_TRY(require_pointers(grads, "rgp_grcn_backward_from_states", "gradient"));
+  return RGP_BY_DTYPE(g->dtype, backward_impl, g, nullptr, nullptr, nullptr, grads, 0, (hipStream_t)stream, d_states);
 }
 
 int rgp_grcn_persistent_workgroups(const rgp_grcn_t* g) {
@@ -695,12 +657,8 @@ int rgp_grcn_wait_grads(rgp_grcn_t* g, int group, rgp_stream_t waiting_stream) {
 int rgp_grcn_backward_input(rgp_grcn_t* g, float* d_rows, rgp_stream_t stream) {
   RGP_REQUIRE(g && d_rows, "rgp_grcn_backward_input: null argument");
   if (!g->ws || !g->save || !g->bwd || !g->weights_set) return set_err(RGP_ESTATE, "rgp_grcn_backward_input: call after rgp_grcn_backward");
-  hipStream_t s = (hipStream_t)stream;
-  GrcnBwd* b = g->bwd;
-  IgemmParams p = make_params(b->b_px, g->ws + b->dE.off + (size_t)g->P * esize(g->dtype), g->ws, (int)b->M);
-  EpiParams e = make_epi(b->b_px, d_rows, g->ws);
-  return g->dtype == RGP_BF16 ? launch_igemm<bf16_t, 1, 1, EpiStore<float, false, false>>(p, e, s)
-                              : launch_igemm<float, 1, 1, EpiStore<float, false, false>>(p, e, s);
+  GrcnBwd* b = g->bwd;                                         // (dE: behind its zero row)
+  return b->pb.backward_input(g->ws, g->dtype, g->ws + b->dE.off + (size_t)g->P * esize(g->dtype), b->M, d_rows, (hipStream_t)stream);
 }
 
 int rgp_adam_clip_step(float* params, const float* grads, float* m, float* v, long long n, float* workspace, int step,

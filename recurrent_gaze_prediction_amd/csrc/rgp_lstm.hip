@@ -17,22 +17,21 @@
 #include <algorithm>
 #include <string>
 
-#include "bwd_kernels.hip.h"
-#include "rgp_grcn_plan.h"
+#include "gaze_stages.h"
 #include "wgrad_launch.h"
 #include "convlstm_seq.hip.h"
 #include "convlstm_bptt.hip.h"
 #include "lstm_kernels.hip.h"
-#include "head_fold.hip.h"
-#include "c3dconv_bwd.hip.h"
 
 using namespace rgp;
 
 struct rgp_lstm {
   int B = 0, T = 0, P = 512, S = 128, dtype = RGP_BF16, F = 0;
   bool save = false, fwd_done = false, bwd_done = false, weights_set = false;
-  ConvDesc proj, proj_rows, xconv, grec, hfold;
-  Buf xt, E, xpre, hall, call, gates, hseq, peep, gfold, hf_h, hf_k, hf_z, hf_part;
+  Projection pj;                           // gaze_stages.h
+  FoldedHead head;                         // on h_t: a GEMM "image" is a clip
+  ConvDesc xconv, grec;
+  Buf E, xpre, hall, call, gates, hseq, peep;
   Buf xch, seq_cnt, bptt_xch, bptt_cnt;
   SeqGroupPlan sg;                         // groups of the persistent kernels (none = per-step launches), error word, fault bits
   bool fwd_persistent = false;             // the plan selected convlstm_seq_kernel ...
@@ -41,12 +40,12 @@ struct rgp_lstm {
   char* ws = nullptr;
   const float *proj_b = nullptr, *out_b = nullptr;
   // ---- training plans
-  long long M = 0, Mp = 0;
-  int ksplit = 1;
-  ConvDesc b_rec, b_x, b_px, b_hf, wg_w;
+  FoldedHeadBwd hb;
+  ProjectionBwd pb;                        // with the GEMM-form weight gradients, as gaze_c3d_conv
+  ConvDesc b_rec, b_x;
   std::vector<int> koff_c;
   size_t o_koff_c = 0;
-  Buf dz, frame_sum, pm, dkf, dhf, dhp, dgp, dy, dh_carry, dc_carry, dpre, dE, xT, part;
+  Buf dy, dh_carry, dc_carry, dpre, dE;
   rgp_lstm_weights w;
 };
 
@@ -73,9 +72,7 @@ int lstm_check_error(rgp_lstm* g) {
 }
 
 int check_ready(rgp_lstm* g) {
-  if (!g) return set_err(RGP_EINVAL, "null plan");
-  if (!g->ws) return set_err(RGP_EWORKSPACE, "rgp_lstm: workspace not bound");
-  if (!g->weights_set) return set_err(RGP_ESTATE, "rgp_lstm: weights not set");
+  RGP_TRY(check_bound_and_set(g, "rgp_lstm"));
   return lstm_check_error(g);
 }
 
@@ -84,8 +81,7 @@ int set_weights_impl(rgp_lstm* g, const rgp_lstm_weights* w, hipStream_t s) {
   char* ws = g->ws;
   const int P = g->P, S = g->S;
   PackBatch<T> pk(ws, s);
-  RGP_TRY(pk.add(g->proj, w->proj_c3d_W, P, 0));
-  RGP_TRY(pk.add(g->proj_rows, w->proj_c3d_W, P, 0));
+  RGP_TRY(g->pj.pack(pk, w->proj_c3d_W));
   // gate-interleaved columns 4 c + q (lstm_kernels.hip.h): x parts q = i, f, g, o; recurrent q = 0 W_hi, 1 W_hf, 3 W_ho
   RGP_TRY(pk.add(g->xconv, w->W_xi, S, 0, 0, 0, 4));
   RGP_TRY(pk.add(g->xconv, w->W_xf, S, 1, 0, 0, 4));
@@ -95,8 +91,7 @@ int set_weights_impl(rgp_lstm* g, const rgp_lstm_weights* w, hipStream_t s) {
   RGP_TRY(pk.add(g->grec, w->W_hf, S, 1, 0, 0, 4));
   RGP_TRY(pk.add(g->grec, w->W_ho, S, 3, 0, 0, 4));
   if (g->save) {
-    RGP_TRY(pk.add(g->b_px, w->proj_c3d_W, 512, 0));            // d = 0: feature channels 0, 2, 4, ...
-    RGP_TRY(pk.add(g->b_px, w->proj_c3d_W + P, 512, 512));      // d = 1: feature channels 1, 3, 5, ...
+    RGP_TRY(g->pb.pack(pk, w->proj_c3d_W));
     RGP_TRY(pk.add(g->b_rec, w->W_hi, S, 0, 0, 1));             // rotated filters on [d(i+g) | df | do]
     RGP_TRY(pk.add(g->b_rec, w->W_hf, S, 0, S, 1));
     RGP_TRY(pk.add(g->b_rec, w->W_ho, S, 0, 2 * S, 1));
@@ -113,18 +108,10 @@ int set_weights_impl(rgp_lstm* g, const rgp_lstm_weights* w, hipStream_t s) {
   RGP_HIP(hipMemcpyAsync(pp + 49 * S, w->W_cf, pb, hipMemcpyDeviceToDevice, s));
   RGP_HIP(hipMemcpyAsync(pp + 98 * S, w->W_co, pb, hipMemcpyDeviceToDevice, s));
   // the head as one 19x19 stride-6 transposed convolution on h_t (head_fold.hip.h; no batch-norm in this graph)
-  float* gf = (float*)(ws + g->gfold.off);
-  float* hf = (float*)(ws + g->hf_h.off);
-  float* kf = (float*)(ws + g->hf_k.off);
-  float* part = (float*)(ws + g->hf_part.off);
-  fold_head_filter_kernel<<<(49 * 32 + 255) / 256, 256, 0, s>>>(w->up_weight3, w->out_W, gf, 49, 12, 32);
-  head_fold_h_kernel<<<(HF_HP * HF_HP * 64 + 255) / 256, 256, 0, s>>>(gf, w->up_weight2, hf);
-  head_fold_k_kernel<<<dim3(HF_KP * HF_KP, 5), 128, 0, s>>>(hf, w->up_weight1, part, S);
-  head_fold_sum_kernel<<<(HF_KP * HF_KP * S + 255) / 256, 256, 0, s>>>(part, kf, HF_KP * HF_KP * S, 5);
-  RGP_HIP(hipGetLastError());
+  RGP_TRY(g->head.fold(ws, w->up_weight3, w->out_W, w->up_weight2, w->up_weight1, s));
   PackBatch<T> pk2(ws, s);
-  RGP_TRY(pk2.add(g->hfold, kf, HF_KP * HF_KP, 0));             // GEMM filter [(r,t)][s]; rows 361 .. 383 stay zero
-  if (g->save) RGP_TRY(pk2.add(g->b_hf, kf, S, 0));
+  RGP_TRY(g->head.pack(pk2));
+  if (g->save) RGP_TRY(g->hb.pack(pk2, g->head.k(ws)));
   RGP_TRY(pk2.flush());
   g->proj_b = w->proj_c3d_b;
   g->out_b = w->out_b;
@@ -204,55 +191,17 @@ int bptt_persistent(rgp_lstm* g, hipStream_t s) {
 template <typename T>
 int forward_impl(rgp_lstm* g, const float* c3d_input, const void* rows, float* logits, float* probs, hipStream_t s) {
   char* ws = g->ws;
-  const void* A = rows;
-  if (!rows) {
-    nchw_to_rows_kernel<T><<<dim3(1024 / 64, g->F), 256, 0, s>>>(c3d_input, (T*)(ws + g->xt.off), 1024);
-    RGP_HIP(hipGetLastError());
-    A = ws + g->xt.off;
-  } else if (g->save) {
-    const long long total = (long long)g->F * 49 * 1024;
-    rows_to_xt_kernel<T><<<(int)std::min<long long>((total + 255) / 256, 8192), 256, 0, s>>>((const T*)rows, (T*)(ws + g->xt.off), total);
-    RGP_HIP(hipGetLastError());
-  }
-  {
-    const ConvDesc& d = rows ? g->proj_rows : g->proj;
-    IgemmParams p = make_params(d, A, ws, g->F);
-    EpiParams e = make_epi(d, ws + g->E.off, ws);
-    e.bias = g->proj_b;
-    RGP_TRY((launch_igemm<T, 1, 1, EpiStore<T, true, false>>(p, e, s)));
-  }
+  RGP_TRY(g->pj.forward<T>(ws, c3d_input, rows, g->save, g->F, ws + g->E.off, g->proj_b, s));
   {
     IgemmParams p = make_params(g->xconv, ws + g->E.off, ws, g->F);
     EpiParams e = make_epi(g->xconv, ws + g->xpre.off, ws);
     RGP_TRY((launch_igemm<T, 1, 1, EpiStore<float, false, false>>(p, e, s)));
   }
   RGP_TRY(seq_impl<T>(g, s));
-  {
-    IgemmParams p = make_params(g->hfold, ws + g->hseq.off, ws, g->B);
-    EpiParams e = make_epi(g->hfold, ws + g->hf_z.off, ws);
-    RGP_TRY((launch_igemm<T, 1, 1, EpiStore<float, false, false>>(p, e, s)));
-  }
-  const long long total = (long long)g->F * 2401;
-  head_col2im_kernel<<<(int)std::min<long long>((total + 255) / 256, 8192), 256, 0, s>>>((const float*)(ws + g->hf_z.off), g->out_b, logits, total);
-  RGP_HIP(hipGetLastError());
+  RGP_TRY(g->head.forward<T>(ws, ws + g->hseq.off, g->B, g->out_b, logits, g->F, s));
   if (probs) RGP_TRY(rgp_softmax_xent_fwd(logits, nullptr, probs, nullptr, nullptr, g->F, 2401, (rgp_stream_t)s));
   g->fwd_done = true;
   g->bwd_done = false;
-  return RGP_OK;
-}
-
-// one filter gradient as a GEMM over the rows (c3dconv_bwd.hip.h): K = Mp split ksplit ways, partial sums stored and
-// added in a fixed order
-template <typename T>
-int wgrad_gemm(rgp_lstm* g, const ConvDesc& d, const void* AT, float* out, hipStream_t s) {
-  char* ws = g->ws;
-  IgemmParams p = make_params(d, AT, ws, 1);
-  EpiParams e = make_epi(d, ws + g->part.off, ws);
-  const long long n = (long long)d.Mw * g->P;
-  e.xpre_img_stride = n;
-  RGP_TRY((launch_igemm<T, 1, 1, EpiStoreSplitF32>(p, e, s, g->ksplit)));
-  head_fold_sum_kernel<<<(int)((n + 255) / 256), 256, 0, s>>>((const float*)(ws + g->part.off), out, (int)n, g->ksplit);
-  RGP_HIP(hipGetLastError());
   return RGP_OK;
 }
 
@@ -261,7 +210,7 @@ int backward_impl(rgp_lstm* g, const float* logits, const float* probs, const fl
                   int loss_l2, hipStream_t s) {
   char* ws = g->ws;
   const int B = g->B, T_ = g->T, S = g->S, P = g->P, F = g->F;
-  const long long M = g->M, Mp = g->Mp;
+  const long long M = g->pb.M;
   const size_t st = (size_t)B * 49 * S;
   auto Fp = [&](const Buf& x) { return (float*)(ws + x.off); };
   auto Tp = [&](const Buf& x) { return (T*)(ws + x.off); };
@@ -272,39 +221,25 @@ int backward_impl(rgp_lstm* g, const float* logits, const float* probs, const fl
     ZeroBatch zb(s);
     for (const float* q : {gr->W_xi, gr->W_xf, gr->W_xc, gr->W_xo}) RGP_TRY(zb.add((void*)q, (size_t)9 * P * S * 4));
     for (const float* q : {gr->W_hi, gr->W_hf, gr->W_ho, gr->W_hc}) RGP_TRY(zb.add((void*)q, (size_t)9 * S * S * 4));
-    RGP_TRY(zb.add(ws + g->dkf.off, g->dkf.bytes));
+    RGP_TRY(zb.add(ws + g->hb.dkf.off, g->hb.dkf.bytes));
     RGP_TRY(zb.flush());
   }
   // 1. d loss / d logits, d out_b
-  dlogits_kernel<<<F, 256, 0, s>>>(loss_l2 ? logits : probs, labels, Fp(g->dz), Fp(g->frame_sum), 2401, 1.0f / (float)F, loss_l2);
-  sum_kernel<<<1, 256, 0, s>>>(Fp(g->frame_sum), (float*)gr->out_b, F, 1.0f);
+  RGP_TRY(g->hb.loss_grad(ws, logits, probs, labels, loss_l2, F, (float*)gr->out_b, s));
   // 2. the folded head with y := h (head_fold.hip.h): patches of dz -> dK -> chain rule; dh_head = Pm x K
-  const long long tot = M * HF_PK;
-  head_fold_patches_kernel<T><<<(int)std::min<long long>((tot + 255) / 256, 8192), 256, 0, s>>>(Fp(g->dz), Tp(g->pm), M);
-  RGP_HIP(hipGetLastError());
+  RGP_TRY(g->hb.patches<T>(ws, F, s));
   {
     WgradParams p = wg_params();
-    p.X = Tp(g->pm); p.dY = Tp(g->hseq); p.dW = Fp(g->dkf);
+    p.X = Tp(g->hb.pm); p.dY = Tp(g->hseq); p.dW = Fp(g->hb.dkf);
     wgrad_grid(p, T_, 7, 7);                                    // image = clip, z = step: h_t is slot t+1 of the clip's images
     p.x_sx = HF_PK; p.x_sy = 7 * HF_PK; p.x_sz = 49 * HF_PK; p.x_img_stride = (long long)T_ * 49 * HF_PK;
     p.y_sx = S; p.y_sy = 9 * S; p.y_sz = 81 * S; p.y_org = (81 + 10) * S; p.y_img_stride = (long long)(T_ + 1) * 81 * S;
     p.koff = I(g->o_koff_c); p.M = M; p.N = S; p.nk = HF_PK / Elem<T>::BKE; p.ldw = S; p.k_valid = HF_PK;
     RGP_TRY((launch_wgrad<T, 1>(p, s)));
   }
-  const float* hf = (const float*)(ws + g->hf_h.off);
-  const float* gf = (const float*)(ws + g->gfold.off);
-  head_unfold_f1_kernel<<<(25 * 64 * S + 255) / 256, 256, 0, s>>>(Fp(g->dkf), hf, (float*)gr->up_weight1, S);
-  head_unfold_h_kernel<<<dim3(HF_HP * HF_HP, 25), 256, 0, s>>>(Fp(g->dkf), g->w.up_weight1, Fp(g->dhp), S);
-  head_fold_sum_kernel<<<(HF_HP * HF_HP * 64 + 255) / 256, 256, 0, s>>>(Fp(g->dhp), Fp(g->dhf), HF_HP * HF_HP * 64, 25);
-  head_unfold_f2_kernel<<<(25 * 32 * 64 + 255) / 256, 256, 0, s>>>(Fp(g->dhf), gf, (float*)gr->up_weight2);
-  head_unfold_g_kernel<<<49, 256, 0, s>>>(Fp(g->dhf), g->w.up_weight2, Fp(g->dgp));
-  head_unfold_grads_kernel<<<1, 256, 0, s>>>(Fp(g->dgp), g->w.up_weight3, g->w.out_W, (float*)gr->up_weight3, (float*)gr->out_W);
-  RGP_HIP(hipGetLastError());
-  {
-    IgemmParams p = make_params(g->b_hf, Tp(g->pm), ws, F);
-    EpiParams e = make_epi(g->b_hf, Fp(g->dy), ws);
-    RGP_TRY((launch_igemm<T, 1, 1, EpiStore<float, false, false>>(p, e, s)));
-  }
+  RGP_TRY(g->hb.unfold_chain(ws, g->head, g->w.up_weight1, g->w.up_weight2, g->w.up_weight3, g->w.out_W, (float*)gr->up_weight1,
+                             (float*)gr->up_weight2, (float*)gr->up_weight3, (float*)gr->out_W, s));
+  RGP_TRY((g->hb.dgrad<T, float>(ws, F, Fp(g->dy), s)));
   // 3. BPTT, t = T-1 .. 0: element-wise step, then dh_{t-1} = rotated [W_hi | W_hf | W_ho] on [d(i+g) | df | do]
   bool bptt_one_launch = false;
   if constexpr (sizeof(T) == 2) {
@@ -363,13 +298,7 @@ int backward_impl(rgp_lstm* g, const float* logits, const float* probs, const fl
     EpiParams e = make_epi(g->b_x, Tp(g->dE), ws);
     RGP_TRY((launch_igemm<T, 1, 1, EpiStore<T, false, false>>(p, e, s)));
   }
-  T* deT = (T*)(ws + g->wg_w.w_off);
-  c3dconv_transpose_kernel<T><<<dim3((unsigned)(Mp / 64), P / 64), 256, 0, s>>>(Tp(g->dE), deT, M, P, Mp);
-  c3dconv_transpose_kernel<T><<<dim3((unsigned)(Mp / 64), 1024 / 64), 256, 0, s>>>(Tp(g->xt), Tp(g->xT), M, 1024, Mp);
-  RGP_HIP(hipGetLastError());
-  RGP_TRY(wgrad_gemm<T>(g, g->wg_w, Tp(g->xT), (float*)gr->proj_c3d_W, s));
-  rowsum_kernel<T><<<P, 256, 0, s>>>(deT, (float*)gr->proj_c3d_b, Mp, M);
-  RGP_HIP(hipGetLastError());
+  RGP_TRY(g->pb.weight_grads<T>(ws, Tp(g->pj.xt), Tp(g->dE), (float*)gr->proj_c3d_W, (float*)gr->proj_c3d_b, s));
   g->bwd_done = true;
   return RGP_OK;
 }
@@ -416,16 +345,7 @@ int rgp_lstm_create(rgp_lstm_t** plan, int batch, int n_steps, int dtype, int fl
   g->save = (flags & RGP_LSTM_SAVE_FOR_BACKWARD) != 0;
   const int P = g->P, S = g->S, F = g->F, T_ = n_steps, es = esize(dtype);
   bool ok = true;
-  for (ConvDesc* d : {&g->proj, &g->proj_rows}) {              // E = X W + b (gaze_lstm.py:238-244), halo-padded 9x9xP
-    d->Mw = 49; d->N = P;
-    d->in_img_stride = 49LL * 1024; d->out_img_stride = 81LL * P;
-    for (int p = 0; p < 49; ++p) d->in_tab.push_back(p * 1024);
-    d->out_tab = pad_tab9(P);
-  }
-  ok &= build_k_schedule(g->proj, {0}, {0}, 1024, dtype);
-  g->proj.s_tap = 0; g->proj.s_n = 1; g->proj.s_c = P;
-  ok &= build_k_schedule(g->proj_rows, {0, 512}, {0, 1}, 512, dtype);      // rows from C3D: K order d*512+c, channel c*2+d
-  g->proj_rows.s_tap = P; g->proj_rows.s_n = 1; g->proj_rows.s_c = 2LL * P;
+  ok &= g->pj.plan(P, dtype, pad_tab9(P), 81LL * P);           // E = X W + b (gaze_lstm.py:238-244), halo-padded 9x9xP
   auto conv3x3 = [&](ConvDesc& d, int Cin) {                   // 3x3 SAME on a padded 9x9 image, N = 4 S interleaved columns
     d.Mw = 49; d.N = 4 * S;
     for (int y = 0; y < 7; ++y) for (int x = 0; x < 7; ++x) d.in_tab.push_back((y * 9 + x) * Cin);
@@ -442,21 +362,20 @@ int rgp_lstm_create(rgp_lstm_t** plan, int batch, int n_steps, int dtype, int fl
   g->grec.in_img_stride = (long long)(T_ + 1) * 81 * S; g->grec.out_img_stride = g->grec.in_img_stride;
   g->grec.out_tab = pad_tab9(S);
   {
-    ConvDesc& d = g->hfold;                                    // folded head: a GEMM "image" is a clip, rows = (step, 7x7 position)
-    d.Mw = T_ * 49; d.N = HF_PK; d.in_img_stride = (long long)(T_ + 1) * 81 * S; d.out_img_stride = (long long)T_ * 49 * HF_PK;
+    ConvDesc& d = g->head.hfold;                               // folded head: a GEMM "image" is a clip, rows = (step, 7x7 position)
+    d.Mw = T_ * 49; d.in_img_stride = (long long)(T_ + 1) * 81 * S; d.out_img_stride = (long long)T_ * 49 * HF_PK;
     for (int t = 0; t < T_; ++t)
       for (int m = 0; m < 7; ++m) for (int n = 0; n < 7; ++n) {
         d.in_tab.push_back(((t + 1) * 81 + (m + 1) * 9 + n + 1) * S);
         d.out_tab.push_back((t * 49 + m * 7 + n) * HF_PK);
       }
-    ok &= build_k_schedule(d, {0}, {0}, S, dtype);
-    d.s_tap = 0; d.s_n = S; d.s_c = 1;
+    ok &= g->head.plan(S, dtype);
   }
   if (!ok) { delete g; return set_err(RGP_EINVAL, "rgp_lstm_create: K schedule failed"); }
   Arena a;
-  for (ConvDesc* d : {&g->proj, &g->proj_rows, &g->xconv, &g->grec, &g->hfold}) d->reserve(a, dtype);
+  for (ConvDesc* d : {&g->pj.proj, &g->pj.proj_rows, &g->xconv, &g->grec, &g->head.hfold}) d->reserve(a, dtype);
   const size_t st = (size_t)batch * 49 * S * 4;
-  g->xt = take(a, (size_t)F * 49 * 1024 * es);
+  g->pj.xt = take(a, (size_t)F * 49 * 1024 * es);
   g->E = take(a, (size_t)F * 81 * P * es);
   g->xpre = take(a, (size_t)F * 49 * 4 * S * 4);
   g->hall = take(a, st * (T_ + 1));
@@ -464,11 +383,11 @@ int rgp_lstm_create(rgp_lstm_t** plan, int batch, int n_steps, int dtype, int fl
   if (g->save) g->gates = take(a, st * T_ * 4);
   g->hseq = take(a, (size_t)batch * (T_ + 1) * 81 * S * es);
   g->peep = take(a, (size_t)3 * 49 * S * 4);
-  g->gfold = take(a, 50 * 32 * 4);
-  g->hf_h = take(a, (size_t)HF_HP * HF_HP * 64 * 4);
-  g->hf_k = take(a, (size_t)HF_PK * S * 4);
-  g->hf_z = take(a, (size_t)F * 49 * HF_PK * 4);
-  g->hf_part = take(a, (size_t)5 * HF_KP * HF_KP * S * 4);
+  g->head.gfold = take(a, FoldedHead::G_BYTES);
+  g->head.hf_h = take(a, FoldedHead::H_BYTES);
+  g->head.hf_k = take(a, g->head.k_bytes(HF_PK));
+  g->head.hf_z = take(a, FoldedHead::z_bytes(F));
+  g->head.hf_part = take(a, g->head.part_bytes());
   // persistent kernels: bf16 operands, up to 2 clips per group of 8 workgroups, at most 32 groups.  The forward's flags and
   // the BPTT's are independent of each other; the groups are sized if either kernel is selected.
   const bool eligible = dtype == RGP_BF16 && batch <= 64;
@@ -484,10 +403,7 @@ int rgp_lstm_create(rgp_lstm_t** plan, int batch, int n_steps, int dtype, int fl
     g->bptt_cnt = take(a, (size_t)g->sg.groups * T_ * 4);
   }
   if (g->save) {
-    g->M = (long long)F * 49;
-    g->Mp = (g->M + 63) / 64 * 64;
-    g->ksplit = std::min(16, (int)(g->Mp / bke(dtype)));
-    bool okb = g->Mp * 1024 < (1LL << 31);
+    bool okb = true;
     // 3x3 SAME input gradients: correlation of the padded gradient image (pixel stride 5 S) with the rotated, in/out-swapped filters
     auto dgrad3x3 = [&](ConvDesc& d, int Cgrad, int Nout, int filt_cin, long long in_stride) {
       d.Mw = 49; d.N = Nout; d.in_img_stride = in_stride; d.out_img_stride = 49LL * Nout;
@@ -501,44 +417,27 @@ int rgp_lstm_create(rgp_lstm_t** plan, int batch, int n_steps, int dtype, int fl
     };
     okb &= dgrad3x3(g->b_rec, 3 * S, S, S, (long long)T_ * 81 * 5 * S);
     okb &= dgrad3x3(g->b_x, 5 * S, P, P, 81LL * 5 * S);
-    {
-      ConvDesc& d = g->b_px;                                   // d rows[m][d*512+c] = sum_p dE[m][p] W[c*2+d][p]
-      d.Mw = 1; d.N = 1024; d.in_img_stride = P; d.out_img_stride = 1024; d.in_tab = {0}; d.out_tab = {0};
-      okb &= build_k_schedule(d, {0}, {0}, P, dtype);
-      d.s_tap = 0; d.s_n = 2LL * P; d.s_c = 1;
-    }
-    {
-      ConvDesc& d = g->b_hf;                                   // dh[(f,m,n), s] = sum_k Pm[(f,m,n), k] K[k, s]
-      d.Mw = 49; d.N = S; d.in_img_stride = 49LL * HF_PK; d.out_img_stride = 49LL * S;
-      for (int pos = 0; pos < 49; ++pos) { d.in_tab.push_back(pos * HF_PK); d.out_tab.push_back(pos * S); }
-      okb &= build_k_schedule(d, {0}, {0}, HF_PK, dtype);
-      d.cin_src = HF_KP * HF_KP;
-      d.s_tap = 0; d.s_n = 1; d.s_c = S;
-    }
-    if (okb) {
-      ConvDesc& d = g->wg_w;                                   // d proj_c3d_W [1024][P] = XT [1024][Mp] x dET [P][Mp]^T
-      d.Mw = 1024; d.N = P; d.in_img_stride = 0; d.out_img_stride = 0;
-      for (int r = 0; r < 1024; ++r) { d.in_tab.push_back((int)(r * g->Mp)); d.out_tab.push_back(r * P); }
-      okb &= build_k_schedule(d, {0}, {0}, (int)g->Mp, dtype);
-    }
+    okb &= g->pb.plan(P, dtype);
+    okb &= g->hb.plan(S, dtype);                               // dh[(f,m,n), s] = sum_k Pm[(f,m,n), k] K[k, s]
+    okb = okb && g->pb.plan_wgrad(F, dtype);                   // d proj_c3d_W [1024][P] = XT [1024][Mp] x dET [P][Mp]^T
     if (!okb) { delete g; return set_err(RGP_EINVAL, "rgp_lstm_create: B*T too large for the backward plan"); }
-    for (ConvDesc* d : {&g->b_rec, &g->b_x, &g->b_px, &g->b_hf, &g->wg_w}) d->reserve(a, dtype);
+    for (ConvDesc* d : {&g->b_rec, &g->b_x, &g->pb.b_px, &g->hb.b_hf, &g->pb.wg_w}) d->reserve(a, dtype);
     for (int k = 0; k < HF_PK / bke(dtype); ++k) g->koff_c.push_back(k * bke(dtype));
     g->o_koff_c = a.take(g->koff_c.size() * 4);
-    g->dz = take(a, (size_t)F * 2401 * 4);
-    g->frame_sum = take(a, (size_t)F * 4);
-    g->pm = take(a, (size_t)g->M * HF_PK * es);
-    g->dkf = take(a, (size_t)HF_PK * S * 4);
-    g->dhf = take(a, (size_t)HF_HP * HF_HP * 64 * 4);
-    g->dhp = take(a, (size_t)25 * HF_HP * HF_HP * 64 * 4);
-    g->dgp = take(a, 50 * 32 * 4);
-    g->dy = take(a, (size_t)g->M * S * 4);
+    g->hb.dz = take(a, FoldedHeadBwd::dz_bytes(F));
+    g->hb.frame_sum = take(a, (size_t)F * 4);
+    g->hb.pm = take(a, FoldedHeadBwd::pm_bytes(F, dtype));
+    g->hb.dkf = take(a, FoldedHeadBwd::dk_bytes(S));
+    g->hb.dhf = take(a, FoldedHeadBwd::DH_BYTES);
+    g->hb.dhp = take(a, FoldedHeadBwd::DHP_BYTES);
+    g->hb.dgp = take(a, FoldedHeadBwd::DG_BYTES);
+    g->dy = take(a, (size_t)g->pb.M * S * 4);
     g->dh_carry = take(a, st);
     g->dc_carry = take(a, st);
     g->dpre = take(a, (size_t)F * 81 * 5 * S * es);
-    g->dE = take(a, (size_t)g->M * P * es);
-    g->xT = take(a, (size_t)1024 * g->Mp * es);
-    g->part = take(a, (size_t)g->ksplit * 1024 * P * 4);
+    g->dE = take(a, (size_t)g->pb.M * P * es);
+    g->pb.xT = take(a, g->pb.xT_bytes(dtype));
+    g->pb.part = take(a, g->pb.part_bytes());
   }
   g->ws_bytes = a.off;
   *plan = g;
@@ -554,9 +453,7 @@ int rgp_lstm_destroy(rgp_lstm_t* plan) {
 size_t rgp_lstm_workspace_bytes(const rgp_lstm_t* plan) { return plan ? plan->ws_bytes : 0; }
 
 int rgp_lstm_bind_workspace(rgp_lstm_t* g, void* workspace, size_t bytes, rgp_stream_t stream) {
-  RGP_REQUIRE(g && workspace, "rgp_lstm_bind_workspace: null argument");
-  if (bytes < g->ws_bytes) return set_err(RGP_EWORKSPACE, "workspace %zu < required %zu bytes", bytes, g->ws_bytes);
-  RGP_REQUIRE(((size_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+  RGP_TRY(check_bind("rgp_lstm_bind_workspace", g, workspace, bytes));
   hipStream_t s = (hipStream_t)stream;
   RGP_TRY(g->sg.alloc_err());
   g->ws = (char*)workspace;
@@ -564,9 +461,9 @@ int rgp_lstm_bind_workspace(rgp_lstm_t* g, void* workspace, size_t bytes, rgp_st
   // zero everything once: the halos of E / h images / dpre, slot 0 of the states and the unused filter rows stay zero,
   // because kernels only ever write interiors and a pack writes the same positions every time
   RGP_HIP(hipMemsetAsync(g->ws, 0, g->ws_bytes, s));
-  for (ConvDesc* d : {&g->proj, &g->proj_rows, &g->xconv, &g->grec, &g->hfold}) RGP_TRY(upload_desc(*d, g->ws, s));
+  for (ConvDesc* d : {&g->pj.proj, &g->pj.proj_rows, &g->xconv, &g->grec, &g->head.hfold}) RGP_TRY(upload_desc(*d, g->ws, s));
   if (g->save) {
-    for (ConvDesc* d : {&g->b_rec, &g->b_x, &g->b_px, &g->b_hf, &g->wg_w}) RGP_TRY(upload_desc(*d, g->ws, s));
+    for (ConvDesc* d : {&g->b_rec, &g->b_x, &g->pb.b_px, &g->hb.b_hf, &g->pb.wg_w}) RGP_TRY(upload_desc(*d, g->ws, s));
     RGP_HIP(hipMemcpyAsync(g->ws + g->o_koff_c, g->koff_c.data(), g->koff_c.size() * 4, hipMemcpyHostToDevice, s));
   }
   return RGP_OK;
@@ -575,28 +472,21 @@ int rgp_lstm_bind_workspace(rgp_lstm_t* g, void* workspace, size_t bytes, rgp_st
 int rgp_lstm_set_weights(rgp_lstm_t* g, const rgp_lstm_weights* w, rgp_stream_t stream) {
   RGP_REQUIRE(g && w, "rgp_lstm_set_weights: null argument");
   if (!g->ws) return set_err(RGP_EWORKSPACE, "rgp_lstm: workspace not bound");
-  const float* const* ptrs = (const float* const*)w;
-  for (size_t i = 0; i < sizeof(rgp_lstm_weights) / sizeof(float*); ++i)
-    RGP_REQUIRE(ptrs[i], "rgp_lstm_set_weights: weight pointer %zu is null", i);
-  hipStream_t s = (hipStream_t)stream;
-  return g->dtype == RGP_BF16 ? set_weights_impl<bf16_t>(g, w, s) : set_weights_impl<float>(g, w, s);
+  RGP_TRY(require_pointers(w, "rgp_lstm_set_weights", "weight"));
+  return RGP_BY_DTYPE(g->dtype, set_weights_impl, g, w, (hipStream_t)stream);
 }
 
 int rgp_lstm_forward(rgp_lstm_t* g, const float* c3d_input, float* logits, float* probs, rgp_stream_t stream) {
   RGP_TRY(check_ready(g));
   RGP_REQUIRE(c3d_input && logits, "rgp_lstm_forward: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  return g->dtype == RGP_BF16 ? forward_impl<bf16_t>(g, c3d_input, nullptr, logits, probs, s)
-                              : forward_impl<float>(g, c3d_input, nullptr, logits, probs, s);
+  return RGP_BY_DTYPE(g->dtype, forward_impl, g, c3d_input, nullptr, logits, probs, (hipStream_t)stream);
 }
 
 int rgp_lstm_forward_rows(rgp_lstm_t* g, const void* c3d_rows, float* logits, float* probs, rgp_stream_t stream) {
   RGP_TRY(check_ready(g));
   RGP_REQUIRE(c3d_rows && logits, "rgp_lstm_forward_rows: null argument");
   RGP_REQUIRE(((size_t)c3d_rows & 15) == 0, "rgp_lstm_forward_rows: rows must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  return g->dtype == RGP_BF16 ? forward_impl<bf16_t>(g, nullptr, c3d_rows, logits, probs, s)
-                              : forward_impl<float>(g, nullptr, c3d_rows, logits, probs, s);
+  return RGP_BY_DTYPE(g->dtype, forward_impl, g, nullptr, c3d_rows, logits, probs, (hipStream_t)stream);
 }
 
 int rgp_lstm_backward(rgp_lstm_t* g, const float* logits, const float* probs, const float* labels, const rgp_lstm_weights* grads,
@@ -606,22 +496,14 @@ int rgp_lstm_backward(rgp_lstm_t* g, const float* logits, const float* probs, co
   RGP_REQUIRE(loss_type == 1 ? logits != nullptr : probs != nullptr, "rgp_lstm_backward: the loss needs %s", loss_type == 1 ? "logits" : "probs");
   if (!g->save) return set_err(RGP_ESTATE, "rgp_lstm_backward: the plan was not created with RGP_LSTM_SAVE_FOR_BACKWARD");
   if (!g->fwd_done) return set_err(RGP_ESTATE, "rgp_lstm_backward: no forward since the weights were set");
-  const float* const* ptrs = (const float* const*)grads;
-  for (size_t i = 0; i < sizeof(rgp_lstm_weights) / sizeof(float*); ++i)
-    RGP_REQUIRE(ptrs[i], "rgp_lstm_backward: gradient pointer %zu is null", i);
-  hipStream_t s = (hipStream_t)stream;
-  return g->dtype == RGP_BF16 ? backward_impl<bf16_t>(g, logits, probs, labels, grads, loss_type, s)
-                              : backward_impl<float>(g, logits, probs, labels, grads, loss_type, s);
+  RGP_TRY(require_pointers(grads, "rgp_lstm_backward", "gradient"));
+  return RGP_BY_DTYPE(g->dtype, backward_impl, g, logits, probs, labels, grads, loss_type, (hipStream_t)stream);
 }
 
 int rgp_lstm_backward_input(rgp_lstm_t* g, float* d_rows, rgp_stream_t stream) {
   RGP_REQUIRE(g && d_rows, "rgp_lstm_backward_input: null argument");
   if (!g->ws || !g->save || !g->weights_set || !g->bwd_done) return set_err(RGP_ESTATE, "rgp_lstm_backward_input: call after rgp_lstm_backward");
-  hipStream_t s = (hipStream_t)stream;
-  IgemmParams p = make_params(g->b_px, g->ws + g->dE.off, g->ws, (int)g->M);
-  EpiParams e = make_epi(g->b_px, d_rows, g->ws);
-  return g->dtype == RGP_BF16 ? launch_igemm<bf16_t, 1, 1, EpiStore<float, false, false>>(p, e, s)
-                              : launch_igemm<float, 1, 1, EpiStore<float, false, false>>(p, e, s);
+  return g->pb.backward_input(g->ws, g->dtype, g->ws + g->dE.off, g->pb.M, d_rows, (hipStream_t)stream);
 }
 
 int rgp_lstm_status(rgp_lstm_t* g, rgp_stream_t stream) {
@@ -668,7 +550,7 @@ int rgp_lstm_read_buffer(rgp_lstm_t* g, const char* name, float* dst, rgp_stream
   } else {
     const long long total = (long long)v.elems;
     const int blocks = (int)std::min<long long>((total + 255) / 256, 8192);
-    const int* tab = (const int*)(g->ws + g->proj.out_tab_off);
+    const int* tab = (const int*)(g->ws + g->pj.proj.out_tab_off);
     if (g->dtype == RGP_BF16) unpad_kernel<bf16_t><<<blocks, 256, 0, s>>>((const bf16_t*)(g->ws + v.off), dst, tab, 49, g->P, 81LL * g->P, total);
     else unpad_kernel<float><<<blocks, 256, 0, s>>>((const float*)(g->ws + v.off), dst, tab, 49, g->P, 81LL * g->P, total);
   }

@@ -157,8 +157,192 @@ class DropoutSite(object):
         _lib.check(self._set(ctypes.c_float(self.keep_prob), _ptr(self.mask)))
 
 
-class GrcnEngine(object):
+def _flat_layout(names, shapes, untrained=()):
+    """[(name, offset, numel)] of a flat fp32 buffer holding `names` in order, those in `untrained` left out."""
+    out, off = [], 0
+    for k in names:
+        if k in untrained:
+            continue
+        n = int(np.prod(shapes[k]))
+        out.append((k, off, n))
+        off += n
+    return out
+
+
+def _flat_views(names, like, device, untrained=()):
+    """One flat fp32 buffer + per-variable views (one all-reduce bucket, one optimizer launch).  like: {name: tensor of
+    the variable's shape}.  Variables in `untrained` get zeros of their own OUTSIDE the flat buffer.
+    Returns (flat, {name: view} in the order of names)."""
+    shapes = {k: tuple(like[k].shape) for k in names}
+    layout = _flat_layout(names, shapes, untrained)
+    flat = torch.zeros(sum(n for _, _, n in layout), dtype=torch.float32, device=device)
+    views = {k: flat[off:off + n].view(shapes[k]) for k, off, n in layout}
+    for k in untrained:
+        views[k] = torch.zeros(shapes[k], dtype=torch.float32, device=device)
+    return flat, {k: views[k] for k in names}
+
+
+def _struct(struct_cls, fields, views):
+    """struct_cls with the device pointers of views; fields: {name in views: field of the struct}."""
+    st = struct_cls()
+    for k, f in fields.items():
+        setattr(st, f, views[k].data_ptr())
+    return st
+
+
+class _GazeEngine(object):
+    """What the three gaze-family engines share: the owner of one rgp_<family>_ plan, its workspace and the flat fp32
+    master buffers.  A subclass names the C prefix, the parameter -> field map, the weights struct and the variables
+    kept out of the flat buffers, and creates the plan with _create()."""
+    PREFIX = PARAM_TO_FIELD = WEIGHTS = None
+    UNTRAINED = ()
+
+    def _create(self, batch, n_steps, dtype, save_for_backward, device, *create_args):
+        """Common part of __init__; create_args: the arguments of rgp_<family>_create behind the plan pointer."""
+        self.lib = _lib.load()
+        self.device = _require_gpu(device)
+        self.B, self.T = int(batch), int(n_steps)
+        self.dtype = dtype
+        self.save_for_backward = bool(save_for_backward)
+        self.torch_dtype = torch.bfloat16 if _lib.DTYPES[dtype] == _lib.RGP_BF16 else torch.float32
+        self.flat_params = self.flat_grads = self.grads = self.weights = None
+        # the family's entry points by their name behind the prefix (resolved once: the training step is host-bound)
+        self._f = {k[len(self.PREFIX):]: getattr(self.lib, k) for k in _lib.SIGNATURES if k.startswith(self.PREFIX)}
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['create'](ctypes.byref(self._h), *create_args))
+            nbytes = self._f['workspace_bytes'](self._h)
+            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _lib.check(self._f['bind_workspace'](self._h, _ptr(self.workspace), nbytes, _stream_ptr(self.device)))
+
+    def __del__(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h:
+            self._f['destroy'](h)
+
+    def _check_shapes(self, src):
+        """Hook: assert what the plan's geometry fixes about the parameters' shapes."""
+
+    def set_weights(self, params):
+        """params: dict keyed by the reference's TF variable names (scope stripped) -> array/tensor (fp32).
+        The values are copied into the engine's flat fp32 master buffer, then packed / folded (repack)."""
+        src = {k: _as_dev_f32(params[k], self.device) for k in self.PARAM_TO_FIELD}
+        self._check_shapes(src)
+        if self.weights is None:
+            self.flat_params, self.weights = _flat_views(self.PARAM_TO_FIELD, src, self.device, self.UNTRAINED)
+        for k in self.PARAM_TO_FIELD:
+            self.weights[k].copy_(src[k])
+        self.repack()
+
+    def repack(self):
+        """Re-pack the master weights into MFMA operand form (after set_weights / an optimizer step)."""
+        st = _struct(self.WEIGHTS, self.PARAM_TO_FIELD, self.weights)   # the plan keeps raw pointers to biases / BN: views stay alive
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['set_weights'](self._h, ctypes.byref(st), _stream_ptr(self.device)))
+
+    def backward(self, logits, probs, labels, loss_type='xentropy'):
+        """Gradients of the reference loss (gaze_rnn.py:363-408) w.r.t. every variable, after a
+        forward() on the same inputs.  labels: normalised gt maps [B,T,49,49] fp32 device tensor.
+        Returns {TF variable name: fp32 gradient view}; the flat buffer is self.flat_grads."""
+        # (GrcnEngine used to leave this check, and the contiguity of forward_rows' rows, to the library: no caller relied on it)
+        assert self.save_for_backward, 'create the engine with save_for_backward=True'
+        assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
+        if self.grads is None:
+            self.flat_grads, self.grads = _flat_views(self.PARAM_TO_FIELD, self.weights, self.device, self.UNTRAINED)
+        st = _struct(self.WEIGHTS, self.PARAM_TO_FIELD, self.grads)
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['backward'](self._h, _ptr(logits), _ptr(probs), _ptr(labels), ctypes.byref(st),
+                                           {'xentropy': 0, 'l2': 1}[loss_type], _stream_ptr(self.device)))
+        return self.grads
+
+    def grad_buckets(self):
+        """[(slice of flat_grads, ready)]: one bucket, complete when backward() returns on the launch stream."""
+        return [(self.flat_grads, lambda stream: stream.wait_stream(torch.cuda.current_stream(self.device)))]
+
+    def backward_input(self, out=None):
+        """After backward(): d loss / d input as conv5b rows [B*T*49, 1024] fp32 (column d*512+c), the
+        gradient C3DEngine.backward(d_rows=...) consumes when the conv stack is fine-tuned."""
+        d = out if out is not None else torch.empty(self.B * self.T * 49, 1024, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['backward_input'](self._h, _ptr(d), _stream_ptr(self.device)))
+        return d
+
+    def adam_step(self, step, lr, max_grad_norm=10.0, method='adam'):
+        """clip_by_global_norm + the chosen optimizer of base.py:268-273 on the flat buffers (the trained variables
+        only), then repack."""
+        return clip_step_multi([self], step, lr, max_grad_norm, method)
+
+    def _outputs(self, want_probs, out_logits, out_probs):
+        logits = out_logits if out_logits is not None else torch.empty(self.B, self.T, 49, 49, device=self.device)
+        probs = None
+        if want_probs:
+            probs = out_probs if out_probs is not None else torch.empty_like(logits)
+        return logits, probs
+
+    def forward(self, c3d_input, want_probs=True, out_logits=None, out_probs=None):
+        """c3d_input [B,T,1024,7,7] fp32 device tensor -> (logits, probs) [B,T,49,49]."""
+        x = c3d_input
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        assert tuple(x.shape) == (self.B, self.T, 1024, 7, 7), tuple(x.shape)
+        logits, probs = self._outputs(want_probs, out_logits, out_probs)
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['forward'](self._h, _ptr(x), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
+        return logits, probs
+
+    def forward_rows(self, rows, want_probs=True, out_logits=None, out_probs=None):
+        """rows: conv5b rows from C3DEngine.forward (operand dtype, [B*T*49, 1024], column d*512+c)."""
+        assert rows.is_cuda and rows.dtype == self.torch_dtype and rows.is_contiguous()
+        assert rows.numel() == self.B * self.T * 49 * 1024
+        logits, probs = self._outputs(want_probs, out_logits, out_probs)
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['forward_rows'](self._h, _ptr(rows), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
+        return logits, probs
+
+    def read_buffer_elems(self, name):
+        """fp32 elements read_buffer(name) returns; 0 = this plan has no such intermediate."""
+        return int(self._f['buffer_elems'](self._h, name.encode()))
+
+    def read_buffer(self, name):
+        n = self.read_buffer_elems(name)
+        if n == 0:
+            raise _lib.RgpError('unknown intermediate %r' % name)
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['read_buffer'](self._h, name.encode(), _ptr(out), _stream_ptr(self.device)))
+        return out
+
+
+class _PersistentEngine(_GazeEngine):
+    """... with a recurrence that may run as a persistent launch (gaze_grcn, gaze_lstm; gaze_c3d_conv has none, and the
+    models ask an engine for `status` / `persistent` with getattr)."""
+
+    def status(self):
+        """Wait for the current stream and raise RgpError (RGP_ETIMEOUT) if a persistent launch of this plan lost a
+        group member since the last check (its outputs are NaN)."""
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['status'](self._h, _stream_ptr(self.device)))
+
+    @property
+    def persistent_workgroups(self):
+        """CUs a persistent sequence launch of this plan occupies (0: the recurrence runs as per-timestep launches)."""
+        with torch.cuda.device(self.device):
+            return int(self._f['persistent_workgroups'](self._h))
+
+    @property
+    def persistent(self):
+        return self.persistent_workgroups > 0
+
+    def inject_fault(self, kind='seq'):
+        """Test hook (rgp_<family>_inject_fault): the next persistent launch of the forward ('seq') or of the BPTT
+        ('bptt') loses a group member."""
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['inject_fault'](self._h, {'seq': _lib.RGP_FAULT_SEQ_LOST_MEMBER,
+                                                         'bptt': _lib.RGP_FAULT_BPTT_LOST_MEMBER}[kind]))
+
+
+class GrcnEngine(_PersistentEngine):
     """gaze_grcn graph (models/gaze_grcn.py:173-376) at fixed (B, T, P, S, dtype)."""
+    PREFIX, PARAM_TO_FIELD, WEIGHTS = 'rgp_grcn_', GRCN_PARAM_TO_FIELD, _lib.GrcnWeights
 
     def __init__(self, batch, n_steps, dim_proj=512, dim_state=128, dtype='bf16', save_for_backward=False,
                  device='cuda:0', per_step=False, unfolded_head=False):
@@ -167,74 +351,14 @@ class GrcnEngine(object):
         unfolded_head=True: an inference plan that runs the three transposed convolutions one by one
         (RGP_GRCN_UNFOLDED_HEAD) instead of their exact fold into one GEMM (csrc/head_fold.hip.h); training plans
         always do."""
-        self.lib = _lib.load()
-        self.device = _require_gpu(device)
-        self.B, self.T, self.P, self.S = int(batch), int(n_steps), int(dim_proj), int(dim_state)
-        self.dtype = dtype
-        self.per_step, self.save_for_backward = bool(per_step), bool(save_for_backward)
-        self.torch_dtype = torch.bfloat16 if _lib.DTYPES[dtype] == _lib.RGP_BF16 else torch.float32
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            flags = (_lib.RGP_GRCN_SAVE_FOR_BACKWARD if save_for_backward else 0) | (_lib.RGP_GRCN_PER_STEP if per_step else 0) | \
-                (_lib.RGP_GRCN_UNFOLDED_HEAD if unfolded_head else 0)
-            _lib.check(self.lib.rgp_grcn_create(ctypes.byref(self._h), self.B, self.T, self.P, self.S,
-                                                _lib.DTYPES[dtype], flags))
-            nbytes = self.lib.rgp_grcn_workspace_bytes(self._h)
-            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.rgp_grcn_bind_workspace(self._h, _ptr(self.workspace), nbytes, _stream_ptr(self.device)))
-        self.weights = None
+        self.P, self.S, self.per_step = int(dim_proj), int(dim_state), bool(per_step)
+        flags = (_lib.RGP_GRCN_SAVE_FOR_BACKWARD if save_for_backward else 0) | (_lib.RGP_GRCN_PER_STEP if per_step else 0) | \
+            (_lib.RGP_GRCN_UNFOLDED_HEAD if unfolded_head else 0)
+        self._create(batch, n_steps, dtype, save_for_backward, device, int(batch), int(n_steps), self.P, self.S,
+                     _lib.DTYPES[dtype], flags)
 
-    def __del__(self):
-        h, self._h = getattr(self, '_h', None), None
-        if h:
-            self.lib.rgp_grcn_destroy(h)
-
-    def _flat_views(self, like):
-        """One flat fp32 buffer + per-variable views (one all-reduce bucket, one Adam launch)."""
-        sizes = [(k, tuple(like[k].shape)) for k in GRCN_PARAM_TO_FIELD]
-        flat = torch.zeros(sum(int(np.prod(s)) for _, s in sizes), dtype=torch.float32, device=self.device)
-        views, off = {}, 0
-        for k, shp in sizes:
-            n = int(np.prod(shp))
-            views[k] = flat[off:off + n].view(shp)
-            off += n
-        return flat, views
-
-    def _struct(self, views):
-        st = _lib.GrcnWeights()
-        for k, f in GRCN_PARAM_TO_FIELD.items():
-            setattr(st, f, views[k].data_ptr())
-        return st
-
-    def set_weights(self, params):
-        """params: dict keyed by the reference's TF variable names -> array/tensor (fp32).
-        The values are copied into the engine's flat fp32 master buffer."""
-        src = {k: _as_dev_f32(params[k], self.device) for k in GRCN_PARAM_TO_FIELD}
+    def _check_shapes(self, src):
         assert tuple(src['bn_gamma'].shape) == (self.T, self.S), 'one batch-norm layer per timestep (SURVEY 9-Q1)'
-        if self.weights is None:
-            self.flat_params, self.weights = self._flat_views(src)
-        for k in GRCN_PARAM_TO_FIELD:
-            self.weights[k].copy_(src[k])
-        self.repack()
-
-    def repack(self):
-        """Re-pack the master weights into MFMA operand form (after set_weights / an optimizer step)."""
-        st = self._struct(self.weights)     # the plan keeps raw pointers to biases / BN: views stay alive
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_grcn_set_weights(self._h, ctypes.byref(st), _stream_ptr(self.device)))
-
-    def backward(self, logits, probs, labels, loss_type='xentropy'):
-        """Gradients of the reference loss (gaze_rnn.py:363-408) w.r.t. every variable, after a
-        forward() on the same inputs.  labels: normalised gt maps [B,T,49,49] fp32 device tensor.
-        Returns {TF variable name: fp32 gradient view}; the flat buffer is self.flat_grads."""
-        assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
-        if getattr(self, 'grads', None) is None:
-            self.flat_grads, self.grads = self._flat_views(self.weights)
-        st = self._struct(self.grads)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_grcn_backward(self._h, _ptr(logits), _ptr(probs), _ptr(labels), ctypes.byref(st),
-                                                  {'xentropy': 0, 'l2': 1}[loss_type], _stream_ptr(self.device)))
-        return self.grads
 
     # gradient groups in the order the backward finishes them (rgp_grcn_wait_grads); each is one contiguous slice of
     # flat_grads because GRCN_PARAM_TO_FIELD lists the variables in this order
@@ -261,14 +385,6 @@ class GrcnEngine(object):
         assert sum(b.numel() for b, _ in out) == self.flat_grads.numel()
         return out
 
-    def backward_input(self, out=None):
-        """After backward(): d loss / d input as conv5b rows [B*T*49, 1024] fp32 (column d*512+c), the
-        gradient C3DEngine.backward(d_rows=...) consumes when the conv stack is fine-tuned."""
-        d = out if out is not None else torch.empty(self.B * self.T * 49, 1024, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_grcn_backward_input(self._h, _ptr(d), _stream_ptr(self.device)))
-        return d
-
     def adam_step(self, step, lr, max_grad_norm=10.0, beta1=0.9, beta2=0.999, eps=1e-8, method='adam'):
         """clip_by_global_norm + TF AdamOptimizer on the flat buffers (base.py:286-297), then repack.
         Returns a 1-element device tensor holding the pre-clip global gradient norm.
@@ -289,71 +405,12 @@ class GrcnEngine(object):
         self.repack()
         return self._gnorm
 
-    def forward(self, c3d_input, want_probs=True, out_logits=None, out_probs=None):
-        """c3d_input [B,T,1024,7,7] fp32 device tensor -> (logits, probs) [B,T,49,49]."""
-        x = c3d_input
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
-        assert tuple(x.shape) == (self.B, self.T, 1024, 7, 7), tuple(x.shape)
-        logits = out_logits if out_logits is not None else torch.empty(self.B, self.T, 49, 49, device=self.device)
-        probs = None
-        if want_probs:
-            probs = out_probs if out_probs is not None else torch.empty_like(logits)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_grcn_forward(self._h, _ptr(x), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
-        return logits, probs
-
-    def forward_rows(self, rows, want_probs=True, out_logits=None, out_probs=None):
-        """rows: conv5b rows from C3DEngine.forward (operand dtype, [B*T*49, 1024])."""
-        assert rows.is_cuda and rows.dtype == self.torch_dtype and rows.numel() == self.B * self.T * 49 * 1024
-        logits = out_logits if out_logits is not None else torch.empty(self.B, self.T, 49, 49, device=self.device)
-        probs = None
-        if want_probs:
-            probs = out_probs if out_probs is not None else torch.empty_like(logits)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_grcn_forward_rows(self._h, _ptr(rows), _ptr(logits), _ptr(probs),
-                                                      _stream_ptr(self.device)))
-        return logits, probs
-
-    def status(self):
-        """Wait for the current stream and raise RgpError (RGP_ETIMEOUT) if a persistent ConvGRU launch of this
-        plan lost a group member since the last check (its outputs are NaN)."""
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_grcn_status(self._h, _stream_ptr(self.device)))
-
-    @property
-    def persistent_workgroups(self):
-        """CUs a persistent ConvGRU / BPTT launch of this plan occupies (0: the recurrence runs as per-timestep launches)."""
-        with torch.cuda.device(self.device):
-            return int(self.lib.rgp_grcn_persistent_workgroups(self._h))
-
-    @property
-    def persistent(self):
-        return self.persistent_workgroups > 0
-
     @property
     def grads_top_early(self):
         """Whether the first gradient bucket (grad_buckets()[0]) is released before the BPTT launch (include/rgp.h: only
         when that launch leaves RGP_RCCL_CU_RESERVE CUs to the collective) or behind it."""
         with torch.cuda.device(self.device):
             return bool(self.lib.rgp_grcn_grads_top_early(self._h))
-
-    def inject_fault(self, kind):
-        """Test hook (rgp_grcn_inject_fault): kind 'seq' / 'bptt' -- the next persistent launch loses a member."""
-        _lib.check(self.lib.rgp_grcn_inject_fault(self._h, {'seq': _lib.RGP_FAULT_SEQ_LOST_MEMBER,
-                                                            'bptt': _lib.RGP_FAULT_BPTT_LOST_MEMBER}[kind]))
-
-    def read_buffer_elems(self, name):
-        """fp32 elements read_buffer(name) returns; 0 = this plan has no such intermediate."""
-        return int(self.lib.rgp_grcn_buffer_elems(self._h, name.encode()))
-
-    def read_buffer(self, name):
-        n = self.lib.rgp_grcn_buffer_elems(self._h, name.encode())
-        if n == 0:
-            raise _lib.RgpError('unknown intermediate %r' % name)
-        out = torch.empty(n, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_grcn_read_buffer(self._h, name.encode(), _ptr(out), _stream_ptr(self.device)))
-        return out
 
     def profile(self, enable=True):
         _lib.check(self.lib.rgp_grcn_profile_enable(self._h, int(enable)))
@@ -372,139 +429,26 @@ C3DCONV_PARAM_TO_FIELD = {   # reference TF variable name (without scope) -> rgp
 }
 
 
-class C3dConvEngine(object):
+class C3dConvEngine(_GazeEngine):
     """gaze_c3d_conv graph (models/gaze_c3d_conv.py:105-218), the no-recurrence baseline, at fixed (B, T, P, dtype).
 
     path=None: the library's choice (bf16 inference plans: the fused kernel, one launch from rows to softmax; everything
     else the staged path); 'fused' / 'staged' force one (RGP_C3DCONV_FUSED / RGP_C3DCONV_STAGED).  Training plans
-    (save_for_backward=True) run the staged path; their backward uses no float atomics (bit-reproducible gradients)."""
+    (save_for_backward=True) run the staged path; their backward uses no float atomics (bit-reproducible gradients,
+    flat_grads fully overwritten).  repack() folds the master weights into the 1024 -> 384 filter and the bias plane (and
+    the staged path's operands).  read_buffer: 'c3d_embedded' [B*T*49, P] (staged plans), 'folded_filter' [384, 1024],
+    'bias_plane' [49, 49] as fp32."""
+    PREFIX, PARAM_TO_FIELD, WEIGHTS = 'rgp_c3dconv_', C3DCONV_PARAM_TO_FIELD, _lib.C3dConvWeights
 
     def __init__(self, batch, n_steps, dim_proj=512, dtype='bf16', save_for_backward=False, device='cuda:0', path=None):
-        self.lib = _lib.load()
-        self.device = _require_gpu(device)
-        self.B, self.T, self.P = int(batch), int(n_steps), int(dim_proj)
-        self.dtype = dtype
-        self.save_for_backward = bool(save_for_backward)
-        self.torch_dtype = torch.bfloat16 if _lib.DTYPES[dtype] == _lib.RGP_BF16 else torch.float32
+        self.P = int(dim_proj)
         flags = {None: 0, 'staged': _lib.RGP_C3DCONV_STAGED, 'fused': _lib.RGP_C3DCONV_FUSED}[path]
         flags |= _lib.RGP_C3DCONV_SAVE_FOR_BACKWARD if save_for_backward else 0
-        self.flat_params = self.flat_grads = self.grads = None
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_c3dconv_create(ctypes.byref(self._h), self.B, self.T, self.P, _lib.DTYPES[dtype], flags))
-            nbytes = self.lib.rgp_c3dconv_workspace_bytes(self._h)
-            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.rgp_c3dconv_bind_workspace(self._h, _ptr(self.workspace), nbytes, _stream_ptr(self.device)))
+        self._create(batch, n_steps, dtype, save_for_backward, device, int(batch), int(n_steps), self.P, _lib.DTYPES[dtype], flags)
         self.path = self.lib.rgp_c3dconv_path(self._h).decode()
-        self.weights = None
 
-    def __del__(self):
-        h, self._h = getattr(self, '_h', None), None
-        if h:
-            self.lib.rgp_c3dconv_destroy(h)
-
-    def _flat_views(self, like):
-        sizes = [(k, tuple(like[k].shape)) for k in C3DCONV_PARAM_TO_FIELD]
-        flat = torch.zeros(sum(int(np.prod(s)) for _, s in sizes), dtype=torch.float32, device=self.device)
-        views, off = {}, 0
-        for k, shp in sizes:
-            n = int(np.prod(shp))
-            views[k] = flat[off:off + n].view(shp)
-            off += n
-        return flat, views
-
-    def _struct(self, views):
-        st = _lib.C3dConvWeights()
-        for k, f in C3DCONV_PARAM_TO_FIELD.items():
-            setattr(st, f, views[k].data_ptr())
-        return st
-
-    def set_weights(self, params):
-        """params: dict keyed by the reference's TF variable names (scope stripped) -> array/tensor (fp32); copied into
-        the engine's flat fp32 master buffer, then folded (repack)."""
-        src = {k: _as_dev_f32(params[k], self.device) for k in C3DCONV_PARAM_TO_FIELD}
+    def _check_shapes(self, src):
         assert tuple(src['proj_c3d_W'].shape) == (1024, self.P) and tuple(src['weight1'].shape) == (5, 5, 64, self.P)
-        if self.weights is None:
-            self.flat_params, self.weights = self._flat_views(src)
-        for k in C3DCONV_PARAM_TO_FIELD:
-            self.weights[k].copy_(src[k])
-        self.repack()
-
-    def repack(self):
-        """Fold the master weights into the 1024 -> 384 filter and the bias plane (and the staged path's operands)."""
-        st = self._struct(self.weights)     # the plan keeps raw pointers to the biases: views stay alive
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_c3dconv_set_weights(self._h, ctypes.byref(st), _stream_ptr(self.device)))
-
-    def backward(self, logits, probs, labels, loss_type='xentropy'):
-        """Gradients of the reference loss (gaze_rnn.py:363-408) w.r.t. the seven variables, after a forward() on the same
-        inputs.  labels: normalised gt maps [B,T,49,49] fp32 device tensor.  Returns {TF variable name: fp32 gradient
-        view}; the flat buffer is self.flat_grads (fully overwritten)."""
-        assert self.save_for_backward, 'create the engine with save_for_backward=True'
-        assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
-        if self.grads is None:
-            self.flat_grads, self.grads = self._flat_views(self.weights)
-        st = self._struct(self.grads)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_c3dconv_backward(self._h, _ptr(logits), _ptr(probs), _ptr(labels), ctypes.byref(st),
-                                                     {'xentropy': 0, 'l2': 1}[loss_type], _stream_ptr(self.device)))
-        return self.grads
-
-    def grad_buckets(self):
-        """[(slice of flat_grads, ready)]: one bucket, complete when backward() returns on the launch stream."""
-        return [(self.flat_grads, lambda stream: stream.wait_stream(torch.cuda.current_stream(self.device)))]
-
-    def backward_input(self, out=None):
-        """After backward(): d loss / d input as conv5b rows [B*T*49, 1024] fp32 (column d*512+c), the gradient
-        C3DEngine.backward(d_rows=...) consumes when the conv stack is fine-tuned."""
-        d = out if out is not None else torch.empty(self.B * self.T * 49, 1024, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_c3dconv_backward_input(self._h, _ptr(d), _stream_ptr(self.device)))
-        return d
-
-    def adam_step(self, step, lr, max_grad_norm=10.0, method='adam'):
-        """clip_by_global_norm + the chosen optimizer of base.py:268-273 on the flat buffers, then repack (re-fold)."""
-        return clip_step_multi([self], step, lr, max_grad_norm, method)
-
-    def _outputs(self, want_probs, out_logits, out_probs):
-        logits = out_logits if out_logits is not None else torch.empty(self.B, self.T, 49, 49, device=self.device)
-        probs = None
-        if want_probs:
-            probs = out_probs if out_probs is not None else torch.empty_like(logits)
-        return logits, probs
-
-    def forward(self, c3d_input, want_probs=True, out_logits=None, out_probs=None):
-        """c3d_input [B,T,1024,7,7] fp32 device tensor -> (logits, probs) [B,T,49,49]."""
-        x = c3d_input
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
-        assert tuple(x.shape) == (self.B, self.T, 1024, 7, 7), tuple(x.shape)
-        logits, probs = self._outputs(want_probs, out_logits, out_probs)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_c3dconv_forward(self._h, _ptr(x), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
-        return logits, probs
-
-    def forward_rows(self, rows, want_probs=True, out_logits=None, out_probs=None):
-        """rows: conv5b rows from C3DEngine.forward (operand dtype, [B*T*49, 1024], column d*512+c)."""
-        assert rows.is_cuda and rows.dtype == self.torch_dtype and rows.is_contiguous()
-        assert rows.numel() == self.B * self.T * 49 * 1024
-        logits, probs = self._outputs(want_probs, out_logits, out_probs)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_c3dconv_forward_rows(self._h, _ptr(rows), _ptr(logits), _ptr(probs),
-                                                         _stream_ptr(self.device)))
-        return logits, probs
-
-    def read_buffer_elems(self, name):
-        return int(self.lib.rgp_c3dconv_buffer_elems(self._h, name.encode()))
-
-    def read_buffer(self, name):
-        """'c3d_embedded' [B*T*49, P] (staged plans), 'folded_filter' [384, 1024], 'bias_plane' [49, 49] as fp32."""
-        n = self.read_buffer_elems(name)
-        if n == 0:
-            raise _lib.RgpError('unknown intermediate %r' % name)
-        out = torch.empty(n, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_c3dconv_read_buffer(self._h, name.encode(), _ptr(out), _stream_ptr(self.device)))
-        return out
 
 
 LSTM_PARAM_TO_FIELD = {   # TF variable name under RGP/ and RGP/RCNBottom/ (scope stripped) -> rgp_lstm_weights field.  TF
@@ -524,143 +468,32 @@ LSTM_UNTRAINED = ('ConvLSTM_Whc',)
 def lstm_flat_layout(shapes):
     """[(name, offset, numel)] of the flat fp32 buffer the clip norm and the optimizer see: every variable of
     LSTM_PARAM_TO_FIELD in order EXCEPT LSTM_UNTRAINED.  shapes: {name: shape}.  Host logic only."""
-    out, off = [], 0
-    for k in LSTM_PARAM_TO_FIELD:
-        if k in LSTM_UNTRAINED:
-            continue
-        n = int(np.prod(shapes[k]))
-        out.append((k, off, n))
-        off += n
-    return out
+    return _flat_layout(LSTM_PARAM_TO_FIELD, shapes, LSTM_UNTRAINED)
 
 
-class LstmEngine(object):
+class LstmEngine(_PersistentEngine):
     """gaze_lstm graph (models/gaze_lstm.py:178-353) at fixed (B, T, dtype): projection, ConvLSTM, up-sampling head.
 
     per_step=True: the recurrence as one launch per timestep (RGP_LSTM_PER_STEP), the library's second implementation;
     otherwise bf16 plans of at most 64 clips run all T steps in one persistent launch (csrc/convlstm_seq.hip.h).
     bptt_persistent=True: the backward-through-time pass of backward() as one persistent launch as well
     (RGP_LSTM_BPTT_PERSISTENT, csrc/convlstm_bptt.hip.h; bf16 training plans of at most 64 clips), whatever the forward runs.
-    flat_params / flat_grads hold the 17 trained variables; W_hc (LSTM_UNTRAINED) lives outside them."""
+    flat_params / flat_grads hold the 17 trained variables; W_hc (LSTM_UNTRAINED) lives outside them: backward() returns
+    zeros for it.  read_buffer: 'h', 'c' (training plans also 'i', 'f', 'g', 'o' and, after a backward, 'd_i', 'd_f', 'd_g',
+    'd_o') [B,T,7,7,128]; 'emb' [B*T*49, 512]; fp32."""
+    PREFIX, PARAM_TO_FIELD, WEIGHTS, UNTRAINED = 'rgp_lstm_', LSTM_PARAM_TO_FIELD, _lib.LstmWeights, LSTM_UNTRAINED
 
     def __init__(self, batch, n_steps, dtype='bf16', save_for_backward=False, device='cuda:0', per_step=False, persistent=False,
                  bptt_persistent=False):
         """persistent=True asks for the persistent kernel by name (RGP_LSTM_PERSISTENT: refused for plans it cannot run);
         with both False the library chooses.  bptt_persistent=False is the library's choice for the BPTT (per step)."""
-        self.lib = _lib.load()
-        self.device = _require_gpu(device)
-        self.B, self.T, self.P, self.S = int(batch), int(n_steps), 512, 128
-        self.dtype = dtype
-        self.per_step, self.save_for_backward = bool(per_step), bool(save_for_backward)
-        self.torch_dtype = torch.bfloat16 if _lib.DTYPES[dtype] == _lib.RGP_BF16 else torch.float32
+        self.P, self.S, self.per_step = 512, 128, bool(per_step)
         flags = (_lib.RGP_LSTM_SAVE_FOR_BACKWARD if save_for_backward else 0) | (_lib.RGP_LSTM_PER_STEP if per_step else 0) | \
             (_lib.RGP_LSTM_PERSISTENT if persistent else 0) | (_lib.RGP_LSTM_BPTT_PERSISTENT if bptt_persistent else 0)
-        self.flat_params = self.flat_grads = self.grads = self.weights = None
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_lstm_create(ctypes.byref(self._h), self.B, self.T, _lib.DTYPES[dtype], flags))
-            nbytes = self.lib.rgp_lstm_workspace_bytes(self._h)
-            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.rgp_lstm_bind_workspace(self._h, _ptr(self.workspace), nbytes, _stream_ptr(self.device)))
+        self._create(batch, n_steps, dtype, save_for_backward, device, int(batch), int(n_steps), _lib.DTYPES[dtype], flags)
 
-    def __del__(self):
-        h, self._h = getattr(self, '_h', None), None
-        if h:
-            self.lib.rgp_lstm_destroy(h)
-
-    def _flat_views(self, like):
-        shapes = {k: tuple(like[k].shape) for k in LSTM_PARAM_TO_FIELD}
-        layout = lstm_flat_layout(shapes)
-        flat = torch.zeros(sum(n for _, _, n in layout), dtype=torch.float32, device=self.device)
-        views = {k: flat[off:off + n].view(shapes[k]) for k, off, n in layout}
-        for k in LSTM_UNTRAINED:
-            views[k] = torch.zeros(shapes[k], dtype=torch.float32, device=self.device)
-        return flat, {k: views[k] for k in LSTM_PARAM_TO_FIELD}
-
-    def _struct(self, views):
-        st = _lib.LstmWeights()
-        for k, f in LSTM_PARAM_TO_FIELD.items():
-            setattr(st, f, views[k].data_ptr())
-        return st
-
-    def set_weights(self, params):
-        src = {k: _as_dev_f32(params[k], self.device) for k in LSTM_PARAM_TO_FIELD}
+    def _check_shapes(self, src):
         assert tuple(src['ConvLSTM_Wxi'].shape) == (3, 3, self.P, self.S) and tuple(src['ConvLSTM_Wci'].shape) == (7, 7, self.S)
-        if self.weights is None:
-            self.flat_params, self.weights = self._flat_views(src)
-        for k in LSTM_PARAM_TO_FIELD:
-            self.weights[k].copy_(src[k])
-        self.repack()
-
-    def repack(self):
-        st = self._struct(self.weights)     # the plan keeps raw pointers to the biases: views stay alive
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_lstm_set_weights(self._h, ctypes.byref(st), _stream_ptr(self.device)))
-
-    def backward(self, logits, probs, labels, loss_type='xentropy'):
-        """Gradients of the reference loss w.r.t. every variable, after a forward() on the same inputs.  Returns
-        {TF variable name: fp32 gradient}; W_hc's is zeros and is not part of self.flat_grads."""
-        assert self.save_for_backward, 'create the engine with save_for_backward=True'
-        assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
-        if self.grads is None:
-            self.flat_grads, self.grads = self._flat_views(self.weights)
-        st = self._struct(self.grads)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_lstm_backward(self._h, _ptr(logits), _ptr(probs), _ptr(labels), ctypes.byref(st),
-                                                  {'xentropy': 0, 'l2': 1}[loss_type], _stream_ptr(self.device)))
-        return self.grads
-
-    def grad_buckets(self):
-        return [(self.flat_grads, lambda stream: stream.wait_stream(torch.cuda.current_stream(self.device)))]
-
-    def backward_input(self, out=None):
-        d = out if out is not None else torch.empty(self.B * self.T * 49, 1024, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_lstm_backward_input(self._h, _ptr(d), _stream_ptr(self.device)))
-        return d
-
-    def adam_step(self, step, lr, max_grad_norm=10.0, method='adam'):
-        """clip_by_global_norm + the chosen optimizer on the flat buffers (the trained variables only), then repack."""
-        return clip_step_multi([self], step, lr, max_grad_norm, method)
-
-    def _outputs(self, want_probs, out_logits, out_probs):
-        logits = out_logits if out_logits is not None else torch.empty(self.B, self.T, 49, 49, device=self.device)
-        probs = None
-        if want_probs:
-            probs = out_probs if out_probs is not None else torch.empty_like(logits)
-        return logits, probs
-
-    def forward(self, c3d_input, want_probs=True, out_logits=None, out_probs=None):
-        """c3d_input [B,T,1024,7,7] fp32 device tensor -> (logits, probs) [B,T,49,49]."""
-        x = c3d_input
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
-        assert tuple(x.shape) == (self.B, self.T, 1024, 7, 7), tuple(x.shape)
-        logits, probs = self._outputs(want_probs, out_logits, out_probs)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_lstm_forward(self._h, _ptr(x), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
-        return logits, probs
-
-    def forward_rows(self, rows, want_probs=True, out_logits=None, out_probs=None):
-        assert rows.is_cuda and rows.dtype == self.torch_dtype and rows.is_contiguous()
-        assert rows.numel() == self.B * self.T * 49 * 1024
-        logits, probs = self._outputs(want_probs, out_logits, out_probs)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_lstm_forward_rows(self._h, _ptr(rows), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
-        return logits, probs
-
-    def status(self):
-        """Wait for the current stream; raises RgpError (RGP_ETIMEOUT) if a persistent launch lost a group member."""
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_lstm_status(self._h, _stream_ptr(self.device)))
-
-    @property
-    def persistent_workgroups(self):
-        with torch.cuda.device(self.device):
-            return int(self.lib.rgp_lstm_persistent_workgroups(self._h))
-
-    @property
-    def persistent(self):
-        return self.persistent_workgroups > 0
 
     @property
     def bptt_persistent_workgroups(self):
@@ -670,26 +503,6 @@ class LstmEngine(object):
     @property
     def bptt_persistent(self):
         return self.bptt_persistent_workgroups > 0
-
-    def inject_fault(self, kind='seq'):
-        """The next persistent launch of the forward ('seq') or of the BPTT ('bptt') loses a group member (test hook)."""
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_lstm_inject_fault(self._h, {'seq': _lib.RGP_FAULT_SEQ_LOST_MEMBER,
-                                                                'bptt': _lib.RGP_FAULT_BPTT_LOST_MEMBER}[kind]))
-
-    def read_buffer_elems(self, name):
-        return int(self.lib.rgp_lstm_buffer_elems(self._h, name.encode()))
-
-    def read_buffer(self, name):
-        """'h', 'c' (training plans also 'i', 'f', 'g', 'o' and, after a backward, 'd_i', 'd_f', 'd_g', 'd_o')
-        [B,T,7,7,128]; 'emb' [B*T*49, 512]; fp32."""
-        n = self.read_buffer_elems(name)
-        if n == 0:
-            raise _lib.RgpError('unknown intermediate %r' % name)
-        out = torch.empty(n, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_lstm_read_buffer(self._h, name.encode(), _ptr(out), _stream_ptr(self.device)))
-        return out
 
 
 def softmax_xent(logits, labels=None, want_probs=True):
@@ -739,20 +552,10 @@ class FcGruEngine(object):
             self.lib.rgp_fcgru_destroy(h)
 
     def _flat(self, like):
-        sizes = [(k, tuple(like[k].shape)) for k in _lib.FcGruWeights.FIELDS]
-        flat = torch.zeros(sum(int(np.prod(s)) for _, s in sizes), dtype=torch.float32, device=self.device)
-        views, off = {}, 0
-        for k, shp in sizes:
-            n = int(np.prod(shp))
-            views[k] = flat[off:off + n].view(shp)
-            off += n
-        return flat, views
+        return _flat_views(_lib.FcGruWeights.FIELDS, like, self.device)
 
     def _struct(self, views):
-        st = _lib.FcGruWeights()
-        for k in _lib.FcGruWeights.FIELDS:
-            setattr(st, k, views[k].data_ptr())
-        return st
+        return _struct(_lib.FcGruWeights, {k: k for k in _lib.FcGruWeights.FIELDS}, views)
 
     def set_weights(self, params):
         src = {k: _as_dev_f32(params[k], self.device) for k in _lib.FcGruWeights.FIELDS}
@@ -827,20 +630,10 @@ class ShallowNetEngine(object):
             self.lib.rgp_shallownet_destroy(h)
 
     def _flat(self, like):
-        sizes = [(k, tuple(like[k].shape)) for k in _lib.ShallowNetWeights.FIELDS]
-        flat = torch.zeros(sum(int(np.prod(s)) for _, s in sizes), dtype=torch.float32, device=self.device)
-        views, off = {}, 0
-        for k, shp in sizes:
-            n = int(np.prod(shp))
-            views[k] = flat[off:off + n].view(shp)
-            off += n
-        return flat, views
+        return _flat_views(_lib.ShallowNetWeights.FIELDS, like, self.device)
 
     def _struct(self, views):
-        st = _lib.ShallowNetWeights()
-        for k in _lib.ShallowNetWeights.FIELDS:
-            setattr(st, k, views[k].data_ptr())
-        return st
+        return _struct(_lib.ShallowNetWeights, {k: k for k in _lib.ShallowNetWeights.FIELDS}, views)
 
     def set_weights(self, params):
         src = {k: _as_dev_f32(params[k], self.device) for k in _lib.ShallowNetWeights.FIELDS}
@@ -923,19 +716,11 @@ class CascadeEngine(object):
         if h:
             self.lib.rgp_cascade_destroy(h)
 
-    def _flat(self, shapes):
-        flat = torch.zeros(sum(int(np.prod(s)) for _, s in shapes), dtype=torch.float32, device=self.device)
-        views, off = {}, 0
-        for f, shp in shapes:
-            n = int(np.prod(shp))
-            views[f] = flat[off:off + n].view(shp)
-            off += n
-        return flat, views
+    def _flat(self, like):
+        return _flat_views([f for f, _ in self.KEYS], like, self.device)
 
     def _struct(self, views):
-        st = _lib.CascadeWeights()
-        for field, _ in self.KEYS:
-            setattr(st, field, views[field].data_ptr())
+        st = _struct(_lib.CascadeWeights, {f: f for f, _ in self.KEYS}, views)
         for k in _lib.ShallowNetWeights.FIELDS:                 # frozen (learning rate 0, base.py:264-265)
             setattr(st.shallownet, k, self.weights['shallownet.' + k].data_ptr())
         return st
@@ -945,7 +730,7 @@ class CascadeEngine(object):
         the ShallowNet's arrays are separate and frozen."""
         src = {field: _as_dev_f32(params[key], self.device) for field, key in self.KEYS}
         if self.flat_params is None:
-            self.flat_params, self.weights = self._flat([(f, tuple(src[f].shape)) for f, _ in self.KEYS])
+            self.flat_params, self.weights = self._flat(src)
         for f, _ in self.KEYS:
             self.weights[f].copy_(src[f])
         for k in _lib.ShallowNetWeights.FIELDS:
@@ -963,7 +748,7 @@ class CascadeEngine(object):
         assert self.save_for_backward, 'create the engine with save_for_backward=True'
         assert gt.is_cuda and gt.dtype == torch.float32 and gt.is_contiguous() and gt.numel() == maps.numel()
         if self.flat_grads is None:
-            self.flat_grads, self.grads = self._flat([(f, tuple(self.weights[f].shape)) for f, _ in self.KEYS])
+            self.flat_grads, self.grads = self._flat(self.weights)
         st = self._struct(self.grads)
         d_rows = torch.empty(self.batch * self.n_steps * 49, 1024, device=self.device) if want_d_rows else None
         with torch.cuda.device(self.device):
