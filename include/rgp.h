@@ -409,6 +409,57 @@ int rgp_lstm_bptt_persistent_workgroups(const rgp_lstm_t* plan);
  * buffer_elems: the element count, 0 = no such buffer. */
 int rgp_lstm_read_buffer(rgp_lstm_t* plan, const char* name, float* dst, rgp_stream_t stream);
 size_t rgp_lstm_buffer_elems(const rgp_lstm_t* plan, const char* name);
+/* ------------------------------------------------------------------ gaze_grcn77 (the 7x7-map ConvGRU model) */
+typedef struct rgp_grcn77 rgp_grcn77_t;
+
+/* GazePredictionGRCN.create_gazeprediction_network of models/gaze_grcn77.py:77-218: gaze_grcn's projection 1024 -> 512 and
+ * GRU_RCN_Cell (128 state channels, 3x3 SAME on 7x7, zero initial state), no batch-norm and no up-sampling: the logit of a
+ * pixel is h_t[b,y,x,:] . out_W + out_b (:206-208), the maps are [B,T,7,7] and the softmax / the loss run over 49 pixels.
+ * Both dropout sites (:160-161, :209) are inert.  All fp32 device pointers: proj_c3d_W [1024,512] proj_c3d_b [512];
+ * gru_W{z,r,} [3,3,512,128] gru_U{z,r,} [3,3,128,128]; out_W [128,1] (16-byte aligned) out_b [1].  The plan reads the
+ * biases and out_W / out_b in place on every call: they stay the caller's and must outlive the plan's use of them.
+ * The read-out (csrc/head_point.hip.h) is fp32 arithmetic on the fp32 state in both plan dtypes: one launch forward
+ * (logits and softmax), one launch plus a fixed-order sum backward.  No float atomics in it: two calls on the same
+ * states give the same bits, and a frame's logits depend on that frame's states only. */
+typedef struct rgp_grcn77_weights {
+  const float *proj_c3d_W, *proj_c3d_b;
+  const float *gru_Wz, *gru_Uz, *gru_Wr, *gru_Ur, *gru_W, *gru_U;
+  const float *out_W, *out_b;
+} rgp_grcn77_weights;
+
+/* flags: the meaning of the RGP_GRCN_* flags of the same value */
+#define RGP_GRCN77_SAVE_FOR_BACKWARD 1
+#define RGP_GRCN77_PER_STEP 2
+int rgp_grcn77_create(rgp_grcn77_t** plan, int batch, int n_steps, int dtype, int flags);
+int rgp_grcn77_destroy(rgp_grcn77_t* plan);
+size_t rgp_grcn77_workspace_bytes(const rgp_grcn77_t* plan);
+int rgp_grcn77_bind_workspace(rgp_grcn77_t* plan, void* workspace, size_t bytes, rgp_stream_t stream);
+int rgp_grcn77_set_weights(rgp_grcn77_t* plan, const rgp_grcn77_weights* w, rgp_stream_t stream);
+/* c3d_input [B,T,1024,7,7] fp32 -> logits [B,T,7,7]; probs (optional) = per-frame softmax over the 49 pixels */
+int rgp_grcn77_forward(rgp_grcn77_t* plan, const float* c3d_input, float* logits, float* probs, rgp_stream_t stream);
+/* c3d_rows: [B*T*49, 1024] in the plan's operand dtype, column d*512+c, 16-byte aligned (what rgp_c3d_forward writes) */
+int rgp_grcn77_forward_rows(rgp_grcn77_t* plan, const void* c3d_rows, float* logits, float* probs, rgp_stream_t stream);
+/* Training plans, after a forward: gradients of the loss of gaze_rnn.py:363-408 over 49 pixels (loss_type 0 xentropy: probs
+ * and labels are read; 1 l2: logits and labels; labels [B,T,7,7]) w.r.t. the ten variables (grads: arrays shaped like
+ * the weights, fully overwritten).  The recurrence is differentiated by rgp_grcn_backward_from_states of the plan's
+ * ConvGRU: persistent or per-step as the forward. */
+int rgp_grcn77_backward(rgp_grcn77_t* plan, const float* logits, const float* probs, const float* labels,
+                        const rgp_grcn77_weights* grads, int loss_type, rgp_stream_t stream);
+/* After rgp_grcn77_backward: d loss / d input as conv5b rows [B*T*49, 1024] fp32 (column d*512+c) */
+int rgp_grcn77_backward_input(rgp_grcn77_t* plan, float* d_rows, rgp_stream_t stream);
+/* The persistent ConvGRU launches fail as rgp_grcn's do (rgp_grcn_status): the next call on the plan and rgp_grcn77_status
+ * (which first waits for `stream`) return RGP_ETIMEOUT once; the poisoned states give NaN logits. */
+int rgp_grcn77_status(rgp_grcn77_t* plan, rgp_stream_t stream);
+/* Workgroups (= CUs) a persistent launch of this plan occupies on the current device; 0 = per-timestep launches */
+int rgp_grcn77_persistent_workgroups(const rgp_grcn77_t* plan);
+/* fp32 copies of "c3d_embedded" [B,T,7,7,512] and "rcn_outputs" [B,T,7,7,128] (h_t) after a forward and, training plans
+ * after a backward, "d_rcn_outputs" [B,T,7,7,128], the read-out's gradient w.r.t. the states.  buffer_elems: the element
+ * count, 0 = no such buffer. */
+int rgp_grcn77_read_buffer(rgp_grcn77_t* plan, const char* name, float* dst, rgp_stream_t stream);
+size_t rgp_grcn77_buffer_elems(const rgp_grcn77_t* plan, const char* name);
+/* The read-out as a stage (for tests / profiling).  states = NULL: the plan's own states of the last forward; otherwise
+ * the caller's fp32 [B,T,7,7,128], 16-byte aligned. */
+int rgp_grcn77_head_fwd(rgp_grcn77_t* plan, const float* states, float* logits, float* probs, rgp_stream_t stream);
 /* ------------------------------------------------------------------ frame-wise ShallowNet */
 typedef struct rgp_shallownet rgp_shallownet_t;
 

@@ -21,6 +21,7 @@ RGP_GRCN_SAVE_FOR_BACKWARD, RGP_GRCN_PER_STEP, RGP_GRCN_UNFOLDED_HEAD = 1, 2, 4
 RGP_C3D_SAVE_FOR_BACKWARD, RGP_C3D_KERNELS_IGEMM, RGP_C3D_KERNELS_TILE128, RGP_C3D_CONV2A_ROWWISE = 1, 2, 4, 8
 RGP_C3DCONV_SAVE_FOR_BACKWARD, RGP_C3DCONV_STAGED, RGP_C3DCONV_FUSED = 1, 2, 4
 RGP_LSTM_SAVE_FOR_BACKWARD, RGP_LSTM_PER_STEP, RGP_LSTM_PERSISTENT, RGP_LSTM_BPTT_PERSISTENT = 1, 2, 4, 8
+RGP_GRCN77_SAVE_FOR_BACKWARD, RGP_GRCN77_PER_STEP = 1, 2
 RGP_FAULT_SEQ_LOST_MEMBER, RGP_FAULT_BPTT_LOST_MEMBER = 1, 2
 RGP_GRCN_GRADS_TOP, RGP_GRCN_GRADS_GRU, RGP_GRCN_GRADS_PROJ = 0, 1, 2
 RGP_SQNORM_PARTIALS = 256          # include/rgp.h
@@ -58,6 +59,11 @@ class C3dConvWeights(ctypes.Structure):
 class LstmWeights(ctypes.Structure):
     FIELDS = ('proj_c3d_W', 'proj_c3d_b', 'W_xi', 'W_hi', 'W_ci', 'W_xf', 'W_hf', 'W_cf', 'W_xc', 'W_hc', 'W_xo', 'W_ho', 'W_co',
               'up_weight1', 'up_weight2', 'up_weight3', 'out_W', 'out_b')
+    _fields_ = [(n, c_void_p) for n in FIELDS]
+
+
+class Grcn77Weights(ctypes.Structure):
+    FIELDS = ('proj_c3d_W', 'proj_c3d_b', 'gru_Wz', 'gru_Uz', 'gru_Wr', 'gru_Ur', 'gru_W', 'gru_U', 'out_W', 'out_b')
     _fields_ = [(n, c_void_p) for n in FIELDS]
 
 
@@ -146,6 +152,20 @@ SIGNATURES = {
     'rgp_lstm_bptt_persistent_workgroups': (c_int, [c_void_p]),
     'rgp_lstm_read_buffer': (c_int, [c_void_p, c_char_p, c_void_p, c_void_p]),
     'rgp_lstm_buffer_elems': (c_size_t, [c_void_p, c_char_p]),
+    'rgp_grcn77_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int]),
+    'rgp_grcn77_destroy': (c_int, [c_void_p]),
+    'rgp_grcn77_workspace_bytes': (c_size_t, [c_void_p]),
+    'rgp_grcn77_bind_workspace': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    'rgp_grcn77_set_weights': (c_int, [c_void_p, ctypes.POINTER(Grcn77Weights), c_void_p]),
+    'rgp_grcn77_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rgp_grcn77_forward_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rgp_grcn77_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Grcn77Weights), c_int, c_void_p]),
+    'rgp_grcn77_backward_input': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'rgp_grcn77_status': (c_int, [c_void_p, c_void_p]),
+    'rgp_grcn77_persistent_workgroups': (c_int, [c_void_p]),
+    'rgp_grcn77_read_buffer': (c_int, [c_void_p, c_char_p, c_void_p, c_void_p]),
+    'rgp_grcn77_buffer_elems': (c_size_t, [c_void_p, c_char_p]),
+    'rgp_grcn77_head_fwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'rgp_shallownet_create_ex': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int]),
     'rgp_shallownet_backward': (c_int, [c_void_p, c_int, c_void_p, ctypes.POINTER(ShallowNetWeights), c_void_p]),
     'rgp_shallownet_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),

@@ -32,6 +32,12 @@ The other three graphs of the gaze family (``model=`` of import_tf_variables / e
       RGP/RCNBottom/ConvLSTM_{Wxi,Wxi_1,Wci,Wxf,Wxf_1,Wcf,Wxc,Whc,Wxo,Wxo_1,Wco} -> same names without the scopes
         (Wxi_1 = W_hi, Wxf_1 = W_hf, Wxo_1 = W_ho; Whc is carried although nothing reads it)
       RGP/proj_c3d_W, RGP/proj_c3d_b, RGP/Upsampling/weight{1,2,3}, RGP/out_W, RGP/out_b -> as gaze_grcn's
+  'gaze_grcn77'  (gaze_grcn77.py:152-153,174-184; NO enclosing RGP scope, cell and read-out under RCNBottom/, unpinned: TF's
+      naming rule restated, no TF at hand; no batch-norm, no up-sampling):
+      proj_c3d_W, proj_c3d_b                                  -> proj_c3d_W, proj_c3d_b
+      RCNBottom/GRU_Conv_{Wz,Uz,Wr,Ur,W,U}                    -> GRU_Conv_{Wz,Uz,Wr,Ur,W,U}
+      RCNBottom/out_W [128,1], RCNBottom/out_b [1]            -> out_W, out_b
+  'gaze_rnn77'  is 'gaze_rnn' with proj_out_W [1617,49], proj_out_b [49]
   'gaze_grcn_cascade'  (gaze_grcn_cascade.py:267-423):
       proj_c3d_W, proj_c3d_b; RCNBottom/GRU_Conv_*; Upsampling/weight; RCNGaze/GRU_Conv_*;
       RCNGaze/LastProjection/fc{1,2}/{weights,biases|bias}    -> LastProjection/fc{1,2}_{w,b}
@@ -254,21 +260,41 @@ def export_lstm_variables(state):
     return {inv[k]: np.asarray(v) for k, v in state.items() if k in inv}
 
 
-_IMPORTERS = {'gaze_lstm': import_lstm_variables, 'gaze_c3d_conv': import_c3d_conv_variables, 'gaze_rnn': import_fcgru_variables, 'shallownet': import_shallownet_variables,
+_GRCN77 = dict({'proj_c3d_W': 'proj_c3d_W', 'proj_c3d_b': 'proj_c3d_b', 'RCNBottom/out_W': 'out_W', 'RCNBottom/out_b': 'out_b'},
+               **{'RCNBottom/GRU_Conv_' + g: 'GRU_Conv_' + g for g in _GRU})
+
+
+def import_grcn77_variables(tf_vars):
+    """gaze_grcn77: the ten variables of _GRCN77, with or without the ':0' suffix."""
+    src = {_strip(k): np.asarray(v) for k, v in dict(tf_vars).items() if not _skip(_strip(k))}
+    out = {key: src[tf_name].astype(np.float32) for tf_name, key in _GRCN77.items() if tf_name in src}
+    missing = sorted(set(_GRCN77.values()) - set(out))
+    if missing:
+        raise KeyError('TF checkpoint lacks gaze_grcn77 variables for: %s' % ', '.join(missing))
+    return out
+
+
+def export_grcn77_variables(state):
+    """state dict -> TF names (cell and read-out under RCNBottom/)."""
+    inv = {v: k for k, v in _GRCN77.items()}
+    return {inv[k]: np.asarray(v) for k, v in state.items() if k in inv}
+
+
+_IMPORTERS = {'gaze_grcn77': import_grcn77_variables, 'gaze_rnn77': import_fcgru_variables, 'gaze_lstm': import_lstm_variables, 'gaze_c3d_conv': import_c3d_conv_variables, 'gaze_rnn': import_fcgru_variables, 'shallownet': import_shallownet_variables,
               'gaze_framewise_shallownet': import_shallownet_variables, 'gaze_grcn_cascade': import_cascade_variables}
-_EXPORTERS = {'gaze_lstm': export_lstm_variables, 'gaze_c3d_conv': export_c3d_conv_variables, 'gaze_rnn': export_fcgru_variables, 'shallownet': export_shallownet_variables,
+_EXPORTERS = {'gaze_grcn77': export_grcn77_variables, 'gaze_rnn77': export_fcgru_variables, 'gaze_lstm': export_lstm_variables, 'gaze_c3d_conv': export_c3d_conv_variables, 'gaze_rnn': export_fcgru_variables, 'shallownet': export_shallownet_variables,
               'gaze_framewise_shallownet': export_shallownet_variables, 'gaze_grcn_cascade': export_cascade_variables}
 
 
 def import_model_variables(model, tf_vars, n_steps=None):
     """Dispatch on the reference's --model name (train_gaze.py:41-69)."""
-    if model in ('gaze_grcn', 'gaze_grcn77'):
+    if model == 'gaze_grcn':
         return import_tf_variables(tf_vars, n_steps)
     return _IMPORTERS[model](tf_vars)
 
 
 def export_model_variables(model, state):
-    if model in ('gaze_grcn', 'gaze_grcn77'):
+    if model == 'gaze_grcn':
         return export_tf_variables(state)
     return _EXPORTERS[model](state)
 

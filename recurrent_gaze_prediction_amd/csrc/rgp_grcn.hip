@@ -536,6 +536,20 @@ int rgp_grcn_forward_rows(rgp_grcn_t* g, const void* c3d_rows, float* logits, fl
   return grcn_tail(g, logits, probs, stream);
 }
 
+}  // extern "C"
+
+// rgp_grcn_forward_rows' projection alone (no ABI symbol: for plans that own a sub-plan and run its stages, rgp_grcn77.hip)
+int grcn_proj_rows_fwd(rgp_grcn* g, const void* c3d_rows, hipStream_t s) {
+  RGP_TRY(check_ready(g));
+  RGP_REQUIRE(c3d_rows, "grcn_proj_rows_fwd: null rows");
+  const int pid = g->prof.begin(0, s);
+  const int rc = RGP_BY_DTYPE(g->dtype, proj_impl, g, nullptr, c3d_rows, s);
+  g->prof.end(pid, s);
+  return rc;
+}
+
+extern "C" {
+
 int rgp_grcn_profile_enable(rgp_grcn_t* g, int enable) {
   RGP_REQUIRE(g, "rgp_grcn_profile_enable: null plan");
   g->prof.enabled = enable != 0;

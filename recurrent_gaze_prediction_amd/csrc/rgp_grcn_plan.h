@@ -37,6 +37,8 @@ struct rgp_grcn {
 
 // rgp_grcn.hip: the plan's persistent BPTT launch leaves RGP_RCCL_CU_RESERVE CUs free (the TOP gradient group may leave before it)
 bool grads_top_early(const rgp_grcn* g);
+// rgp_grcn.hip: the projection from conv5b rows as a stage of its own (what rgp_grcn_forward_rows runs first)
+int grcn_proj_rows_fwd(rgp_grcn* g, const void* c3d_rows, hipStream_t s);
 // rgp_grcn_bwd.hip
 // returns RGP_ETIMEOUT (and clears the word) if a persistent launch of this plan reported a lost group member
 int grcn_check_error(rgp_grcn* g);

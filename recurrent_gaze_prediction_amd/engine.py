@@ -505,6 +505,52 @@ class LstmEngine(_PersistentEngine):
         return self.bptt_persistent_workgroups > 0
 
 
+GRCN77_PARAM_TO_FIELD = {   # TF variable name (scope RCNBottom/ stripped, gaze_grcn77.py:152-153,174-184) -> rgp_grcn77_weights field
+    'proj_c3d_W': 'proj_c3d_W', 'proj_c3d_b': 'proj_c3d_b',
+    'GRU_Conv_Wz': 'gru_Wz', 'GRU_Conv_Uz': 'gru_Uz', 'GRU_Conv_Wr': 'gru_Wr', 'GRU_Conv_Ur': 'gru_Ur',
+    'GRU_Conv_W': 'gru_W', 'GRU_Conv_U': 'gru_U', 'out_W': 'out_W', 'out_b': 'out_b',
+}
+
+
+class Grcn77Engine(_PersistentEngine):
+    """gaze_grcn77 graph (models/gaze_grcn77.py:77-218) at fixed (B, T, dtype): gaze_grcn's projection and ConvGRU, then a
+    per-pixel 128 -> 1 read-out on the fp32 state and a 49-way softmax (csrc/head_point.hip.h).  Maps are [B,T,7,7].
+
+    per_step=True: the recurrence and its BPTT as per-timestep launches (RGP_GRCN77_PER_STEP); otherwise bf16 plans of at
+    most 64 clips run them as persistent launches, as GrcnEngine does.  read_buffer: 'c3d_embedded' [B,T,7,7,512],
+    'rcn_outputs' [B,T,7,7,128] and, after a backward, 'd_rcn_outputs' [B,T,7,7,128]; fp32."""
+    PREFIX, PARAM_TO_FIELD, WEIGHTS = 'rgp_grcn77_', GRCN77_PARAM_TO_FIELD, _lib.Grcn77Weights
+
+    def __init__(self, batch, n_steps, dtype='bf16', save_for_backward=False, device='cuda:0', per_step=False):
+        self.P, self.S, self.per_step = 512, 128, bool(per_step)
+        flags = (_lib.RGP_GRCN77_SAVE_FOR_BACKWARD if save_for_backward else 0) | (_lib.RGP_GRCN77_PER_STEP if per_step else 0)
+        self._create(batch, n_steps, dtype, save_for_backward, device, int(batch), int(n_steps), _lib.DTYPES[dtype], flags)
+
+    def _check_shapes(self, src):
+        assert tuple(src['GRU_Conv_Wz'].shape) == (3, 3, self.P, self.S) and tuple(src['out_W'].shape) == (self.S, 1)
+
+    def _outputs(self, want_probs, out_logits, out_probs):
+        logits = out_logits if out_logits is not None else torch.empty(self.B, self.T, 7, 7, device=self.device)
+        probs = None
+        if want_probs:
+            probs = out_probs if out_probs is not None else torch.empty_like(logits)
+        return logits, probs
+
+    def head_forward(self, states=None, want_probs=True):
+        """The read-out alone (rgp_grcn77_head_fwd): on the plan's own states of the last forward, or on the caller's
+        fp32 device tensor [B,T,7,7,128] -> (logits, probs) [B,T,7,7]."""
+        if states is not None:
+            assert states.is_cuda and states.dtype == torch.float32 and states.is_contiguous()
+            assert tuple(states.shape) == (self.B, self.T, 7, 7, self.S), tuple(states.shape)
+        logits, probs = self._outputs(want_probs, None, None)
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['head_fwd'](self._h, _ptr(states), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
+        return logits, probs
+
+    def inject_fault(self, kind='seq'):
+        raise NotImplementedError('rgp_grcn77 exports no fault hook: the time-out path is the ConvGRU plan\'s (GrcnEngine)')
+
+
 def softmax_xent(logits, labels=None, want_probs=True):
     """Per-frame softmax / cross entropy (model_util.py:61-72; gaze_rnn.py:390-407).
     logits [..., H, W] fp32 device tensor -> (probs, frame_loss, loss)."""

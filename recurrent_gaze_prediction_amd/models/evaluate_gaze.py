@@ -123,7 +123,8 @@ def run_evaluation(model, data_sets, out_dir, num_frames=1000, seed=0, dump_imag
 def predict_long_clip(model, c3d, frames=None, pool_to_7x7=False):
     """extract_map.py:148-229: a clip of any length through a fixed-T model.  c3d [N,1024,7,7]
     (or [N,512,2,7,7]) is cut into T-chunks, the tail zero-padded, B chunks per call; returns
-    [N,49,49] (or [N,7,7] with a 7x7 average re-pool of each map)."""
+    [N,GH,GW] of the model (49x49; 7x7 for gaze_grcn77 / gaze_rnn77), or [N,7,7] with a 7x7 average re-pool of each 49x49 map
+    (a 7x7 model's maps are at that resolution already)."""
     c3d = np.asarray(c3d, np.float32).reshape(len(c3d), 1024, 7, 7)
     n, T, B = len(c3d), model.n_lstm_steps, model.batch_size
     n_chunks = -(-n // T)

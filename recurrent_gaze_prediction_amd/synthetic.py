@@ -67,6 +67,19 @@ def grcn_params(seed, n_steps, dim_proj=512, dim_state=128, gru_std=0.05, random
     return p
 
 
+def grcn77_params(seed, gru_std=0.05):
+    """Weights of the 7x7-map GazePredictionGRCN (gaze_grcn77.py:152-153 U(-0.1, 0.1); the GRU_RCN_Cell of gaze_grcn;
+    :183-184 out_W [128,1], out_b [1] U(-0.1, 0.1)), keyed by the TF variable names without the RCNBottom/ scope."""
+    rs = np.random.RandomState(seed)
+    u = lambda *s: rs.uniform(-0.1, 0.1, size=s).astype(np.float32)
+    P, S = 512, 128
+    p = {'proj_c3d_W': u(1024, P), 'proj_c3d_b': u(P)}
+    for n, cin in (('Wz', P), ('Uz', S), ('Wr', P), ('Ur', S), ('W', P), ('U', S)):
+        p['GRU_Conv_' + n] = _trunc_normal(rs, (3, 3, cin, S), gru_std)
+    p['out_W'], p['out_b'] = u(S, 1), u(1)
+    return p
+
+
 def c3d_conv_params(seed, dim_proj=512):
     """Weights of GazePredictionConv (gaze_c3d_conv.py:124-125 U(-0.1, 0.1); :153-173 Xavier-uniform / U(-0.1, 0.1)),
     keyed as grcn_params keys the same variables."""
@@ -219,11 +232,12 @@ def fixation_maps(seed, centres, hw=49, n_fix=6, spread=3.0):
 class SyntheticDataSet(object):
     """Stands in for crc_input_data_seq.CRCDataSet: ``len(ds)`` and ``next_batch(B)`` returning the
     reference's 6-tuple (crc_input_data_seq.py:132-156): images [B,T,98,98,3] f32 in [0,1],
-    gazemaps [B,T,49,49] f32, fixationmaps [B,T,49,49], c3d [B,T,512,2,7,7] f32, pupils [B,T],
-    clipnames."""
+    gazemaps [B,T,49,49] f32, fixationmaps [B,T,49,49] (both [B,T,7,7] with gazemap_hw=7), c3d [B,T,512,2,7,7] f32,
+    pupils [B,T], clipnames."""
 
-    def __init__(self, n_clips, n_steps, seed=0, image_hw=98):
-        self.n_clips, self.n_steps, self.seed, self.image_hw = n_clips, n_steps, seed, image_hw
+    def __init__(self, n_clips, n_steps, seed=0, image_hw=98, gazemap_hw=49):
+        """gazemap_hw=7: gaze and fixation maps for the 7x7-map models (gaze_grcn77 / gaze_rnn77)."""
+        self.n_clips, self.n_steps, self.seed, self.image_hw, self.gazemap_hw = n_clips, n_steps, seed, image_hw, gazemap_hw
         self._cursor = 0
 
     def __len__(self):
@@ -235,9 +249,11 @@ class SyntheticDataSet(object):
         T = self.n_steps
         rs = np.random.RandomState(self.seed)
         images = rs.rand(batch_size, T, self.image_hw, self.image_hw, 3).astype(np.float32)
-        maps = np.concatenate([gaze_maps(self.seed + 17 * i + 1, 1, T)[0] for i in idx])
-        cents = np.concatenate([gaze_maps(self.seed + 17 * i + 1, 1, T)[1] for i in idx])
-        fix = fixation_maps(self.seed + 3, cents)
+        hw = self.gazemap_hw
+        sigma = 2.0 if hw == 49 else 1.0
+        maps = np.concatenate([gaze_maps(self.seed + 17 * i + 1, 1, T, hw=hw, sigma=sigma)[0] for i in idx])
+        cents = np.concatenate([gaze_maps(self.seed + 17 * i + 1, 1, T, hw=hw, sigma=sigma)[1] for i in idx])
+        fix = fixation_maps(self.seed + 3, cents, hw=hw, **({} if hw == 49 else {'n_fix': 3, 'spread': 1.0}))
         feats = np.concatenate([c3d_features(self.seed + 17 * i + 2, 1, T) for i in idx])
         c3d = feats.reshape(batch_size, T, 512, 2, 7, 7)          # channel = c*2+d (gaze_rnn.py:494-497)
         pupils = np.zeros((batch_size, T), np.float32)
