@@ -708,6 +708,66 @@ int rgp_saliency_scores(const rgp_metrics_args* args, rgp_stream_t stream);
  * RGP_EINVAL with the number of refused frames in rgp_last_error(). */
 int rgp_metrics_status(const void* workspace, rgp_stream_t stream);
 
+/* ------------------------------------------------------------------ action classifier on gaze-attended C3D features */
+typedef struct rgp_action rgp_action_t;
+
+/* Classifier.projection + classification_graph_nn / _svm (models/action_classification.py:210-292).  Inputs per batch:
+ * c3d [B, C, 49] fp32 (the placeholder layout; C = 1024 in the reference), gazemap [B, 49, 49] fp32 (ground truth or a
+ * gaze model's probs), labels [B, 13] in {0, 1}.  With RGP_ACTION_USE_GAZEMAP (:224-238) a = gazemap.reshape(B, 2401) Wg
+ * and x[b, c*49+p] = c3d[b, c, p] a[b, p]; without it x is the flattened c3d.  K = 49 C.
+ *  RGP_ACTION_NN  (:265-292): h1 = x W1 + b1, h2 = h1 W2 + b2, logits = h2 W3 + b3 -- NO non-linearity between the layers
+ *    (use_relu=False) -- y_pred = sigmoid(logits), loss = mean over B x 13 of max(z,0) - z y + log(1 + exp(-|z|)); Adam
+ *    in the TF form of rgp_adam_clip_step (beta1 0.9, beta2 0.999, eps 1e-8, no clipping).  The caller passes the
+ *    learning rate of the step: 0.002 * 0.96^(step/10), the exponent continuous (tf.train.exponential_decay default).
+ *  RGP_ACTION_SVM (:242-263): y = x W1 + b1 (logits and y_pred are both y), loss = 0.5 sum W1^2 + 50 sum max(0, 1 - labels y),
+ *    plain SGD (the reference's lr: 0.01).  The labels stay {0, 1} AS THE REFERENCE WRITES THEM: a zero label adds the
+ *    constant 1 to the hinge sum and passes no gradient; the hinge passes gradient only where 1 - labels y > 0, strictly.
+ * fp32 device pointers: W1 [K, 256] (SVM: [K, 13]; 16-byte aligned), Wg [2401, 49] (gaze-map plans), b1 [256] (SVM: [13]),
+ * W2 [256, 256], b2 [256], W3 [256, 13], b3 [13] (NN).  The plan keeps these pointers: a training step updates the arrays
+ * IN PLACE, and the operand copy of W1 (the plan's dtype) with them. */
+typedef struct rgp_action_weights {
+  float *W1, *Wg, *b1, *W2, *b2, *W3, *b3;
+} rgp_action_weights;
+
+#define RGP_ACTION_NN 0
+#define RGP_ACTION_SVM 1
+#define RGP_ACTION_USE_GAZEMAP 1
+#define RGP_ACTION_SAVE_FOR_BACKWARD 2   /* a training plan */
+#define RGP_ACTION_UNFUSED 4             /* the second implementation: x, dW1 and dx in memory, existing optimizer kernels */
+/* dim_feat: C in [1, 8192]; batch in [1, 64]; anything else, or an unknown flag: RGP_EINVAL. */
+int rgp_action_create(rgp_action_t** plan, int batch, int dim_feat, int mode, int dtype, int flags);
+int rgp_action_destroy(rgp_action_t* plan);
+size_t rgp_action_workspace_bytes(const rgp_action_t* plan);
+int rgp_action_bind_workspace(rgp_action_t* plan, void* workspace, size_t bytes, rgp_stream_t stream);
+int rgp_action_set_weights(rgp_action_t* plan, const rgp_action_weights* w, rgp_stream_t stream);
+/* Copies the current values into the arrays of dst (a no-op for an array the plan already updates in place). */
+int rgp_action_get_weights(rgp_action_t* plan, const rgp_action_weights* dst, rgp_stream_t stream);
+/* NN training plans: Adam's m and v, arrays shaped like the weights, owned and initialised by the caller. */
+int rgp_action_bind_slots(rgp_action_t* plan, const rgp_action_weights* m, const rgp_action_weights* v);
+/* -> logits [B, 13], y_pred [B, 13] (either may be null).  No float atomics: two calls give the same bits. */
+int rgp_action_forward(rgp_action_t* plan, const float* c3d, const float* gazemap, float* logits, float* y_pred, rgp_stream_t stream);
+/* c3d_rows: conv5b rows [B*49, 1024] in the plan's operand dtype, column d*512+c (what rgp_c3d_forward writes); C = 1024 plans */
+int rgp_action_forward_rows(rgp_action_t* plan, const void* c3d_rows, const float* gazemap, float* logits, float* y_pred,
+                            rgp_stream_t stream);
+/* After a forward: the loss of its batch against labels -> loss_dev[0]. */
+int rgp_action_loss(rgp_action_t* plan, const float* labels, float* loss_dev, rgp_stream_t stream);
+/* One training step (training plans): forward, loss (-> loss_dev, optional; the loss BEFORE the update), every gradient, the
+ * update of W1 in one pass over W1, m and v (dW1 never exists in memory), and the small variables' optimizer step. */
+int rgp_action_train_step(rgp_action_t* plan, const float* c3d, const float* gazemap, const float* labels, int step, float lr,
+                          float* loss_dev, rgp_stream_t stream);
+/* The stages of a step, for tests.  fc1_fwd: a and the per-slab partial sums of x W1; tail: their sum in slab order and
+ * the rest of the network (training plans: with the gradients; labels then required); fc1_update: the pass over W1 with
+ * the caller's d_h1 [B, 256] (SVM [B, 13]: d hinge sum / d y, the factor 50 is applied inside), recomputing a. */
+int rgp_action_fc1_fwd(rgp_action_t* plan, const float* c3d, const float* gazemap, rgp_stream_t stream);
+int rgp_action_tail(rgp_action_t* plan, const float* labels, rgp_stream_t stream);
+int rgp_action_fc1_update(rgp_action_t* plan, const float* c3d, const float* gazemap, const float* d_h1, int step, float lr,
+                          rgp_stream_t stream);
+/* fp32 copies of "a" [B,49], "h1" [B,256] (SVM: y [B,13]), "h2", "loss" [1]; training plans: "d_h1", "d_h2", "d_logits",
+ * "dx" [B,K] (SVM: including the factor 50), "d_a", and the small gradients "d_Wg", "d_b1", "d_W2", "d_b2", "d_W3", "d_b3".
+ * buffer_elems: the element count, 0 = this plan has no such buffer. */
+int rgp_action_read_buffer(rgp_action_t* plan, const char* name, float* dst, rgp_stream_t stream);
+size_t rgp_action_buffer_elems(const rgp_action_t* plan, const char* name);
+
 #ifdef __cplusplus
 }
 #endif

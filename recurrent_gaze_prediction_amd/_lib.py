@@ -23,6 +23,8 @@ RGP_C3DCONV_SAVE_FOR_BACKWARD, RGP_C3DCONV_STAGED, RGP_C3DCONV_FUSED = 1, 2, 4
 RGP_LSTM_SAVE_FOR_BACKWARD, RGP_LSTM_PER_STEP, RGP_LSTM_PERSISTENT, RGP_LSTM_BPTT_PERSISTENT = 1, 2, 4, 8
 RGP_GRCN77_SAVE_FOR_BACKWARD, RGP_GRCN77_PER_STEP = 1, 2
 RGP_FAULT_SEQ_LOST_MEMBER, RGP_FAULT_BPTT_LOST_MEMBER = 1, 2
+RGP_ACTION_NN, RGP_ACTION_SVM = 0, 1
+RGP_ACTION_USE_GAZEMAP, RGP_ACTION_SAVE_FOR_BACKWARD, RGP_ACTION_UNFUSED = 1, 2, 4
 RGP_GRCN_GRADS_TOP, RGP_GRCN_GRADS_GRU, RGP_GRCN_GRADS_PROJ = 0, 1, 2
 RGP_SQNORM_PARTIALS = 256          # include/rgp.h
 # saliency metrics (include/rgp.h): caps, metric bits (row of `scores` = bit position), flags
@@ -77,6 +79,11 @@ class CascadeWeights(ctypes.Structure):
               'upsampling_weight', 'top_Wz', 'top_Uz', 'top_Wr', 'top_Ur', 'top_W', 'top_U',
               'fc1_w', 'fc1_b', 'fc2_w', 'fc2_b')
     _fields_ = [(n, c_void_p) for n in FIELDS] + [('shallownet', ShallowNetWeights)]
+
+
+class ActionWeights(ctypes.Structure):
+    FIELDS = ('W1', 'Wg', 'b1', 'W2', 'b2', 'W3', 'b3')
+    _fields_ = [(n, c_void_p) for n in FIELDS]
 
 
 class C3DWeights(ctypes.Structure):
@@ -233,6 +240,22 @@ SIGNATURES = {
     'rgp_grcn_profile_read': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong)]),
     'rgp_c3d_profile_enable': (c_int, [c_void_p, c_int]),
     'rgp_c3d_profile_read': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong)]),
+    'rgp_action_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int]),
+    'rgp_action_destroy': (c_int, [c_void_p]),
+    'rgp_action_workspace_bytes': (c_size_t, [c_void_p]),
+    'rgp_action_bind_workspace': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    'rgp_action_set_weights': (c_int, [c_void_p, ctypes.POINTER(ActionWeights), c_void_p]),
+    'rgp_action_get_weights': (c_int, [c_void_p, ctypes.POINTER(ActionWeights), c_void_p]),
+    'rgp_action_bind_slots': (c_int, [c_void_p, ctypes.POINTER(ActionWeights), ctypes.POINTER(ActionWeights)]),
+    'rgp_action_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rgp_action_forward_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rgp_action_loss': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rgp_action_train_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p]),
+    'rgp_action_fc1_fwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rgp_action_tail': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'rgp_action_fc1_update': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p]),
+    'rgp_action_read_buffer': (c_int, [c_void_p, c_char_p, c_void_p, c_void_p]),
+    'rgp_action_buffer_elems': (c_size_t, [c_void_p, c_char_p]),
 }
 GRCN_STAGES = ('proj', 'xconv', 'convgru_seq', 'head', 'softmax')
 C3D_STAGES = ('conv1a', 'conv2a', 'conv3a', 'conv3b', 'conv4a', 'conv4b', 'conv5a', 'conv5b', 'video_prep')

@@ -42,6 +42,15 @@ The other three graphs of the gaze family (``model=`` of import_tf_variables / e
       proj_c3d_W, proj_c3d_b; RCNBottom/GRU_Conv_*; Upsampling/weight; RCNGaze/GRU_Conv_*;
       RCNGaze/LastProjection/fc{1,2}/{weights,biases|bias}    -> LastProjection/fc{1,2}_{w,b}
       ShallowNet/*                                            -> ShallowNet/<shallownet names>
+  'action_svm'  (action_classification.py:210-263):
+      SVM/weights [49*C, 13], SVM/bias [13]                   -> W1, b1
+      projection/Variable [2401, 49] (use_gazemap only)       -> Wg
+  'action_nn'  (action_classification.py:210-240,265-292; basic_graphs.py:83-118,149-158): get_weights / get_bias call
+      tf.Variable(initializer, name), i.e. pass `name` in the position of `trainable`, so TF names the variables itself, in
+      creation order inside each scope: fc_layer creates the weights, then the bias, for h1, h2, output.  Unpinned: TF's
+      default-name rule (Variable, Variable_1, ...) restated from those lines, no TensorFlow run at hand.
+      NN/Variable, NN/Variable_1 ... NN/Variable_5            -> W1, b1, W2, b2, W3, b3
+      projection/Variable                                     -> Wg
 """
 import re
 
@@ -280,9 +289,43 @@ def export_grcn77_variables(state):
     return {inv[k]: np.asarray(v) for k, v in state.items() if k in inv}
 
 
-_IMPORTERS = {'gaze_grcn77': import_grcn77_variables, 'gaze_rnn77': import_fcgru_variables, 'gaze_lstm': import_lstm_variables, 'gaze_c3d_conv': import_c3d_conv_variables, 'gaze_rnn': import_fcgru_variables, 'shallownet': import_shallownet_variables,
+_ACTION_NN = {'NN/Variable': 'W1', 'NN/Variable_1': 'b1', 'NN/Variable_2': 'W2', 'NN/Variable_3': 'b2',
+              'NN/Variable_4': 'W3', 'NN/Variable_5': 'b3'}
+_ACTION_SVM = {'SVM/weights': 'W1', 'SVM/bias': 'b1'}
+_ACTION_GAZE = {'projection/Variable': 'Wg'}
+
+
+def _import_action(table, tf_vars):
+    src = {_strip(k): np.asarray(v) for k, v in dict(tf_vars).items() if not _skip(_strip(k))}
+    out = {key: src[n].astype(np.float32) for n, key in dict(table, **_ACTION_GAZE).items() if n in src}
+    missing = sorted(set(table.values()) - set(out))
+    if missing:
+        raise KeyError('TF checkpoint lacks action-classifier variables for: %s' % ', '.join(missing))
+    return out
+
+
+def import_action_nn_variables(tf_vars):
+    """The NN classifier's six variables (+ Wg when the checkpoint has projection/Variable)."""
+    return _import_action(_ACTION_NN, tf_vars)
+
+
+def import_action_svm_variables(tf_vars):
+    return _import_action(_ACTION_SVM, tf_vars)
+
+
+def export_action_nn_variables(state):
+    inv = {v: k for k, v in dict(_ACTION_NN, **_ACTION_GAZE).items()}
+    return {inv[k]: np.asarray(v) for k, v in state.items() if k in inv}
+
+
+def export_action_svm_variables(state):
+    inv = {v: k for k, v in dict(_ACTION_SVM, **_ACTION_GAZE).items()}
+    return {inv[k]: np.asarray(v) for k, v in state.items() if k in inv}
+
+
+_IMPORTERS = {'action_nn': import_action_nn_variables, 'action_svm': import_action_svm_variables, 'gaze_grcn77': import_grcn77_variables, 'gaze_rnn77': import_fcgru_variables, 'gaze_lstm': import_lstm_variables, 'gaze_c3d_conv': import_c3d_conv_variables, 'gaze_rnn': import_fcgru_variables, 'shallownet': import_shallownet_variables,
               'gaze_framewise_shallownet': import_shallownet_variables, 'gaze_grcn_cascade': import_cascade_variables}
-_EXPORTERS = {'gaze_grcn77': export_grcn77_variables, 'gaze_rnn77': export_fcgru_variables, 'gaze_lstm': export_lstm_variables, 'gaze_c3d_conv': export_c3d_conv_variables, 'gaze_rnn': export_fcgru_variables, 'shallownet': export_shallownet_variables,
+_EXPORTERS = {'action_nn': export_action_nn_variables, 'action_svm': export_action_svm_variables, 'gaze_grcn77': export_grcn77_variables, 'gaze_rnn77': export_fcgru_variables, 'gaze_lstm': export_lstm_variables, 'gaze_c3d_conv': export_c3d_conv_variables, 'gaze_rnn': export_fcgru_variables, 'shallownet': export_shallownet_variables,
               'gaze_framewise_shallownet': export_shallownet_variables, 'gaze_grcn_cascade': export_cascade_variables}
 
 

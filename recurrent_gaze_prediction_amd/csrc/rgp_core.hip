@@ -172,7 +172,7 @@ extern "C" {
 
 const char* rgp_last_error(void) { return g_err; }
 
-int rgp_version(void) { return 102; }
+int rgp_version(void) { return 103; }
 
 int rgp_device_arch(char* buf, int buflen) {
   if (!buf || buflen <= 0) return set_err(RGP_EINVAL, "rgp_device_arch: no buffer");

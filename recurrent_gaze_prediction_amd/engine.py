@@ -1004,3 +1004,172 @@ class C3DEngine(object):
         ms, calls = (ctypes.c_double * n)(), (ctypes.c_longlong * n)()
         _lib.check(self.lib.rgp_c3d_profile_read(self._h, ms, calls))
         return {k: (ms[i], calls[i]) for i, k in enumerate(_lib.C3D_STAGES)}
+
+
+ACTION_PARAM_TO_FIELD = {      # state-dict name -> rgp_action_weights field, in the struct's order (= the flat buffer's)
+    'NN': {'W1': 'W1', 'Wg': 'Wg', 'b1': 'b1', 'W2': 'W2', 'b2': 'b2', 'W3': 'W3', 'b3': 'b3'},
+    'SVM': {'W1': 'W1', 'Wg': 'Wg', 'b1': 'b1'},
+}
+
+
+def action_learning_rate(step, lr0=0.002, decay=0.96, decay_steps=10):
+    """tf.train.exponential_decay(lr0, step, 10, 0.96), staircase=False: the exponent is continuous
+    (action_classification.py:282-283)."""
+    return float(lr0) * float(decay) ** (float(step) / float(decay_steps))
+
+
+class ActionEngine(object):
+    """Owner of one rgp_action_ plan (action_classification.py:210-292), its workspace, the flat fp32 master buffer
+    (W1 first, then Wg / b1 / W2 / b2 / W3 / b3: the small variables lie back to back, one optimizer launch) and, for NN
+    training plans, Adam's slots adam_m / adam_v in the same layout.  A training step updates flat_params in place."""
+
+    def __init__(self, batch, dim_feat=1024, mode='NN', use_gazemap=False, dtype='bf16', save_for_backward=False,
+                 device='cuda:0', unfused=False):
+        self.lib = _lib.load()
+        self.device = _require_gpu(device)
+        self.B, self.C, self.K = int(batch), int(dim_feat), 49 * int(dim_feat)
+        self.mode, self.use_gazemap, self.dtype = mode, bool(use_gazemap), dtype
+        self.N = 256 if mode == 'NN' else 13
+        self.save_for_backward, self.unfused = bool(save_for_backward), bool(unfused)
+        self.torch_dtype = torch.bfloat16 if _lib.DTYPES[dtype] == _lib.RGP_BF16 else torch.float32
+        self.names = tuple(k for k in ACTION_PARAM_TO_FIELD[mode] if k != 'Wg' or self.use_gazemap)
+        self.flat_params = self.weights = self.adam_m = self.adam_v = None
+        flags = (_lib.RGP_ACTION_USE_GAZEMAP if use_gazemap else 0) | (_lib.RGP_ACTION_SAVE_FOR_BACKWARD if save_for_backward else 0) \
+            | (_lib.RGP_ACTION_UNFUSED if unfused else 0)
+        self._f = {k[len('rgp_action_'):]: getattr(self.lib, k) for k in _lib.SIGNATURES if k.startswith('rgp_action_')}
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['create'](ctypes.byref(self._h), self.B, self.C, {'NN': _lib.RGP_ACTION_NN, 'SVM': _lib.RGP_ACTION_SVM}[mode],
+                                         _lib.DTYPES[dtype], flags))
+            nbytes = self._f['workspace_bytes'](self._h)
+            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _lib.check(self._f['bind_workspace'](self._h, _ptr(self.workspace), nbytes, _stream_ptr(self.device)))
+
+    def __del__(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h:
+            self._f['destroy'](h)
+
+    def _st(self, views):
+        return _struct(_lib.ActionWeights, {k: ACTION_PARAM_TO_FIELD[self.mode][k] for k in self.names}, views)
+
+    def shapes(self):
+        s = {'W1': (self.K, self.N), 'Wg': (2401, 49), 'b1': (self.N,), 'W2': (256, 256), 'b2': (256,), 'W3': (256, 13), 'b3': (13,)}
+        return {k: s[k] for k in self.names}
+
+    def set_weights(self, params):
+        """params: {name: array} (synthetic.action_params / checkpoint.import_action_*_variables) -> the flat master
+        buffer and the operand copy of W1.  Adam's slots are left as they are (zero on first use)."""
+        src = {k: _as_dev_f32(params[k], self.device) for k in self.names}
+        for k, shp in self.shapes().items():
+            assert tuple(src[k].shape) == shp, (k, tuple(src[k].shape), shp)
+        if self.weights is None:
+            self.flat_params, self.weights = _flat_views(self.names, src, self.device)
+        for k in self.names:
+            self.weights[k].copy_(src[k])
+        self.repack()
+
+    def repack(self):
+        st = self._st(self.weights)
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['set_weights'](self._h, ctypes.byref(st), _stream_ptr(self.device)))
+
+    def get_weights(self):
+        """{name: device tensor}: copies made by the library (rgp_action_get_weights)."""
+        flat, views = _flat_views(self.names, self.weights, self.device)
+        st = self._st(views)
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['get_weights'](self._h, ctypes.byref(st), _stream_ptr(self.device)))
+        return views
+
+    def slots(self):
+        """Adam's m and v as {name: view} (NN training plans; created as zeros and bound on first use)."""
+        if self.adam_m is None:
+            self.adam_m, self.adam_v = torch.zeros_like(self.flat_params), torch.zeros_like(self.flat_params)
+        if getattr(self, '_bound_m', None) is not self.adam_m or self._bound_v is not self.adam_v:   # (load_optimizer_state swaps them)
+            layout = _flat_layout(self.names, self.shapes())
+            self._mv = tuple({k: buf[off:off + n].view(self.shapes()[k]) for k, off, n in layout} for buf in (self.adam_m, self.adam_v))
+            _lib.check(self._f['bind_slots'](self._h, ctypes.byref(self._st(self._mv[0])), ctypes.byref(self._st(self._mv[1]))))
+            self._bound_m, self._bound_v = self.adam_m, self.adam_v
+        return self._mv
+
+    def _check_inputs(self, c3d, gazemap, labels=None):
+        assert c3d.is_cuda and c3d.dtype == torch.float32 and c3d.is_contiguous() and c3d.numel() == self.B * self.K, tuple(c3d.shape)
+        if self.use_gazemap:
+            assert gazemap is not None and gazemap.is_cuda and gazemap.dtype == torch.float32 and gazemap.is_contiguous()
+            assert gazemap.numel() == self.B * 2401, tuple(gazemap.shape)
+        if labels is not None:
+            assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous() and labels.numel() == self.B * 13
+
+    def _gm(self, gazemap):
+        return _ptr(gazemap) if self.use_gazemap else None
+
+    def forward(self, c3d, gazemap=None):
+        """c3d [B,C,49] (or [B,C,7,7]) fp32, gazemap [B,49,49] fp32 device tensors -> (logits, y_pred) [B,13]."""
+        self._check_inputs(c3d, gazemap)
+        logits = torch.empty(self.B, 13, device=self.device)
+        y_pred = torch.empty_like(logits)
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['forward'](self._h, _ptr(c3d), self._gm(gazemap), _ptr(logits), _ptr(y_pred), _stream_ptr(self.device)))
+        return logits, y_pred
+
+    def forward_rows(self, rows, gazemap=None):
+        """rows: conv5b rows of C3DEngine.forward for B windows (operand dtype, [B*49, 1024], column d*512+c)."""
+        assert rows.is_cuda and rows.dtype == self.torch_dtype and rows.is_contiguous() and rows.numel() == self.B * 49 * 1024
+        logits = torch.empty(self.B, 13, device=self.device)
+        y_pred = torch.empty_like(logits)
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['forward_rows'](self._h, _ptr(rows), self._gm(gazemap), _ptr(logits), _ptr(y_pred), _stream_ptr(self.device)))
+        return logits, y_pred
+
+    def loss(self, labels):
+        """The loss of the last forward's batch -> 1-element device tensor."""
+        assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous() and labels.numel() == self.B * 13
+        out = torch.empty(1, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['loss'](self._h, _ptr(labels), _ptr(out), _stream_ptr(self.device)))
+        return out
+
+    def train_step(self, c3d, gazemap, labels, step, lr=None):
+        """One optimizer step; lr None = the reference's (NN: 0.002 * 0.96^(step/10); SVM: 0.01).  Returns the loss
+        before the update (1-element device tensor)."""
+        self._check_inputs(c3d, gazemap, labels)
+        if lr is None:
+            lr = action_learning_rate(step) if self.mode == 'NN' else 0.01
+        if self.mode == 'NN':
+            self.slots()
+        out = torch.empty(1, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['train_step'](self._h, _ptr(c3d), self._gm(gazemap), _ptr(labels), int(step), float(lr), _ptr(out),
+                                             _stream_ptr(self.device)))
+        return out
+
+    # ---- the stages of a step (tests)
+    def fc1_fwd(self, c3d, gazemap=None):
+        self._check_inputs(c3d, gazemap)
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['fc1_fwd'](self._h, _ptr(c3d), self._gm(gazemap), _stream_ptr(self.device)))
+
+    def tail(self, labels=None):
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['tail'](self._h, _ptr(labels), _stream_ptr(self.device)))
+
+    def fc1_update(self, c3d, gazemap, d_h1, step, lr):
+        self._check_inputs(c3d, gazemap)
+        assert d_h1.is_cuda and d_h1.dtype == torch.float32 and d_h1.is_contiguous() and d_h1.numel() == self.B * self.N
+        if self.mode == 'NN':
+            self.slots()
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['fc1_update'](self._h, _ptr(c3d), self._gm(gazemap), _ptr(d_h1), int(step), float(lr), _stream_ptr(self.device)))
+
+    def read_buffer_elems(self, name):
+        return int(self._f['buffer_elems'](self._h, name.encode()))
+
+    def read_buffer(self, name):
+        n = self.read_buffer_elems(name)
+        if n == 0:
+            raise _lib.RgpError('unknown intermediate %r' % name)
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['read_buffer'](self._h, name.encode(), _ptr(out), _stream_ptr(self.device)))
+        return out

@@ -259,3 +259,28 @@ class SyntheticDataSet(object):
         pupils = np.zeros((batch_size, T), np.float32)
         names = ['synthetic_%04d' % i for i in idx]
         return images, maps, fix, c3d, pupils, names
+
+
+ACTION_HIDDEN, ACTION_CLASSES = 256, 13
+
+
+def action_params(seed, mode='NN', use_gazemap=False, dim_feat=1024):
+    """Initial variables of the action classifier (models/action_classification.py:210-292, basic_graphs.py:83-118):
+    Wg [2401,49] truncated normal, sigma 0.05 (use_gazemap only); 'NN': W1 [49*dim_feat,256], W2 [256,256], W3 [256,13]
+    glorot-uniform, b1..b3 constant 0.05; 'SVM': W1 [49*dim_feat,13] and b1 [13] zero."""
+    rs = np.random.RandomState(seed)
+    K = 49 * int(dim_feat)
+    p = {}
+    if use_gazemap:
+        p['Wg'] = _trunc_normal(rs, (2401, 49), 0.05)
+    if mode == 'NN':
+        for w, b, n_in, n_out in (('W1', 'b1', K, ACTION_HIDDEN), ('W2', 'b2', ACTION_HIDDEN, ACTION_HIDDEN),
+                                  ('W3', 'b3', ACTION_HIDDEN, ACTION_CLASSES)):
+            p[w] = _xavier_fc(rs, n_in, n_out)
+            p[b] = np.full((n_out,), 0.05, np.float32)
+    elif mode == 'SVM':
+        p['W1'] = np.zeros((K, ACTION_CLASSES), np.float32)
+        p['b1'] = np.zeros((ACTION_CLASSES,), np.float32)
+    else:
+        raise ValueError('mode must be NN or SVM')
+    return p
