@@ -121,6 +121,26 @@ int rgp_grcn_forward(rgp_grcn_t* plan, const float* c3d_input, float* logits, fl
  * [B*T*49][1024] with K order d*512+c), skipping the transpose of gaze_grcn.py:225-227. */
 int rgp_grcn_forward_rows(rgp_grcn_t* plan, const void* c3d_rows, float* logits, float* probs, rgp_stream_t stream);
 
+/* Streaming inference: the same graph with the recurrent state carried across calls, so that a video longer than the
+ * plan's T steps is one recurrence and not a row of unrelated clips.  Streaming is a call, not a plan property.
+ *   c3d_input / c3d_rows  exactly one is non-NULL; laid out as for rgp_grcn_forward / _forward_rows, always [B,T,...]
+ *   state_in   fp32 [B][49][S] (16-byte aligned), NULL = the zero state; never written
+ *   state_out  may be NULL; must not alias state_in; receives the state behind step n_valid
+ *   n_valid    1..T: the recurrence is defined for steps 0..n_valid-1.  The outputs of later steps are unspecified; their
+ *              inputs are read, but influence neither the first n_valid outputs nor state_out
+ *   bn_phase   0..T-1: step t of the call uses batch-norm slot (bn_phase + t) % T.  A caller that passes its stream
+ *              position mod T gets results that do not depend on where the stream was cut; with cuts at multiples of T
+ *              this is the reference's chunked evaluation plus a carried state.
+ * rgp_grcn_forward_stream(.., NULL, state_out, T, 0, ..) computes what rgp_grcn_forward computes.  Argument errors are
+ * RGP_EINVAL and are reported ahead of the plan's bound / weights state.  A training plan accepts the call, but a
+ * following rgp_grcn_backward / _from_states returns RGP_ESTATE (no truncated BPTT) until a plain forward has run.
+ * A persistent launch that times out (rgp_grcn_status) NaN-poisons state_out of its clips along with the maps; state_in
+ * being read-only, the caller repeats the call.
+ * rgp_grcn_state_elems: B*49*S, the fp32 elements of a state; host-only, works on an unbound plan. */
+size_t rgp_grcn_state_elems(const rgp_grcn_t* plan);
+int rgp_grcn_forward_stream(rgp_grcn_t* plan, const float* c3d_input, const void* c3d_rows, const float* state_in, float* state_out,
+                            int n_valid, int bn_phase, float* logits, float* probs, rgp_stream_t stream);
+
 /* Stages of the same graph on the plan's workspace (for tests / profiling):
  * rgp_proj_fwd          transpose + xw_plus_b                  gaze_grcn.py:225-254
  * rgp_convgru_xconv_fwd W_z,W_r,W convs of all T steps at once gaze_grcn.py:108-109,112-113,122-123
@@ -384,6 +404,12 @@ int rgp_lstm_set_weights(rgp_lstm_t* plan, const rgp_lstm_weights* w, rgp_stream
 int rgp_lstm_forward(rgp_lstm_t* plan, const float* c3d_input, float* logits, float* probs, rgp_stream_t stream);
 /* c3d_rows: [B*T*49, 1024] in the plan's operand dtype, column d*512+c, 16-byte aligned (what rgp_c3d_forward writes) */
 int rgp_lstm_forward_rows(rgp_lstm_t* plan, const void* c3d_rows, float* logits, float* probs, rgp_stream_t stream);
+/* Streaming inference, as rgp_grcn_forward_stream without bn_phase (this graph has no per-timestep batch-norm).  The
+ * state is [2][B][49][128] fp32: h, then c.  rgp_lstm_state_elems: 2*B*49*128.  After the call rgp_lstm_backward returns
+ * RGP_ESTATE until a plain forward has run. */
+size_t rgp_lstm_state_elems(const rgp_lstm_t* plan);
+int rgp_lstm_forward_stream(rgp_lstm_t* plan, const float* c3d_input, const void* c3d_rows, const float* state_in, float* state_out,
+                            int n_valid, float* logits, float* probs, rgp_stream_t stream);
 /* Training plans, after a forward: gradients of the loss of gaze_rnn.py:363-408 (loss_type 0 xentropy, 1 l2) w.r.t. the
  * 18 variables (grads: arrays shaped like the weights).  BPTT runs as per-timestep launches, or as one persistent launch
  * on plans created with RGP_LSTM_BPTT_PERSISTENT; grads->W_hc is zeroed. */
@@ -439,6 +465,12 @@ int rgp_grcn77_set_weights(rgp_grcn77_t* plan, const rgp_grcn77_weights* w, rgp_
 int rgp_grcn77_forward(rgp_grcn77_t* plan, const float* c3d_input, float* logits, float* probs, rgp_stream_t stream);
 /* c3d_rows: [B*T*49, 1024] in the plan's operand dtype, column d*512+c, 16-byte aligned (what rgp_c3d_forward writes) */
 int rgp_grcn77_forward_rows(rgp_grcn77_t* plan, const void* c3d_rows, float* logits, float* probs, rgp_stream_t stream);
+/* Streaming inference, as rgp_grcn_forward_stream without bn_phase (this graph has no per-timestep batch-norm): the
+ * state [B][49][128] goes through the plan's rgp_grcn sub-plan.  After the call rgp_grcn77_backward returns RGP_ESTATE
+ * until a plain forward has run. */
+size_t rgp_grcn77_state_elems(const rgp_grcn77_t* plan);
+int rgp_grcn77_forward_stream(rgp_grcn77_t* plan, const float* c3d_input, const void* c3d_rows, const float* state_in, float* state_out,
+                              int n_valid, float* logits, float* probs, rgp_stream_t stream);
 /* Training plans, after a forward: gradients of the loss of gaze_rnn.py:363-408 over 49 pixels (loss_type 0 xentropy: probs
  * and labels are read; 1 l2: logits and labels; labels [B,T,7,7]) w.r.t. the ten variables (grads: arrays shaped like
  * the weights, fully overwritten).  The recurrence is differentiated by rgp_grcn_backward_from_states of the plan's

@@ -115,6 +115,8 @@ SIGNATURES = {
     'rgp_grcn_set_weights': (c_int, [c_void_p, ctypes.POINTER(GrcnWeights), c_void_p]),
     'rgp_grcn_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'rgp_grcn_forward_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rgp_grcn_state_elems': (c_size_t, [c_void_p]),
+    'rgp_grcn_forward_stream': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'rgp_proj_fwd': (c_int, [c_void_p, c_void_p, c_void_p]),
     'rgp_convgru_xconv_fwd': (c_int, [c_void_p, c_void_p]),
     'rgp_convgru_seq_fwd': (c_int, [c_void_p, c_void_p]),
@@ -151,6 +153,8 @@ SIGNATURES = {
     'rgp_lstm_set_weights': (c_int, [c_void_p, ctypes.POINTER(LstmWeights), c_void_p]),
     'rgp_lstm_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'rgp_lstm_forward_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rgp_lstm_state_elems': (c_size_t, [c_void_p]),
+    'rgp_lstm_forward_stream': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'rgp_lstm_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(LstmWeights), c_int, c_void_p]),
     'rgp_lstm_backward_input': (c_int, [c_void_p, c_void_p, c_void_p]),
     'rgp_lstm_status': (c_int, [c_void_p, c_void_p]),
@@ -166,6 +170,8 @@ SIGNATURES = {
     'rgp_grcn77_set_weights': (c_int, [c_void_p, ctypes.POINTER(Grcn77Weights), c_void_p]),
     'rgp_grcn77_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'rgp_grcn77_forward_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rgp_grcn77_state_elems': (c_size_t, [c_void_p]),
+    'rgp_grcn77_forward_stream': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'rgp_grcn77_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Grcn77Weights), c_int, c_void_p]),
     'rgp_grcn77_backward_input': (c_int, [c_void_p, c_void_p, c_void_p]),
     'rgp_grcn77_status': (c_int, [c_void_p, c_void_p]),

@@ -20,7 +20,7 @@ struct SeqParams {
   const bf16_t* w_zr;        // packed [256][K] (rows 0..127 U_z columns, 128..255 U_r), K = tap*128 + c
   const bf16_t* w_c;         // packed [128][K]
   const float* xpre;         // [B][T][49][384] hoisted W_z|W_r|W * x
-  float* hall;               // [T+1][B][49][128] fp32 states (slot 0 = h_0 = 0, pre-zeroed)
+  float* hall;               // [T+1][B][49][128] fp32 states (slot 0 = h_0: zeroed, or seeded by a streaming call)
   float* uall;               // [T][B][49][128]
   float* rall;               // optional (training)
   float* call;               // optional (training)
@@ -32,6 +32,8 @@ struct SeqParams {
   bf16_t* xch_rh;            // [ngroups][98][128] exchange image of r.h
   SeqGroupArgs g;            // 2 T phase counters per group
   int T, K;
+  int carry;                 // streaming call with a state: h_0 = slot 0 of hall, its operand image seeded in xch_h (seq_seed_kernel)
+  int bn_phase;              // step t uses batch-norm slot (bn_phase + t) % T
 };
 
 constexpr int SEQ_RED_OFF = 2 * SEQ_IMG;             // 4 waves x 7 fragments x 2 gates partial tiles of 1 KiB (56 KiB)
@@ -40,7 +42,11 @@ constexpr int SEQ_FLAG_OFF = SEQ_STAGE_OFF + 4 * 512;
 constexpr int SEQ_SMEM = SEQ_FLAG_OFF + 16;          // 160 592 B (no static __shared__: the dynamic base stays 16-B aligned)
 static_assert(SEQ_SMEM <= 160 * 1024, "LDS budget");
 
-template <int NF>
+// STREAM: the instantiation of the streaming calls (a carried state and / or a batch-norm phase).  The zero-state forward runs
+// <NF, false>, whose source -- and so whose loop -- is the one it had before streaming existed: convgru_seq_kernel<7> sits at
+// the edge of its register file, and a run-time branch in front of the loop moved its register allocation enough to show in
+// the plain forward.
+template <int NF, bool STREAM>
 static __global__ __launch_bounds__(SEQ_NT) void convgru_seq_kernel(const SeqParams p) {
   extern __shared__ __attribute__((aligned(16))) char sq_smem[];
   char* img_h = sq_smem;
@@ -80,6 +86,18 @@ static __global__ __launch_bounds__(SEQ_NT) void convgru_seq_kernel(const SeqPar
     }
   float h_prev[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   __syncthreads();                                       // images zeroed, flag cleared (init)
+  // A carried state (wave-uniform, outside the loop): the fp32 state from slot 0, the operand image from the seeded
+  // exchange image -- what the hand-off of a step -1 would have left.  Without one nothing here runs.
+  if (STREAM && p.carry) {
+#pragma unroll
+    for (int o = 0; o < 2; ++o)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (ovalid[o][r]) h_prev[o][r] = p.hall[((long long)(clip0 * 49 + orow[o][r])) * S + ch];
+    g.load_image(p.xch_h, xbytes, g.group, img_h);
+    __syncthreads();
+  }
+  int bn_slot = STREAM ? p.bn_phase : 0;                 // (scalar; no division in the loop)
   // hand-off of phase `ph`: publish this wave's tiles v, rendezvous, load the group's exchange image into an LDS image.
   // (The step's plain output stores are issued after it, see the loop.)
   auto hand_off = [&](int ph, bf16_t* xch, char* img, const float (&v)[2][4]) {
@@ -107,8 +125,14 @@ static __global__ __launch_bounds__(SEQ_NT) void convgru_seq_kernel(const SeqPar
           xz[o][r] = xp[0]; xr[o][r] = xp[S]; xc[o][r] = xp[2 * S];
         }
       }
-    gam = p.bn_gamma[t * S + ch];
-    bet = p.bn_beta[t * S + ch];
+    if constexpr (STREAM) {
+      gam = p.bn_gamma[bn_slot * S + ch];
+      bet = p.bn_beta[bn_slot * S + ch];
+      bn_slot = bn_slot + 1 == T_ ? 0 : bn_slot + 1;
+    } else {
+      gam = p.bn_gamma[t * S + ch];
+      bet = p.bn_beta[t * S + ch];
+    }
 
     // ---- z | r phase: partial sums of this wave's K quarter, reduced over the 4 quarters through LDS
     {

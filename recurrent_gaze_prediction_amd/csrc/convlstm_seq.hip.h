@@ -27,13 +27,14 @@ struct LstmSeqParams {
   const bf16_t* w_rec;       // packed [512][K]: row 4 c + q, q = 0 W_hi, 1 W_hf, 3 W_ho (2 stays zero); K = tap*128 + channel
   const float* xpre;         // [B][T][49][512] hoisted x parts, column 4 c + q, q = i, f, g, o
   const float* peep;         // [3][49][128] W_ci, W_cf, W_co
-  float* hall;               // [T+1][B][49][128] fp32 h (slot 0 = zero state, pre-zeroed)
+  float* hall;               // [T+1][B][49][128] fp32 h (slot 0 = the zero state, or seeded by a streaming call)
   float* call;               // [T+1][B][49][128] fp32 c
   float* gates;              // optional (training): [4][T][B][49][128] i, f, g, o
   bf16_t* hseq;              // [B][T+1][81][128] halo-padded h_t at slot t+1 (slot 0 zero): the head's input
   bf16_t* xch;               // [2][ngroups][98][128] exchange images of h' (step parity)
   SeqGroupArgs g;            // T phase counters per group
   int T, K;
+  int carry;                 // streaming call with a state: c_0 = slot 0 of call, the image of h_0 seeded in parity 1 of xch
 };
 
 constexpr int LSQ_RED_OFF = SEQ_IMG;                   // 4 waves x 7 fragments x 3 gates partial tiles of 1 KiB
@@ -42,7 +43,9 @@ constexpr int LSQ_FLAG_OFF = LSQ_STAGE_OFF + 4 * 512;
 constexpr int LSQ_SMEM = LSQ_FLAG_OFF + 16;
 static_assert(LSQ_SMEM <= 160 * 1024, "LDS budget");
 
-template <int NF>
+// STREAM: the instantiation of the streaming calls with a carried state; the zero-state forward runs <NF, false>, whose
+// source is the one it had before streaming existed (convgru_seq.hip.h says why).
+template <int NF, bool STREAM>
 static __global__ __launch_bounds__(SEQ_NT) void convlstm_seq_kernel(const LstmSeqParams p) {
   extern __shared__ __attribute__((aligned(16))) char lq_smem[];
   char* img_h = lq_smem;
@@ -89,6 +92,19 @@ static __global__ __launch_bounds__(SEQ_NT) void convlstm_seq_kernel(const LstmS
     }
   float c_prev[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   __syncthreads();                                       // image zeroed, flag cleared (init)
+  // A carried state (wave-uniform, outside the loop): c from slot 0, the operand image of h_0 from the exchange image
+  // of parity 1, where a step -1 would have published it (seq_seed_kernel).  The parity argument above holds for it: a
+  // member stores into parity 1 again at step 1, behind wait(0), which follows everybody's loads here.
+  const bool carry = STREAM && p.carry != 0;
+  if (carry) {
+#pragma unroll
+    for (int o = 0; o < 2; ++o)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (xo[o][r] >= 0) c_prev[o][r] = p.call[so_[o][r]];
+    g.load_image(p.xch, xbytes, p.g.ngroups + g.group, img_h);
+    __syncthreads();
+  }
 
   for (int t = 0; t < T_; ++t) {
     // hoisted input parts of this lane's rows: one 16-byte load per row (i, f, g, o of its channel), in flight during the MFMAs
@@ -102,7 +118,7 @@ static __global__ __launch_bounds__(SEQ_NT) void convlstm_seq_kernel(const LstmS
         if (xo[o][r] >= 0) xv[o][r] = *(const f32x4*)(xpre_t + xo[o][r]);
       }
     // ---- the three recurrent convolutions on h_{t-1}: partial sums of this wave's K quarter, reduced through LDS
-    if (t > 0) {
+    if (t > 0 || carry) {
       f32x4 ai[NF], af[NF], ao[NF];
 #pragma unroll
       for (int f = 0; f < NF; ++f) { ai[f] = (f32x4){0.f, 0.f, 0.f, 0.f}; af[f] = ai[f]; ao[f] = ai[f]; }
@@ -127,7 +143,7 @@ static __global__ __launch_bounds__(SEQ_NT) void convlstm_seq_kernel(const LstmS
     for (int o = 0; o < 2; ++o) {
       const int f = kq + 4 * o;
       f32x4 si = (f32x4){0.f, 0.f, 0.f, 0.f}, sf = si, so = si;
-      if (f < NF && t > 0) {                              // (step 0: h_0 = 0, the sums are exact zeros)
+      if (f < NF && (t > 0 || carry)) {                   // (step 0 from the zero state: the sums are exact zeros)
         si = g.template reduce_tile<3>(red, 0, f);
         sf = g.template reduce_tile<3>(red, 1, f);
         so = g.template reduce_tile<3>(red, 2, f);

@@ -124,11 +124,16 @@ namespace {
 int seq_persistent(rgp_grcn* g, hipStream_t s) {
   const int B = g->B, T_ = g->T, S = g->S;
   const size_t st = (size_t)B * 49 * S;
+  const bool carry = g->st_on && g->st_in;                                   // a streaming call with a state
   {
     ZeroBatch z(s);
-    RGP_TRY(z.add(g->ws + g->hall.off, st * 4));                             // h_0 = 0 (gaze_grcn.py:262)
+    if (!carry) RGP_TRY(z.add(g->ws + g->hall.off, st * 4));                 // h_0 = 0 (gaze_grcn.py:262)
     RGP_TRY(z.add(g->ws + g->seq_cnt.off, g->seq_cnt.bytes));                // phase counters: zeroed EVERY call
     RGP_TRY(z.flush());
+  }
+  if (carry) {                                                               // h_0 = the state: slot 0 + the groups' exchange image
+    SeqSeedArgs a{g->st_in, nullptr, (float*)(g->ws + g->hall.off), nullptr, nullptr, 0, (bf16_t*)(g->ws + g->xch_h.off), 0, g->sg.nc, B, S};
+    RGP_TRY(launch_seq_seed<bf16_t>(a, s));
   }
   SeqParams p;
   p.w_zr = (const bf16_t*)(g->ws + g->gzr.w_off);
@@ -146,8 +151,11 @@ int seq_persistent(rgp_grcn* g, hipStream_t s) {
   p.xch_rh = (bf16_t*)(g->ws + g->xch_rh.off);
   p.g = g->sg.args(B, (unsigned*)(g->ws + g->seq_cnt.off), RGP_FAULT_SEQ_LOST_MEMBER);
   p.T = T_; p.K = g->gzr.K;
+  p.carry = carry ? 1 : 0;
+  p.bn_phase = g->st_on ? g->st_phase : 0;
   RGP_REQUIRE(g->gzr.K == 9 * S && g->gc.K == 9 * S && g->gzr.chunk_major == 0, "convgru_seq: unexpected filter packing");
-  return launch_seq_group(g->sg, convgru_seq_kernel<4>, convgru_seq_kernel<7>, p, SEQ_SMEM, s);
+  if (p.carry || p.bn_phase) return launch_seq_group(g->sg, convgru_seq_kernel<4, true>, convgru_seq_kernel<7, true>, p, SEQ_SMEM, s);
+  return launch_seq_group(g->sg, convgru_seq_kernel<4, false>, convgru_seq_kernel<7, false>, p, SEQ_SMEM, s);
 }
 
 template <typename T>
@@ -155,8 +163,14 @@ int seq_impl(rgp_grcn* g, hipStream_t s) {
   const int B = g->B, T_ = g->T, S = g->S;
   if (sizeof(T) == 2 && g->sg.resident() && dev_knob("RGP_SEQ", 1)) return seq_persistent(g, s);
   const size_t st = (size_t)B * 49 * S;  // fp32 elements per state snapshot
-  RGP_HIP(hipMemsetAsync(g->ws + g->hp.off, 0, g->hp.bytes, s));      // h_0 = 0 (gaze_grcn.py:262)
-  RGP_HIP(hipMemsetAsync(g->ws + g->hall.off, 0, st * 4, s));
+  const int phase = g->st_on ? g->st_phase : 0;
+  if (g->st_on && g->st_in) {                                         // streaming call: h_0 = the state, copied and padded
+    SeqSeedArgs a{g->st_in, nullptr, (float*)(g->ws + g->hall.off), nullptr, g->ws + g->hp.off, 81LL * S, nullptr, 0, 1, B, S};
+    RGP_TRY(launch_seq_seed<T>(a, s));
+  } else {
+    RGP_HIP(hipMemsetAsync(g->ws + g->hp.off, 0, g->hp.bytes, s));    // h_0 = 0 (gaze_grcn.py:262)
+    RGP_HIP(hipMemsetAsync(g->ws + g->hall.off, 0, st * 4, s));
+  }
   float* hall = (float*)(g->ws + g->hall.off);
   float* uall = (float*)(g->ws + g->uall.off);
   float* rall = g->save ? (float*)(g->ws + g->rall.off) : nullptr;
@@ -186,8 +200,8 @@ int seq_impl(rgp_grcn* g, hipStream_t s) {
     e.out2_img_stride = 81LL * S;
     e.out2_img_mul = T_;
     e.out2_img_add = t;
-    e.bn_gamma = g->bn_gamma + (size_t)t * S;
-    e.bn_beta = g->bn_beta + (size_t)t * S;
+    e.bn_gamma = g->bn_gamma + (size_t)((t + phase) % T_) * S;
+    e.bn_beta = g->bn_beta + (size_t)((t + phase) % T_) * S;
     e.bn_inv_std = 1.0f / sqrtf(1.0f + 1e-3f);  // moving mean 0 / var 1, eps 1e-3
     IgemmParams pc = make_params(g->gc, g->ws + g->rhp.off, g->ws, B);
     RGP_TRY((launch_igemm<T, 1, 1, EpiGruC<T>>(pc, e, s)));
@@ -496,6 +510,7 @@ int rgp_convgru_seq_fwd(rgp_grcn_t* g, rgp_stream_t stream) {
   const int pid = g->prof.begin(2, s);
   const int rc = RGP_BY_DTYPE(g->dtype, seq_impl, g, s);
   g->prof.end(pid, s);
+  g->streamed = g->st_on;
   return rc;
 }
 
@@ -536,7 +551,30 @@ int rgp_grcn_forward_rows(rgp_grcn_t* g, const void* c3d_rows, float* logits, fl
   return grcn_tail(g, logits, probs, stream);
 }
 
+size_t rgp_grcn_state_elems(const rgp_grcn_t* g) { return g ? (size_t)g->B * 49 * g->S : 0; }
+
+int rgp_grcn_forward_stream(rgp_grcn_t* g, const float* c3d_input, const void* c3d_rows, const float* state_in, float* state_out,
+                            int n_valid, int bn_phase, float* logits, float* probs, rgp_stream_t stream) {
+  RGP_REQUIRE(g, "rgp_grcn_forward_stream: null plan");
+  RGP_TRY(check_stream_args("rgp_grcn_forward_stream", g->T, c3d_input, c3d_rows, state_in, state_out, n_valid, bn_phase, logits));
+  RGP_TRY(check_ready(g));
+  hipStream_t s = (hipStream_t)stream;
+  g->st_on = true; g->st_in = state_in; g->st_phase = bn_phase;
+  int rc = c3d_input ? rgp_proj_fwd(g, c3d_input, stream) : grcn_proj_rows_fwd(g, c3d_rows, s);
+  if (rc == RGP_OK) rc = grcn_tail(g, logits, probs, stream);
+  g->st_on = false; g->st_in = nullptr; g->st_phase = 0;
+  RGP_TRY(rc);
+  return grcn_copy_state(g, state_out, n_valid, s);
+}
+
 }  // extern "C"
+
+int grcn_copy_state(rgp_grcn* g, float* state_out, int n_valid, hipStream_t s) {
+  if (!state_out) return RGP_OK;
+  const size_t st = (size_t)g->B * 49 * g->S * 4;
+  RGP_HIP(hipMemcpyAsync(state_out, g->ws + g->hall.off + (size_t)n_valid * st, st, hipMemcpyDeviceToDevice, s));
+  return RGP_OK;
+}
 
 // rgp_grcn_forward_rows' projection alone (no ABI symbol: for plans that own a sub-plan and run its stages, rgp_grcn77.hip)
 int grcn_proj_rows_fwd(rgp_grcn* g, const void* c3d_rows, hipStream_t s) {

@@ -157,6 +157,24 @@ int rgp_grcn77_forward_rows(rgp_grcn77_t* g, const void* c3d_rows, float* logits
   return tail(g, logits, probs, stream);
 }
 
+size_t rgp_grcn77_state_elems(const rgp_grcn77_t* g) { return g ? rgp_grcn_state_elems(g->inner) : 0; }
+
+// The state goes through the sub-plan (its batch-norm is the identity in every slot: no phase); head_point reads the states as ever.
+int rgp_grcn77_forward_stream(rgp_grcn77_t* g, const float* c3d_input, const void* c3d_rows, const float* state_in, float* state_out,
+                              int n_valid, float* logits, float* probs, rgp_stream_t stream) {
+  RGP_REQUIRE(g, "rgp_grcn77_forward_stream: null plan");
+  RGP_TRY(check_stream_args("rgp_grcn77_forward_stream", g->T, c3d_input, c3d_rows, state_in, state_out, n_valid, 0, logits));
+  RGP_TRY(check_ready(g));
+  rgp_grcn* in = g->inner;
+  in->st_on = true; in->st_in = state_in; in->st_phase = 0;
+  int rc = c3d_input ? rgp_proj_fwd(in, c3d_input, stream) : grcn_proj_rows_fwd(in, c3d_rows, (hipStream_t)stream);
+  if (rc == RGP_OK) rc = tail(g, logits, probs, stream);
+  in->st_on = false; in->st_in = nullptr;
+  g->fwd_done = false;                                     // no backward behind a streaming call (RGP_ESTATE)
+  RGP_TRY(rc);
+  return grcn_copy_state(in, state_out, n_valid, (hipStream_t)stream);
+}
+
 int rgp_grcn77_head_fwd(rgp_grcn77_t* g, const float* states, float* logits, float* probs, rgp_stream_t stream) {
   RGP_TRY(check_ready(g));
   RGP_REQUIRE(logits, "rgp_grcn77_head_fwd: null logits");
@@ -175,7 +193,7 @@ int rgp_grcn77_backward(rgp_grcn77_t* g, const float* logits, const float* probs
   RGP_REQUIRE(labels && grads && (loss_type == 0 || loss_type == 1), "rgp_grcn77_backward: bad arguments");
   RGP_REQUIRE(loss_type == 1 ? logits != nullptr : probs != nullptr, "rgp_grcn77_backward: the loss needs %s", loss_type == 1 ? "logits" : "probs");
   if (!g->save) return set_err(RGP_ESTATE, "rgp_grcn77_backward: the plan was not created with RGP_GRCN77_SAVE_FOR_BACKWARD");
-  if (!g->fwd_done) return set_err(RGP_ESTATE, "rgp_grcn77_backward: no forward since the weights were set");
+  if (!g->fwd_done) return set_err(RGP_ESTATE, "rgp_grcn77_backward: no forward since the weights were set (a streaming call is none: no truncated BPTT)");
   RGP_TRY(require_pointers(grads, "rgp_grcn77_backward", "gradient"));
   hipStream_t s = (hipStream_t)stream;
   constexpr int S = rgp_grcn77::S;

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -124,6 +125,29 @@ int launch_seq_group(const SeqGroupPlan& sg, void (*k4)(P), void (*k7)(P), const
   kern<<<sg.groups * 8, SEQ_NT, smem, s>>>(p);
   RGP_HIP(hipGetLastError());
   return guard.commit();
+}
+
+// The seed launch of a streaming call (seq_group.hip.h, seq_seed_kernel), T = the operand type of a.pad
+template <typename T>
+int launch_seq_seed(const SeqSeedArgs& a, hipStream_t s) {
+  const int total = a.B * 49 * (a.S / 4);
+  seq_seed_kernel<T><<<std::min((total + 255) / 256, 1024), 256, 0, s>>>(a);
+  RGP_HIP(hipGetLastError());
+  return RGP_OK;
+}
+
+// Argument rules common to the rgp_*_forward_stream calls (include/rgp.h), checked AHEAD of the plan's bound / ready
+// state.  T = the plan's steps; the families without a per-timestep batch-norm pass bn_phase = 0.
+inline int check_stream_args(const char* fn, int T, const void* c3d_input, const void* c3d_rows, const float* state_in,
+                             const float* state_out, int n_valid, int bn_phase, const void* logits) {
+  RGP_REQUIRE((c3d_input != nullptr) != (c3d_rows != nullptr), "%s: exactly one of c3d_input and c3d_rows must be set", fn);
+  RGP_REQUIRE(n_valid >= 1 && n_valid <= T, "%s: n_valid=%d must be in 1..%d", fn, n_valid, T);
+  RGP_REQUIRE(bn_phase >= 0 && bn_phase < T, "%s: bn_phase=%d must be in 0..%d", fn, bn_phase, T - 1);
+  RGP_REQUIRE(!state_out || state_out != state_in, "%s: state_out must not alias state_in", fn);
+  RGP_REQUIRE((((size_t)state_in | (size_t)state_out | (size_t)c3d_rows) & 15) == 0,
+              "%s: state_in, state_out and c3d_rows must be 16-byte aligned", fn);
+  RGP_REQUIRE(logits, "%s: null logits", fn);
+  return RGP_OK;
 }
 
 // Row tables of the filter-gradient kernel (wgrad.hip.h): byte offset of row m = (z*H + y)*W + x of a D x H x W grid

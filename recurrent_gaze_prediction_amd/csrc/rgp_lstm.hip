@@ -28,6 +28,10 @@ using namespace rgp;
 struct rgp_lstm {
   int B = 0, T = 0, P = 512, S = 128, dtype = RGP_BF16, F = 0;
   bool save = false, fwd_done = false, bwd_done = false, weights_set = false;
+  // Streaming (rgp_lstm_forward_stream): set around one call's forward_impl.  slot0_seeded: slot 0 of hall / call / the h
+  // images holds a caller's state, not the zeros the bind left there -- the next zero-state forward clears it first.
+  bool st_on = false, slot0_seeded = false;
+  const float* st_in = nullptr;
   Projection pj;                           // gaze_stages.h
   FoldedHead head;                         // on h_t: a GEMM "image" is a clip
   ConvDesc xconv, grec;
@@ -122,7 +126,7 @@ int set_weights_impl(rgp_lstm* g, const rgp_lstm_weights* w, hipStream_t s) {
 }
 
 // All T steps in one persistent launch (convlstm_seq.hip.h)
-int seq_persistent(rgp_lstm* g, hipStream_t s) {
+int seq_persistent(rgp_lstm* g, bool carry, hipStream_t s) {
   char* ws = g->ws;
   RGP_HIP(hipMemsetAsync(ws + g->seq_cnt.off, 0, g->seq_cnt.bytes, s));       // phase counters: zeroed EVERY call
   LstmSeqParams p;
@@ -136,16 +140,30 @@ int seq_persistent(rgp_lstm* g, hipStream_t s) {
   p.xch = (bf16_t*)(ws + g->xch.off);
   p.g = g->sg.args(g->B, (unsigned*)(ws + g->seq_cnt.off), RGP_FAULT_SEQ_LOST_MEMBER);
   p.T = g->T; p.K = g->grec.K;
+  p.carry = carry ? 1 : 0;
   RGP_REQUIRE(g->grec.K == 9 * g->S && g->grec.chunk_major == 0, "convlstm_seq: unexpected filter packing");
-  return launch_seq_group(g->sg, convlstm_seq_kernel<4>, convlstm_seq_kernel<7>, p, LSQ_SMEM, s);
+  if (carry) return launch_seq_group(g->sg, convlstm_seq_kernel<4, true>, convlstm_seq_kernel<7, true>, p, LSQ_SMEM, s);
+  return launch_seq_group(g->sg, convlstm_seq_kernel<4, false>, convlstm_seq_kernel<7, false>, p, LSQ_SMEM, s);
 }
 
 template <typename T>
 int seq_impl(rgp_lstm* g, hipStream_t s) {
   char* ws = g->ws;
   const int B = g->B, T_ = g->T, S = g->S;
+  const bool persistent = sizeof(T) == 2 && g->fwd_persistent && g->sg.resident();
+  const bool carry = g->st_on && g->st_in;
+  // Slot 0 of the states and of the h images is zero from the bind on; a streaming call seeds it with its state (both
+  // paths: [h | c] -> hall, call, the padded h image; the persistent kernel's exchange image of parity 1), and the first
+  // zero-state call behind one seeds zeros again.
+  if (carry || g->slot0_seeded) {
+    const float* si = carry ? g->st_in : nullptr;
+    SeqSeedArgs a{si, si ? si + (size_t)B * 49 * S : nullptr, (float*)(ws + g->hall.off), (float*)(ws + g->call.off), ws + g->hseq.off,
+                  (long long)(T_ + 1) * 81 * S, persistent ? (bf16_t*)(ws + g->xch.off) : nullptr, g->sg.groups, std::max(g->sg.nc, 1), B, S};
+    RGP_TRY(launch_seq_seed<T>(a, s));
+    g->slot0_seeded = carry;
+  }
   if constexpr (sizeof(T) == 2) {
-    if (g->fwd_persistent && g->sg.resident()) return seq_persistent(g, s);
+    if (persistent) return seq_persistent(g, carry, s);
   }
   const size_t st = (size_t)B * 49 * S;
   float* hall = (float*)(ws + g->hall.off);
@@ -200,7 +218,7 @@ int forward_impl(rgp_lstm* g, const float* c3d_input, const void* rows, float* l
   RGP_TRY(seq_impl<T>(g, s));
   RGP_TRY(g->head.forward<T>(ws, ws + g->hseq.off, g->B, g->out_b, logits, g->F, s));
   if (probs) RGP_TRY(rgp_softmax_xent_fwd(logits, nullptr, probs, nullptr, nullptr, g->F, 2401, (rgp_stream_t)s));
-  g->fwd_done = true;
+  g->fwd_done = !g->st_on;                                    // no backward behind a streaming call (no truncated BPTT)
   g->bwd_done = false;
   return RGP_OK;
 }
@@ -458,6 +476,7 @@ int rgp_lstm_bind_workspace(rgp_lstm_t* g, void* workspace, size_t bytes, rgp_st
   RGP_TRY(g->sg.alloc_err());
   g->ws = (char*)workspace;
   g->weights_set = false;
+  g->slot0_seeded = false;
   // zero everything once: the halos of E / h images / dpre, slot 0 of the states and the unused filter rows stay zero,
   // because kernels only ever write interiors and a pack writes the same positions every time
   RGP_HIP(hipMemsetAsync(g->ws, 0, g->ws_bytes, s));
@@ -489,13 +508,33 @@ int rgp_lstm_forward_rows(rgp_lstm_t* g, const void* c3d_rows, float* logits, fl
   return RGP_BY_DTYPE(g->dtype, forward_impl, g, nullptr, c3d_rows, logits, probs, (hipStream_t)stream);
 }
 
+size_t rgp_lstm_state_elems(const rgp_lstm_t* g) { return g ? (size_t)2 * g->B * 49 * g->S : 0; }
+
+int rgp_lstm_forward_stream(rgp_lstm_t* g, const float* c3d_input, const void* c3d_rows, const float* state_in, float* state_out,
+                            int n_valid, float* logits, float* probs, rgp_stream_t stream) {
+  RGP_REQUIRE(g, "rgp_lstm_forward_stream: null plan");
+  RGP_TRY(check_stream_args("rgp_lstm_forward_stream", g->T, c3d_input, c3d_rows, state_in, state_out, n_valid, 0, logits));
+  RGP_TRY(check_ready(g));
+  hipStream_t s = (hipStream_t)stream;
+  g->st_on = true; g->st_in = state_in;
+  const int rc = RGP_BY_DTYPE(g->dtype, forward_impl, g, c3d_input, c3d_rows, logits, probs, s);
+  g->st_on = false; g->st_in = nullptr;
+  RGP_TRY(rc);
+  if (state_out) {                                           // [h | c] behind step n_valid
+    const size_t st = (size_t)g->B * 49 * g->S * 4;
+    RGP_HIP(hipMemcpyAsync(state_out, g->ws + g->hall.off + (size_t)n_valid * st, st, hipMemcpyDeviceToDevice, s));
+    RGP_HIP(hipMemcpyAsync((char*)state_out + st, g->ws + g->call.off + (size_t)n_valid * st, st, hipMemcpyDeviceToDevice, s));
+  }
+  return RGP_OK;
+}
+
 int rgp_lstm_backward(rgp_lstm_t* g, const float* logits, const float* probs, const float* labels, const rgp_lstm_weights* grads,
                       int loss_type, rgp_stream_t stream) {
   RGP_TRY(check_ready(g));
   RGP_REQUIRE(labels && grads && (loss_type == 0 || loss_type == 1), "rgp_lstm_backward: bad arguments");
   RGP_REQUIRE(loss_type == 1 ? logits != nullptr : probs != nullptr, "rgp_lstm_backward: the loss needs %s", loss_type == 1 ? "logits" : "probs");
   if (!g->save) return set_err(RGP_ESTATE, "rgp_lstm_backward: the plan was not created with RGP_LSTM_SAVE_FOR_BACKWARD");
-  if (!g->fwd_done) return set_err(RGP_ESTATE, "rgp_lstm_backward: no forward since the weights were set");
+  if (!g->fwd_done) return set_err(RGP_ESTATE, "rgp_lstm_backward: no forward since the weights were set (a streaming call is none: no truncated BPTT)");
   RGP_TRY(require_pointers(grads, "rgp_lstm_backward", "gradient"));
   return RGP_BY_DTYPE(g->dtype, backward_impl, g, logits, probs, labels, grads, loss_type, (hipStream_t)stream);
 }

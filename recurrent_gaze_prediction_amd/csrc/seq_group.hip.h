@@ -67,6 +67,49 @@ __device__ __forceinline__ bool seq_wait_phase(const unsigned* cnt) {      // tr
 // pixel of position r49 = 7 y + x in a halo-padded 9x9 image
 __device__ __forceinline__ int seq_pad_pix(int r49) { return (r49 / 7 + 1) * 9 + (r49 % 7 + 1); }
 
+// Streaming calls (rgp_*_forward_stream): a recurrence that starts from a caller's state instead of zeros.  One launch
+// ahead of the recurrence puts the state where each path reads its step -1 from: the fp32 slot 0 of the state
+// snapshots (and of the cell state), the halo-padded operand image of the per-step launches, and the groups' exchange
+// image of the persistent kernels, which then `load_image` it as they do behind every hand-off.  The conversion of the
+// operand copies is Elem<T>::to = f2bf, the one of publish_tile and of the per-step epilogues: a stream cut anywhere
+// sees the bits an uncut recurrence has at that step.  A null source seeds zeros.
+struct SeqSeedArgs {
+  const float* h_in;         // [B][49][S] fp32, or null
+  const float* c_in;         // the same for a cell state (h_in null <=> c_in null)
+  float* h0;                 // slot 0 of hall
+  float* c0;                 // slot 0 of call, or null: no cell state
+  void* pad;                 // operand images (T) of h_0, interior of clip b at pad + b * pad_img_stride; or null
+  long long pad_img_stride;  // elements
+  bf16_t* xch;               // exchange images [..][98][128], clip b = rows 49 (b % NC) .. of image xch_image0 + b / NC; or null
+  int xch_image0, NC;
+  int B, S;
+};
+template <typename T>
+static __global__ __launch_bounds__(256) void seq_seed_kernel(const SeqSeedArgs a) {
+  const int S4 = a.S >> 2;
+  const int total = a.B * 49 * S4;                       // (B <= 2^31 / 2401: far below 2^31)
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int c4 = i % S4, row = i / S4;                 // row = 49 b + r49
+    const int b = row / 49, r49 = row - b * 49;
+    const long long e = (long long)row * a.S + 4 * c4;
+    f32x4 h = (f32x4){0.f, 0.f, 0.f, 0.f}, c = h;
+    if (a.h_in) h = *(const f32x4*)(a.h_in + e);
+    if (a.c_in) c = *(const f32x4*)(a.c_in + e);
+    *(f32x4*)(a.h0 + e) = h;
+    if (a.c0) *(f32x4*)(a.c0 + e) = c;
+    if (a.pad) {
+      T* d = (T*)a.pad + (long long)b * a.pad_img_stride + (long long)seq_pad_pix(r49) * a.S + 4 * c4;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) d[k] = Elem<T>::to(h[k]);
+    }
+    if (a.xch) {
+      bf16_t* d = a.xch + ((long long)(a.xch_image0 + b / a.NC) * 98 + (b % a.NC) * 49 + r49) * 128 + 4 * c4;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) d[k] = f2bf(h[k]);
+    }
+  }
+}
+
 // NF is a template parameter so that the MFMA loops carry no run-time guards (measured: wave-uniform `if (f < MF)`
 // around the reads / MFMAs cost 25 %).  Every member function is inlined into the kernel: the object is a set of registers.
 template <int NF>

@@ -332,6 +332,41 @@ class _PersistentEngine(_GazeEngine):
     def persistent(self):
         return self.persistent_workgroups > 0
 
+    STREAM_BN_PHASE = False     # the family's forward_stream takes a batch-norm phase (gaze_grcn: one BN layer per timestep)
+
+    @property
+    def state_elems(self):
+        """fp32 elements of the recurrent state forward_stream carries (rgp_<family>_state_elems)."""
+        return int(self._f['state_elems'](self._h))
+
+    def forward_stream(self, c3d_input=None, rows=None, state=None, n_valid=None, bn_phase=0, want_probs=True):
+        """One call of a stream (rgp_<family>_forward_stream): the graph of forward() / forward_rows() started from
+        `state` instead of zeros.  Exactly one of c3d_input [B,T,1024,7,7] fp32 and rows (as forward_rows) is given, always at
+        the full plan size; the recurrence is defined for the first n_valid (default T) steps, later outputs are unspecified.
+        state: fp32 device tensor of state_elems elements from an earlier call, or None = the zero state; never modified.
+        bn_phase: step t uses batch-norm slot (bn_phase + t) % T (gaze_grcn only; the others have no per-timestep BN).
+        Returns (logits, probs, new_state); new_state is a fresh tensor on every call: the state behind step n_valid."""
+        assert (c3d_input is None) != (rows is None), 'exactly one of c3d_input and rows'
+        if c3d_input is not None:
+            x = c3d_input
+            assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+            assert tuple(x.shape) == (self.B, self.T, 1024, 7, 7), tuple(x.shape)
+        else:
+            assert rows.is_cuda and rows.dtype == self.torch_dtype and rows.is_contiguous()
+            assert rows.numel() == self.B * self.T * 49 * 1024
+        n_valid = self.T if n_valid is None else int(n_valid)
+        if state is not None:
+            assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous()
+            assert state.numel() == self.state_elems, (state.numel(), self.state_elems)
+        assert self.STREAM_BN_PHASE or bn_phase == 0, 'this family has no per-timestep batch-norm'
+        logits, probs = self._outputs(want_probs, None, None)
+        new_state = torch.empty(self.state_elems, dtype=torch.float32, device=self.device)
+        phase = (int(bn_phase),) if self.STREAM_BN_PHASE else ()
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['forward_stream'](self._h, _ptr(c3d_input), _ptr(rows), _ptr(state), _ptr(new_state), n_valid,
+                                                 *(phase + (_ptr(logits), _ptr(probs), _stream_ptr(self.device)))))
+        return logits, probs, new_state
+
     def inject_fault(self, kind='seq'):
         """Test hook (rgp_<family>_inject_fault): the next persistent launch of the forward ('seq') or of the BPTT
         ('bptt') loses a group member."""
@@ -343,6 +378,7 @@ class _PersistentEngine(_GazeEngine):
 class GrcnEngine(_PersistentEngine):
     """gaze_grcn graph (models/gaze_grcn.py:173-376) at fixed (B, T, P, S, dtype)."""
     PREFIX, PARAM_TO_FIELD, WEIGHTS = 'rgp_grcn_', GRCN_PARAM_TO_FIELD, _lib.GrcnWeights
+    STREAM_BN_PHASE = True
 
     def __init__(self, batch, n_steps, dim_proj=512, dim_state=128, dtype='bf16', save_for_backward=False,
                  device='cuda:0', per_step=False, unfolded_head=False):

@@ -120,13 +120,21 @@ def run_evaluation(model, data_sets, out_dir, num_frames=1000, seed=0, dump_imag
     return overall
 
 
-def predict_long_clip(model, c3d, frames=None, pool_to_7x7=False):
+def predict_long_clip(model, c3d, frames=None, pool_to_7x7=False, carry_state=False):
     """extract_map.py:148-229: a clip of any length through a fixed-T model.  c3d [N,1024,7,7]
     (or [N,512,2,7,7]) is cut into T-chunks, the tail zero-padded, B chunks per call; returns
     [N,GH,GW] of the model (49x49; 7x7 for gaze_grcn77 / gaze_rnn77), or [N,7,7] with a 7x7 average re-pool of each 49x49 map
-    (a 7x7 model's maps are at that resolution already)."""
+    (a 7x7 model's maps are at that resolution already).
+    carry_state=False is the reference's evaluation: every chunk starts from the zero state (extract_map.py:65).
+    carry_state=True runs the clip as ONE recurrence (stream.predict_long_clips; the conv-recurrent models only)."""
     c3d = np.asarray(c3d, np.float32).reshape(len(c3d), 1024, 7, 7)
     n, T, B = len(c3d), model.n_lstm_steps, model.batch_size
+    if carry_state:
+        from ..stream import predict_long_clips
+        maps = predict_long_clips(model, [c3d])[0]
+        if pool_to_7x7 and maps.shape[-1] == 49:
+            maps = maps.reshape(n, 7, 7, 7, 7).mean(axis=(2, 4))
+        return maps
     n_chunks = -(-n // T)
     padded = np.zeros((n_chunks * T, 1024, 7, 7), np.float32)
     padded[:n] = c3d

@@ -42,6 +42,7 @@ class GazePredictionGRCN(GazePredictionGRU):
 
     DIM_CNN_PROJ = 512      # gaze_grcn.py:206
     RNN_STATE_SIZE = 128    # gaze_grcn.py:211
+    STREAMS = True
 
     def __init__(self, session, data_sets, config=None):
         super(GazePredictionGRCN, self).__init__(session, data_sets, config=config)

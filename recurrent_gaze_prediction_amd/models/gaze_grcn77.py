@@ -23,6 +23,7 @@ class GazePredictionGRCN(GazePredictionGRU):
 
     DIM_CNN_PROJ = 512      # gaze_grcn77.py:109
     RNN_STATE_SIZE = 128    # gaze_grcn77.py:114
+    STREAMS = True
 
     def __init__(self, session, data_sets, config=None):
         super(GazePredictionGRCN, self).__init__(session, data_sets, config=config,
@@ -79,3 +80,6 @@ class GazePredictionGRCN(GazePredictionGRU):
         assert not missing, 'missing variables: %s' % missing
         self.variables = {k: np.asarray(state[k], np.float32) for k in GRCN77_PARAM_TO_FIELD}
         self.engine.set_weights(self.variables)
+
+
+GazePredictionGRCN77 = GazePredictionGRCN     # the name the module's class goes by next to models/gaze_grcn.py's

@@ -53,6 +53,8 @@ class GazePredictionLSTM(GazePredictionGRU):
 
     DIM_CNN_PROJ = 512      # gaze_lstm.py:210
     RNN_STATE_SIZE = 128    # gaze_lstm.py:215
+    STREAMS = True
+    STATE_PARTS = 2         # [h | c]
 
     def __init__(self, session, data_sets, config=None):
         super(GazePredictionLSTM, self).__init__(session, data_sets, config=config)

@@ -261,6 +261,31 @@ class GazePredictionGRU(ModelBase):
         self.predicted_gazemaps = probs if want_probs else logits
         return self.predicted_gazemaps
 
+    # the conv-recurrent models whose engines carry a recurrent state across calls (engine.forward_stream)
+    STREAMS = False
+    STATE_PARTS = 1             # tensors of [B, ...] the engine's flat state holds one after the other (gaze_lstm: h, c)
+
+    def predict_stream(self, c3d, state=None, n_valid=None, position=0):
+        """One call of a stream: predict() started from `state` (None = zeros; never modified) instead of zeros.
+        c3d [B,T,1024,7,7] at the full plan size; the first n_valid (default T) steps count.  position: stream position
+        of step 0; gaze_grcn's per-timestep batch-norm uses slot (position + t) % T for step t.
+        -> (maps [B,T,GH,GW] device tensor, valid for the first n_valid steps; new_state, a fresh tensor)."""
+        if not self.STREAMS:
+            raise NotImplementedError('predict_stream: GazePredictionGRCN (gaze_grcn), GazePredictionGRCN77 (gaze_grcn77) and '
+                                      'GazePredictionLSTM (gaze_lstm) stream; %s has no carried state' % type(self).__name__)
+        x = torch.as_tensor(np.asarray(c3d, dtype=np.float32) if not torch.is_tensor(c3d) else c3d)
+        x = x.to(self.session.device, torch.float32).reshape(self.batch_size, self.n_lstm_steps, 1024, 7, 7).contiguous()
+        want_probs = self.config.loss_type in ('xentropy', 'KLD')
+
+        def run():
+            kw = {'bn_phase': int(position) % self.n_lstm_steps} if self.engine.STREAM_BN_PHASE else {}
+            return self.engine.forward_stream(x, state=state, n_valid=n_valid, want_probs=want_probs, **kw)
+        logits, probs, new_state = run()
+        if self._status_or_recover():             # the engine was replaced: `state` is untouched, compute the call again
+            logits, probs, new_state = run()
+            self._status_or_recover(final=True)
+        return (probs if want_probs else logits), new_state
+
     def _status_or_recover(self, final=False):
         """"A TF session either returns or raises" (gaze_rnn.py:603-611).  Engines with persistent launches report a lost
         group member asynchronously (RGP_ETIMEOUT, NaN-poisoned outputs, include/rgp.h): wait for the stream, and on

@@ -1,0 +1,110 @@
+"""Streaming gaze prediction: a conv-recurrent model run on a video longer than its plan as ONE recurrence, the state
+carried from call to call (engine.forward_stream, include/rgp.h rgp_*_forward_stream), instead of the reference's
+T-step chunks that each start from zeros (extract_map.py:65; SURVEY "State is not carried between chunks")."""
+import numpy as np
+import torch
+
+
+class GazeStream(object):
+    """B lanes, one clip per lane, all at the same stream position.
+
+    model: GazePredictionGRCN / GazePredictionGRCN77 / GazePredictionLSTM (anything with predict_stream, batch_size,
+    n_lstm_steps).  c3d_engine: a C3DEngine of the model's operand dtype for push_windows.
+    `position` is the stream position of the next step; gaze_grcn's per-timestep batch-norm slot is position % T, so the
+    maps do not depend on how the stream is cut into calls."""
+
+    def __init__(self, model, c3d_engine=None):
+        self.model, self.c3d_engine = model, c3d_engine
+        self.B, self.T = model.batch_size, model.n_lstm_steps
+        self.state = None            # None = the zero state
+        self.position = 0
+
+    def reset(self, lanes=None):
+        """Zero the state of `lanes` (default: all, which also rewinds `position` to 0).  A lane reset while position % T != 0
+        starts its clip in a later batch-norm slot than slot 0 (gaze_grcn): reset at multiples of T for the reference's slots."""
+        if lanes is None:
+            self.state, self.position = None, 0
+            return
+        if self.state is not None:
+            s = self.state.clone()                                      # states handed out earlier stay as they were
+            s.view(getattr(self.model, 'STATE_PARTS', 1), self.B, -1)[:, list(lanes)] = 0
+            self.state = s
+
+    def _advance(self, maps, new_state, n, n_valid):
+        self.state = new_state
+        self.position += n_valid
+        return maps[:, :n]
+
+    def push_features(self, c3d, n_valid=None):
+        """c3d [B, n <= T, 1024, 7, 7] C3D features of the next n steps of every lane -> maps [B, n, GH, GW].  The
+        state advances by n_valid (default n) steps; maps behind step n_valid are unspecified."""
+        x = c3d if torch.is_tensor(c3d) else torch.as_tensor(np.asarray(c3d, np.float32))
+        x = x.reshape(self.B, -1, 1024, 7, 7)
+        n = x.shape[1]
+        assert 1 <= n <= self.T, 'push at most T = %d steps per call, got %d' % (self.T, n)
+        n_valid = n if n_valid is None else int(n_valid)
+        assert 1 <= n_valid <= n, n_valid
+        if n < self.T:
+            x = torch.cat([x, x.new_zeros((self.B, self.T - n) + tuple(x.shape[2:]))], 1)
+        maps, new_state = self.model.predict_stream(x, state=self.state, n_valid=n_valid, position=self.position)
+        return self._advance(maps, new_state, n, n_valid)
+
+    def push_windows(self, video, n_valid=None):
+        """video [B*T, 16, 112, 112, 3] fp32 device tensor (window b*T + t = step t of lane b, the full plan size) -> maps
+        [B, T, GH, GW].  C3D conv5b rows go straight into the recurrent engine (C3DEngine.forward(want_rows=True), the rows
+        variant of forward_stream): frames to maps without leaving the device."""
+        assert self.c3d_engine is not None, 'GazeStream(model, c3d_engine=...) for push_windows'
+        model, T = self.model, self.T
+        n_valid = T if n_valid is None else int(n_valid)
+        rows = self.c3d_engine.forward(video, want_features=False, want_rows=True)[1]
+        want_probs = model.config.loss_type in ('xentropy', 'KLD')
+
+        def run():
+            kw = {'bn_phase': self.position % T} if model.engine.STREAM_BN_PHASE else {}
+            return model.engine.forward_stream(rows=rows, state=self.state, n_valid=n_valid, want_probs=want_probs, **kw)
+        logits, probs, new_state = run()
+        if model._status_or_recover():
+            logits, probs, new_state = run()
+            model._status_or_recover(final=True)
+        return self._advance(probs if want_probs else logits, new_state, T, n_valid)
+
+
+def predict_long_clips(model, clips):
+    """clips: a list of C3D feature arrays [N_i, 1024, 7, 7] of any lengths -> a list of maps [N_i, GH, GW] (numpy), each
+    clip one recurrence from the zero state.  B lanes, T steps per call; a lane that finishes its clip takes the next one
+    with a zeroed state at the next call boundary, so every clip starts at batch-norm slot 0 (the calls are whole: all
+    lanes share position % T == 0); tails are zero-padded and trimmed."""
+    stream = GazeStream(model)
+    B, T = stream.B, stream.T
+    clips = [np.asarray(c, np.float32).reshape(len(c), 1024, 7, 7) for c in clips]
+    outs = [[] for _ in clips]
+    lane_clip, lane_pos = [None] * B, [0] * B
+    nxt = 0
+    while True:
+        fresh = []
+        for b in range(B):
+            if lane_clip[b] is not None and lane_pos[b] >= len(clips[lane_clip[b]]):
+                lane_clip[b] = None
+            while lane_clip[b] is None and nxt < len(clips):
+                if len(clips[nxt]):
+                    lane_clip[b], lane_pos[b] = nxt, 0
+                    fresh.append(b)
+                nxt += 1
+        if all(c is None for c in lane_clip):
+            break
+        if fresh:
+            stream.reset(fresh)
+        x = np.zeros((B, T, 1024, 7, 7), np.float32)
+        for b in range(B):
+            if lane_clip[b] is not None:
+                part = clips[lane_clip[b]][lane_pos[b]:lane_pos[b] + T]
+                x[b, :len(part)] = part
+        maps = stream.push_features(x)
+        maps = maps.detach().cpu().numpy() if torch.is_tensor(maps) else np.asarray(maps)
+        for b in range(B):
+            if lane_clip[b] is not None:
+                k = min(T, len(clips[lane_clip[b]]) - lane_pos[b])
+                outs[lane_clip[b]].append(maps[b, :k].copy())
+                lane_pos[b] += T
+    gh_gw = (getattr(model, 'gazemap_height', 0), getattr(model, 'gazemap_width', 0))
+    return [np.concatenate(o) if o else np.zeros((0,) + gh_gw, np.float32) for o in outs]
