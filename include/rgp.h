@@ -740,6 +740,54 @@ int rgp_saliency_scores(const rgp_metrics_args* args, rgp_stream_t stream);
  * RGP_EINVAL with the number of refused frames in rgp_last_error(). */
 int rgp_metrics_status(const void* workspace, rgp_stream_t stream);
 
+/* ------------------------------------------------------------------ ground-truth maps from fixation points
+ * The arithmetic of the reference's loader (process_gazemap.py:35-58, crc_input_data_seq.py:41-53, 261-288) on the
+ * device: ONE launch builds n_frames frames, one workgroup per frame.  Per frame n, whose samples are rows
+ * frame_ptr[n] .. frame_ptr[n+1] of `samples` (int32 [n_samples][3] = observer u, raw coordinates a, b):
+ *   a_ = (int)(rint((double)a * (out_s1 - 1.0) / (raw_d1 - 1.0)) + 1e-9), b_ likewise with out_s2 / raw_d2 (rint: half
+ *   to even, np.round); the cell is row b_, column a_ of a frame [out_s2][out_s1] (the loader's swapaxes, :280).  An
+ *   observer who hits a cell twice counts once, different observers add:
+ *   fixationmaps = the count as fp32 (what rgp_metrics_args.fix takes);
+ *   gazemaps     = count / n_observers in fp32, then scipy.ndimage.gaussian_filter on an fp32 frame (first along the
+ *                  frame's first axis, then along its second; boundary `reflect`; every output
+ *                  tmp = c w[r]; for i = -r .. -1: tmp += (line[l+i] + line[l-i]) w[i+r] in fp64, rounded to fp32, the
+ *                  intermediate frame between the passes being fp32), then, unless the frame is all zero,
+ *                  g -= min(g); g /= max(g) in fp32 (a constant non-zero frame: NaN, as numpy);
+ *   labels       = gazemaps / their sum (normalize_probability_map, model_util.py:40-58): the sum accumulated in fp64 in
+ *                  a fixed order and rounded once to fp32; an all-zero frame gives NaN as the host helper does.
+ * weights: DEVICE double [2 radius + 1], made by the HOST (w = exp(-0.5 / sigma^2 x^2) / sum, x = -radius .. radius,
+ * radius = (int)(4 sigma + 0.5)): the device's exp is not numpy's.  No fused multiply-add, no fast-math: with the same
+ * weights the maps equal the host's bit for bit.
+ *
+ * Limits: out_s1*out_s2 <= RGP_GTMAPS_MAX_PIX, 1 <= n_observers <= RGP_GTMAPS_MAX_OBSERVERS, 0 <= radius <=
+ * RGP_GTMAPS_MAX_RADIUS, raw_d1, raw_d2 >= 2; the host refuses what it can see (RGP_EINVAL before any device call).  A
+ * sample with u outside [0, n_observers), a outside [0, raw_d1) or b outside [0, raw_d2), or a frame whose frame_ptr
+ * pair is negative or decreasing, refuses its frame on the device: NaN in every requested output of that frame, the
+ * frame counted in the workspace's status word (rgp_gtmaps_status); the other frames are unaffected.  n_frames == 0:
+ * RGP_OK, nothing is launched.  The original-scale path of the loader (sigma = 19 on the raw frame) is not covered.
+ *
+ * workspace (device, 8-byte aligned, rgp_gtmaps_workspace_bytes): the status word, cleared on the stream before the
+ * launch. */
+#define RGP_GTMAPS_MAX_PIX 4096
+#define RGP_GTMAPS_MAX_OBSERVERS 32
+#define RGP_GTMAPS_MAX_RADIUS 32
+
+typedef struct rgp_gtmaps_args {
+  const int* frame_ptr;        /* [n_frames + 1] */
+  const int* samples;          /* [n_samples][3] */
+  const double* weights;       /* [2 radius + 1] */
+  int n_frames, n_observers, raw_d1, raw_d2, out_s1, out_s2, radius;
+  float *gazemaps, *fixationmaps, *labels;   /* [n_frames][out_s2][out_s1]; any may be NULL, not all three */
+  void* workspace;
+  size_t workspace_bytes;
+} rgp_gtmaps_args;
+
+size_t rgp_gtmaps_workspace_bytes(void);
+int rgp_gazemaps_from_fixations(const rgp_gtmaps_args* args, rgp_stream_t stream);
+/* Waits for `stream`, reads the status word of the last rgp_gazemaps_from_fixations that used `workspace`: RGP_OK, or
+ * RGP_EINVAL with the number of refused frames in rgp_last_error(). */
+int rgp_gtmaps_status(const void* workspace, rgp_stream_t stream);
+
 /* ------------------------------------------------------------------ action classifier on gaze-attended C3D features */
 typedef struct rgp_action rgp_action_t;
 

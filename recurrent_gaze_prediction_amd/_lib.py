@@ -32,6 +32,8 @@ RGP_METRICS_MAX_PIX, RGP_METRICS_MAX_FIX, RGP_METRICS_MAX_THRESHOLDS, RGP_METRIC
 METRIC_BITS = {'sim': 1, 'cc': 2, 'AUC_Judd': 4, 'AUC_Borji': 8, 'AUC_shuffled': 16, 'NSS': 32}
 METRIC_ROWS = {'sim': 0, 'cc': 1, 'AUC_Judd': 2, 'AUC_Borji': 3, 'AUC_shuffled': 4, 'NSS': 5}
 RGP_METRICS_DEVICE_DRAWS, RGP_METRICS_NO_JITTER, RGP_METRICS_PRED_F64, RGP_METRICS_GT_F64 = 1, 2, 4, 8
+# ground-truth maps from fixation points (include/rgp.h): caps
+RGP_GTMAPS_MAX_PIX, RGP_GTMAPS_MAX_OBSERVERS, RGP_GTMAPS_MAX_RADIUS = 4096, 32, 32
 DTYPES = {'f32': RGP_F32, 'fp32': RGP_F32, 'float32': RGP_F32, 'bf16': RGP_BF16, 'bfloat16': RGP_BF16}
 
 c_void_p, c_int, c_size_t, c_char_p = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_char_p
@@ -98,6 +100,13 @@ class MetricsArgs(ctypes.Structure):
                 ('shuf_neg', c_void_p), ('shuf_cnt', c_void_p), ('seed', ctypes.c_ulonglong),
                 ('offset', ctypes.c_ulonglong), ('workspace', c_void_p), ('workspace_bytes', c_size_t),
                 ('scores', c_void_p)]
+
+
+class GtmapsArgs(ctypes.Structure):
+    _fields_ = [('frame_ptr', c_void_p), ('samples', c_void_p), ('weights', c_void_p), ('n_frames', c_int),
+                ('n_observers', c_int), ('raw_d1', c_int), ('raw_d2', c_int), ('out_s1', c_int), ('out_s2', c_int),
+                ('radius', c_int), ('gazemaps', c_void_p), ('fixationmaps', c_void_p), ('labels', c_void_p),
+                ('workspace', c_void_p), ('workspace_bytes', c_size_t)]
 
 
 # name -> (restype, argtypes); every symbol include/rgp.h declares
@@ -235,6 +244,9 @@ SIGNATURES = {
     'rgp_metrics_workspace_bytes': (c_size_t, [c_int, c_int, c_int, ctypes.c_uint]),
     'rgp_saliency_scores': (c_int, [ctypes.POINTER(MetricsArgs), c_void_p]),
     'rgp_metrics_status': (c_int, [c_void_p, c_void_p]),
+    'rgp_gtmaps_workspace_bytes': (c_size_t, []),
+    'rgp_gazemaps_from_fixations': (c_int, [ctypes.POINTER(GtmapsArgs), c_void_p]),
+    'rgp_gtmaps_status': (c_int, [c_void_p, c_void_p]),
     'rgp_dropout_apply': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_float, c_void_p]),
     'rgp_fcgru_set_dropout': (c_int, [c_void_p, ctypes.c_float, c_void_p]),
     'rgp_cascade_set_dropout': (c_int, [c_void_p, ctypes.c_float, c_void_p]),

@@ -114,6 +114,23 @@ def clip_to_dataset(images, gazemaps, fixationmaps, c3d, pupils, clipname, seq_l
     return CRCDataSet(parts[0], parts[1], parts[2], parts[3], parts[4], names)
 
 
+def clip_from_fixations(images, observers, raw_shape, c3d, pupils, clipname, seq_len, out_shape=(49, 49), sigma=None,
+                        fill_missing=False, device=None):
+    """``clip_to_dataset`` for a clip whose ground truth comes as fixation lists: ``observers`` is a list of
+    ``(t, a, b, length)`` per observer (``gazemaps.pack_fixations``), ``raw_shape`` the extents a and b live in.  The
+    loader's frame selection, the gaze maps and the fixation maps (crc_input_data_seq.py:261-288) are built on the
+    device in one launch (``gazemaps.gazemaps_from_fixations``).  The batch tuples of a CRCDataSet are numpy arrays
+    (the models normalise and flip them on the host), so the maps cross to the host once, here; a caller that scores
+    or classifies on the device calls ``gazemaps_from_fixations`` itself and keeps the tensors.  ``images``, ``c3d``
+    and ``pupils`` are the caller's per-frame arrays for the selected frames."""
+    from . import gazemaps as gm
+    packed = gm.pack_fixations(observers, raw_shape, frames='reference', fill_missing=fill_missing)
+    maps = gm.gazemaps_from_fixations(packed, out_shape=out_shape, sigma=sigma, want=('gazemaps', 'fixationmaps'), device=device)
+    import torch
+    host = torch.stack([maps['gazemaps'], maps['fixationmaps']]).cpu().numpy()
+    return clip_to_dataset(images, host[0], host[1], c3d, pupils, clipname, seq_len)
+
+
 class DeviceFeeder(object):
     """Double-buffered host->device upload of feature batches.
 
