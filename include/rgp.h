@@ -740,6 +740,81 @@ int rgp_saliency_scores(const rgp_metrics_args* args, rgp_stream_t stream);
  * RGP_EINVAL with the number of refused frames in rgp_last_error(). */
 int rgp_metrics_status(const void* workspace, rgp_stream_t stream);
 
+/* ------------------------------------------------------------------ saliency metrics at the fixation maps' shape
+ * What evaluate_gaze.py runs (fixation_original_scale=True): saliency_score_single (:239-272) min-max normalises the
+ * prediction at its own shape height x width, upsizes prediction and ground truth to the fixation map's shape
+ * target_height x target_width with an order-3 spline resize, and scores there.  ONE launch, one workgroup per frame; the
+ * upsized maps are never stored: the kernel keeps each frame's B-spline coefficients in LDS and evaluates the spline
+ * inside every sweep of the metrics.
+ *
+ * The resize is scipy.ndimage.map_coordinates(order=3, mode='reflect') at the coordinates
+ * (arange(o) + 0.5) * (float(i) / o) - 0.5 per axis (this package's evaluation_metrics.resize): the recursive prefilter
+ * with pole sqrt(3) - 2 and exact 'reflect' initialisation along axis 0, then axis 1, then per target pixel the 16-term
+ * sum of wy wx c over the taps floor(x) - 1 .. floor(x) + 2 with reflected indices, rows outer.  The pole's powers and
+ * the per-axis weight / index tables are made on the host in float64; the device only multiplies and adds (no fused
+ * multiply-add), so the resized values are a fixed sequence of IEEE operations (tests/spline_ref.py restates it) that
+ * agrees with scipy to about 2e-15.  At equal shapes the host's resize is the identity and rgp_saliency_scores is the
+ * entry point; this one applies the spline whatever the shapes.
+ *
+ * pred, gt [n_frames, height, width] fp32 / fp64 as for rgp_saliency_scores (an fp32 pred is normalised in fp32, then
+ * widened).  Fixations are POINTS: frame n owns fix_idx[fix_ptr[n] .. fix_ptr[n + 1]), flat pixel indices
+ * row * target_width + col on the target grid, strictly increasing within a frame (the order of np.nonzero(F.ravel()));
+ * fix_len = the length of fix_idx.  The negative set of AUC_shuffled in the same form, other_ptr [n_frames + 1], or [2]
+ * with RGP_METRICS_SCALED_OTHER_SHARED (one set for all frames, saliency_score :275-295); read for device draws, and
+ * checked whenever given.  Draws: both forms of rgp_saliency_scores with the same layout and Philox counters, the
+ * indices on the TARGET grid, judd_jitter [n_frames, target_height * target_width].
+ *
+ * Semantics per metric as rgp_saliency_scores, on the target_height * target_width resized values: AUC_Judd normalises
+ * the jittered full-size map, AUC_Borji / AUC_shuffled the resized map (the spline overshoots [0, 1]) and evaluate it
+ * only at the fixations and the drawn negatives.  Every sum has an order fixed by the shapes alone: frames [a, b) of a
+ * call with offset o equal frames [0, b - a) of a call with offset o + a bit for bit.
+ *
+ * Limits: 2 <= height, width and height*width <= RGP_METRICS_MAX_PIX; target_height*target_width <=
+ * RGP_METRICS_SCALED_MAX_PIX; neg_stride <= RGP_METRICS_MAX_FIX; 1/step_size <= RGP_METRICS_MAX_THRESHOLDS: refused
+ * by the host with RGP_EINVAL before any launch.  Seen by the device only, and answered with NaN in every requested
+ * score of that frame and a count in the status word (rgp_metrics_status, the first 64 workspace bytes): an index outside
+ * [0, target_height*target_width), indices that do not increase, a fix_ptr / other_ptr pair that decreases or leaves
+ * [0, fix_len] / [0, other_len], more fixations than neg_stride, more negatives than RGP_METRICS_SCALED_MAX_OTHER, a
+ * draw index or shuf_cnt out of range.  Nothing out of range is used as an address.
+ *
+ * workspace (device, 8-byte aligned, rgp_metrics_scaled_workspace_bytes): bytes [0, 64) status; with
+ * RGP_METRICS_DEVICE_DRAWS borji_neg, shuf_neg, shuf_cnt as rgp_saliency_scores leaves them; then the kernel's own
+ * (the saliency at the negatives, the resize tables).
+ *
+ * rgp_spline_resize writes the resized maps themselves, [n_frames, H, W] fp64 (dst_f64) or fp32 (rounded once), from
+ * src [n_frames, h, w] fp32 or fp64 (src_f64): the frame-size map for overlays and dumps; no normalisation.  Its
+ * workspace (rgp_spline_resize_workspace_bytes) holds the tables. */
+#define RGP_METRICS_SCALED_MAX_PIX   (1 << 22)     /* target pixels per frame: covers 1080 x 1920 */
+#define RGP_METRICS_SCALED_MAX_OTHER 4096          /* members of a frame's AUC_shuffled negative set */
+#define RGP_METRICS_SCALED_OTHER_SHARED 16         /* flag: other_ptr is [2], one negative set for all frames */
+
+typedef struct rgp_metrics_scaled_args {
+  const void* pred;            /* [n_frames, height, width] fp32 (fp64 with RGP_METRICS_PRED_F64) */
+  const void* gt;              /* same shape, fp32 (fp64 with RGP_METRICS_GT_F64); read by sim and cc only */
+  const int* fix_ptr;          /* [n_frames + 1] */
+  const int* fix_idx;          /* [fix_len] */
+  const int* other_ptr;        /* [n_frames + 1], or [2] with RGP_METRICS_SCALED_OTHER_SHARED; may be NULL with the caller's draws */
+  const int* other_idx;        /* [other_len] */
+  int fix_len, other_len;
+  int n_frames, height, width, target_height, target_width;
+  unsigned metrics;            /* RGP_METRIC_* bits */
+  unsigned flags;              /* RGP_METRICS_* bits */
+  int n_rep, neg_stride;
+  double step_size;
+  const double* judd_jitter;   /* [n_frames, target_height * target_width] */
+  const int *borji_neg, *shuf_neg, *shuf_cnt;
+  unsigned long long seed, offset;
+  void* workspace;
+  size_t workspace_bytes;
+  double* scores;              /* [RGP_METRICS_COUNT, n_frames] */
+} rgp_metrics_scaled_args;
+
+size_t rgp_metrics_scaled_workspace_bytes(int n_frames, int n_rep, int neg_stride, int height, int width, unsigned flags);
+int rgp_saliency_scores_scaled(const rgp_metrics_scaled_args* args, rgp_stream_t stream);
+size_t rgp_spline_resize_workspace_bytes(int H, int W);
+int rgp_spline_resize(const void* src, int src_f64, int n_frames, int h, int w, void* dst, int dst_f64, int H, int W,
+                      void* workspace, size_t workspace_bytes, rgp_stream_t stream);
+
 /* ------------------------------------------------------------------ ground-truth maps from fixation points
  * The arithmetic of the reference's loader (process_gazemap.py:35-58, crc_input_data_seq.py:41-53, 261-288) on the
  * device: ONE launch builds n_frames frames, one workgroup per frame.  Per frame n, whose samples are rows

@@ -32,6 +32,8 @@ RGP_METRICS_MAX_PIX, RGP_METRICS_MAX_FIX, RGP_METRICS_MAX_THRESHOLDS, RGP_METRIC
 METRIC_BITS = {'sim': 1, 'cc': 2, 'AUC_Judd': 4, 'AUC_Borji': 8, 'AUC_shuffled': 16, 'NSS': 32}
 METRIC_ROWS = {'sim': 0, 'cc': 1, 'AUC_Judd': 2, 'AUC_Borji': 3, 'AUC_shuffled': 4, 'NSS': 5}
 RGP_METRICS_DEVICE_DRAWS, RGP_METRICS_NO_JITTER, RGP_METRICS_PRED_F64, RGP_METRICS_GT_F64 = 1, 2, 4, 8
+# the same metrics at the fixation maps' shape (include/rgp.h): caps and the flag of a shared negative set
+RGP_METRICS_SCALED_MAX_PIX, RGP_METRICS_SCALED_MAX_OTHER, RGP_METRICS_SCALED_OTHER_SHARED = 1 << 22, 4096, 16
 # ground-truth maps from fixation points (include/rgp.h): caps
 RGP_GTMAPS_MAX_PIX, RGP_GTMAPS_MAX_OBSERVERS, RGP_GTMAPS_MAX_RADIUS = 4096, 32, 32
 DTYPES = {'f32': RGP_F32, 'fp32': RGP_F32, 'float32': RGP_F32, 'bf16': RGP_BF16, 'bfloat16': RGP_BF16}
@@ -100,6 +102,16 @@ class MetricsArgs(ctypes.Structure):
                 ('shuf_neg', c_void_p), ('shuf_cnt', c_void_p), ('seed', ctypes.c_ulonglong),
                 ('offset', ctypes.c_ulonglong), ('workspace', c_void_p), ('workspace_bytes', c_size_t),
                 ('scores', c_void_p)]
+
+
+class MetricsScaledArgs(ctypes.Structure):
+    _fields_ = [('pred', c_void_p), ('gt', c_void_p), ('fix_ptr', c_void_p), ('fix_idx', c_void_p), ('other_ptr', c_void_p),
+                ('other_idx', c_void_p), ('fix_len', c_int), ('other_len', c_int), ('n_frames', c_int), ('height', c_int),
+                ('width', c_int), ('target_height', c_int), ('target_width', c_int), ('metrics', ctypes.c_uint),
+                ('flags', ctypes.c_uint), ('n_rep', c_int), ('neg_stride', c_int), ('step_size', ctypes.c_double),
+                ('judd_jitter', c_void_p), ('borji_neg', c_void_p), ('shuf_neg', c_void_p), ('shuf_cnt', c_void_p),
+                ('seed', ctypes.c_ulonglong), ('offset', ctypes.c_ulonglong), ('workspace', c_void_p),
+                ('workspace_bytes', c_size_t), ('scores', c_void_p)]
 
 
 class GtmapsArgs(ctypes.Structure):
@@ -244,6 +256,10 @@ SIGNATURES = {
     'rgp_metrics_workspace_bytes': (c_size_t, [c_int, c_int, c_int, ctypes.c_uint]),
     'rgp_saliency_scores': (c_int, [ctypes.POINTER(MetricsArgs), c_void_p]),
     'rgp_metrics_status': (c_int, [c_void_p, c_void_p]),
+    'rgp_metrics_scaled_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, ctypes.c_uint]),
+    'rgp_saliency_scores_scaled': (c_int, [ctypes.POINTER(MetricsScaledArgs), c_void_p]),
+    'rgp_spline_resize_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'rgp_spline_resize': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     'rgp_gtmaps_workspace_bytes': (c_size_t, []),
     'rgp_gazemaps_from_fixations': (c_int, [ctypes.POINTER(GtmapsArgs), c_void_p]),
     'rgp_gtmaps_status': (c_int, [c_void_p, c_void_p]),

@@ -1,8 +1,8 @@
 """Saliency metrics scored on the GPU: all frames and all requested metrics in one launch.
 
 Device-side counterpart of ``evaluation_metrics`` (the host module, pinned to the reference's
-evaluation_metrics.py by tests/golden/metrics_ref.npz) for the case every caller of this package has:
-prediction, ground truth and fixation maps of one common shape of at most 4096 pixels.  The kernel
+evaluation_metrics.py by tests/golden/metrics_ref.npz) for prediction, ground truth and
+fixation maps of one common shape of at most 4096 pixels (:func:`saliency_scores_single`).  The kernel
 (csrc/rgp_metrics.hip, ``rgp_saliency_scores`` in include/rgp.h) follows the host module statement for
 statement in fp64, so with the host's own random draws it returns the host's scores to summation order
 (about 1e-12); the averaging over frames stays here (``np.mean``).
@@ -13,9 +13,15 @@ Random draws come in two forms:
   functions do and hands the draws to the kernel -- same seed, same scores as the host module;
 * ``draws='device'``: the kernel draws with Philox-4x32-10 keyed by ``seed`` -- nothing but the launch.
 
-What the kernel does not cover -- maps and fixation maps of different shapes (the host's spline
-``resize``), more than 4096 pixels, more than 256 fixations in a frame -- raises ``ValueError``; there is
-no silent fallback: use ``evaluation_metrics`` for those.
+Fixation maps of another shape than the maps -- what the reference's evaluation runs, fixations at the video
+frame's resolution -- go through :func:`saliency_scores_resized`: the kernel of csrc/rgp_metrics_scaled.hip
+(``rgp_saliency_scores_scaled``) upsizes prediction and ground truth with the host's cubic-spline ``resize`` on the
+fly, inside the metric sweeps, and takes the fixations as point lists (:func:`pack_points`).  :func:`saliency_score`
+dispatches on the shapes; :func:`resize_maps` returns the resized maps themselves (overlays, dumps).
+
+What the kernels do not cover -- equal shapes of more than 4096 pixels, source maps of more than 4096 pixels, more
+than 256 fixations in a frame, frames of different shapes -- raises ``ValueError``; there is no silent fallback: use
+``evaluation_metrics`` for those.
 """
 import ctypes
 
@@ -29,6 +35,7 @@ from . import _lib
 METRICS = ('sim', 'cc', 'AUC_Judd', 'AUC_Borji', 'AUC_shuffled', 'NSS')       # rows of the kernel's score table
 FRAME_METRICS = ('sim', 'cc', 'AUC_Borji', 'AUC_Judd', 'AUC_shuffled')        # evaluate_gaze.py:135
 MAX_PIX, MAX_FIX = _lib.RGP_METRICS_MAX_PIX, _lib.RGP_METRICS_MAX_FIX
+SCALED_MAX_PIX, SCALED_MAX_OTHER = _lib.RGP_METRICS_SCALED_MAX_PIX, _lib.RGP_METRICS_SCALED_MAX_OTHER
 _HOST = 'recurrent_gaze_prediction_amd.evaluation_metrics (the host module) scores such input'
 
 
@@ -80,14 +87,43 @@ def draw_reference_samples(fixation_maps, other_union, metrics, n_rep=100, order
     Returns a dict: ``judd_jitter`` f64 [N, n_pix] (None when AUC_Judd is not requested or ``jitter`` is off),
     ``borji_neg`` / ``shuf_neg`` int32 [N, n_rep, neg_stride] pixel indices (None when not requested), ``shuf_cnt``
     int32 [N] = min(n_fix, M), ``n_fix`` int32 [N] and ``neg_stride`` = the largest n_fix (at least 1)."""
+    fix = np.asarray(stack_maps(fixation_maps, 'fixation_maps')) > 0.5
+    N, H, W = fix.shape
+    n_fix = fix.reshape(N, H * W).sum(1).astype(np.int32)
+    negatives = None
+    if 'AUC_shuffled' in _check_metrics(metrics):
+        if other_union is None:
+            raise ValueError('other_map_union required')
+        other = np.asarray(_dense(other_union)) > 0.5
+        if other.shape not in ((H, W), (N, H, W)):
+            raise ValueError('other_map.shape != fixation_map.shape')
+        negatives = [np.nonzero(o)[0] for o in other.reshape(-1, H * W)]
+    return _draw_reference(n_fix, negatives, H, W, metrics, n_rep, order, jitter)
+
+
+def draw_reference_samples_points(fix_points, other_points, shape, metrics, n_rep=100, order='metric', jitter=True):
+    """:func:`draw_reference_samples` for fixations given as points (:func:`pack_points` on the host): the same draws
+    in the same order without a dense [N,H,W] array.  ``other_points``: (ptr, idx) with N + 1 (one set per frame) or 2
+    (one set for all frames) entries in ptr; None unless AUC_shuffled is requested."""
+    H, W = (int(v) for v in shape)
+    ptr = np.asarray(fix_points[0], np.int64)
+    negatives = None
+    if 'AUC_shuffled' in _check_metrics(metrics):
+        if other_points is None:
+            raise ValueError('other_map_union required')
+        optr, oidx = np.asarray(other_points[0], np.int64), np.asarray(other_points[1], np.int64)
+        if len(optr) not in (2, len(ptr)):
+            raise ValueError('other_map.shape != fixation_map.shape')
+        negatives = [oidx[a:b] for a, b in zip(optr[:-1], optr[1:])]
+    return _draw_reference(np.diff(ptr).astype(np.int32), negatives, H, W, metrics, n_rep, order, jitter)
+
+
+def _draw_reference(n_fix, negatives, H, W, metrics, n_rep, order, jitter):
+    """The draws of :func:`draw_reference_samples` from the fixation counts and the members of the negative sets."""
     metrics = _check_metrics(metrics)
     if order not in ('metric', 'frame'):
         raise ValueError(order)
-    fix = np.asarray(stack_maps(fixation_maps, 'fixation_maps')) > 0.5
-    N, H, W = fix.shape
-    n_pix = H * W
-    fix = fix.reshape(N, n_pix)
-    n_fix = fix.sum(1).astype(np.int32)
+    N, n_pix = len(n_fix), H * W
     if n_fix.max(initial=0) > MAX_FIX:
         raise ValueError('a frame has %d fixations, more than RGP_METRICS_MAX_FIX = %d; %s' % (n_fix.max(), MAX_FIX, _HOST))
     stride = max(1, int(n_fix.max(initial=0)))
@@ -97,13 +133,6 @@ def draw_reference_samples(fixation_maps, other_union, metrics, n_rep=100, order
     if 'AUC_Borji' in metrics:
         out['borji_neg'] = np.zeros((N, n_rep, stride), np.int32)
     if 'AUC_shuffled' in metrics:
-        if other_union is None:
-            raise ValueError('other_map_union required')
-        other = np.asarray(_dense(other_union)) > 0.5
-        if other.shape not in ((H, W), (N, H, W)):
-            raise ValueError('other_map.shape != fixation_map.shape')
-        other = other.reshape(-1, n_pix)
-        negatives = [np.nonzero(o)[0] for o in other]
         out['shuf_neg'] = np.zeros((N, n_rep, stride), np.int32)
         out['shuf_cnt'] = np.zeros(N, np.int32)
 
@@ -260,6 +289,241 @@ def saliency_scores_single(pred, gt, fix, other, metrics, draws='device', seed=0
     return out
 
 
+def _maps_shape(maps):
+    """(H, W) of a [N,H,W] array / tensor or of a list of (sparse) maps (the first one's)."""
+    if _is_tensor(maps) or (isinstance(maps, np.ndarray) and maps.dtype != object):
+        return tuple(int(v) for v in maps.shape[-2:])
+    first = maps[0]
+    return tuple(int(v) for v in (first.shape if scipy.sparse.issparse(first) else np.asarray(first).shape))
+
+
+def _is_packed(x):
+    return isinstance(x, tuple) and len(x) == 2 and (_is_tensor(x[0]) or isinstance(x[0], np.ndarray)) and x[0].ndim == 1
+
+
+def pack_points(maps_or_points, shape):
+    """Fixation (or negative-set) maps as the point lists the frame-resolution scorer takes: ``(ptr, idx)``, int32, frame
+    n owning ``idx[ptr[n]:ptr[n + 1]]``, the flat indices ``row * W + col`` of its pixels ``> 0.5`` on the ``shape`` =
+    (H, W) grid, unique and increasing -- the order of ``np.nonzero(F.ravel())``.
+
+    Accepted: a dense [N,H,W] array; a [N,H,W] device tensor (``torch.nonzero`` on the device, no host round trip:
+    the result is a pair of device tensors); a list of ``scipy.sparse`` matrices or dense maps; a list of per-frame
+    ``(rows, cols)`` pairs.  Frames of another shape than ``shape`` raise ValueError naming the host module."""
+    H, W = (int(v) for v in shape)
+    if _is_tensor(maps_or_points):
+        t = maps_or_points
+        if t.ndim != 3 or tuple(t.shape[1:]) != (H, W):
+            raise ValueError('maps of shape %s on a grid of %s; %s' % (tuple(t.shape), (H, W), _HOST))
+        nz = torch.nonzero(t.reshape(t.shape[0], H * W) > 0.5)                      # sorted by frame, then pixel
+        ptr = torch.zeros(t.shape[0] + 1, dtype=torch.int64, device=t.device)
+        ptr[1:] = torch.cumsum(torch.bincount(nz[:, 0], minlength=t.shape[0]), 0)
+        return ptr.to(torch.int32), nz[:, 1].to(torch.int32).contiguous()
+    if isinstance(maps_or_points, np.ndarray) and maps_or_points.dtype != object:
+        a = maps_or_points
+        if a.ndim != 3 or a.shape[1:] != (H, W):
+            raise ValueError('maps of shape %s on a grid of %s; %s' % (a.shape, (H, W), _HOST))
+        frames, pix = np.nonzero(a.reshape(len(a), H * W) > 0.5)
+        ptr = np.zeros(len(a) + 1, np.int64)
+        ptr[1:] = np.cumsum(np.bincount(frames, minlength=len(a)))
+        return ptr.astype(np.int32), pix.astype(np.int32)
+    per_frame = []
+    for m in maps_or_points:
+        if isinstance(m, (tuple, list)) and len(m) == 2 and np.ndim(m[0]) == 1:
+            rows, cols = (np.asarray(v).astype(np.int64).reshape(-1) for v in m)
+            if len(rows) != len(cols) or (len(rows) and (rows.min() < 0 or rows.max() >= H or cols.min() < 0 or cols.max() >= W)):
+                raise ValueError('a point lies outside the grid of %s' % ((H, W),))
+        else:
+            if tuple(m.shape) != (H, W):
+                raise ValueError('a map of shape %s among maps of %s: frames of different shapes; %s' % (tuple(m.shape), (H, W), _HOST))
+            if scipy.sparse.issparse(m):
+                c = m.tocoo()
+                keep = c.data > 0.5
+                rows, cols = c.row[keep].astype(np.int64), c.col[keep].astype(np.int64)
+            else:
+                rows, cols = np.nonzero(np.asarray(m) > 0.5)
+        per_frame.append(np.unique(rows * W + cols))
+    ptr = np.zeros(len(per_frame) + 1, np.int64)
+    ptr[1:] = np.cumsum([len(v) for v in per_frame])
+    if ptr[-1] >= 2 ** 31:
+        raise ValueError('more than 2^31 points')
+    idx = np.concatenate(per_frame) if per_frame else np.zeros(0, np.int64)
+    return ptr.astype(np.int32), idx.astype(np.int32)
+
+
+def _host_points(points):
+    return tuple(v.cpu().numpy() if _is_tensor(v) else np.asarray(v) for v in points)
+
+
+def _device_points(points, dev):
+    """(ptr, idx) -> int32 device tensors (idx never empty: the kernel is handed a valid pointer) and len(idx)."""
+    ptr, idx = (v.to(dev, torch.int32) if _is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, np.int32)).to(dev)
+                for v in points)
+    n = int(idx.numel())
+    if n == 0:
+        idx = torch.zeros(1, dtype=torch.int32, device=dev)
+    return ptr.contiguous(), idx.contiguous(), n
+
+
+def saliency_scores_resized(pred, gt, fix, other, metrics, draws='device', seed=0, offset=0, n_rep=100, step_size=0.1,
+                            jitter=True, max_fix=None, device=None, return_draws=False, shape=None):
+    """:func:`saliency_scores_single` for fixation maps of ANOTHER shape than the maps: per-frame scores
+    {metric: f64 [N]} of ``evaluation_metrics.saliency_score_single``, which upsizes prediction and ground truth to the
+    fixation map's shape with a cubic spline and scores there.  One launch; the upsized maps are never stored.
+
+    pred, gt: [N,h,w] as for saliency_scores_single.  fix: fixation maps of shape (H, W) in any form
+    :func:`pack_points` takes, or its result ``(ptr, idx)`` together with ``shape=(H, W)``.  other: the AUC_shuffled
+    negative set likewise -- one map / ``ptr`` of two entries for all frames, or N of them; None if AUC_shuffled is not
+    requested.  Draws, seed, offset, n_rep, step_size, jitter, max_fix, return_draws and the return value as in
+    saliency_scores_single; ``draws='reference'`` takes the host's draws on the full-size grid
+    (:func:`draw_reference_samples_points`).  Raises ValueError for what the kernel does not cover."""
+    metrics = _check_metrics(metrics)
+    pred, gt = stack_maps(pred, 'pred'), stack_maps(gt, 'gt')
+    if tuple(pred.shape) != tuple(gt.shape):
+        raise ValueError('pred %s and gt %s differ in shape; %s' % (tuple(pred.shape), tuple(gt.shape), _HOST))
+    N, h, w = (int(v) for v in pred.shape)
+    if N < 1:
+        raise ValueError('no frames')
+    if _is_packed(fix):
+        if shape is None:
+            raise ValueError('fixations given as (ptr, idx) need shape=(H, W)')
+    else:
+        shape = _maps_shape(fix) if shape is None else shape
+        fix = pack_points(fix, shape)
+    H, W = (int(v) for v in shape)
+    if (H, W) == (h, w):
+        raise ValueError('maps and fixation maps share the shape %s: saliency_scores_single scores those' % ((H, W),))
+    if h < 2 or w < 2 or h * w > MAX_PIX:
+        raise ValueError('maps of %d x %d pixels: sides of at least 2 and at most RGP_METRICS_MAX_PIX = %d pixels; %s' % (h, w, MAX_PIX, _HOST))
+    if H < 1 or W < 1 or H * W > SCALED_MAX_PIX:
+        raise ValueError('fixation maps of %d x %d pixels, more than RGP_METRICS_SCALED_MAX_PIX = %d; %s' % (H, W, SCALED_MAX_PIX, _HOST))
+    if len(fix[0]) != N + 1:
+        raise ValueError('%d frames of fixations for %d maps' % (len(fix[0]) - 1, N))
+    if device is None:
+        device = next((t.device for t in (pred, gt, fix[0]) if _is_tensor(t) and t.is_cuda), torch.device('cuda:0'))
+    dev = torch.device(device)
+    shared = False
+    if other is not None:
+        if not _is_packed(other):
+            if scipy.sparse.issparse(other) or (not isinstance(other, (list, tuple)) and other.ndim == 2):
+                other = _dense(other)[None]
+            other = pack_points(other, (H, W))
+        if len(other[0]) not in (2, N + 1):
+            raise ValueError('other_map.shape != fixation_map.shape')
+        shared = len(other[0]) == 2 and N != 1
+
+    flags, packed = (_lib.RGP_METRICS_SCALED_OTHER_SHARED if shared else 0), None
+    if isinstance(draws, dict) or draws == 'reference':
+        if not isinstance(draws, dict):
+            draws = draw_reference_samples_points(_host_points(fix), None if other is None else _host_points(other), (H, W),
+                                                  metrics, n_rep=n_rep, jitter=jitter)
+        packed = draws
+        stride = int(packed['neg_stride'])
+        for key, want in (('judd_jitter', (N, H * W)), ('borji_neg', (N, int(n_rep), stride)), ('shuf_neg', (N, int(n_rep), stride)),
+                          ('shuf_cnt', (N,))):                       # the kernel reads them by these extents
+            if packed.get(key) is not None and tuple(np.shape(packed[key])) != want:
+                raise ValueError('draws[%r] has shape %s, expected %s' % (key, tuple(np.shape(packed[key])), want))
+    elif draws == 'device':
+        flags |= _lib.RGP_METRICS_DEVICE_DRAWS | (0 if jitter else _lib.RGP_METRICS_NO_JITTER)
+        if 'AUC_shuffled' in metrics and other is None:
+            raise ValueError('other_map_union required')
+        if max_fix is None:
+            counts = fix[0][1:] - fix[0][:-1]
+            max_fix = int(counts.max().item() if _is_tensor(counts) else counts.max(initial=0))
+        stride = max(1, int(max_fix))
+    else:
+        raise ValueError("draws must be 'device', 'reference' or the result of draw_reference_samples")
+    if stride > MAX_FIX:
+        raise ValueError('a frame has %d fixations, more than RGP_METRICS_MAX_FIX = %d; %s' % (stride, MAX_FIX, _HOST))
+
+    d_pred, d_gt = _device_maps(pred, 'pred', dev), _device_maps(gt, 'gt', dev)
+    flags |= _lib.RGP_METRICS_PRED_F64 if d_pred.dtype == torch.float64 else 0
+    flags |= _lib.RGP_METRICS_GT_F64 if d_gt.dtype == torch.float64 else 0
+    d_fptr, d_fidx, fix_len = _device_points(fix, dev)
+    d_optr, d_oidx, other_len = (None, None, 0) if other is None else _device_points(other, dev)
+
+    def up(key, dtype):
+        a = packed.get(key) if packed is not None else None
+        return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype)).to(dev)
+    d_jit, d_borji = up('judd_jitter', np.float64), up('borji_neg', np.int32)
+    d_shuf, d_cnt = up('shuf_neg', np.int32), up('shuf_cnt', np.int32)
+
+    lib = _lib.load()
+    bits = 0
+    for m in metrics:
+        bits |= _lib.METRIC_BITS[m]
+    ws_bytes = int(lib.rgp_metrics_scaled_workspace_bytes(N, n_rep, stride, H, W, flags))
+    ws = torch.empty(max(ws_bytes, 64), dtype=torch.uint8, device=dev)
+    scores = torch.full((_lib.RGP_METRICS_COUNT, N), float('nan'), dtype=torch.float64, device=dev)
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+    args = _lib.MetricsScaledArgs(pred=ptr(d_pred), gt=ptr(d_gt), fix_ptr=ptr(d_fptr), fix_idx=ptr(d_fidx), other_ptr=ptr(d_optr),
+                                  other_idx=ptr(d_oidx), fix_len=fix_len, other_len=other_len, n_frames=N, height=h, width=w,
+                                  target_height=H, target_width=W, metrics=bits, flags=flags, n_rep=int(n_rep), neg_stride=stride,
+                                  step_size=float(step_size), judd_jitter=ptr(d_jit), borji_neg=ptr(d_borji), shuf_neg=ptr(d_shuf),
+                                  shuf_cnt=ptr(d_cnt), seed=int(seed) & (2 ** 64 - 1), offset=int(offset), workspace=ws.data_ptr(),
+                                  workspace_bytes=ws.numel(), scores=scores.data_ptr())
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.rgp_saliency_scores_scaled(ctypes.byref(args), stream)
+        if rc == 0:
+            rc = lib.rgp_metrics_status(ws.data_ptr(), stream)
+    if rc == -1:
+        raise ValueError('%s; %s' % (lib.rgp_last_error().decode(), _HOST))
+    _lib.check(rc)
+    host_scores = scores.cpu().numpy()
+    out = {m: host_scores[_lib.METRIC_ROWS[m]].copy() for m in metrics}
+    if return_draws:
+        if packed is not None:
+            out['draws'] = packed
+        else:
+            e = N * int(n_rep) * stride
+            ints = ws[64:64 + (2 * e + N) * 4].view(torch.int32).cpu().numpy()
+            out['draws'] = {'borji_neg': ints[:e].reshape(N, n_rep, stride), 'shuf_neg': ints[e:2 * e].reshape(N, n_rep, stride),
+                            'shuf_cnt': ints[2 * e:], 'neg_stride': stride,
+                            'n_fix': np.diff(_host_points(fix)[0]).astype(np.int32)}
+    return out
+
+
+def resize_maps(maps, out_shape, out_dtype=torch.float64, device=None):
+    """[N,h,w] maps (array, list or device tensor; fp32 / fp64 read in place, anything else as fp64) -> device tensor
+    [N,H,W] of ``out_dtype`` (float64 or float32): ``evaluation_metrics.resize`` -- scipy's order-3 spline, mode
+    'reflect' -- of every map, in one launch.  The frame-size map for overlays and dumps; the spline is applied at
+    equal shapes too (there the host's ``resize`` is the identity).  fp32 output is the fp64 value rounded once."""
+    maps = stack_maps(maps, 'maps')
+    N, h, w = (int(v) for v in maps.shape)
+    H, W = (int(v) for v in out_shape)
+    if out_dtype not in (torch.float64, torch.float32):
+        raise ValueError('out_dtype must be torch.float64 or torch.float32')
+    if N < 1:
+        raise ValueError('no frames')
+    if h < 2 or w < 2 or h * w > MAX_PIX:
+        raise ValueError('maps of %d x %d pixels: sides of at least 2 and at most RGP_METRICS_MAX_PIX = %d pixels; %s' % (h, w, MAX_PIX, _HOST))
+    if H < 1 or W < 1 or H * W > SCALED_MAX_PIX:
+        raise ValueError('target of %d x %d pixels, more than RGP_METRICS_SCALED_MAX_PIX = %d; %s' % (H, W, SCALED_MAX_PIX, _HOST))
+    if device is None:
+        device = maps.device if _is_tensor(maps) and maps.is_cuda else torch.device('cuda:0')
+    dev = torch.device(device)
+    src = _device_maps(maps, 'maps', dev)
+    dst = torch.empty((N, H, W), dtype=out_dtype, device=dev)
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.rgp_spline_resize_workspace_bytes(H, W)), 64), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.rgp_spline_resize(src.data_ptr(), int(src.dtype == torch.float64), N, h, w, dst.data_ptr(),
+                                         int(out_dtype == torch.float64), H, W, ws.data_ptr(), ws.numel(), stream))
+        torch.cuda.current_stream(dev).synchronize()          # the workspace is released on return
+    return dst
+
+
+def union_of_ten_points(point_lists, rng=random):
+    """:func:`union_of_ten` on per-frame arrays of flat pixel indices: the sorted union of ten of them drawn without
+    replacement from ``rng`` -- the same ``choice`` -- without a dense map."""
+    n = len(point_lists)
+    assert n >= 10
+    return np.unique(np.concatenate([point_lists[int(i)] for i in rng.choice(range(n), 10, replace=False)]))
+
+
 def union_of_ten(fixation_maps, rng=random):
     """The AUC_shuffled negative set of ``saliency_score`` (evaluation_metrics.py:275-295): the sum of ``> 0`` of ten
     fixation maps drawn without replacement from ``rng`` (numpy's global RNG by default)."""
@@ -277,11 +541,17 @@ def saliency_score(metric, pred_maps, gt_maps, fixation_maps, draws='device', se
     """``evaluation_metrics.saliency_score`` with the frames scored on the device: the mean over the frames of
     ``metric``, AUC_shuffled's negatives from the union of ten fixation maps chosen with numpy's global RNG (both
     forms of ``draws`` consume that ``choice``).  With ``draws='reference'`` the result is the host function's for the
-    same global RNG state."""
+    same global RNG state.  Fixation maps of the maps' shape go to :func:`saliency_scores_single`, of another shape
+    (sparse ones included) to :func:`saliency_scores_resized`."""
     assert len(gt_maps) == len(pred_maps) == len(fixation_maps)
     union = union_of_ten(fixation_maps)
-    scores = saliency_scores_single(pred_maps, gt_maps, fixation_maps, union, (metric,), draws=draws, seed=seed)
+    if _maps_shape(fixation_maps) != _maps_shape(pred_maps):       # the reference's case: fixations at frame resolution
+        score = saliency_scores_resized
+    else:
+        score = saliency_scores_single
+    scores = score(pred_maps, gt_maps, fixation_maps, union, (metric,), draws=draws, seed=seed)
     return np.mean(scores[metric])
 
 
-__all__ = ['METRICS', 'FRAME_METRICS', 'stack_maps', 'draw_reference_samples', 'saliency_scores_single', 'saliency_score', 'union_of_ten']
+__all__ = ['METRICS', 'FRAME_METRICS', 'stack_maps', 'draw_reference_samples', 'draw_reference_samples_points', 'pack_points',
+           'saliency_scores_single', 'saliency_scores_resized', 'resize_maps', 'saliency_score', 'union_of_ten', 'union_of_ten_points']

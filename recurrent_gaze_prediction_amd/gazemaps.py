@@ -11,6 +11,9 @@ leaves ``gazemaps`` / ``fixationmaps`` (and, if asked, the xentropy ``labels``) 
 Host side (numpy): :func:`pack_fixations` selects the frames and packs the observers' samples per frame;
 :func:`gaussian_weights` makes scipy's kernel in float64 (the device's ``exp`` is not numpy's).
 
+:func:`fixation_points` gives the same fixations at the raw resolution as point lists, the form the frame-resolution
+scorer takes.
+
 Not covered: the loader's original-scale path (sigma = 19 on the raw frame); maps of more than 4096 cells, more than
 32 observers, a filter radius above 32.  Those raise ``ValueError``; there is no host fallback.
 """
@@ -190,5 +193,23 @@ def gazemaps_from_fixations(packed, out_shape=(49, 49), sigma=None, want=('gazem
     return out
 
 
+def fixation_points(packed):
+    """Packed fixations -> ``(ptr, idx)`` int32: per frame the union over the observers of its samples at the RAW
+    resolution, as sorted flat indices ``b * D1 + a`` on the (D2, D1) grid -- row ``b``, column ``a``, the axes of
+    ``gazemaps_from_fixations``' ``fixationmaps``.  What ``evaluation_metrics_gpu.saliency_scores_resized`` takes
+    as ``fix`` (with ``shape=(D2, D1)``) when the targets came from fixation lists."""
+    frame_ptr, samples, _, raw_shape = packed
+    D1, D2 = (int(v) for v in raw_shape)
+    frame_ptr = np.asarray(frame_ptr, np.int64).reshape(-1)
+    samples = np.asarray(samples, np.int64).reshape(-1, 3)
+    N = len(frame_ptr) - 1
+    if len(samples) and (samples[:, 1].min() < 0 or samples[:, 1].max() >= D1 or samples[:, 2].min() < 0 or samples[:, 2].max() >= D2):
+        raise ValueError('a sample lies outside the raw frame %s' % ((D1, D2),))
+    frame = np.repeat(np.arange(N, dtype=np.int64), np.diff(frame_ptr))
+    key = np.unique(frame * (D1 * D2) + samples[:, 2] * D1 + samples[:, 1])
+    ptr = np.searchsorted(key, np.arange(N + 1, dtype=np.int64) * (D1 * D2))
+    return ptr.astype(np.int32), (key % (D1 * D2)).astype(np.int32)
+
+
 __all__ = ['SIGMA_FOR_SHAPE', 'OUTPUTS', 'PackedFixations', 'gaussian_weights', 'reference_frames', 'pack_fixations',
-           'gazemaps_from_fixations']
+           'gazemaps_from_fixations', 'fixation_points']

@@ -1,7 +1,8 @@
 """Mirror of /root/reference/models/evaluate_gaze.py: per-frame scoring of a
 model's generate() output, per-frame dumps and ``overall.txt``; plus the long-clip inference of
 models/extract_map.py:148-229.  The two ``pdb.set_trace()`` calls of the reference (:100, :189)
-are not reproduced."""
+are not reproduced.  The frames are scored by the host module or, on request, on the GPU -- at the maps' own shape or
+at the fixation maps' (frame resolution, the reference's setting) with the spline resize fused into the kernel."""
 import logging
 import os
 from collections import OrderedDict, defaultdict
@@ -60,14 +61,26 @@ def handle_frame(i, n_images, image, pred_gazemap, gt_gazemap, fixationmap, out_
 
 
 def _device_frame_scores(pred, gt, fix, rng, scorer, seed):
-    """All frames in one launch of the HIP metrics kernel (evaluation_metrics_gpu): per frame the union of 10 random
+    """All frames in one launch of the HIP metrics kernels (evaluation_metrics_gpu): per frame the union of 10 random
     other fixation maps drawn from ``rng`` as handle_frame draws them, then the five FRAME_METRICS.  'device-reference'
     feeds the kernel the draws the host loop would take from numpy's global RNG (frame after frame, FRAME_METRICS
-    order); 'device' lets the kernel draw from ``seed``."""
+    order); 'device' lets the kernel draw from ``seed``.  Fixation maps of the maps' shape go to the equal-shape kernel;
+    of another shape -- the reference's evaluation, fixations at frame resolution, usually sparse -- to the kernel that
+    resizes on the fly, as point lists: no dense [N,H,W] array is built."""
     from .. import evaluation_metrics_gpu as emg
+    shape = emg._maps_shape(fix)
+    if shape != tuple(pred.shape[1:]):
+        ptr, idx = emg.pack_points(fix, shape)
+        points = [idx[a:b] for a, b in zip(ptr[:-1], ptr[1:])]
+        unions = [emg.union_of_ten_points(points, rng) for _ in range(len(points))]
+        other_ptr = np.zeros(len(unions) + 1, np.int64)
+        other_ptr[1:] = np.cumsum([len(u) for u in unions])
+        other = (other_ptr.astype(np.int32), np.concatenate(unions).astype(np.int32))
+        draws = 'device'
+        if scorer == 'device-reference':
+            draws = emg.draw_reference_samples_points((ptr, idx), other, shape, FRAME_METRICS, order='frame')
+        return emg.saliency_scores_resized(pred, gt, (ptr, idx), other, FRAME_METRICS, draws=draws, seed=seed, shape=shape)
     fix = np.asarray(emg.stack_maps(fix, 'fixationmap_list'))
-    if fix.shape != pred.shape:
-        raise ValueError('fixation maps %s and predicted maps %s differ in shape; %s' % (fix.shape, pred.shape, emg._HOST))
     positive = (fix > 0).astype(np.uint8)
     unions = np.stack([positive[rng.choice(range(len(fix)), 10, replace=False)].sum(0, dtype=np.uint8) for _ in range(len(fix))])
     draws = 'device'
@@ -81,7 +94,9 @@ def run_evaluation(model, data_sets, out_dir, num_frames=1000, seed=0, dump_imag
 
     ``scorer``: 'host' (default) scores frame by frame with evaluation_metrics; 'device-reference' and 'device' score all
     frames in one launch on the GPU (see _device_frame_scores), the former with the host's own draws -- same numbers, same
-    files -- the latter with draws made on the device from ``seed``.  Both need fixation maps of the maps' shape."""
+    files -- the latter with draws made on the device from ``seed``.  Fixation maps of the maps' shape or, as in the reference's
+    evaluation, of the video frame's (dense or scipy.sparse; the maps are then upsized on the device, inside the scoring
+    kernel) are both scored on the device; frames of different shapes are the host scorer's."""
     assert out_dir is not None
     if scorer not in ('host', 'device', 'device-reference'):
         raise ValueError("scorer must be 'host', 'device' or 'device-reference', got %r" % (scorer,))

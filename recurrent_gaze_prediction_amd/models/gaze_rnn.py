@@ -411,8 +411,9 @@ class GazePredictionGRU(ModelBase):
         ``scorer``: 'host' (default) scores with evaluation_metrics, frame by frame on the CPU; 'device' scores all
         frames of a metric in one launch of the HIP metrics kernel with draws made on the device from ``seed``
         (evaluation_metrics_gpu); 'device-reference' the same kernel fed with the host's own draws from numpy's global
-        RNG, which reproduces the host's scores for the same RNG state.  The device scorers need maps and fixation maps
-        of one shape and raise ValueError otherwise."""
+        RNG, which reproduces the host's scores for the same RNG state.  Fixation maps of another shape than the maps
+        (frame resolution, dense or scipy.sparse: the reference's evaluation) are scored on the device too, the maps
+        upsized inside the kernel (evaluation_metrics_gpu.saliency_scores_resized)."""
         assert len(pred_gazemap_list) == len(gt_gazemap_list) == len(fixationmap_list) == len(images_list), \
             "Length mismatch: %d %d %d %d" % (len(pred_gazemap_list), len(gt_gazemap_list),
                                               len(fixationmap_list), len(images_list))
@@ -422,9 +423,11 @@ class GazePredictionGRU(ModelBase):
             from .. import evaluation_metrics_gpu as emg
             if scorer == 'device':      # one upload for the four metrics
                 dev = self.session.device
-                pred_gazemap_list, gt_gazemap_list, fixationmap_list = (
+                pred_gazemap_list, gt_gazemap_list = (
                     torch.as_tensor(np.asarray(emg.stack_maps(m, name))).to(dev)
-                    for m, name in ((pred_gazemap_list, 'pred'), (gt_gazemap_list, 'gt'), (fixationmap_list, 'fix')))
+                    for m, name in ((pred_gazemap_list, 'pred'), (gt_gazemap_list, 'gt')))
+                if emg._maps_shape(fixationmap_list) == tuple(pred_gazemap_list.shape[1:]):
+                    fixationmap_list = torch.as_tensor(np.asarray(emg.stack_maps(fixationmap_list, 'fix'))).to(dev)
             score = partial(emg.saliency_score, draws='device' if scorer == 'device' else 'reference', seed=seed)
         else:
             raise ValueError("scorer must be 'host', 'device' or 'device-reference', got %r" % (scorer,))
