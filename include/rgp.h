@@ -839,7 +839,8 @@ int rgp_spline_resize(const void* src, int src_f64, int n_frames, int h, int w, 
  * sample with u outside [0, n_observers), a outside [0, raw_d1) or b outside [0, raw_d2), or a frame whose frame_ptr
  * pair is negative or decreasing, refuses its frame on the device: NaN in every requested output of that frame, the
  * frame counted in the workspace's status word (rgp_gtmaps_status); the other frames are unaffected.  n_frames == 0:
- * RGP_OK, nothing is launched.  The original-scale path of the loader (sigma = 19 on the raw frame) is not covered.
+ * RGP_OK, nothing is launched.  The original-scale path of the loader (sigma = 19 on the raw frame) has an entry of its
+ * own: rgp_gazemaps_full_from_fixations, below.
  *
  * workspace (device, 8-byte aligned, rgp_gtmaps_workspace_bytes): the status word, cleared on the stream before the
  * launch. */
@@ -862,6 +863,49 @@ int rgp_gazemaps_from_fixations(const rgp_gtmaps_args* args, rgp_stream_t stream
 /* Waits for `stream`, reads the status word of the last rgp_gazemaps_from_fixations that used `workspace`: RGP_OK, or
  * RGP_EINVAL with the number of refused frames in rgp_last_error(). */
 int rgp_gtmaps_status(const void* workspace, rgp_stream_t stream);
+
+/* ------------------------------------------------------------------ ground-truth maps at the frame's resolution
+ * The loader's original-scale path (crc_input_data_seq.py:237-240 with :41-53 and :261-288): the maps above with
+ * out_shape = raw_shape, i.e. frames [raw_d2][raw_d1] of up to RGP_GTMAPS_FULL_MAX_PIX cells (405 x 720, 1080 x 1920)
+ * and sigma = 19 (radius 76).  Same arithmetic, same weights from the host, same bits as the host: the rescale is the
+ * identity, fixationmaps = observers per cell, gazemaps = count / n_observers filtered along the frame's first axis,
+ * then its second (scipy's correlate1d sums in fp64, each rounded once to fp32, the plane between the passes fp32,
+ * `reflect` at any distance), then g -= min(g); g /= max(g) unless the frame is all zero.  There are no `labels`.
+ * The planes live in the workspace; the filter is tiled over them in a fixed number of launches on `stream` (scatter,
+ * pass 1, pass 2 with the frame's min and max, normalise), none of which waits for another workgroup.  A filter radius up
+ * to RGP_GTMAPS_FULL_LDS_RADIUS stages its taps in LDS; above it they are read through the caches, same sums.
+ *
+ * Limits: raw_d1, raw_d2 >= 2, raw_d1*raw_d2 <= RGP_GTMAPS_FULL_MAX_PIX, 1 <= n_observers <= RGP_GTMAPS_MAX_OBSERVERS,
+ * 0 <= radius <= RGP_GTMAPS_FULL_MAX_RADIUS; the host refuses what it can see (RGP_EINVAL before any device call).  A bad
+ * sample or frame_ptr pair refuses its frame on the device as above: NaN in every requested output of that frame, the
+ * frame counted in the status word (rgp_gtmaps_full_status), no out-of-range value used as an address, the other frames
+ * unaffected.  n_frames == 0: RGP_OK, nothing is launched.
+ *
+ * workspace (device, 8-byte aligned, rgp_gtmaps_full_workspace_bytes(n_frames, raw_d1, raw_d2): the status word, three
+ * words and a column bitmap per frame, then a uint32 observer-mask plane and an fp32 plane per frame -- 8 bytes per cell
+ * and frame; 0 for arguments the entry refuses).  Frames are independent: a caller short of memory splits the call.
+ * RGP_GTMAPS_FULL_TILE_COLS / _ROWS: every tile extent of either pass divides them (for tests that straddle tiles). */
+#define RGP_GTMAPS_FULL_MAX_PIX (1 << 22)
+#define RGP_GTMAPS_FULL_MAX_RADIUS 256
+#define RGP_GTMAPS_FULL_LDS_RADIUS 76
+#define RGP_GTMAPS_FULL_TILE_COLS 128
+#define RGP_GTMAPS_FULL_TILE_ROWS 64
+
+typedef struct rgp_gtmaps_full_args {
+  const int* frame_ptr;        /* [n_frames + 1] */
+  const int* samples;          /* [n_samples][3] */
+  const double* weights;       /* [2 radius + 1] */
+  int n_frames, n_observers, raw_d1, raw_d2, radius;
+  float *gazemaps, *fixationmaps;            /* [n_frames][raw_d2][raw_d1]; either may be NULL, not both */
+  void* workspace;
+  size_t workspace_bytes;
+} rgp_gtmaps_full_args;
+
+size_t rgp_gtmaps_full_workspace_bytes(int n_frames, int raw_d1, int raw_d2);
+int rgp_gazemaps_full_from_fixations(const rgp_gtmaps_full_args* args, rgp_stream_t stream);
+/* Waits for `stream`, reads the status word of the last rgp_gazemaps_full_from_fixations that used `workspace`: RGP_OK,
+ * or RGP_EINVAL with the number of refused frames in rgp_last_error() and, if refused is not NULL, in *refused. */
+int rgp_gtmaps_full_status(const void* workspace, int* refused, rgp_stream_t stream);
 
 /* ------------------------------------------------------------------ action classifier on gaze-attended C3D features */
 typedef struct rgp_action rgp_action_t;

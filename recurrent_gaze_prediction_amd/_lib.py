@@ -36,6 +36,10 @@ RGP_METRICS_DEVICE_DRAWS, RGP_METRICS_NO_JITTER, RGP_METRICS_PRED_F64, RGP_METRI
 RGP_METRICS_SCALED_MAX_PIX, RGP_METRICS_SCALED_MAX_OTHER, RGP_METRICS_SCALED_OTHER_SHARED = 1 << 22, 4096, 16
 # ground-truth maps from fixation points (include/rgp.h): caps
 RGP_GTMAPS_MAX_PIX, RGP_GTMAPS_MAX_OBSERVERS, RGP_GTMAPS_MAX_RADIUS = 4096, 32, 32
+# the same maps at the frame's resolution (include/rgp.h): caps, the largest radius the LDS tiles hold, and extents every
+# tile extent of either filter pass divides
+RGP_GTMAPS_FULL_MAX_PIX, RGP_GTMAPS_FULL_MAX_RADIUS, RGP_GTMAPS_FULL_LDS_RADIUS = 1 << 22, 256, 76
+RGP_GTMAPS_FULL_TILE_COLS, RGP_GTMAPS_FULL_TILE_ROWS = 128, 64
 DTYPES = {'f32': RGP_F32, 'fp32': RGP_F32, 'float32': RGP_F32, 'bf16': RGP_BF16, 'bfloat16': RGP_BF16}
 
 c_void_p, c_int, c_size_t, c_char_p = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_char_p
@@ -119,6 +123,12 @@ class GtmapsArgs(ctypes.Structure):
                 ('n_observers', c_int), ('raw_d1', c_int), ('raw_d2', c_int), ('out_s1', c_int), ('out_s2', c_int),
                 ('radius', c_int), ('gazemaps', c_void_p), ('fixationmaps', c_void_p), ('labels', c_void_p),
                 ('workspace', c_void_p), ('workspace_bytes', c_size_t)]
+
+
+class GtmapsFullArgs(ctypes.Structure):
+    _fields_ = [('frame_ptr', c_void_p), ('samples', c_void_p), ('weights', c_void_p), ('n_frames', c_int),
+                ('n_observers', c_int), ('raw_d1', c_int), ('raw_d2', c_int), ('radius', c_int), ('gazemaps', c_void_p),
+                ('fixationmaps', c_void_p), ('workspace', c_void_p), ('workspace_bytes', c_size_t)]
 
 
 # name -> (restype, argtypes); every symbol include/rgp.h declares
@@ -263,6 +273,9 @@ SIGNATURES = {
     'rgp_gtmaps_workspace_bytes': (c_size_t, []),
     'rgp_gazemaps_from_fixations': (c_int, [ctypes.POINTER(GtmapsArgs), c_void_p]),
     'rgp_gtmaps_status': (c_int, [c_void_p, c_void_p]),
+    'rgp_gtmaps_full_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'rgp_gazemaps_full_from_fixations': (c_int, [ctypes.POINTER(GtmapsFullArgs), c_void_p]),
+    'rgp_gtmaps_full_status': (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
     'rgp_dropout_apply': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_float, c_void_p]),
     'rgp_fcgru_set_dropout': (c_int, [c_void_p, ctypes.c_float, c_void_p]),
     'rgp_cascade_set_dropout': (c_int, [c_void_p, ctypes.c_float, c_void_p]),

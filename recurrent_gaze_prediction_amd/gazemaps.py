@@ -14,8 +14,13 @@ Host side (numpy): :func:`pack_fixations` selects the frames and packs the obser
 :func:`fixation_points` gives the same fixations at the raw resolution as point lists, the form the frame-resolution
 scorer takes.
 
-Not covered: the loader's original-scale path (sigma = 19 on the raw frame); maps of more than 4096 cells, more than
-32 observers, a filter radius above 32.  Those raise ``ValueError``; there is no host fallback.
+The loader's original-scale path (``gazemap_height is None``: sigma = 19 on the raw frame, 405 x 720 cells) is
+:func:`gazemaps_original_scale` (csrc/rgp_gtmaps_full.hip, ``rgp_gazemaps_full_from_fixations``): the same arithmetic
+with the planes in HBM and the filter tiled over them, the same bits as the host; it has no ``labels``.
+
+Not covered by :func:`gazemaps_from_fixations`: maps of more than 4096 cells, more than 32 observers, a filter radius
+above 32; by :func:`gazemaps_original_scale`: frames of more than 2^22 cells, more than 32 observers, a radius above
+256.  Those raise ``ValueError``; there is no host fallback.
 """
 import collections
 import ctypes
@@ -29,6 +34,11 @@ from . import _lib
 SIGMA_FOR_SHAPE = {(49, 49): 2.0, (48, 48): 2.0, (14, 14): 0.6, (7, 7): 0.3}
 OUTPUTS = ('gazemaps', 'fixationmaps', 'labels')
 MAX_PIX, MAX_OBSERVERS, MAX_RADIUS = _lib.RGP_GTMAPS_MAX_PIX, _lib.RGP_GTMAPS_MAX_OBSERVERS, _lib.RGP_GTMAPS_MAX_RADIUS
+# the original-scale path: the loader's sigma on the raw frame (crc_input_data_seq.py:237-240), its outputs and caps
+SIGMA_ORIGINAL_SCALE = 19
+OUTPUTS_ORIGINAL_SCALE = ('gazemaps', 'fixationmaps')
+FULL_MAX_PIX, FULL_MAX_RADIUS = _lib.RGP_GTMAPS_FULL_MAX_PIX, _lib.RGP_GTMAPS_FULL_MAX_RADIUS
+FULL_WORKSPACE_TARGET = 256 << 20      # frames_per_call by default: as many frames as keep the workspace under this
 
 # frame_ptr int32 [N + 1], samples int32 [n_samples, 3] = (observer, a, b), rows frame_ptr[n] .. frame_ptr[n + 1] being
 # frame n's; n_observers = the divisor; raw_shape = (D1, D2), the extents a and b live in
@@ -150,7 +160,7 @@ def gazemaps_from_fixations(packed, out_shape=(49, 49), sigma=None, want=('gazem
         sigma = SIGMA_FOR_SHAPE[(S1, S2)]
     w, r = gaussian_weights(sigma)
     if S1 < 1 or S2 < 1 or S1 * S2 > MAX_PIX:
-        raise ValueError('maps of %d x %d cells: more than RGP_GTMAPS_MAX_PIX = %d (the original-scale path is not covered)'
+        raise ValueError('maps of %d x %d cells: more than RGP_GTMAPS_MAX_PIX = %d (the original-scale path is gazemaps_original_scale)'
                          % (S1, S2, MAX_PIX))
     if r > MAX_RADIUS:
         raise ValueError('sigma = %g: filter radius %d above RGP_GTMAPS_MAX_RADIUS = %d' % (sigma, r, MAX_RADIUS))
@@ -193,6 +203,86 @@ def gazemaps_from_fixations(packed, out_shape=(49, 49), sigma=None, want=('gazem
     return out
 
 
+def gazemaps_original_scale(packed, sigma=SIGMA_ORIGINAL_SCALE, want=OUTPUTS_ORIGINAL_SCALE, device=None, frames_per_call=None):
+    """Packed fixations -> {name: device tensor fp32 [N, D2, D1]} at the raw frame's own resolution (row ``b``, column
+    ``a``): the loader's original-scale maps.  ``fixationmaps``: observers per cell; ``gazemaps``: their mean filtered
+    with ``sigma`` (the loader's 19) and min-max normalised per frame.  Bit for bit what
+    ``gazemaps_from_fixations(out_shape=raw_shape)`` would give if it reached this size.
+
+    The kernels keep two 4-byte planes per frame in a workspace, so the frames go through in calls of at most
+    ``frames_per_call`` (default: what keeps the workspace under 256 MB) that reuse one workspace; frames are
+    independent, so the split changes no bit.  Raises ValueError for what the entry does not cover (``labels`` among
+    it) and ``_lib.RgpError`` if the device refused a frame (a sample out of range: that frame is NaN; the error carries
+    the tensors as ``.outputs``)."""
+    frame_ptr, samples, n_observers, raw_shape = packed
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in OUTPUTS_ORIGINAL_SCALE for w in want):
+        raise ValueError('want = %r: choose from %s (the original-scale path has no labels)' % (want, OUTPUTS_ORIGINAL_SCALE))
+    D1, D2 = (int(v) for v in raw_shape)
+    w, r = gaussian_weights(sigma)
+    if D1 < 2 or D2 < 2:
+        raise ValueError('raw_shape %s: both extents must be at least 2' % ((D1, D2),))
+    if D1 * D2 > FULL_MAX_PIX:
+        raise ValueError('frames of %d x %d cells: more than RGP_GTMAPS_FULL_MAX_PIX = %d' % (D1, D2, FULL_MAX_PIX))
+    if r > FULL_MAX_RADIUS:
+        raise ValueError('sigma = %g: filter radius %d above RGP_GTMAPS_FULL_MAX_RADIUS = %d' % (sigma, r, FULL_MAX_RADIUS))
+    n_observers = int(n_observers)
+    if not 1 <= n_observers <= MAX_OBSERVERS:
+        raise ValueError('%d observers: must be in [1, RGP_GTMAPS_MAX_OBSERVERS = %d]' % (n_observers, MAX_OBSERVERS))
+    frame_ptr = np.ascontiguousarray(frame_ptr, np.int32).reshape(-1)
+    samples = np.ascontiguousarray(samples, np.int32).reshape(-1, 3)
+    N = len(frame_ptr) - 1
+    if N < 0 or frame_ptr[0] != 0 or np.any(np.diff(frame_ptr) < 0) or frame_ptr[-1] != len(samples):
+        raise ValueError('frame_ptr must start at 0, not decrease and end at len(samples)')
+    if frames_per_call is None:
+        frames_per_call = max(1, FULL_WORKSPACE_TARGET // (8 * D1 * D2 + 4 * (3 + (D1 + 31) // 32)))
+    frames_per_call = int(frames_per_call)
+    if frames_per_call < 1:
+        raise ValueError('frames_per_call = %d must be at least 1' % frames_per_call)
+    dev = torch.device('cuda:0' if device is None else device)
+    out = {name: torch.empty((N, D2, D1), dtype=torch.float32, device=dev) for name in want}
+    if N == 0:
+        return out
+    d_ptr = torch.from_numpy(frame_ptr).to(dev)
+    d_samples = torch.from_numpy(samples if len(samples) else np.zeros((1, 3), np.int32)).to(dev)
+    d_w = torch.from_numpy(np.ascontiguousarray(w, np.float64)).to(dev)
+    lib = _lib.load()
+    per_call = min(frames_per_call, N)
+    ws = torch.empty(int(lib.rgp_gtmaps_full_workspace_bytes(per_call, D1, D2)), dtype=torch.uint8, device=dev)
+    refused_total, rc = 0, 0
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        for lo in range(0, N, per_call):
+            n = min(per_call, N - lo)
+
+            def ptr(name):
+                return out[name][lo:].data_ptr() if name in out else None
+            # frame_ptr holds absolute rows of `samples`: a later chunk takes the same samples and a shifted frame_ptr
+            args = _lib.GtmapsFullArgs(frame_ptr=d_ptr[lo:].data_ptr(), samples=d_samples.data_ptr(), weights=d_w.data_ptr(),
+                                       n_frames=n, n_observers=n_observers, raw_d1=D1, raw_d2=D2, radius=r,
+                                       gazemaps=ptr('gazemaps'), fixationmaps=ptr('fixationmaps'),
+                                       workspace=ws.data_ptr(), workspace_bytes=ws.numel())
+            rc = lib.rgp_gazemaps_full_from_fixations(ctypes.byref(args), stream)
+            if rc != 0:
+                break
+            refused = ctypes.c_int(0)
+            rc = lib.rgp_gtmaps_full_status(ws.data_ptr(), ctypes.byref(refused), stream)
+            if rc != 0 and refused.value == 0:
+                break
+            refused_total, rc = refused_total + refused.value, 0
+    if rc == 0 and refused_total:
+        err = _lib.RgpError('librgp_hip error -1: rgp_gazemaps_full_from_fixations: %d frame(s) refused (a sample\'s observer, a or '
+                            'b out of range, or a bad frame_ptr pair): their outputs are NaN' % refused_total)
+        err.code, err.outputs = -1, out
+        raise err
+    try:
+        _lib.check(rc)
+    except _lib.RgpError as err:
+        err.outputs = out
+        raise
+    return out
+
+
 def fixation_points(packed):
     """Packed fixations -> ``(ptr, idx)`` int32: per frame the union over the observers of its samples at the RAW
     resolution, as sorted flat indices ``b * D1 + a`` on the (D2, D1) grid -- row ``b``, column ``a``, the axes of
@@ -211,5 +301,5 @@ def fixation_points(packed):
     return ptr.astype(np.int32), (key % (D1 * D2)).astype(np.int32)
 
 
-__all__ = ['SIGMA_FOR_SHAPE', 'OUTPUTS', 'PackedFixations', 'gaussian_weights', 'reference_frames', 'pack_fixations',
-           'gazemaps_from_fixations', 'fixation_points']
+__all__ = ['SIGMA_FOR_SHAPE', 'SIGMA_ORIGINAL_SCALE', 'OUTPUTS', 'OUTPUTS_ORIGINAL_SCALE', 'PackedFixations', 'gaussian_weights',
+           'reference_frames', 'pack_fixations', 'gazemaps_from_fixations', 'gazemaps_original_scale', 'fixation_points']
