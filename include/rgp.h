@@ -907,6 +907,71 @@ int rgp_gazemaps_full_from_fixations(const rgp_gtmaps_full_args* args, rgp_strea
  * or RGP_EINVAL with the number of refused frames in rgp_last_error() and, if refused is not NULL, in *refused. */
 int rgp_gtmaps_full_status(const void* workspace, int* refused, rgp_stream_t stream);
 
+/* ------------------------------------------------------------------ loader frame images: Pillow's antialiased resize
+ * The loader's frame step (crc_input_data_seq.py:186-209) for the ShallowNet branch: selected uint8 RGB frames resized
+ * with Image.resize((w, h), Image.ANTIALIAS) -- Pillow's two-pass 8-bit resample -- and scaled by float32(1 / 255).
+ * ONE launch; a workgroup owns one output frame and one band of its output rows: it streams the band's input rows from
+ * HBM, resamples each horizontally into an 8-bit image of the band in LDS, runs the vertical pass from LDS and stores
+ * the fp32 and / or uint8 image.  The 8-bit intermediate never reaches HBM.  Integer arithmetic throughout: the same
+ * bits as Pillow with the same tables, whatever the banding.
+ *
+ * Tables (DEVICE int32, made by the HOST, frames.resample_coeffs): per axis, in -> out, k [out][ksize] the 22-bit
+ * fixed-point weights and b [out][2] = (xmin, n): output xx = clamp((2^21 + sum_{x < n} pixel[xmin + x] k[xx][x]) >> 22,
+ * 0, 255), arithmetic shift, int32 accumulator (exact while 255 sum|k| + 2^21 < 2^31, which the host builder checks;
+ * every |k| must be below 2^23: the products are 24-bit multiplies).  Horizontal first, on the input rows the band's
+ * vertical entries touch, then vertical on the 8-bit intermediate.  A pass whose in == out is skipped: its bytes go
+ * through unchanged and its tables are not read (they may be NULL, its ksize 0).  images = (float)u8 * 0.003921569f.
+ *
+ * frame_index (device, [n_out]; NULL = frames 0 .. n_out-1) selects the source frame of every output frame.  An entry
+ * outside [0, n_frames) refuses that output frame on the device: NaN in `images`, 0 in `images_u8`, counted in the
+ * status word (rgp_frames_status), never used as an address, the other frames unaffected.  The bounds tables are
+ * checked the same way before they address anything (xmin >= 0, 0 <= n <= ksize, xmin + n <= in, and a band's input
+ * rows within what its LDS image holds): a bad entry refuses every output frame.
+ *
+ * bands: the least number of bands the output rows are cut into (band i = rows [i out_h / B, (i + 1) out_h / B));
+ * 0 = the library's choice (enough workgroups to fill the chip).  The library raises the count until a band's LDS
+ * image fits RGP_FRAMES_LDS_BYTES; if not even one output row per band fits: RGP_EINVAL.
+ *
+ * Limits (the host refuses what it can see with RGP_EINVAL, naming the argument, before any device call): 3 channels;
+ * 1 <= out_h, out_w <= RGP_FRAMES_MAX_OUT; ksize <= RGP_FRAMES_MAX_KSIZE; fw <= RGP_FRAMES_MAX_IN_W (four input rows
+ * are staged at a time); n_frames * fh * fw * 3 and n_out * out_h * out_w * 3 below RGP_FRAMES_MAX_BYTES; both outputs
+ * NULL; bands > out_h; a missing table.  n_out == 0: RGP_OK, nothing is launched.
+ * workspace (device, 8-byte aligned, rgp_frames_workspace_bytes()): the status word, cleared on the stream before
+ * the launch. */
+#define RGP_FRAMES_MAX_OUT 256
+#define RGP_FRAMES_MAX_KSIZE 128
+#define RGP_FRAMES_MAX_IN_W 2040
+#define RGP_FRAMES_MAX_BYTES (1ll << 40)
+#define RGP_FRAMES_LDS_BYTES (156 * 1024)     /* the most a workgroup may take */
+#define RGP_FRAMES_LDS_TARGET (80 * 1024)     /* the library's own choice of bands keeps two workgroups per CU */
+#define RGP_FRAMES_STAGE_BYTES 24576          /* input rows staged per step (and the band's output image) */
+
+typedef struct rgp_frames_args {
+  const unsigned char* frames;      /* [n_frames][fh][fw][3] */
+  int n_frames, fh, fw;
+  const int* frame_index;           /* [n_out] or NULL */
+  int n_out, out_h, out_w;
+  const int *kh, *bh;               /* [out_w][ksize_h], [out_w][2]; unused when fw == out_w */
+  int ksize_h;
+  const int *kv, *bv;               /* [out_h][ksize_v], [out_h][2]; unused when fh == out_h */
+  int ksize_v;
+  int bands;
+  float* images;                    /* [n_out][out_h][out_w][3]; either may be NULL, not both */
+  unsigned char* images_u8;
+  void* workspace;
+  size_t workspace_bytes;
+} rgp_frames_args;
+
+size_t rgp_frames_workspace_bytes(void);
+/* The band count the entry would use (>= bands), the LDS bytes of its workgroups and the input rows a band's LDS image
+ * holds; 0 if no banding fits or an argument is out of range.  ksize of a skipped pass: 0.  Host arithmetic only. */
+int rgp_frames_plan(int fh, int fw, int out_h, int out_w, int ksize_h, int ksize_v, int n_out, int bands, int* lds_bytes,
+                    int* mid_rows);
+int rgp_frame_images(const rgp_frames_args* args, rgp_stream_t stream);
+/* Waits for `stream`, reads the status word of the last rgp_frame_images that used `workspace`: RGP_OK, or RGP_EINVAL
+ * with the number of refused output frames in rgp_last_error() and, if refused is not NULL, in *refused. */
+int rgp_frames_status(const void* workspace, int* refused, rgp_stream_t stream);
+
 /* ------------------------------------------------------------------ action classifier on gaze-attended C3D features */
 typedef struct rgp_action rgp_action_t;
 

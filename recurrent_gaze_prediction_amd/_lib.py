@@ -40,6 +40,10 @@ RGP_GTMAPS_MAX_PIX, RGP_GTMAPS_MAX_OBSERVERS, RGP_GTMAPS_MAX_RADIUS = 4096, 32, 
 # tile extent of either filter pass divides
 RGP_GTMAPS_FULL_MAX_PIX, RGP_GTMAPS_FULL_MAX_RADIUS, RGP_GTMAPS_FULL_LDS_RADIUS = 1 << 22, 256, 76
 RGP_GTMAPS_FULL_TILE_COLS, RGP_GTMAPS_FULL_TILE_ROWS = 128, 64
+# loader frame images (include/rgp.h): caps, the LDS a workgroup may take / takes by the library's own choice of bands, and
+# the bytes of input rows staged per step
+RGP_FRAMES_MAX_OUT, RGP_FRAMES_MAX_KSIZE, RGP_FRAMES_MAX_IN_W, RGP_FRAMES_MAX_BYTES = 256, 128, 2040, 1 << 40
+RGP_FRAMES_LDS_BYTES, RGP_FRAMES_LDS_TARGET, RGP_FRAMES_STAGE_BYTES = 156 * 1024, 80 * 1024, 24576
 DTYPES = {'f32': RGP_F32, 'fp32': RGP_F32, 'float32': RGP_F32, 'bf16': RGP_BF16, 'bfloat16': RGP_BF16}
 
 c_void_p, c_int, c_size_t, c_char_p = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_char_p
@@ -129,6 +133,13 @@ class GtmapsFullArgs(ctypes.Structure):
     _fields_ = [('frame_ptr', c_void_p), ('samples', c_void_p), ('weights', c_void_p), ('n_frames', c_int),
                 ('n_observers', c_int), ('raw_d1', c_int), ('raw_d2', c_int), ('radius', c_int), ('gazemaps', c_void_p),
                 ('fixationmaps', c_void_p), ('workspace', c_void_p), ('workspace_bytes', c_size_t)]
+
+
+class FramesArgs(ctypes.Structure):
+    _fields_ = [('frames', c_void_p), ('n_frames', c_int), ('fh', c_int), ('fw', c_int), ('frame_index', c_void_p),
+                ('n_out', c_int), ('out_h', c_int), ('out_w', c_int), ('kh', c_void_p), ('bh', c_void_p), ('ksize_h', c_int),
+                ('kv', c_void_p), ('bv', c_void_p), ('ksize_v', c_int), ('bands', c_int), ('images', c_void_p),
+                ('images_u8', c_void_p), ('workspace', c_void_p), ('workspace_bytes', c_size_t)]
 
 
 # name -> (restype, argtypes); every symbol include/rgp.h declares
@@ -276,6 +287,10 @@ SIGNATURES = {
     'rgp_gtmaps_full_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'rgp_gazemaps_full_from_fixations': (c_int, [ctypes.POINTER(GtmapsFullArgs), c_void_p]),
     'rgp_gtmaps_full_status': (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    'rgp_frames_workspace_bytes': (c_size_t, []),
+    'rgp_frames_plan': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    'rgp_frame_images': (c_int, [ctypes.POINTER(FramesArgs), c_void_p]),
+    'rgp_frames_status': (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
     'rgp_dropout_apply': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_float, c_void_p]),
     'rgp_fcgru_set_dropout': (c_int, [c_void_p, ctypes.c_float, c_void_p]),
     'rgp_cascade_set_dropout': (c_int, [c_void_p, ctypes.c_float, c_void_p]),
