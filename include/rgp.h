@@ -972,6 +972,54 @@ int rgp_frame_images(const rgp_frames_args* args, rgp_stream_t stream);
  * with the number of refused output frames in rgp_last_error() and, if refused is not NULL, in *refused. */
 int rgp_frames_status(const void* workspace, int* refused, rgp_stream_t stream);
 
+/* ------------------------------------------------------------------ gaze-map export: scipy's bytescale and imresize
+ * extract_map.py:35-41 writes the 7 x 7 map of every step as avg_pool(a) = scipy.misc.imresize(a[i], (7, 7)) / its sum,
+ * and scipy.misc.imsave (evaluate_gaze.py:148-152) encodes bytescale(a).  ONE launch for n fp32 maps [n][h][w], one wave
+ * per map, any of three outputs.  Per map (scipy <= 1.2, a NumPy before NEP 50):
+ *   bytes      cmin, cmax fp32; cscale = cmax - cmin in fp32, 1 if that is 0; scale = float32(255.0 / float64(cscale));
+ *              b = (a - cmin) * scale, an fp32 subtract and an fp32 multiply; u = uint8(trunc(clip(b, 0, 255) + 0.5f)).
+ *              Where 255 / cscale overflows fp32 (cscale below about 7.5e-37) scale is +inf and the cells equal to cmin
+ *              are 0 * inf = NaN: they give byte 0, the x86 conversion's result; the other cells give 255.
+ *   pooled_u8  Pillow's 8-bit resample of `bytes` as one channel, h x w -> out_h x out_w, with the tables of "loader
+ *              frame images" above (frames.resample_coeffs; made by the HOST, int32 on the DEVICE): horizontal, then
+ *              vertical on the 8-bit intermediate; a pass whose in == out is skipped and its tables are not read.
+ *   pooled     float64(pooled_u8) / float64(sum of pooled_u8): an exact integer sum, one IEEE division per cell.  A zero
+ *              sum (a constant map, a very peaked one) gives NaN in every cell, as NumPy's 0 / 0 does: not an error.
+ * With pooled and pooled_u8 both NULL only `bytes` is made and out_h, out_w and the tables are not read.
+ *
+ * A map that holds a NaN or an Inf is refused on the device: NaN in `pooled`, 0 in `pooled_u8` and `bytes`, counted in
+ * the status word (rgp_mapexport_status), the other maps unaffected.  The bounds tables are checked on the device before
+ * they address anything (xmin >= 0, 0 <= n <= ksize, xmin + n <= in): a bad entry refuses every map.
+ *
+ * Limits (the host refuses what it can see with RGP_EINVAL, naming the argument, before any device call): 1 <= h, w <=
+ * RGP_MAPEXPORT_MAX_SIDE; 1 <= out_h <= h and 1 <= out_w <= w (no upscale); ksize <= RGP_MAPEXPORT_MAX_KSIZE; all three
+ * outputs NULL; a missing table for a pass that runs; the workspace.  n == 0: RGP_OK, nothing is launched.
+ * workspace (device, 8-byte aligned, rgp_mapexport_workspace_bytes()): the status word, cleared on the stream before the
+ * launch. */
+#define RGP_MAPEXPORT_MAX_SIDE 64
+#define RGP_MAPEXPORT_MAX_KSIZE 512
+#define RGP_MAPEXPORT_LDS_BYTES (152 * 1024)  /* the most a workgroup may take (64 x 64 maps); 49 x 49 -> 7 x 7 takes 50 KB */
+
+typedef struct rgp_mapexport_args {
+  const float* maps;                /* [n][h][w] */
+  int n, h, w, out_h, out_w;
+  const int *kh, *bh;               /* [out_w][ksize_h], [out_w][2]; unused when w == out_w */
+  int ksize_h;
+  const int *kv, *bv;               /* [out_h][ksize_v], [out_h][2]; unused when h == out_h */
+  int ksize_v;
+  double* pooled;                   /* [n][out_h][out_w]; any may be NULL, not all three */
+  unsigned char* pooled_u8;         /* [n][out_h][out_w] */
+  unsigned char* bytes;             /* [n][h][w] */
+  void* workspace;
+  size_t workspace_bytes;
+} rgp_mapexport_args;
+
+size_t rgp_mapexport_workspace_bytes(void);
+int rgp_mapexport(const rgp_mapexport_args* args, rgp_stream_t stream);
+/* Waits for `stream`, reads the status word of the last rgp_mapexport that used `workspace`: RGP_OK, or RGP_EINVAL with
+ * the number of refused maps in rgp_last_error() and, if refused is not NULL, in *refused. */
+int rgp_mapexport_status(const void* workspace, int* refused, rgp_stream_t stream);
+
 /* ------------------------------------------------------------------ action classifier on gaze-attended C3D features */
 typedef struct rgp_action rgp_action_t;
 

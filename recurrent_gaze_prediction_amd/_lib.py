@@ -44,6 +44,8 @@ RGP_GTMAPS_FULL_TILE_COLS, RGP_GTMAPS_FULL_TILE_ROWS = 128, 64
 # the bytes of input rows staged per step
 RGP_FRAMES_MAX_OUT, RGP_FRAMES_MAX_KSIZE, RGP_FRAMES_MAX_IN_W, RGP_FRAMES_MAX_BYTES = 256, 128, 2040, 1 << 40
 RGP_FRAMES_LDS_BYTES, RGP_FRAMES_LDS_TARGET, RGP_FRAMES_STAGE_BYTES = 156 * 1024, 80 * 1024, 24576
+# gaze-map export (include/rgp.h): caps and the LDS a workgroup may take
+RGP_MAPEXPORT_MAX_SIDE, RGP_MAPEXPORT_MAX_KSIZE, RGP_MAPEXPORT_LDS_BYTES = 64, 512, 152 * 1024
 DTYPES = {'f32': RGP_F32, 'fp32': RGP_F32, 'float32': RGP_F32, 'bf16': RGP_BF16, 'bfloat16': RGP_BF16}
 
 c_void_p, c_int, c_size_t, c_char_p = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_char_p
@@ -140,6 +142,13 @@ class FramesArgs(ctypes.Structure):
                 ('n_out', c_int), ('out_h', c_int), ('out_w', c_int), ('kh', c_void_p), ('bh', c_void_p), ('ksize_h', c_int),
                 ('kv', c_void_p), ('bv', c_void_p), ('ksize_v', c_int), ('bands', c_int), ('images', c_void_p),
                 ('images_u8', c_void_p), ('workspace', c_void_p), ('workspace_bytes', c_size_t)]
+
+
+class MapExportArgs(ctypes.Structure):
+    _fields_ = [('maps', c_void_p), ('n', c_int), ('h', c_int), ('w', c_int), ('out_h', c_int), ('out_w', c_int),
+                ('kh', c_void_p), ('bh', c_void_p), ('ksize_h', c_int), ('kv', c_void_p), ('bv', c_void_p), ('ksize_v', c_int),
+                ('pooled', c_void_p), ('pooled_u8', c_void_p), ('bytes', c_void_p), ('workspace', c_void_p),
+                ('workspace_bytes', c_size_t)]
 
 
 # name -> (restype, argtypes); every symbol include/rgp.h declares
@@ -291,6 +300,9 @@ SIGNATURES = {
     'rgp_frames_plan': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     'rgp_frame_images': (c_int, [ctypes.POINTER(FramesArgs), c_void_p]),
     'rgp_frames_status': (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    'rgp_mapexport_workspace_bytes': (c_size_t, []),
+    'rgp_mapexport': (c_int, [ctypes.POINTER(MapExportArgs), c_void_p]),
+    'rgp_mapexport_status': (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
     'rgp_dropout_apply': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_float, c_void_p]),
     'rgp_fcgru_set_dropout': (c_int, [c_void_p, ctypes.c_float, c_void_p]),
     'rgp_cascade_set_dropout': (c_int, [c_void_p, ctypes.c_float, c_void_p]),

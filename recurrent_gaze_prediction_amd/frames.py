@@ -13,8 +13,9 @@ checks that the int32 accumulator of a pass cannot overflow; the device computes
 :func:`video_inputs` makes both inputs of the cascade -- conv5b features and frame images -- from one uploaded clip.
 
 Not covered: more or fewer than 3 channels, an output side above 256, a filter of more than 128 taps (a downscale
-beyond about 21x with Lanczos), frames wider than 2040 pixels, ``extract_map.py``'s 49 -> 7 ``scipy.misc.imresize``
-export.  Those raise ``ValueError``; there is no host fallback.
+beyond about 21x with Lanczos), frames wider than 2040 pixels.  Those raise ``ValueError``; there is no host fallback.
+``extract_map.py``'s 49 -> 7 ``scipy.misc.imresize`` export -- one channel, scipy's bytescale in front, a float64
+normalisation behind -- is ``models/extract_map.py``'s (csrc/rgp_mapexport.hip), with the tables made here.
 """
 import ctypes
 

@@ -9,29 +9,41 @@ from collections import OrderedDict, defaultdict
 
 import numpy as np
 import scipy.sparse
+import torch
 
 from ..evaluation_metrics import resize_onehot_tensor_sparse, saliency_score_single
 
 log = logging.getLogger('rgp')
 FRAME_METRICS = ('sim', 'cc', 'AUC_Borji', 'AUC_Judd', 'AUC_shuffled')       # evaluate_gaze.py:135
+DUMP_SCALES = ('minmax', 'bytescale')
 
 
 def _dense(m):
     return m.toarray() if scipy.sparse.issparse(m) else np.asarray(m)
 
 
-def _write_frame(i, n_images, image, pred_gazemap, gt_gazemap, scores, out_dir, dump_images):
-    """evaluate_gaze.py:137-158: the per-frame dumps."""
+def _write_frame(i, n_images, image, pred_gazemap, gt_gazemap, scores, out_dir, dump_images, dump_scale='minmax',
+                 pred_bytes=None):
+    """evaluate_gaze.py:137-158: the per-frame dumps.  ``dump_scale='minmax'`` (default) scales in float64 and truncates
+    a * 255; ``'bytescale'`` writes the bytes scipy.misc.imsave encodes (models/extract_map.py: ``bytescale``, which
+    rounds).  ``pred_bytes``: the predicted map's bytes where the caller has them already (``bytescale_maps``)."""
+    if dump_scale not in DUMP_SCALES:
+        raise ValueError('dump_scale must be one of %s, got %r' % (DUMP_SCALES, dump_scale))
     if dump_images:
         try:
             from PIL import Image
 
-            def save(name, arr):
+            def save(name, arr, ready=None):
+                if dump_scale == 'bytescale':
+                    from .extract_map import bytescale
+                    u8 = np.asarray(ready, np.uint8) if ready is not None else bytescale(np.asarray(arr, np.float32))
+                    Image.fromarray(u8).save(os.path.join(out_dir, name))
+                    return
                 a = np.asarray(arr, np.float64)
                 a = (a - a.min()) / max(a.max() - a.min(), 1e-12)
                 Image.fromarray((a * 255).astype(np.uint8)).save(os.path.join(out_dir, name))
             save('%05d.frame.jpg' % i, image)
-            save('%05d.gaze_pred.jpg' % i, pred_gazemap)
+            save('%05d.gaze_pred.jpg' % i, pred_gazemap, pred_bytes)
             save('%05d.gaze_gt.jpg' % i, gt_gazemap)
         except ImportError:
             pass
@@ -42,7 +54,7 @@ def _write_frame(i, n_images, image, pred_gazemap, gt_gazemap, scores, out_dir, 
 
 
 def handle_frame(i, n_images, image, pred_gazemap, gt_gazemap, fixationmap, out_dir, fixationmaps_all, rng,
-                 dump_images=True):
+                 dump_images=True, dump_scale='minmax'):
     """evaluate_gaze.py:116-158: union of 10 random other fixation maps, 5 metrics, dumps."""
     fixationmap = _dense(fixationmap)
     other_map_union = np.zeros(fixationmap.shape, np.uint8)
@@ -56,7 +68,7 @@ def handle_frame(i, n_images, image, pred_gazemap, gt_gazemap, fixationmap, out_
         scores[metric] = saliency_score_single(metric, pred_map=pred_gazemap, gt_map=gt_gazemap,
                                                fixation_map=fixationmap, other_map_union=other_map_union)
     if out_dir is not None:
-        _write_frame(i, n_images, image, pred_gazemap, gt_gazemap, scores, out_dir, dump_images)
+        _write_frame(i, n_images, image, pred_gazemap, gt_gazemap, scores, out_dir, dump_images, dump_scale)
     return scores
 
 
@@ -89,15 +101,21 @@ def _device_frame_scores(pred, gt, fix, rng, scorer, seed):
     return emg.saliency_scores_single(pred, gt, fix, unions, FRAME_METRICS, draws=draws, seed=seed)
 
 
-def run_evaluation(model, data_sets, out_dir, num_frames=1000, seed=0, dump_images=False, scorer='host'):
+def run_evaluation(model, data_sets, out_dir, num_frames=1000, seed=0, dump_images=False, scorer='host', dump_scale='minmax'):
     """evaluate_gaze.py:172-227 -> {metric: mean}; writes <out_dir>/overall.txt in the reference's format.
 
     ``scorer``: 'host' (default) scores frame by frame with evaluation_metrics; 'device-reference' and 'device' score all
     frames in one launch on the GPU (see _device_frame_scores), the former with the host's own draws -- same numbers, same
     files -- the latter with draws made on the device from ``seed``.  Fixation maps of the maps' shape or, as in the reference's
     evaluation, of the video frame's (dense or scipy.sparse; the maps are then upsized on the device, inside the scoring
-    kernel) are both scored on the device; frames of different shapes are the host scorer's."""
+    kernel) are both scored on the device; frames of different shapes are the host scorer's.
+
+    ``dump_scale``: how the per-frame images are scaled to 8 bits (``dump_images=True``): 'minmax' (default), or
+    'bytescale', the bytes the reference's scipy.misc.imsave encodes; with the device scorers the predicted maps' bytes
+    then come from one ``extract_map.bytescale_maps`` launch for all frames."""
     assert out_dir is not None
+    if dump_scale not in DUMP_SCALES:
+        raise ValueError('dump_scale must be one of %s, got %r' % (DUMP_SCALES, dump_scale))
     if scorer not in ('host', 'device', 'device-reference'):
         raise ValueError("scorer must be 'host', 'device' or 'device-reference', got %r" % (scorer,))
     os.makedirs(out_dir, exist_ok=True)
@@ -114,16 +132,21 @@ def run_evaluation(model, data_sets, out_dir, num_frames=1000, seed=0, dump_imag
         aggregated = defaultdict(list)
         if scorer == 'host':
             for i in range(n_images):
-                scores = handle_frame(i, n_images, images[i], pred[i], gt[i], fix[i], out_dir, fix, rng, dump_images)
+                scores = handle_frame(i, n_images, images[i], pred[i], gt[i], fix[i], out_dir, fix, rng, dump_images, dump_scale)
                 for metric, score in scores.items():
                     aggregated[metric].append(score)
         else:
             per_frame = _device_frame_scores(pred, gt, fix, rng, scorer, seed)
             for metric in FRAME_METRICS:
                 aggregated[metric] = [float(v) for v in per_frame[metric]]
+            pred_bytes = None
+            if dump_images and dump_scale == 'bytescale' and n_images:
+                from .extract_map import bytescale_maps
+                pred_bytes = bytescale_maps(np.ascontiguousarray(pred, np.float32), device=model.session.device)
             for i in range(n_images):
                 scores = OrderedDict((metric, aggregated[metric][i]) for metric in FRAME_METRICS)
-                _write_frame(i, n_images, images[i], pred[i], gt[i], scores, out_dir, dump_images)
+                _write_frame(i, n_images, images[i], pred[i], gt[i], scores, out_dir, dump_images, dump_scale,
+                             None if pred_bytes is None else pred_bytes[i])
     finally:
         np.random.set_state(state)
     overall = OrderedDict()
@@ -139,14 +162,22 @@ def predict_long_clip(model, c3d, frames=None, pool_to_7x7=False, carry_state=Fa
     """extract_map.py:148-229: a clip of any length through a fixed-T model.  c3d [N,1024,7,7]
     (or [N,512,2,7,7]) is cut into T-chunks, the tail zero-padded, B chunks per call; returns
     [N,GH,GW] of the model (49x49; 7x7 for gaze_grcn77 / gaze_rnn77), or [N,7,7] with a 7x7 average re-pool of each 49x49 map
-    (a 7x7 model's maps are at that resolution already).
+    (a 7x7 model's maps are at that resolution already).  pool_to_7x7='imresize' returns instead what the reference's export
+    writes to <clip>.gazemap.npy: extract_map.avg_pool of every map (scipy's imresize to 7x7 over its sum, float64, NaN
+    where the resized bytes sum to 0), made on the device from the maps predict() left there.
     carry_state=False is the reference's evaluation: every chunk starts from the zero state (extract_map.py:65).
     carry_state=True runs the clip as ONE recurrence (stream.predict_long_clips; the conv-recurrent models only)."""
+    if isinstance(pool_to_7x7, str) and pool_to_7x7 != 'imresize':
+        raise ValueError("pool_to_7x7 must be False, True or 'imresize', got %r" % (pool_to_7x7,))
+    imresize = isinstance(pool_to_7x7, str)
     c3d = np.asarray(c3d, np.float32).reshape(len(c3d), 1024, 7, 7)
     n, T, B = len(c3d), model.n_lstm_steps, model.batch_size
     if carry_state:
         from ..stream import predict_long_clips
         maps = predict_long_clips(model, [c3d])[0]
+        if imresize:
+            from .extract_map import avg_pool
+            return avg_pool(np.ascontiguousarray(maps, np.float32), device=model.session.device)
         if pool_to_7x7 and maps.shape[-1] == 49:
             maps = maps.reshape(n, 7, 7, 7, 7).mean(axis=(2, 4))
         return maps
@@ -159,8 +190,17 @@ def predict_long_clip(model, c3d, frames=None, pool_to_7x7=False, carry_state=Fa
         batch = chunks[i:i + B]
         if len(batch) < B:
             batch = np.concatenate([batch, np.zeros((B - len(batch),) + batch.shape[1:], np.float32)])
-        maps = model.predict(batch, frames).cpu().numpy()
+        maps = model.predict(batch, frames)
+        if imresize:
+            from .extract_map import avg_pool
+            k = min(B, n_chunks - i) * T
+            pooled = avg_pool(maps.reshape((B * T,) + tuple(maps.shape[-2:]))[:k].to(torch.float32).contiguous())
+            outs.append(pooled.cpu().numpy() if torch.is_tensor(pooled) else pooled)
+            continue
+        maps = maps.cpu().numpy()
         outs.append(maps[:min(B, n_chunks - i)])
+    if imresize:
+        return np.concatenate(outs)[:n]
     maps = np.concatenate(outs).reshape(n_chunks * T, model.gazemap_height, model.gazemap_width)[:n]
     if pool_to_7x7 and maps.shape[-1] == 49:
         maps = maps.reshape(n, 7, 7, 7, 7).mean(axis=(2, 4))
