@@ -1020,6 +1020,54 @@ int rgp_mapexport(const rgp_mapexport_args* args, rgp_stream_t stream);
  * the number of refused maps in rgp_last_error() and, if refused is not NULL, in *refused. */
 int rgp_mapexport_status(const void* workspace, int* refused, rgp_stream_t stream);
 
+/* ------------------------------------------------------------------ frame overlays: spline resize, colormap, Pillow's blend
+ * n fp32 maps [n][h][w] drawn over uint8 RGB frames [n_src][H][W][3] that are in device memory, two launches, the bytes the
+ * host libraries give.  Per map i and its frame (frame_idx[i], or i when frame_idx is NULL):
+ *   resize     v[Y][X] = the fp32 value rgp_spline_resize writes (fp64 prefilter and taps, rounded once); the map as it is
+ *              where (h, w) == (H, W), as the host's resize is the identity there
+ *   bytescale  scipy's, on v at [H][W]: cmin / cmax fp32 from the data (or limits[i][0], limits[i][1]: scipy's
+ *              bytescale(data, cmin=, cmax=)); cscale = cmax - cmin, 1 if 0; scale = float32(255.0 / float64(cscale));
+ *              b = (v - cmin) * scale, an fp32 subtract and an fp32 multiply; u = uint8(trunc(clip(b, 0, 255) + 0.5f)); a NaN b
+ *              (0 * inf) gives 0.  These bytes are heat_u8.
+ *   colour     c = lut[u], lut uint8 [256][3] (matplotlib: cmap(u8, bytes=True)[..., :3])
+ *   blend      PIL.Image.blend(frame, colour, alpha) per byte: alpha == 0 the frame's byte, alpha == 1 the colour's, otherwise
+ *              uint8(trunc(float(f) + alpha * float(c - f))), one fp32 multiply and one fp32 add, not fused.
+ * RGP_OVERLAY_SHARED_LIMITS: one (cmin, cmax) for the call, the min and max over all resized maps that are not refused.
+ * The resized floats are never stored: the first launch leaves per-band min / max in the workspace, the second evaluates
+ * the spline again and renders.  Maps [a, b) of a call with limits equal maps [0, b - a) of a call on that slice.
+ *
+ * Refused on the device, counted in the status word (rgp_overlay_status), the other maps unaffected: a map that holds a
+ * NaN or an Inf, limits that are not finite or with cmax < cmin, a frame_idx entry outside [0, n_src) (checked before it
+ * addresses anything).  A refused map's frame goes to `out` unchanged (zeros for a bad frame index) and its heat_u8 is 0;
+ * under RGP_OVERLAY_SHARED_LIMITS it does not count towards the limits.
+ *
+ * The host refuses with RGP_EINVAL, naming the argument, before any device call: NULL maps, lut, frames (when out is set);
+ * maps, limits or frame_idx not 4-byte aligned; out and heat_u8 both NULL; h or w below 2, or h*w above
+ * RGP_METRICS_MAX_PIX, when a resize is needed; H*W above RGP_METRICS_SCALED_MAX_PIX; alpha outside [0, 1] or NaN; n_src
+ * below n without frame_idx; out overlapping frames; unknown flags, limits together with RGP_OVERLAY_SHARED_LIMITS.  A
+ * missing, misaligned (8 bytes) or short workspace is RGP_EWORKSPACE.  n == 0: RGP_OK, nothing is launched.  frames, out and
+ * heat_u8 need no alignment. */
+#define RGP_OVERLAY_SHARED_LIMITS 1
+
+typedef struct rgp_overlay_args {
+  const unsigned char* frames;      /* [n_src][H][W][3] */
+  const int* frame_idx;             /* [n], or NULL: map i on frame i; repeats and any order allowed */
+  const float* maps;                /* [n][h][w] */
+  const float* limits;              /* [n][2] (cmin, cmax), or NULL: from the data */
+  const unsigned char* lut;         /* [256][3] */
+  float alpha;
+  unsigned flags;
+  unsigned char* out;               /* [n][H][W][3], or NULL */
+  unsigned char* heat_u8;           /* [n][H][W], or NULL; not both */
+  int n, n_src, h, w, H, W;
+} rgp_overlay_args;
+
+size_t rgp_overlay_workspace_bytes(int n, int h, int w, int H, int W);
+int rgp_overlay(const rgp_overlay_args* args, void* workspace, size_t workspace_bytes, rgp_stream_t stream);
+/* Waits for `stream`, reads the status word of the last rgp_overlay that used `workspace`: RGP_OK, or RGP_EINVAL with the
+ * number of refused maps in rgp_last_error() and, if refused is not NULL, in *refused. */
+int rgp_overlay_status(const void* workspace, int* refused, rgp_stream_t stream);
+
 /* ------------------------------------------------------------------ action classifier on gaze-attended C3D features */
 typedef struct rgp_action rgp_action_t;
 

@@ -46,6 +46,8 @@ RGP_FRAMES_MAX_OUT, RGP_FRAMES_MAX_KSIZE, RGP_FRAMES_MAX_IN_W, RGP_FRAMES_MAX_BY
 RGP_FRAMES_LDS_BYTES, RGP_FRAMES_LDS_TARGET, RGP_FRAMES_STAGE_BYTES = 156 * 1024, 80 * 1024, 24576
 # gaze-map export (include/rgp.h): caps and the LDS a workgroup may take
 RGP_MAPEXPORT_MAX_SIDE, RGP_MAPEXPORT_MAX_KSIZE, RGP_MAPEXPORT_LDS_BYTES = 64, 512, 152 * 1024
+# frame overlays (include/rgp.h): the flag of one (cmin, cmax) for the whole call
+RGP_OVERLAY_SHARED_LIMITS = 1
 DTYPES = {'f32': RGP_F32, 'fp32': RGP_F32, 'float32': RGP_F32, 'bf16': RGP_BF16, 'bfloat16': RGP_BF16}
 
 c_void_p, c_int, c_size_t, c_char_p = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_char_p
@@ -149,6 +151,12 @@ class MapExportArgs(ctypes.Structure):
                 ('kh', c_void_p), ('bh', c_void_p), ('ksize_h', c_int), ('kv', c_void_p), ('bv', c_void_p), ('ksize_v', c_int),
                 ('pooled', c_void_p), ('pooled_u8', c_void_p), ('bytes', c_void_p), ('workspace', c_void_p),
                 ('workspace_bytes', c_size_t)]
+
+
+class OverlayArgs(ctypes.Structure):
+    _fields_ = [('frames', c_void_p), ('frame_idx', c_void_p), ('maps', c_void_p), ('limits', c_void_p), ('lut', c_void_p),
+                ('alpha', ctypes.c_float), ('flags', ctypes.c_uint), ('out', c_void_p), ('heat_u8', c_void_p), ('n', c_int),
+                ('n_src', c_int), ('h', c_int), ('w', c_int), ('H', c_int), ('W', c_int)]
 
 
 # name -> (restype, argtypes); every symbol include/rgp.h declares
@@ -303,6 +311,9 @@ SIGNATURES = {
     'rgp_mapexport_workspace_bytes': (c_size_t, []),
     'rgp_mapexport': (c_int, [ctypes.POINTER(MapExportArgs), c_void_p]),
     'rgp_mapexport_status': (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    'rgp_overlay_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'rgp_overlay': (c_int, [ctypes.POINTER(OverlayArgs), c_void_p, c_size_t, c_void_p]),
+    'rgp_overlay_status': (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
     'rgp_dropout_apply': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_float, c_void_p]),
     'rgp_fcgru_set_dropout': (c_int, [c_void_p, ctypes.c_float, c_void_p]),
     'rgp_cascade_set_dropout': (c_int, [c_void_p, ctypes.c_float, c_void_p]),

@@ -27,6 +27,7 @@
 
 #include "rgp_host.h"
 #include "philox.hip.h"
+#include "spline.hip.h"
 
 using namespace rgp;
 
@@ -42,11 +43,6 @@ constexpr int kStatusBytes = 64;
 constexpr int kResizeThreads = 256;
 enum { kDrawJudd = 0, kDrawBorji = 1, kDrawShuffled = 2 };
 
-// constants of the order-3 prefilter, made on the host in float64 (axis 0: lines of h samples, axis 1: of w)
-struct SplineConsts {
-  double z, gain, last;   // the pole sqrt(3) - 2; (1 - z)(1 - 1/z); z / (z - 1)
-  double zn[2], k0[2];    // z^n by repeated multiplication; z / (1 - z^n z^n)
-};
 
 struct ScaledParams {
   const void *pred, *gt;
@@ -127,26 +123,6 @@ __device__ __forceinline__ void draw_block(unsigned out[4], unsigned blk, unsign
   philox4x32_10(out, (unsigned)seed, (unsigned)(seed >> 32));
 }
 
-// scipy's spline_filter1d (order 3, mode 'reflect') on the n samples c[0], c[stride], ...: gain, exact causal
-// initialisation, forward and backward recursion.  tests/spline_ref.py restates this statement for statement.
-__device__ __forceinline__ void filter_line(double* c, int n, int stride, double z, double zn, double gain, double k0, double last) {
-  for (int i = 0; i < n; ++i) c[i * stride] = c[i * stride] * gain;
-  const double c0 = c[0];
-  double acc = c0 + zn * c[(n - 1) * stride];
-  double zi = z;
-  for (int i = 1; i < n; ++i) {   // scipy accumulates in c[0] itself: the last term's mirrored sample is the running value
-    const double mirrored = i == n - 1 ? acc : c[(n - 1 - i) * stride];
-    acc = acc + zi * (c[i * stride] + zn * mirrored);
-    zi = zi * z;
-  }
-  acc = acc * k0;
-  acc = acc + c0;
-  c[0] = acc;
-  for (int i = 1; i < n; ++i) c[i * stride] = c[i * stride] + z * c[(i - 1) * stride];
-  c[(n - 1) * stride] = c[(n - 1) * stride] * last;
-  for (int i = n - 2; i >= 0; --i) c[i * stride] = z * (c[(i + 1) * stride] - c[i * stride]);
-}
-
 // both passes over `n_maps` maps of h x w that lie kMaxSrc apart, by `threads` threads of the block
 __device__ __forceinline__ void prefilter(double* maps, int n_maps, int h, int w, const SplineConsts& sc, int threads) {
   for (int l = threadIdx.x; l < n_maps * w; l += threads)
@@ -155,36 +131,6 @@ __device__ __forceinline__ void prefilter(double* maps, int n_maps, int h, int w
   for (int l = threadIdx.x; l < n_maps * h; l += threads)
     filter_line(maps + (l / h) * kMaxSrc + (l % h) * w, w, 1, sc.z, sc.zn[1], sc.gain, sc.k0[1], sc.last);
   __syncthreads();
-}
-
-struct Taps {
-  double wy[4], wx[4];
-  int ry[4], cx[4];
-};
-
-__device__ __forceinline__ void load_taps(Taps& t, const double* tw, const unsigned short* ti, int H, int Y, int X) {
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    t.wy[a] = tw[Y * 4 + a];
-    t.ry[a] = ti[Y * 4 + a];
-    t.wx[a] = tw[(H + X) * 4 + a];
-    t.cx[a] = ti[(H + X) * 4 + a];
-  }
-}
-
-// the resized value: rows outer, v = wy0 s0 + wy1 s1 + wy2 s2 + wy3 s3 with s_a = wx0 c + wx1 c + wx2 c + wx3 c, left to right
-__device__ __forceinline__ double spline_at(const double* C, const Taps& t) {
-  double v = 0.0;
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    const double* r = C + t.ry[a];
-    double s = t.wx[0] * r[t.cx[0]];
-    s = s + t.wx[1] * r[t.cx[1]];
-    s = s + t.wx[2] * r[t.cx[2]];
-    s = s + t.wx[3] * r[t.cx[3]];
-    v = a == 0 ? t.wy[0] * s : v + t.wy[a] * s;
-  }
-  return v;
 }
 
 // f(pixel, row, column) for the pixels tid, tid + kThreads, ... of the target grid, no division in the loop
@@ -586,69 +532,6 @@ __global__ __launch_bounds__(kResizeThreads) void spline_resize_kernel(const Res
 }
 
 size_t draws_elems(int n_frames, int n_rep, int neg_stride) { return (size_t)n_frames * (size_t)n_rep * (size_t)neg_stride; }
-size_t tables_bytes(int H, int W) { return align_up((size_t)(H + W) * 4 * (sizeof(double) + sizeof(unsigned short)), 64); }
-
-// z^n as n - 1 multiplies: the device's and libm's pow are not numpy's, a product is the same everywhere
-double pow_by_products(double z, int n) {
-  double v = z;
-  for (int i = 1; i < n; ++i) v = v * z;
-  return v;
-}
-
-SplineConsts spline_consts(int h, int w) {
-  SplineConsts c;
-  c.z = std::sqrt(3.0) - 2.0;
-  c.gain = (1.0 - c.z) * (1.0 - 1.0 / c.z);
-  c.last = c.z / (c.z - 1.0);
-  const int n[2] = {h, w};
-  for (int a = 0; a < 2; ++a) {
-    c.zn[a] = pow_by_products(c.z, n[a]);
-    c.k0[a] = c.z / (1.0 - c.zn[a] * c.zn[a]);
-  }
-  return c;
-}
-
-// weights and reflected indices of one axis (n_in samples -> n_out), appended; the indices times `scale`
-void axis_table(int n_in, int n_out, int scale, std::vector<double>& tw, std::vector<unsigned short>& ti) {
-  for (int o = 0; o < n_out; ++o) {
-    const double x = ((double)o + 0.5) * ((double)n_in / (double)n_out) - 0.5;
-    const double f = std::floor(x), t = x - f, u = 1.0 - t;
-    tw.push_back(u * u * u / 6.0);
-    tw.push_back((t * t * (t - 2.0) * 3.0 + 4.0) / 6.0);
-    tw.push_back((u * u * (u - 2.0) * 3.0 + 4.0) / 6.0);
-    tw.push_back(t * t * t / 6.0);
-    for (int k = -1; k <= 2; ++k) {
-      long long i = (long long)f + k;
-      if (i < 0) i = -i - 1;
-      i %= 2 * (long long)n_in;
-      if (i >= n_in) i = 2 * (long long)n_in - 1 - i;
-      ti.push_back((unsigned short)(i * scale));
-    }
-  }
-}
-
-// both axes' tables into `dst` (device, tables_bytes): weights [H + W][4] fp64, then indices [H + W][4] uint16
-int upload_tables(int h, int w, int H, int W, void* dst, hipStream_t s, const double** tab_w, const unsigned short** tab_i) {
-  // kept per host thread and rebuilt only when the shapes change: an asynchronous copy out of pageable memory may still
-  // be reading them, so they are rewritten only behind a wait for the stream
-  thread_local std::vector<double> tw;
-  thread_local std::vector<unsigned short> ti;
-  thread_local int key[4] = {0, 0, 0, 0};
-  if (key[0] != h || key[1] != w || key[2] != H || key[3] != W) {
-    RGP_HIP(hipStreamSynchronize(s));
-    tw.clear(); ti.clear();
-    axis_table(h, H, w, tw, ti);
-    axis_table(w, W, 1, tw, ti);
-    key[0] = h; key[1] = w; key[2] = H; key[3] = W;
-  }
-  char* d = (char*)dst;
-  RGP_HIP(hipMemcpyAsync(d, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice, s));
-  RGP_HIP(hipMemcpyAsync(d + tw.size() * sizeof(double), ti.data(), ti.size() * sizeof(unsigned short), hipMemcpyHostToDevice, s));
-  *tab_w = (const double*)d;
-  *tab_i = (const unsigned short*)(d + tw.size() * sizeof(double));
-  return RGP_OK;
-}
-
 int check_shapes(const char* fn, int h, int w, int H, int W) {
   RGP_REQUIRE(h >= 2 && w >= 2 && (long long)h * w <= RGP_METRICS_MAX_PIX,
               "%s: source maps of %d x %d: height and width must be at least 2 and height*width at most RGP_METRICS_MAX_PIX = %d", fn, h, w,
@@ -669,10 +552,10 @@ size_t rgp_metrics_scaled_workspace_bytes(int n_frames, int n_rep, int neg_strid
   size_t b = kStatusBytes;
   if (flags & RGP_METRICS_DEVICE_DRAWS) b += (2 * e + (size_t)n_frames) * sizeof(int);
   b = align_up(b, 64) + 2 * e * sizeof(double);
-  return align_up(b, 64) + tables_bytes(height, width);
+  return align_up(b, 64) + spline_tables_bytes(height, width);
 }
 
-size_t rgp_spline_resize_workspace_bytes(int H, int W) { return H <= 0 || W <= 0 ? 0 : tables_bytes(H, W); }
+size_t rgp_spline_resize_workspace_bytes(int H, int W) { return H <= 0 || W <= 0 ? 0 : spline_tables_bytes(H, W); }
 
 int rgp_saliency_scores_scaled(const rgp_metrics_scaled_args* a, rgp_stream_t stream) {
   const char* fn = "rgp_saliency_scores_scaled";

@@ -101,7 +101,22 @@ def _device_frame_scores(pred, gt, fix, rng, scorer, seed):
     return emg.saliency_scores_single(pred, gt, fix, unions, FRAME_METRICS, draws=draws, seed=seed)
 
 
-def run_evaluation(model, data_sets, out_dir, num_frames=1000, seed=0, dump_images=False, scorer='host', dump_scale='minmax'):
+def _write_overlays(images, pred, gt, out_dir, device, alpha=0.4, colormap='jet'):
+    """%05d.overlay_pred.jpg and %05d.overlay_gt.jpg: every frame's maps drawn over it (overlay.overlay_maps, one call for
+    all predictions and one for all ground-truth maps).  The loader's float images go back to bytes with rint(img * 255)."""
+    from PIL import Image
+    from ..overlay import overlay_maps
+    frames = np.stack([np.asarray(im) for im in images])
+    if frames.dtype != np.uint8:
+        frames = np.rint(frames.astype(np.float32) * np.float32(255.0)).clip(0, 255).astype(np.uint8)
+    for name, maps in (('overlay_pred', pred), ('overlay_gt', gt)):
+        drawn = overlay_maps(frames, np.ascontiguousarray(maps, np.float32), alpha=alpha, colormap=colormap, device=device).cpu().numpy()
+        for i in range(len(drawn)):
+            Image.fromarray(drawn[i]).save(os.path.join(out_dir, '%05d.%s.jpg' % (i, name)))
+
+
+def run_evaluation(model, data_sets, out_dir, num_frames=1000, seed=0, dump_images=False, scorer='host', dump_scale='minmax',
+                   dump_overlays=False):
     """evaluate_gaze.py:172-227 -> {metric: mean}; writes <out_dir>/overall.txt in the reference's format.
 
     ``scorer``: 'host' (default) scores frame by frame with evaluation_metrics; 'device-reference' and 'device' score all
@@ -112,7 +127,10 @@ def run_evaluation(model, data_sets, out_dir, num_frames=1000, seed=0, dump_imag
 
     ``dump_scale``: how the per-frame images are scaled to 8 bits (``dump_images=True``): 'minmax' (default), or
     'bytescale', the bytes the reference's scipy.misc.imsave encodes; with the device scorers the predicted maps' bytes
-    then come from one ``extract_map.bytescale_maps`` launch for all frames."""
+    then come from one ``extract_map.bytescale_maps`` launch for all frames.
+
+    ``dump_overlays=True`` also writes ``%05d.overlay_pred.jpg`` and ``%05d.overlay_gt.jpg`` beside the dumps: the maps drawn
+    over their frames on the device (overlay.overlay_maps; jet, alpha 0.4).  The default writes exactly the files above."""
     assert out_dir is not None
     if dump_scale not in DUMP_SCALES:
         raise ValueError('dump_scale must be one of %s, got %r' % (DUMP_SCALES, dump_scale))
@@ -149,6 +167,8 @@ def run_evaluation(model, data_sets, out_dir, num_frames=1000, seed=0, dump_imag
                              None if pred_bytes is None else pred_bytes[i])
     finally:
         np.random.set_state(state)
+    if dump_overlays and n_images:
+        _write_overlays(images, pred, gt, out_dir, model.session.device)
     overall = OrderedDict()
     with open(os.path.join(out_dir, 'overall.txt'), 'w') as fp:
         for metric, score_list in aggregated.items():
