@@ -519,6 +519,11 @@ int rgp_shallownet_forward(rgp_shallownet_t* plan, const float* frames, int n_fr
 int rgp_shallownet_create_ex(rgp_shallownet_t** plan, int max_frames, int image_hw, int dtype, int save_for_backward);
 int rgp_shallownet_backward(rgp_shallownet_t* plan, int n_frames, const float* d_saliency, const rgp_shallownet_weights* grads,
                             rgp_stream_t stream);
+/* Training-time dropout on fc1's ReLU output, before the maxout (saliency_shallownet.py:152-158; SaliencyModel feeds
+ * keep 0.4 when training, :330).  mask: device bytes [n_frames, 4802] in the layer's own unit order (unit j and j + 2401
+ * are maxout partners), the caller's; keep_prob in (0, 1]; keep_prob = 1 or NULL = off, and the plan then launches
+ * exactly what it launches without the site.  The backward gates with the same draw and 1 / keep_prob. */
+int rgp_shallownet_set_dropout(rgp_shallownet_t* plan, float keep_prob, const unsigned char* mask);
 
 /* ------------------------------------------------------------------ two-level cascade (config 5) */
 typedef struct rgp_cascade rgp_cascade_t;
@@ -1127,6 +1132,52 @@ int rgp_action_fc1_update(rgp_action_t* plan, const float* c3d, const float* gaz
  * buffer_elems: the element count, 0 = this plan has no such buffer. */
 int rgp_action_read_buffer(rgp_action_t* plan, const char* name, float* dst, rgp_stream_t stream);
 size_t rgp_action_buffer_elems(const rgp_action_t* plan, const char* name);
+
+/* ------------------------------------------------------------------ ShallowNet pre-training on SALICON (SaliencyModel)
+ * The step of models/saliency_shallownet.py:246-250, :291-332 around rgp_shallownet_forward / _backward.
+ *
+ * rgp_salicon_batch: the batch of :297-311 from an image set RESIDENT on the device, in ONE launch.  images_u8
+ * [n][h][w][3] and maps_u8 [n][49][49] are the decoded set (salicon_input_data.py:95-111); output sample s is image
+ * index[s]: images[s] = (float)u8 * 0.003921569f (the loader's np.multiply(x.astype(float32), 1.0 / 255.0), the constant of
+ * rgp_frame_images), maps[s] the same.  flip (device, [batch], NULL = none): a non-zero byte mirrors image AND map of
+ * that sample along the width axis (:310-311; pixels keep their RGB order).  An index entry outside [0, n) refuses that
+ * sample on the device: NaN in both of its outputs, counted in the status word (rgp_salicon_status), never used as an
+ * address, the other samples unaffected.  Element offsets are 64-bit.
+ * Limits (RGP_EINVAL naming the argument, before any device call): h == w, 98 or 112; map_h == map_w == 49; batch >= 0;
+ * n > 0; a NULL array other than flip; outputs 4-byte aligned.  batch == 0: RGP_OK, nothing is launched.
+ * workspace (device, 8-byte aligned, rgp_salicon_workspace_bytes()): the status word, cleared on the stream before the
+ * launch. */
+typedef struct rgp_salicon_batch_args {
+  const unsigned char* images_u8;   /* [n][h][w][3] */
+  const unsigned char* maps_u8;     /* [n][map_h][map_w] */
+  int n, h, w, map_h, map_w;
+  const int* index;                 /* [batch], device */
+  const unsigned char* flip;        /* [batch], device, or NULL */
+  int batch;
+  float* images;                    /* [batch][h][w][3] */
+  float* maps;                      /* [batch][map_h][map_w] */
+  void* workspace;
+  size_t workspace_bytes;
+} rgp_salicon_batch_args;
+
+size_t rgp_salicon_workspace_bytes(void);
+int rgp_salicon_batch(const rgp_salicon_batch_args* args, rgp_stream_t stream);
+/* Waits for `stream`, reads the status word of the last rgp_salicon_batch that used `workspace`: RGP_OK, or RGP_EINVAL
+ * with the number of refused samples in rgp_last_error() and, if refused is not NULL, in *refused. */
+int rgp_salicon_status(const void* workspace, int* refused, rgp_stream_t stream);
+
+/* The target loss of :248-249 and its gradient in one pass: loss[0] = scale / 2 * sum (maps - labels)^2 over n elements,
+ * d_maps[i] = (maps[i] - labels[i]) * scale (one fp32 subtract, one fp32 multiply).  scale = 2 / (2401 * config.batch_size),
+ * computed by the host in double: the reference divides by the CONFIGURED batch size whatever the number of frames fed.
+ * workspace: RGP_SQNORM_PARTIALS floats (deterministic two-stage sum). */
+int rgp_euclid_loss_fwd_bwd(const float* maps, const float* labels, long long n, float scale, float* workspace, float* loss,
+                            float* d_maps, rgp_stream_t stream);
+
+/* The regulariser of :247 over a flat parameter buffer and its gradient buffer (every variable, biases included):
+ * reg_loss[0] = coeff * sum w^2 / 2 (deterministic two-stage sum), grads[i] += coeff * params[i].  Runs after the backward and
+ * before the clip: the reference clips the gradient of the total loss.  grads == NULL: the value alone (a validation step).
+ * workspace: RGP_SQNORM_PARTIALS floats. */
+int rgp_l2_reg(const float* params, float* grads, long long n, float coeff, float* workspace, float* reg_loss, rgp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -159,6 +159,12 @@ class OverlayArgs(ctypes.Structure):
                 ('n_src', c_int), ('h', c_int), ('w', c_int), ('H', c_int), ('W', c_int)]
 
 
+class SaliconBatchArgs(ctypes.Structure):
+    _fields_ = [('images_u8', c_void_p), ('maps_u8', c_void_p), ('n', c_int), ('h', c_int), ('w', c_int), ('map_h', c_int),
+                ('map_w', c_int), ('index', c_void_p), ('flip', c_void_p), ('batch', c_int), ('images', c_void_p),
+                ('maps', c_void_p), ('workspace', c_void_p), ('workspace_bytes', c_size_t)]
+
+
 # name -> (restype, argtypes); every symbol include/rgp.h declares
 SIGNATURES = {
     'rgp_last_error': (c_char_p, []),
@@ -341,6 +347,13 @@ SIGNATURES = {
     'rgp_action_fc1_update': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p]),
     'rgp_action_read_buffer': (c_int, [c_void_p, c_char_p, c_void_p, c_void_p]),
     'rgp_action_buffer_elems': (c_size_t, [c_void_p, c_char_p]),
+    'rgp_shallownet_set_dropout': (c_int, [c_void_p, ctypes.c_float, c_void_p]),
+    'rgp_salicon_workspace_bytes': (c_size_t, []),
+    'rgp_salicon_batch': (c_int, [ctypes.POINTER(SaliconBatchArgs), c_void_p]),
+    'rgp_salicon_status': (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    'rgp_euclid_loss_fwd_bwd': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_float, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
+    'rgp_l2_reg': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_float, c_void_p, c_void_p, c_void_p]),
 }
 GRCN_STAGES = ('proj', 'xconv', 'convgru_seq', 'head', 'softmax')
 C3D_STAGES = ('conv1a', 'conv2a', 'conv3a', 'conv3b', 'conv4a', 'conv4b', 'conv5a', 'conv5b', 'video_prep')

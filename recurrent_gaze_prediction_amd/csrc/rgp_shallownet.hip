@@ -37,6 +37,9 @@ struct rgp_shallownet {
   size_t dy3 = 0, dy2 = 0;                         // T [n][(c+4)^2][C]: gradient w.r.t. the conv outputs, halo 2
   size_t dy1 = 0;                                  // T [128 zeros][n][c1*c1][32]
   size_t dw1 = 0;                                  // fp32 conv1 filter gradient in its packed K order
+  // tf.nn.dropout on relu(fc1) before the maxout (saliency_shallownet.py:152-158): the caller's keep bytes [n][4802], null = off
+  const unsigned char* drop_mask = nullptr;
+  float drop_keep = 1.0f;
 };
 
 namespace {
@@ -134,6 +137,7 @@ int forward_impl(rgp_shallownet* g, const float* frames, int n, float* sal, floa
     EpiParams e = make_epi(g->fc1, ws + g->mo1, ws);
     e.bias = (const float*)(ws + g->b1i);
     if (g->save) e.argmax = (unsigned char*)(ws + g->mask1);
+    if (g->drop_mask && g->drop_keep < 1.0f) { e.drop_mask = g->drop_mask; e.drop_inv_keep = 1.0f / g->drop_keep; }
     RGP_TRY((launch_igemm<T, 1, 1, EpiReluMaxout<T>>(p, e, s)));
   }
   {
@@ -354,7 +358,9 @@ int backward_impl(rgp_shallownet* g, int n, const float* d_sal, const rgp_shallo
     EpiParams e = make_epi(g->b_fc2, Fp(g->dmo1), ws);
     RGP_TRY((launch_igemm<T, 1, 1, EpiStore<float, false, false>>(p, e, s)));
   }
-  maxout_bwd_kernel<T><<<nblk((long long)n * 2401), 256, 0, s>>>(Fp(g->dmo1), g->K2, nullptr, 1.0f, (const unsigned char*)(ws + g->mask1),
+  // a dropped unit never wins the maxout (mask1 is taken after the dropout), so the keep bytes gate through mask1 and
+  // only the 1 / keep of the kept ones is left to apply; the site off: keep = 1
+  maxout_bwd_kernel<T><<<nblk((long long)n * 2401), 256, 0, s>>>(Fp(g->dmo1), g->K2, nullptr, 1.0f / g->drop_keep, (const unsigned char*)(ws + g->mask1),
                                                                  Tp(g->dz1), (long long)n * 2401);
   RGP_TRY(g->side.fork(s, 1, &sw));
   fc_bias_grad_kernel<T><<<(4802 + 31) / 32, 256, 0, sw>>>(Tp(g->dz1), n, (float*)gr->fc1_b);
@@ -556,6 +562,14 @@ int rgp_shallownet_forward(rgp_shallownet_t* g, const float* frames, int n_frame
   hipStream_t s = (hipStream_t)stream;
   return g->dtype == RGP_BF16 ? forward_impl<bf16_t>(g, frames, n_frames, saliency, saliency7, s)
                               : forward_impl<float>(g, frames, n_frames, saliency, saliency7, s);
+}
+
+int rgp_shallownet_set_dropout(rgp_shallownet_t* g, float keep_prob, const unsigned char* mask) {
+  RGP_REQUIRE(g, "rgp_shallownet_set_dropout: null plan");
+  RGP_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f, "rgp_shallownet_set_dropout: keep_prob %g not in (0, 1]", (double)keep_prob);
+  g->drop_mask = keep_prob < 1.f ? mask : nullptr;
+  g->drop_keep = g->drop_mask ? keep_prob : 1.0f;
+  return RGP_OK;
 }
 
 }  // extern "C"

@@ -123,6 +123,87 @@ def l2_loss(maps, labels, frames):
     return loss
 
 
+def euclid_loss_fwd_bwd(maps, labels, batch_size, d_maps=None):
+    """Target loss of saliency_shallownet.py:248-249 and its gradient in one pass (rgp_euclid_loss_fwd_bwd):
+    2 l2_loss(maps - labels) / 2401 / batch_size with the CONFIGURED batch size, whatever the number of frames.
+    -> (1-element device tensor, d_maps shaped like maps)."""
+    lib = _lib.load()
+    assert maps.is_cuda and maps.dtype == torch.float32 and maps.is_contiguous()
+    assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous() and labels.numel() == maps.numel()
+    if d_maps is None:
+        d_maps = torch.empty_like(maps)
+    assert d_maps.is_cuda and d_maps.dtype == torch.float32 and d_maps.is_contiguous() and d_maps.numel() == maps.numel()
+    ws = torch.empty(_lib.RGP_SQNORM_PARTIALS, dtype=torch.float32, device=maps.device)
+    loss = torch.empty(1, dtype=torch.float32, device=maps.device)
+    scale = 2.0 / (2401.0 * int(batch_size))
+    with torch.cuda.device(maps.device):
+        _lib.check(lib.rgp_euclid_loss_fwd_bwd(_ptr(maps), _ptr(labels), maps.numel(), scale, _ptr(ws), _ptr(loss),
+                                               _ptr(d_maps), _stream_ptr(maps.device)))
+    return loss, d_maps
+
+
+def l2_reg(params, grads, coeff):
+    """coeff * sum of tf.nn.l2_loss over a flat parameter buffer (saliency_shallownet.py:247); grads += coeff * params
+    in place (rgp_l2_reg); grads None: the value alone.  -> 1-element device tensor with the regulariser's value."""
+    lib = _lib.load()
+    for t in (params, grads):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous())
+    assert grads is None or params.numel() == grads.numel()
+    ws = torch.empty(_lib.RGP_SQNORM_PARTIALS, dtype=torch.float32, device=params.device)
+    reg = torch.empty(1, dtype=torch.float32, device=params.device)
+    with torch.cuda.device(params.device):
+        _lib.check(lib.rgp_l2_reg(_ptr(params), _ptr(grads), params.numel(), float(coeff), _ptr(ws), _ptr(reg),
+                                  _stream_ptr(params.device)))
+    return reg
+
+
+class SaliconBatcher(object):
+    """Owner of the status word of rgp_salicon_batch for one resident image set: images_u8 [N,H,W,3] and maps_u8
+    [N,49,49] uint8 device tensors -> batches gathered, mirrored and scaled by 1 / 255 in one launch."""
+
+    def __init__(self, images_u8, maps_u8):
+        self.lib = _lib.load()
+        for t in (images_u8, maps_u8):
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+        assert images_u8.dim() == 4 and images_u8.shape[3] == 3 and maps_u8.dim() == 3 and len(maps_u8) == len(images_u8)
+        self.images_u8, self.maps_u8, self.device = images_u8, maps_u8, images_u8.device
+        self.workspace = torch.zeros(self.lib.rgp_salicon_workspace_bytes(), dtype=torch.uint8, device=self.device)
+
+    def batch(self, index, flip=None, check=True):
+        """index: [B] int32 device tensor (or anything torch.as_tensor takes); flip: [B] uint8 / bool or None.
+        -> (images [B,H,W,3], maps [B,49,49]) fp32 device tensors.  check: wait for the launch and raise if an index
+        was refused (RgpError, code RGP_EINVAL); a caller that knows its indices skips the wait."""
+        dev = self.device
+        index = torch.as_tensor(index).to(dev, torch.int32).contiguous()
+        B = index.numel()
+        if flip is not None:
+            flip = torch.as_tensor(np.asarray(flip).astype(np.uint8) if not torch.is_tensor(flip) else flip)
+            flip = flip.to(dev, torch.uint8).contiguous()
+            assert flip.numel() == B
+        N, H, W = self.images_u8.shape[:3]
+        images = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev)
+        maps = torch.empty((B,) + tuple(self.maps_u8.shape[1:]), dtype=torch.float32, device=dev)
+        a = _lib.SaliconBatchArgs(images_u8=self.images_u8.data_ptr(), maps_u8=self.maps_u8.data_ptr(), n=N, h=H, w=W,
+                                  map_h=self.maps_u8.shape[1], map_w=self.maps_u8.shape[2],
+                                  index=index.data_ptr() if B else self.workspace.data_ptr(),     # empty tensors have no address
+                                  flip=flip.data_ptr() if flip is not None and B else None, batch=B,
+                                  images=images.data_ptr() if B else self.workspace.data_ptr(),
+                                  maps=maps.data_ptr() if B else self.workspace.data_ptr(),
+                                  workspace=self.workspace.data_ptr(), workspace_bytes=self.workspace.numel())
+        with torch.cuda.device(dev):
+            _lib.check(self.lib.rgp_salicon_batch(ctypes.byref(a), _stream_ptr(dev)))
+            if check and B:
+                self.status()
+        return images, maps
+
+    def status(self):
+        """Waits for the stream; raises RgpError if the last batch refused a sample, returns 0 otherwise."""
+        refused = ctypes.c_int(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_salicon_status(_ptr(self.workspace), ctypes.byref(refused), _stream_ptr(self.device)))
+        return refused.value
+
+
 class DropoutSite(object):
     """Keep-mask owner of one tf.nn.dropout site: draws a fresh Philox mask per training step on the device
     (rgp_dropout_mask), or takes the caller's bytes (parity tests feed the oracle the same mask)."""
@@ -690,7 +771,7 @@ class FcGruEngine(object):
 class ShallowNetEngine(object):
     """Frame-wise ShallowNet (models/saliency_shallownet.py:74-216, BASELINE config 1)."""
 
-    def __init__(self, max_frames, image_hw=98, dtype='f32', device='cuda:0', save_for_backward=False):
+    def __init__(self, max_frames, image_hw=98, dtype='f32', device='cuda:0', save_for_backward=False, dropout=False):
         self.lib = _lib.load()
         self.device = _require_gpu(device)
         self.max_frames, self.image_hw, self.dtype = int(max_frames), int(image_hw), dtype
@@ -705,6 +786,10 @@ class ShallowNetEngine(object):
             _lib.check(self.lib.rgp_shallownet_bind_workspace(self._h, _ptr(self.workspace), nbytes,
                                                               _stream_ptr(self.device)))
         self.weights = None
+        # tf.nn.dropout on relu(fc1) [n, 4802] before the maxout (saliency_shallownet.py:152-158): only SaliencyModel has
+        # the site; the gaze models build the net with dropout off, and their checkpoints hold no site for it
+        self.dropout = DropoutSite(self.lib, self.device, self.max_frames * 4802,
+                                   lambda keep, mask: self.lib.rgp_shallownet_set_dropout(self._h, keep, mask)) if dropout else None
 
     def __del__(self):
         h, self._h = getattr(self, '_h', None), None
@@ -746,11 +831,21 @@ class ShallowNetEngine(object):
     def adam_step(self, step, lr, max_grad_norm=10.0, method='adam'):
         return clip_step_multi([self], step, lr, max_grad_norm, method)
 
-    def forward(self, frames, want_7x7=False):
-        """frames [n,H,W,3] fp32 device tensor -> (saliency [n,49,49], saliency7 [n,7,7] or None)."""
+    def forward(self, frames, want_7x7=False, train=False):
+        """frames [n,H,W,3] fp32 device tensor -> (saliency [n,49,49], saliency7 [n,7,7] or None).
+        train (engines created with dropout=True): True = draw a dropout mask (if configured), 'keep' = leave the mask
+        dropout.use() installed (row f of its [max_frames, 4802] bytes belongs to frame f), False = site off."""
         assert frames.is_cuda and frames.dtype == torch.float32 and frames.is_contiguous()
         n = frames.shape[0]
         assert tuple(frames.shape[1:]) == (self.image_hw, self.image_hw, 3) and n <= self.max_frames
+        if self.dropout is None:
+            assert not train, 'create the engine with dropout=True'
+        elif train == 'keep':
+            pass
+        elif train:
+            self.dropout.draw()
+        else:
+            self.dropout.off()
         sal = torch.empty(n, 49, 49, device=self.device)
         sal7 = torch.empty(n, 7, 7, device=self.device) if want_7x7 else None
         with torch.cuda.device(self.device):

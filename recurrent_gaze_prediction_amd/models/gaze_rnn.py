@@ -154,10 +154,19 @@ class GazePredictionGRU(ModelBase):
 
     def initialize_pretrained_shallownet(self, checkpoint_path):
         """gaze_rnn.py:412-433: copy the ``ShallowNet/*`` variables of a separately trained checkpoint into this
-        model (optimizer slots and tflearn's is_training flags skipped).  checkpoint_path: an exported ``.npz`` of
-        {TF variable name: array} (checkpoint.load_tf_export)."""
+        model (optimizer slots and tflearn's is_training flags skipped).  checkpoint_path: a checkpoint SaliencyModel
+        saved (``.pt``, models/saliency_shallownet.py: its ten variables are taken, its optimizer slots, step and
+        dropout state are not), or an exported ``.npz`` of {TF variable name: array} (checkpoint.load_tf_export)."""
         from .. import checkpoint
-        shallow = checkpoint.import_shallownet_variables(checkpoint.load_tf_export(checkpoint_path))
+        if str(checkpoint_path).endswith('.pt'):
+            from .._lib import ShallowNetWeights
+            saved = torch.load(checkpoint_path, map_location='cpu', weights_only=False)['variables']
+            missing = [k for k in ShallowNetWeights.FIELDS if k not in saved]
+            if missing:
+                raise KeyError('%s holds no ShallowNet variable(s) %s' % (checkpoint_path, missing))
+            shallow = {k: np.asarray(saved[k], np.float32) for k in ShallowNetWeights.FIELDS}
+        else:
+            shallow = checkpoint.import_shallownet_variables(checkpoint.load_tf_export(checkpoint_path))
         state = self.state_dict()
         if any(k.startswith('ShallowNet/') for k in state):          # cascade: nested sub-network
             state.update({'ShallowNet/' + k: v for k, v in shallow.items()})
