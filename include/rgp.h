@@ -524,6 +524,22 @@ int rgp_shallownet_backward(rgp_shallownet_t* plan, int n_frames, const float* d
  * are maxout partners), the caller's; keep_prob in (0, 1]; keep_prob = 1 or NULL = off, and the plan then launches
  * exactly what it launches without the site.  The backward gates with the same draw and 1 / keep_prob. */
 int rgp_shallownet_set_dropout(rgp_shallownet_t* plan, float keep_prob, const unsigned char* mask);
+/* fp32 copies of the plan's intermediates for the n frames of the last forward, un-padded, in the reference's layouts
+ * (c1 = H - 4, p1 = c1 / 2, c2 = p1 - 2, p2 = ceil(c2 / 2), c3 = p2 - 2, p3 = ceil(c3 / 2), n_flat = p3 p3 32):
+ *   after a forward     "frames4" [n,H,H,3] (the frames in the operand dtype), "pool1" [n,p1,p1,32], "act2" [n,c2,c2,64],
+ *                       "pool2" [n,p2,p2,64], "act3" [n,c3,c3,32], "pool3" [n,n_flat], "mo1" [n,2401] (fc1 after its maxout);
+ *   training plans      "amax1" [n,p1,p1,32] (member 2 dy + dx of conv1's 2x2 window that held the first maximum),
+ *                       "amax2" [n,p2,p2,64], "amax3" [n,p3,p3,32] (place 3 a + b of the first maximum in the 3x3 window,
+ *                       counted from the window's corner, padding cells included), "mask1", "mask2" [n,2401] (maxout: 1 =
+ *                       unit j, 2 = unit j + 2401, 0 = both ReLU-gated): the codes as floats;
+ *   after a backward    "dz2", "dz1" [n,4802] (gradients of the FC pre-activations, natural unit order), "dmo1" [n,2401],
+ *                       "dpool3" [n,n_flat], "dy3" [n,c3,c3,32], "dpool2" [n,p2,p2,64], "dy2" [n,c2,c2,64], "dpool1"
+ *                       [n,p1,p1,32], "dy1" [n,c1,c1,32] (dy: gradients of the conv pre-activations).
+ * RGP_EINVAL for an unknown name; RGP_ESTATE before the first forward, for a training-plan buffer of an inference plan and
+ * for a gradient buffer when no backward has run since the last forward.  buffer_elems: the element count for the frames
+ * of the last forward (max_frames before the first), 0 = this plan has no such buffer. */
+int rgp_shallownet_read_buffer(rgp_shallownet_t* plan, const char* name, float* dst, rgp_stream_t stream);
+size_t rgp_shallownet_buffer_elems(const rgp_shallownet_t* plan, const char* name);
 
 /* ------------------------------------------------------------------ two-level cascade (config 5) */
 typedef struct rgp_cascade rgp_cascade_t;

@@ -348,6 +348,8 @@ SIGNATURES = {
     'rgp_action_read_buffer': (c_int, [c_void_p, c_char_p, c_void_p, c_void_p]),
     'rgp_action_buffer_elems': (c_size_t, [c_void_p, c_char_p]),
     'rgp_shallownet_set_dropout': (c_int, [c_void_p, ctypes.c_float, c_void_p]),
+    'rgp_shallownet_read_buffer': (c_int, [c_void_p, c_char_p, c_void_p, c_void_p]),
+    'rgp_shallownet_buffer_elems': (c_size_t, [c_void_p, c_char_p]),
     'rgp_salicon_workspace_bytes': (c_size_t, []),
     'rgp_salicon_batch': (c_int, [ctypes.POINTER(SaliconBatchArgs), c_void_p]),
     'rgp_salicon_status': (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),

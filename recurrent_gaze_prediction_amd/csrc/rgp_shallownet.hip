@@ -29,6 +29,7 @@ struct rgp_shallownet {
   // ---- training ----
   bool save = false;
   int last_n = 0;
+  bool bwd_done = false;     // a backward has run on the frames of the last forward (rgp_shallownet_read_buffer's gradient names)
   size_t amax1 = 0, mask1 = 0, mask2 = 0;         // conv1 pool arg-max [n][p1*p1][32]; maxout masks [n][2401]
   size_t amax2 = 0, amax3 = 0;                    // pool2 / pool3 first-maximum places [n][p2*p2][64], [n][p3*p3][32]
   ConvDesc b_fc2, b_fc1, b_c3, b_c2;               // input-gradient GEMMs / "full" correlations with the rotated filters
@@ -99,6 +100,7 @@ int forward_impl(rgp_shallownet* g, const float* frames, int n, float* sal, floa
   constexpr int G32 = sizeof(T) == 2 ? 2 : 1;     // 32-element taps: two per 128-byte chunk in bf16
   const long long npix = (long long)n * g->IH * g->IH;
   g->last_n = n;
+  g->bwd_done = false;
   frame_prep_kernel<T><<<(int)std::min<long long>((npix + 255) / 256, 8192), 256, 0, s>>>(frames, (T*)(ws + g->frames4), npix);
   RGP_HIP(hipGetLastError());
   // bf16, 112 / 98 pixel frames, enough frames to give the CUs a workgroup each: the frame kernel (shallow_conv1.hip.h);
@@ -440,6 +442,84 @@ int backward_impl(rgp_shallownet* g, int n, const float* d_sal, const rgp_shallo
   return RGP_OK;
 }
 
+// ---------------------------------------------------------------- read-back (rgp_shallownet_read_buffer)
+// One plan buffer as the reference lays it out: [frame][H][W][C], un-padded.  Element (f, y, x, c) sits at
+// org + f * img_stride + y * row_stride + x * px_stride + c of a buffer of `kind` elements.
+enum ViewKind { kViewT, kViewF32, kViewU8 };
+enum ViewWhen { kViewAlways, kViewTraining, kViewAfterBackward };
+struct BufView {
+  size_t off = 0;                   // bytes into the workspace
+  ViewKind kind = kViewT;
+  ViewWhen when = kViewAlways;
+  long long org = 0, img_stride = 0;
+  int row_stride = 0, px_stride = 0, H = 1, W = 1, C = 0;
+  long long per_frame() const { return (long long)H * W * C; }
+};
+
+bool find_view(const rgp_shallownet* g, const char* name, BufView& v) {
+  const std::string n(name);
+  auto dense = [&](size_t off, ViewKind kind, ViewWhen when, int H, int C) {       // [n][H][H][C], no padding
+    v.off = off; v.kind = kind; v.when = when; v.H = v.W = H; v.C = C;
+    v.px_stride = C; v.row_stride = H * C; v.img_stride = (long long)H * H * C; v.org = 0;
+  };
+  auto rows = [&](size_t off, ViewKind kind, ViewWhen when, int C, long long ld, long long org) {   // [n][C], row stride ld
+    v.off = off; v.kind = kind; v.when = when; v.H = v.W = 1; v.C = C;
+    v.px_stride = v.row_stride = 0; v.img_stride = ld; v.org = org;
+  };
+  auto halo2 = [&](size_t off, int H, int C) {                                     // [n][H+4][H+4][C], halo of 2 stripped
+    const int Wp = H + 4;
+    dense(off, kViewT, kViewAfterBackward, H, C);
+    v.row_stride = Wp * C; v.img_stride = (long long)Wp * Wp * C; v.org = (long long)(2 * Wp + 2) * C;
+  };
+  if (n == "frames4") { dense(g->frames4, kViewT, kViewAlways, g->IH, 3); v.px_stride = 4; v.row_stride = g->IH * 4; v.img_stride = (long long)g->IH * g->IH * 4; }
+  else if (n == "pool1") dense(g->pool1, kViewT, kViewAlways, g->p1, 32);
+  else if (n == "act2") dense(g->act2, kViewT, kViewAlways, g->c2, 64);
+  else if (n == "pool2") dense(g->pool2, kViewT, kViewAlways, g->p2, 64);
+  else if (n == "act3") dense(g->act3, kViewT, kViewAlways, g->c3, 32);
+  else if (n == "pool3") rows(g->pool3, kViewT, kViewAlways, g->nflat, g->Kf, 0);
+  else if (n == "mo1") rows(g->mo1, kViewT, kViewAlways, 2401, g->K2, 0);
+  else if (n == "amax1") dense(g->amax1, kViewU8, kViewTraining, g->p1, 32);
+  else if (n == "amax2") dense(g->amax2, kViewU8, kViewTraining, g->p2, 64);
+  else if (n == "amax3") dense(g->amax3, kViewU8, kViewTraining, g->p3, 32);
+  else if (n == "mask1") rows(g->mask1, kViewU8, kViewTraining, 2401, 2401, 0);
+  else if (n == "mask2") rows(g->mask2, kViewU8, kViewTraining, 2401, 2401, 0);
+  else if (n == "dz2") rows(g->dz2, kViewT, kViewAfterBackward, 4802, kFcN2, kFcN2);          // row 0 is the zero row
+  else if (n == "dz1") rows(g->dz1, kViewT, kViewAfterBackward, 4802, kFcN2, kFcN2);
+  else if (n == "dmo1") rows(g->dmo1, kViewF32, kViewAfterBackward, 2401, g->K2, 0);
+  else if (n == "dpool3") rows(g->dpool3, kViewF32, kViewAfterBackward, g->nflat, g->Kf, 0);
+  else if (n == "dy3") halo2(g->dy3, g->c3, 32);
+  else if (n == "dy2") halo2(g->dy2, g->c2, 64);
+  else if (n == "dpool2") dense(g->dpool2, kViewF32, kViewAfterBackward, g->p2, 64);
+  else if (n == "dpool1") dense(g->dpool1, kViewF32, kViewAfterBackward, g->p1, 32);
+  else if (n == "dy1") { dense(g->dy1, kViewT, kViewAfterBackward, g->c1, 32); v.org = 128; }  // 128 leading zeros
+  else return false;
+  return true;
+}
+
+__device__ __forceinline__ float view_elem(const float* p) { return *p; }
+__device__ __forceinline__ float view_elem(const bf16_t* p) { return bf2f(*p); }
+__device__ __forceinline__ float view_elem(const unsigned char* p) { return (float)*p; }
+
+template <typename S>
+__global__ __launch_bounds__(256) void read_view_kernel(const S* __restrict__ src, float* __restrict__ dst, long long img_stride,
+                                                        int row_stride, int px_stride, int W, int C, long long per_frame, long long total) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long f = i / per_frame;
+    const int r = (int)(i - f * per_frame);
+    const int c = r % C, x = (r / C) % W, y = r / (C * W);
+    dst[i] = view_elem(src + f * img_stride + (long long)y * row_stride + (long long)x * px_stride + c);
+  }
+}
+
+template <typename S>
+int read_view(const rgp_shallownet* g, const BufView& v, float* dst, hipStream_t s) {
+  const long long total = (long long)g->last_n * v.per_frame();
+  read_view_kernel<S><<<(int)std::min<long long>((total + 255) / 256, 8192), 256, 0, s>>>((const S*)(g->ws + v.off) + v.org, dst, v.img_stride, v.row_stride,
+                                                                                         v.px_stride, v.W, v.C, v.per_frame(), total);
+  RGP_HIP(hipGetLastError());
+  return RGP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -455,8 +535,10 @@ int rgp_shallownet_backward(rgp_shallownet_t* g, int n_frames, const float* d_sa
   for (size_t i = 0; i < sizeof(rgp_shallownet_weights) / sizeof(float*); ++i)
     RGP_REQUIRE(ptrs[i], "rgp_shallownet_backward: gradient pointer %zu is null", i);
   hipStream_t s = (hipStream_t)stream;
-  return g->dtype == RGP_BF16 ? backward_impl<bf16_t>(g, n_frames, d_saliency, grads, s)
-                              : backward_impl<float>(g, n_frames, d_saliency, grads, s);
+  RGP_TRY(g->dtype == RGP_BF16 ? backward_impl<bf16_t>(g, n_frames, d_saliency, grads, s)
+                               : backward_impl<float>(g, n_frames, d_saliency, grads, s));
+  g->bwd_done = true;
+  return RGP_OK;
 }
 
 int rgp_shallownet_create(rgp_shallownet_t** plan, int max_frames, int image_hw, int dtype) {
@@ -570,6 +652,28 @@ int rgp_shallownet_set_dropout(rgp_shallownet_t* g, float keep_prob, const unsig
   g->drop_mask = keep_prob < 1.f ? mask : nullptr;
   g->drop_keep = g->drop_mask ? keep_prob : 1.0f;
   return RGP_OK;
+}
+
+size_t rgp_shallownet_buffer_elems(const rgp_shallownet_t* g, const char* name) {
+  BufView v;
+  if (!g || !name || !find_view(g, name, v)) return 0;
+  if (v.when != kViewAlways && !g->save) return 0;
+  return (size_t)(g->last_n ? g->last_n : g->N) * (size_t)v.per_frame();
+}
+
+int rgp_shallownet_read_buffer(rgp_shallownet_t* g, const char* name, float* dst, rgp_stream_t stream) {
+  RGP_REQUIRE(g && g->ws && name && dst, "rgp_shallownet_read_buffer: null argument");
+  BufView v;
+  if (!find_view(g, name, v)) return set_err(RGP_EINVAL, "rgp_shallownet_read_buffer: unknown buffer '%s'", name);
+  if (v.when != kViewAlways && !g->save)
+    return set_err(RGP_ESTATE, "rgp_shallownet_read_buffer: '%s' exists on plans created with save_for_backward", name);
+  if (g->last_n <= 0) return set_err(RGP_ESTATE, "rgp_shallownet_read_buffer: no forward has run");
+  if (v.when == kViewAfterBackward && !g->bwd_done)
+    return set_err(RGP_ESTATE, "rgp_shallownet_read_buffer: '%s' exists after rgp_shallownet_backward", name);
+  hipStream_t s = (hipStream_t)stream;
+  if (v.kind == kViewU8) return read_view<unsigned char>(g, v, dst, s);
+  if (v.kind == kViewF32 || g->dtype == RGP_F32) return read_view<float>(g, v, dst, s);
+  return read_view<bf16_t>(g, v, dst, s);
 }
 
 }  // extern "C"

@@ -831,6 +831,19 @@ class ShallowNetEngine(object):
     def adam_step(self, step, lr, max_grad_norm=10.0, method='adam'):
         return clip_step_multi([self], step, lr, max_grad_norm, method)
 
+    def read_buffer_elems(self, name):
+        """fp32 elements read_buffer(name) returns for the frames of the last forward; 0 = this plan has no such buffer."""
+        return int(self.lib.rgp_shallownet_buffer_elems(self._h, name.encode()))
+
+    def read_buffer(self, name):
+        """Flat fp32 copy of an intermediate of the last forward / backward (names and layouts: rgp_shallownet_read_buffer,
+        include/rgp.h).  Raises RgpError for an unknown name (RGP_EINVAL) and for a buffer this plan does not hold yet
+        (RGP_ESTATE: a training-plan buffer of an inference plan, a gradient before a backward)."""
+        out = torch.empty(max(self.read_buffer_elems(name), 1), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_shallownet_read_buffer(self._h, name.encode(), _ptr(out), _stream_ptr(self.device)))
+        return out
+
     def forward(self, frames, want_7x7=False, train=False):
         """frames [n,H,W,3] fp32 device tensor -> (saliency [n,49,49], saliency7 [n,7,7] or None).
         train (engines created with dropout=True): True = draw a dropout mask (if configured), 'keep' = leave the mask

@@ -74,7 +74,9 @@ def test_shallownet_backward_matches_autograd(gpu, dtype, hw):
     grads = eng.backward(torch.tensor(g, device=gpu))
     # bf16: with ~3 significant digits the first maximum of a 3x3 window (9 near-equal candidates) often is a
     # neighbour of the fp64 one, which re-routes that window's gradient; the kernels' logic is pinned by the fp32
-    # runs, the bf16 run must stay well aligned with the reference gradient (cosine) and of the same size
+    # runs, the bf16 run must stay well aligned with the reference gradient (cosine) and of the same size.
+    # The kernel logic IN bf16 is pinned by tests/test_shallownet_local_gpu.py: every stage, forward and backward, on the
+    # device's own operands (rgp_shallownet_read_buffer), where a bf16 plan is held to the f32 bounds
     bad = {}
     for k in p:
         ref = pt[k].grad.numpy()
