@@ -15,18 +15,20 @@
 // global memory, where they stay cached: they are the same for all frames), 11.5 KiB of small arrays: 135.5 KiB of
 // the CU's 160, 124 KiB of them requested as dynamic shared memory.  One workgroup per CU, so the block size is the
 // occupancy: 1024 threads would leave 128 VGPRs per thread and the sweeps spill (436 B of scratch per lane); 512
-// threads take 179 VGPRs, no scratch, two waves per SIMD behind which the LDS latency of the sweeps hides
+// threads take 177 VGPRs, no scratch, two waves per SIMD behind which the LDS latency of the sweeps hides
 // (profiles/metrics_scaled_kernel_resources.txt).
 //
 // Exactness.  Compiled with -ffp-contract=off, no fast-math, IEEE division.  The resized VALUES are a fixed sequence
-// of multiplies and adds (filter_line, spline_at below; tests/spline_ref.py restates them), so they are reproducible
+// of multiplies and adds (filter_line, spline_at in spline.hip.h; tests/spline_ref.py restates them), so they are reproducible
 // bit for bit; normalisations, jitter and comparisons are element-wise, counts are integers, and what is left against
 // the host is the order of the sums (H W 2^-53).  The order of every sum is fixed by (H, W) alone.
+// The metrics' arithmetic -- numpy's rules, the chains, the draws -- is in metrics_shared.hip.h, shared with
+// rgp_metrics.hip; this file holds the table staging, the prefilter, the point lists, the sweeps over the target grid
+// (for_pixels), AUC_Judd's histogram count and the staging of the negatives' values (ws_val).
 #include <cmath>
 #include <vector>
 
-#include "rgp_host.h"
-#include "philox.hip.h"
+#include "metrics_shared.hip.h"
 #include "spline.hip.h"
 
 using namespace rgp;
@@ -39,28 +41,15 @@ constexpr int kMaxFix = RGP_METRICS_MAX_FIX;
 constexpr int kMaxOther = RGP_METRICS_SCALED_MAX_OTHER;
 constexpr int kSrcPerThread = kMaxSrc / kThreads;
 constexpr int kTabLds = 1536;   // H + W up to which the per-axis tables live in LDS
-constexpr int kStatusBytes = 64;
 constexpr int kResizeThreads = 256;
-enum { kDrawJudd = 0, kDrawBorji = 1, kDrawShuffled = 2 };
 
-
-struct ScaledParams {
-  const void *pred, *gt;
+struct ScaledParams : MetricsCommon {
   const int *fix_ptr, *fix_idx, *other_ptr, *other_idx;
   int fix_len, other_len;
-  int n_frames, h, w, H, W;
-  unsigned metrics, flags;
-  int n_rep, neg_stride;
-  double step_size;
-  const double* judd_jitter;
-  const int *borji_neg, *shuf_neg, *shuf_cnt;   // the caller's draws
-  int *ws_borji, *ws_shuf, *ws_cnt;             // device draws: written, then read back by the same workgroup
+  int h, w, H, W;
   double* ws_val;                               // [2][n_frames, n_rep, neg_stride]: normalised saliency at the negatives
   const double* tab_w;                          // [H + W][4] weights, rows first
   const unsigned short* tab_i;                  // [H + W][4] reflected source index (rows: times w)
-  unsigned long long seed, offset;
-  int* status;
-  double* scores;
   SplineConsts sc;
 };
 
@@ -72,56 +61,6 @@ struct ResizeParams {
   const unsigned short* tab_i;
   SplineConsts sc;
 };
-
-// numpy's order for floating point (sort, searchsorted): a < b, NaN after everything
-__device__ __forceinline__ bool np_less(double a, double b) { return a < b || (b != b && a == a); }
-// np.max / np.min of two: NaN propagates
-__device__ __forceinline__ double np_max(double a, double b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
-__device__ __forceinline__ double np_min(double a, double b) { return a != a ? a : (b != b ? b : (a < b ? a : b)); }
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// every thread gets the K block sums: wave butterflies, then the waves' sums in wave order
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double* sh) {
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) sh[wave * K + k] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double s = sh[k];
-    for (int wv = 1; wv < kWaves; ++wv) s += sh[wv * K + k];
-    v[k] = s;
-  }
-}
-
-// np.min and np.max over the block (NaN propagates)
-__device__ __forceinline__ void block_minmax(double& mn, double& mx, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    mn = np_min(mn, __shfl_xor(mn, o));
-    mx = np_max(mx, __shfl_xor(mx, o));
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) { sh[wave * 2] = mn; sh[wave * 2 + 1] = mx; }
-  __syncthreads();
-  mn = sh[0]; mx = sh[1];
-  for (int wv = 1; wv < kWaves; ++wv) { mn = np_min(mn, sh[wv * 2]); mx = np_max(mx, sh[wv * 2 + 1]); }
-}
-
-// word `sample & 3` of the Philox block (sample / 4, rep, frame, metric): the counter of rgp_metrics.hip
-__device__ __forceinline__ void draw_block(unsigned out[4], unsigned blk, unsigned rep, unsigned long long frame, int what,
-                                           unsigned long long seed) {
-  out[0] = blk; out[1] = rep; out[2] = (unsigned)frame; out[3] = ((unsigned)(frame >> 32) << 2) | (unsigned)what;
-  philox4x32_10(out, (unsigned)seed, (unsigned)(seed >> 32));
-}
 
 // both passes over `n_maps` maps of h x w that lie kMaxSrc apart, by `threads` threads of the block
 __device__ __forceinline__ void prefilter(double* maps, int n_maps, int h, int w, const SplineConsts& sc, int threads) {
@@ -194,7 +133,7 @@ __global__ __launch_bounds__(kThreads) void scaled_scores_kernel(const ScaledPar
         mx = np_max(mx, pv[j]);
       }
     }
-    block_minmax(mn, mx, sRed);
+    block_minmax<kWaves>(mn, mx, sRed);
     const double den = mx - mn;
     const float mnf = (float)mn, denf = (float)mx - (float)mn;
 #pragma unroll
@@ -242,11 +181,7 @@ __global__ __launch_bounds__(kThreads) void scaled_scores_kernel(const ScaledPar
   }
   __syncthreads();
   if (sBad != 0) {   // uniform over the block: no finite score, the call reports it
-    if (tid == 0) {
-      atomicAdd(p.status, 1);
-      for (int r = 0; r < RGP_METRICS_COUNT; ++r)
-        if (M >> r & 1) p.scores[(long long)r * p.n_frames + n] = nan;
-    }
+    if (tid == 0) refuse_frame(p, n);
     return;
   }
   if (device_draws && (M & RGP_METRIC_AUC_SHUFFLED) && tid == 0) p.ws_cnt[n] = n_fix > 0 ? cnt_shuf : 0;
@@ -266,8 +201,8 @@ __global__ __launch_bounds__(kThreads) void scaled_scores_kernel(const ScaledPar
       mx = np_max(mx, r);
       if (want_gt) s1[0] += spline_at(sCg, t);
     });
-    block_sum(s1, sRed);
-    block_minmax(mn, mx, sRed);
+    block_sum<kWaves>(s1, sRed);
+    block_minmax<kWaves>(mn, mx, sRed);
     gsum = s1[0]; psum = s1[1]; pmn = mn; pden = mx - mn;
   }
   if (tid < n_fix) {
@@ -281,67 +216,18 @@ __global__ __launch_bounds__(kThreads) void scaled_scores_kernel(const ScaledPar
 
   // ---- sim (:207-218), cc (:221-236), NSS: one sweep per dependent statement of the host, every value recomputed
   if (M & (RGP_METRIC_SIM | RGP_METRIC_CC | RGP_METRIC_NSS)) {
-    const double mg = gsum / dn, mp = psum / dn;
-    double s2[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for_pixels(H, W, [&](int, int Y, int X) {
-      Taps t;
-      load_taps(t, tw, ti, H, Y, X);
-      const double r = spline_at(sCp, t), g = want_gt ? spline_at(sCg, t) : 0.0;
-      const double a = g / gsum, b = r / psum;
-      s2[0] += (a != a) ? a : ((b != b) ? b : (a < b ? a : b));     // np.minimum
-      const double g1 = g - mg, r1 = r - mp;
-      s2[1] += g1; s2[2] += r1;
-      s2[3] += g1 > 0.0 ? 1.0 : 0.0; s2[4] += r1 > 0.0 ? 1.0 : 0.0;
-      s2[5] += r1 * r1;
-    });
-    block_sum(s2, sRed);
-    score[RGP_METRIC_ROW_SIM] = s2[0];
-    if (M & RGP_METRIC_CC) {
-      const double m2g = s2[1] / dn, m2r = s2[2] / dn;
-      const bool pos_g = s2[3] > 0.0, pos_r = s2[4] > 0.0;
-      double s3[2] = {0.0, 0.0};
+    auto sweep = [&](auto&& f) {   // the thread's pixels, both maps recomputed from the coefficients
       for_pixels(H, W, [&](int, int Y, int X) {
         Taps t;
         load_taps(t, tw, ti, H, Y, X);
-        const double a = (spline_at(sCg, t) - mg) - m2g, b = (spline_at(sCp, t) - mp) - m2r;
-        s3[0] += a * a; s3[1] += b * b;
+        double r = spline_at(sCp, t), g = want_gt ? spline_at(sCg, t) : 0.0;
+        f(g, r);
       });
-      block_sum(s3, sRed);
-      const double sdg = sqrt(s3[0] / dn), sdr = sqrt(s3[1] / dn);
-      double s4[2] = {0.0, 0.0};
-      for_pixels(H, W, [&](int, int Y, int X) {   // the standardised maps np.corrcoef is given
-        Taps t;
-        load_taps(t, tw, ti, H, Y, X);
-        double g = spline_at(sCg, t) - mg, r = spline_at(sCp, t) - mp;
-        if (pos_g) g = g / sdg;
-        if (pos_r) r = r / sdr;
-        s4[0] += g; s4[1] += r;
-      });
-      block_sum(s4, sRed);
-      const double ag = s4[0] / dn, ar = s4[1] / dn;
-      double s5[3] = {0.0, 0.0, 0.0};
-      for_pixels(H, W, [&](int, int Y, int X) {
-        Taps t;
-        load_taps(t, tw, ti, H, Y, X);
-        double g = spline_at(sCg, t) - mg, r = spline_at(sCp, t) - mp;
-        if (pos_g) g = g / sdg;
-        if (pos_r) r = r / sdr;
-        const double xg = g - ag, xr = r - ar;
-        s5[0] += xr * xr; s5[1] += xg * xg; s5[2] += xr * xg;
-      });
-      block_sum(s5, sRed);
-      const double f = 1.0 / (dn - 1.0);                                   // np.cov: c *= 1 / (n - ddof)
-      const double c00 = s5[0] * f, c11 = s5[1] * f, c01 = s5[2] * f;
-      double c = (c01 / sqrt(c00)) / sqrt(c11);                            // np.corrcoef, then its clip to [-1, 1]
-      c = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);
-      score[RGP_METRIC_ROW_CC] = c;
-    }
-    if ((M & RGP_METRIC_NSS) && n_fix > 0 && tid == 0) {
-      const double sd = sqrt(s2[5] / dn), den = sd > 0.0 ? sd : 1.0;
-      double acc = 0.0;
-      for (int k = 0; k < n_fix; ++k) acc += (sFixRaw[k] - mp) / den;
-      score[RGP_METRIC_ROW_NSS] = acc / (double)n_fix;
-    }
+    };
+    const ChainResult c = sim_cc_chain<kWaves, false>(sweep, gsum, psum, dn, (M & RGP_METRIC_CC) != 0, sRed);
+    score[RGP_METRIC_ROW_SIM] = c.sim;
+    score[RGP_METRIC_ROW_CC] = c.cc;
+    if ((M & RGP_METRIC_NSS) && n_fix > 0 && tid == 0) score[RGP_METRIC_ROW_NSS] = nss_score(sFixRaw, n_fix, c, dn);
   }
 
   // ---- AUC_Judd (:42-98): jitter per target pixel, normalize_range over the jittered full-size map
@@ -353,15 +239,7 @@ __global__ __launch_bounds__(kThreads) void scaled_scores_kernel(const ScaledPar
       load_taps(t, tw, ti, H, Y, X);
       double r = spline_at(sCp, t);
       if (jitter) {
-        double u;
-        if (device_draws) {
-          unsigned wd[4];
-          draw_block(wd, (unsigned)pix >> 1, 0u, frame, kDrawJudd, p.seed);
-          const unsigned hi = wd[(pix & 1) * 2] >> 5, lo = wd[(pix & 1) * 2 + 1] >> 6;
-          u = (double)(((unsigned long long)hi << 26) | lo) * (1.0 / 9007199254740992.0);
-        } else {
-          u = p.judd_jitter[jo + pix];
-        }
+        const double u = device_draws ? judd_jitter_u((unsigned)pix, frame, p.seed) : p.judd_jitter[jo + pix];
         r = r + u * 1e-7;
       }
       return r;
@@ -372,20 +250,12 @@ __global__ __launch_bounds__(kThreads) void scaled_scores_kernel(const ScaledPar
       mn = np_min(mn, r);
       mx = np_max(mx, r);
     });
-    block_minmax(mn, mx, sRed);
+    block_minmax<kWaves>(mn, mx, sRed);
     const double den = mx - mn;
     if (tid < n_fix) sFixJ[tid] = (jittered(sFixPix[tid], sFixPix[tid] / W, sFixPix[tid] % W) - mn) / den;
     if (tid <= n_fix) sHist[tid] = 0;
     __syncthreads();
-    if (tid < n_fix) {   // thresholds = saliency at the fixations, descending (np.sort(...)[::-1]: NaN first)
-      const double v = sFixJ[tid];
-      int rank = 0;
-      for (int k = 0; k < n_fix; ++k) {
-        const double x = sFixJ[k];
-        rank += (np_less(v, x) || (!np_less(x, v) && k < tid)) ? 1 : 0;
-      }
-      sThr[rank] = v;
-    }
+    judd_rank_thresholds(sFixJ, sThr, n_fix);
     __syncthreads();
     // a pixel is below the first m thresholds (they descend): hist[m]++, and #(S < thr_k) = sum of hist[m], m > k
     int below_all = 0;
@@ -405,15 +275,7 @@ __global__ __launch_bounds__(kThreads) void scaled_scores_kernel(const ScaledPar
     if (tid == 0) {
       int run = 0;
       for (int k = n_fix - 1; k >= 0; --k) { run += sHist[k + 1]; sCnt[k] = run; }
-      double ptp = 0.0, pfp = 0.0, acc = 0.0;
-      for (int k = 1; k <= n_fix; ++k) {
-        const double tp = (double)k / (double)n_fix;
-        const double fp = (double)((n_pix - sCnt[k - 1]) - k) / (double)(n_pix - n_fix);
-        acc += (fp - pfp) * (tp + ptp) / 2.0;
-        ptp = tp; pfp = fp;
-      }
-      acc += (1.0 - pfp) * (1.0 + ptp) / 2.0;
-      score[RGP_METRIC_ROW_AUC_JUDD] = acc;
+      score[RGP_METRIC_ROW_AUC_JUDD] = judd_trapezoid(sCnt, n_fix, n_pix);
     }
   }
 
@@ -421,34 +283,15 @@ __global__ __launch_bounds__(kThreads) void scaled_scores_kernel(const ScaledPar
   if ((M & (RGP_METRIC_AUC_BORJI | RGP_METRIC_AUC_SHUFFLED)) && n_fix > 0) {
     const long long E = (long long)p.n_frames * p.n_rep * p.neg_stride;
     const long long frame_off = (long long)n * p.n_rep * p.neg_stride;
-    if (tid == 0) {
-      double m = sFixP[0];
-      for (int k = 1; k < n_fix; ++k) m = np_max(m, sFixP[k]);
-      sFixMax = m;
-    }
+    if (tid == 0) sFixMax = np_max_of(sFixP, n_fix);
     // 1. device draws: one thread per (metric, repetition) leaves the indices in the workspace
     if (device_draws)
       for (int item = tid; item < 2 * p.n_rep; item += kThreads) {
         const int which = item >= p.n_rep ? 1 : 0, rep = item - which * p.n_rep;
         if (!(M & (which ? RGP_METRIC_AUC_SHUFFLED : RGP_METRIC_AUC_BORJI))) continue;
         int* wrow = (which ? p.ws_shuf : p.ws_borji) + frame_off + (long long)rep * p.neg_stride;
-        if (!which) {   // uniform over the target grid
-          for (int s = 0; s < n_fix; s += 4) {
-            unsigned wd[4];
-            draw_block(wd, (unsigned)(s >> 2), (unsigned)rep, frame, kDrawBorji, p.seed);
-            for (int q = 0; q < 4 && s + q < n_fix; ++q) wrow[s + q] = (int)__umulhi(wd[q], (unsigned)n_pix);
-          }
-        } else {        // Floyd: a uniform subset of cnt_shuf distinct members of the negative set
-          unsigned wd[4] = {0u, 0u, 0u, 0u};
-          for (int s = 0; s < cnt_shuf; ++s) {
-            if ((s & 3) == 0) draw_block(wd, (unsigned)(s >> 2), (unsigned)rep, frame, kDrawShuffled, p.seed);
-            const int j = n_other - cnt_shuf + s;
-            const int pick = p.other_idx[o_base + (int)__umulhi(wd[s & 3], (unsigned)(j + 1))];
-            bool taken = false;
-            for (int q = 0; q < s; ++q) taken = taken || wrow[q] == pick;
-            wrow[s] = taken ? p.other_idx[o_base + j] : pick;
-          }
-        }
+        if (!which) draw_borji_row(wrow, n_fix, n_pix, rep, frame, p.seed);
+        else draw_floyd_row(wrow, cnt_shuf, n_other, rep, frame, p.seed, [&](int i) { return p.other_idx[o_base + i]; });
       }
     __syncthreads();
     // 2. the normalised saliency at every negative, from the coefficients: one thread per (metric, repetition, sample)
@@ -466,47 +309,21 @@ __global__ __launch_bounds__(kThreads) void scaled_scores_kernel(const ScaledPar
     }
     __syncthreads();
     // 3. the ROC sweep of each repetition
-    const double fix_max = sFixMax, dfix = (double)n_fix;
+    const double fix_max = sFixMax;
     double auc[2] = {0.0, 0.0};
     for (int item = tid; item < 2 * p.n_rep; item += kThreads) {
       const int which = item >= p.n_rep ? 1 : 0, rep = item - which * p.n_rep;
       if (!(M & (which ? RGP_METRIC_AUC_SHUFFLED : RGP_METRIC_AUC_BORJI))) continue;
       const double* vals = p.ws_val + which * E + frame_off + (long long)rep * p.neg_stride;
-      const int cnt = which ? cnt_shuf : n_fix;
-      // top = max(s_fix.max(), col.max()) as Python's max(a, b) evaluates it; col.max() of no sample: NaN
-      double col_max = nan;
-      for (int s = 0; s < cnt; ++s) col_max = s == 0 ? vals[s] : np_max(col_max, vals[s]);
-      const double top = col_max > fix_max ? col_max : fix_max;
-      double a = nan;
-      if (top == top && cnt > 0) {
-        const int n_thr = (int)ceil(top / p.step_size);   // len(np.arange(0, top, step))
-        double ptp = 0.0, pfp = 0.0;
-        a = 0.0;
-        for (int i = n_thr - 1; i >= 0; --i) {
-          const double thr = (double)i * p.step_size;
-          int lf = 0, lc = 0;
-          for (int k = 0; k < n_fix; ++k) lf += np_less(sFixP[k], thr) ? 1 : 0;
-          for (int s = 0; s < cnt; ++s) lc += np_less(vals[s], thr) ? 1 : 0;
-          const double tp = (double)(n_fix - lf) / dfix, fp = (double)(n_fix - lc) / dfix;
-          a += (fp - pfp) * (tp + ptp) / 2.0;
-          ptp = tp; pfp = fp;
-        }
-        a += (1.0 - pfp) * (1.0 + ptp) / 2.0;
-      }
-      auc[which] += a;
+      auc[which] += roc_auc(sFixP, n_fix, fix_max, which ? cnt_shuf : n_fix, p.step_size, [&](int s) { return vals[s]; });
     }
-    block_sum(auc, sRed);
+    block_sum<kWaves>(auc, sRed);
     score[RGP_METRIC_ROW_AUC_BORJI] = auc[0] / (double)p.n_rep;
     score[RGP_METRIC_ROW_AUC_SHUFFLED] = auc[1] / (double)p.n_rep;
   }
 
   __syncthreads();
-  if (tid == 0) {
-    const bool bad = sBad != 0;
-    if (bad) atomicAdd(p.status, 1);
-    for (int r = 0; r < RGP_METRICS_COUNT; ++r)
-      if (M >> r & 1) p.scores[(long long)r * p.n_frames + n] = bad ? nan : score[r];
-  }
+  if (tid == 0) write_scores(p, n, sBad != 0, score);
 }
 
 // the resized maps themselves: grid (frames, row blocks); every block prefilters its frame again (a few microseconds)
@@ -531,7 +348,6 @@ __global__ __launch_bounds__(kResizeThreads) void spline_resize_kernel(const Res
   }
 }
 
-size_t draws_elems(int n_frames, int n_rep, int neg_stride) { return (size_t)n_frames * (size_t)n_rep * (size_t)neg_stride; }
 int check_shapes(const char* fn, int h, int w, int H, int W) {
   RGP_REQUIRE(h >= 2 && w >= 2 && (long long)h * w <= RGP_METRICS_MAX_PIX,
               "%s: source maps of %d x %d: height and width must be at least 2 and height*width at most RGP_METRICS_MAX_PIX = %d", fn, h, w,
@@ -548,10 +364,7 @@ extern "C" {
 
 size_t rgp_metrics_scaled_workspace_bytes(int n_frames, int n_rep, int neg_stride, int height, int width, unsigned flags) {
   if (n_frames <= 0 || n_rep <= 0 || neg_stride <= 0 || height <= 0 || width <= 0) return 0;
-  const size_t e = draws_elems(n_frames, n_rep, neg_stride);
-  size_t b = kStatusBytes;
-  if (flags & RGP_METRICS_DEVICE_DRAWS) b += (2 * e + (size_t)n_frames) * sizeof(int);
-  b = align_up(b, 64) + 2 * e * sizeof(double);
+  const size_t b = align_up(draws_layout_bytes(n_frames, n_rep, neg_stride, flags), 64) + 2 * draws_elems(n_frames, n_rep, neg_stride) * sizeof(double);
   return align_up(b, 64) + spline_tables_bytes(height, width);
 }
 
@@ -562,58 +375,26 @@ int rgp_saliency_scores_scaled(const rgp_metrics_scaled_args* a, rgp_stream_t st
   RGP_REQUIRE(a != nullptr, "%s: args is NULL", fn);
   RGP_REQUIRE(a->n_frames > 0, "%s: n_frames = %d must be positive", fn, a->n_frames);
   RGP_TRY(check_shapes(fn, a->height, a->width, a->target_height, a->target_width));
-  const unsigned M = a->metrics, F = a->flags;
-  RGP_REQUIRE(M != 0 && (M & ~(unsigned)RGP_METRIC_ALL) == 0, "%s: metrics mask 0x%x: no or unknown metric bits", fn, M);
-  RGP_REQUIRE((F & ~(unsigned)(RGP_METRICS_DEVICE_DRAWS | RGP_METRICS_NO_JITTER | RGP_METRICS_PRED_F64 | RGP_METRICS_GT_F64 |
-                               RGP_METRICS_SCALED_OTHER_SHARED)) == 0, "%s: unknown flags 0x%x", fn, F);
-  RGP_REQUIRE(a->n_rep > 0, "%s: n_rep = %d must be positive", fn, a->n_rep);
-  RGP_REQUIRE(a->step_size > 0.0 && 1.0 / a->step_size <= (double)RGP_METRICS_MAX_THRESHOLDS,
-              "%s: step_size = %g must be positive and at least 1 / RGP_METRICS_MAX_THRESHOLDS", fn, a->step_size);
-  RGP_REQUIRE(a->neg_stride > 0 && a->neg_stride <= RGP_METRICS_MAX_FIX,
-              "%s: neg_stride = %d (fixations per frame) must be in [1, RGP_METRICS_MAX_FIX = %d]", fn, a->neg_stride, RGP_METRICS_MAX_FIX);
+  RGP_TRY(check_common_args(fn, a, RGP_METRICS_DEVICE_DRAWS | RGP_METRICS_NO_JITTER | RGP_METRICS_PRED_F64 | RGP_METRICS_GT_F64 |
+                                       RGP_METRICS_SCALED_OTHER_SHARED));
   RGP_REQUIRE(a->pred && a->fix_ptr && a->fix_idx && a->scores, "%s: pred, fix_ptr, fix_idx and scores must not be NULL", fn);
   RGP_REQUIRE(a->fix_len >= 0 && a->other_len >= 0, "%s: fix_len = %d and other_len = %d must not be negative", fn, a->fix_len, a->other_len);
-  RGP_REQUIRE(a->gt || !(M & (RGP_METRIC_SIM | RGP_METRIC_CC)), "%s: sim and cc need gt", fn);
   RGP_REQUIRE((a->other_ptr == nullptr) == (a->other_idx == nullptr), "%s: other_ptr and other_idx go together", fn);
-  const bool dev = (F & RGP_METRICS_DEVICE_DRAWS) != 0;
-  if (dev) {
-    RGP_REQUIRE(!a->judd_jitter && !a->borji_neg && !a->shuf_neg && !a->shuf_cnt,
-                "%s: RGP_METRICS_DEVICE_DRAWS takes no draws from the caller (the four pointers must be NULL)", fn);
-    RGP_REQUIRE(a->other_ptr || !(M & RGP_METRIC_AUC_SHUFFLED), "%s: AUC_shuffled with device draws needs the negative set other_ptr / other_idx", fn);
-  } else {
-    RGP_REQUIRE(!(F & RGP_METRICS_NO_JITTER), "%s: with the caller's draws a NULL judd_jitter means no jitter", fn);
-    RGP_REQUIRE(a->borji_neg || !(M & RGP_METRIC_AUC_BORJI), "%s: AUC_Borji with the caller's draws needs borji_neg", fn);
-    RGP_REQUIRE((a->shuf_neg && a->shuf_cnt) || !(M & RGP_METRIC_AUC_SHUFFLED),
-                "%s: AUC_shuffled with the caller's draws needs shuf_neg and shuf_cnt", fn);
-  }
+  RGP_REQUIRE(a->other_ptr || !(a->flags & RGP_METRICS_DEVICE_DRAWS) || !(a->metrics & RGP_METRIC_AUC_SHUFFLED),
+              "%s: AUC_shuffled with device draws needs the negative set other_ptr / other_idx", fn);
   const int H = a->target_height, W = a->target_width;
-  const size_t need = rgp_metrics_scaled_workspace_bytes(a->n_frames, a->n_rep, a->neg_stride, H, W, F);
-  if (!a->workspace || a->workspace_bytes < need || ((size_t)a->workspace & 7) != 0)
-    return set_err(RGP_EWORKSPACE, "%s: workspace missing, misaligned or too small (%zu < %zu bytes)", fn,
-                   a->workspace ? a->workspace_bytes : (size_t)0, need);
+  RGP_TRY(check_workspace(fn, a->workspace, a->workspace_bytes,
+                          rgp_metrics_scaled_workspace_bytes(a->n_frames, a->n_rep, a->neg_stride, H, W, a->flags)));
 
   ScaledParams p{};
-  p.pred = a->pred; p.gt = a->gt; p.fix_ptr = a->fix_ptr; p.fix_idx = a->fix_idx; p.other_ptr = a->other_ptr; p.other_idx = a->other_idx;
-  p.fix_len = a->fix_len; p.other_len = a->other_len;
-  p.n_frames = a->n_frames; p.h = a->height; p.w = a->width; p.H = H; p.W = W; p.metrics = M; p.flags = F;
-  p.n_rep = a->n_rep; p.neg_stride = a->neg_stride; p.step_size = a->step_size;
-  p.judd_jitter = a->judd_jitter; p.borji_neg = a->borji_neg; p.shuf_neg = a->shuf_neg; p.shuf_cnt = a->shuf_cnt;
-  p.seed = a->seed; p.offset = a->offset;
-  p.status = (int*)a->workspace;
-  p.scores = a->scores;
-  p.sc = spline_consts(a->height, a->width);
-  const size_t e = draws_elems(a->n_frames, a->n_rep, a->neg_stride);
   char* ws = (char*)a->workspace;
-  size_t off = kStatusBytes;
-  if (dev) {
-    p.ws_borji = (int*)(ws + off);
-    p.ws_shuf = p.ws_borji + e;
-    p.ws_cnt = p.ws_shuf + e;
-    off += (2 * e + (size_t)a->n_frames) * sizeof(int);
-  }
-  off = align_up(off, 64);
+  size_t off = align_up(fill_common(p, a), 64);
+  p.fix_ptr = a->fix_ptr; p.fix_idx = a->fix_idx; p.other_ptr = a->other_ptr; p.other_idx = a->other_idx;
+  p.fix_len = a->fix_len; p.other_len = a->other_len;
+  p.h = a->height; p.w = a->width; p.H = H; p.W = W;
+  p.sc = spline_consts(a->height, a->width);
   p.ws_val = (double*)(ws + off);
-  off = align_up(off + 2 * e * sizeof(double), 64);
+  off = align_up(off + 2 * draws_elems(a->n_frames, a->n_rep, a->neg_stride) * sizeof(double), 64);
   hipStream_t s = (hipStream_t)stream;
   RGP_TRY(upload_tables(a->height, a->width, H, W, ws + off, s, &p.tab_w, &p.tab_i));
   RGP_HIP(hipMemsetAsync(a->workspace, 0, kStatusBytes, s));
@@ -632,10 +413,7 @@ int rgp_spline_resize(const void* src, int src_f64, int n_frames, int h, int w, 
   RGP_REQUIRE(src && dst, "%s: src and dst must not be NULL", fn);
   RGP_REQUIRE(n_frames > 0, "%s: n_frames = %d must be positive", fn, n_frames);
   RGP_TRY(check_shapes(fn, h, w, H, W));
-  const size_t need = rgp_spline_resize_workspace_bytes(H, W);
-  if (!workspace || workspace_bytes < need || ((size_t)workspace & 7) != 0)
-    return set_err(RGP_EWORKSPACE, "%s: workspace missing, misaligned or too small (%zu < %zu bytes)", fn,
-                   workspace ? workspace_bytes : (size_t)0, need);
+  RGP_TRY(check_workspace(fn, workspace, workspace_bytes, rgp_spline_resize_workspace_bytes(H, W)));
   ResizeParams p{};
   p.src = src; p.dst = dst; p.src_f64 = src_f64 != 0; p.dst_f64 = dst_f64 != 0; p.h = h; p.w = w; p.H = H; p.W = W;
   p.sc = spline_consts(h, w);

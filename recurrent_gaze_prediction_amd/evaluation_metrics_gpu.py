@@ -182,6 +182,67 @@ def _device_maps(x, what, dev, binary=False):
     return t.contiguous()
 
 
+def _resolve_draws(draws, metrics, other, jitter, reference):
+    """-> (flags, packed) of the ``draws`` argument of the scorers: the host's draws (the dict given, or ``reference()``
+    for ``'reference'``), or None and the flags of device draws."""
+    if isinstance(draws, dict):
+        return 0, draws
+    if draws == 'reference':
+        return 0, reference()
+    if draws == 'device':
+        if 'AUC_shuffled' in metrics and other is None:
+            raise ValueError('other_map_union required')
+        return _lib.RGP_METRICS_DEVICE_DRAWS | (0 if jitter else _lib.RGP_METRICS_NO_JITTER), None
+    raise ValueError("draws must be 'device', 'reference' or the result of draw_reference_samples")
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _upload_draws(packed, dev):
+    """The caller's draws as device tensors, by the argument structs' field names (None: not given, or device draws)."""
+    def up(key, dtype):
+        a = packed.get(key) if packed is not None else None
+        return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype)).to(dev)
+    return {'judd_jitter': up('judd_jitter', np.float64), 'borji_neg': up('borji_neg', np.int32),
+            'shuf_neg': up('shuf_neg', np.int32), 'shuf_cnt': up('shuf_cnt', np.int32)}
+
+
+def _metric_bits(metrics):
+    return sum({_lib.METRIC_BITS[m] for m in metrics})       # one bit each: the sum over the set is their OR
+
+
+def _score_buffers(ws_bytes, N, dev):
+    """-> the workspace and the [6, N] score table of one launch."""
+    ws = torch.empty(max(int(ws_bytes), 64), dtype=torch.uint8, device=dev)
+    return ws, torch.full((_lib.RGP_METRICS_COUNT, N), float('nan'), dtype=torch.float64, device=dev)
+
+
+def _launch_scores(lib_fn, args, ws, scores, metrics, dev):
+    """The launch, the count of refused frames (rgp_metrics_status), ValueError for what the kernel refuses (naming the
+    host module), and the rows of the score table as {metric: f64 [N]}."""
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib_fn(ctypes.byref(args), stream)
+        if rc == 0:
+            rc = lib.rgp_metrics_status(ws.data_ptr(), stream)
+    if rc == -1:
+        raise ValueError('%s; %s' % (lib.rgp_last_error().decode(), _HOST))
+    _lib.check(rc)
+    host_scores = scores.cpu().numpy()
+    return {m: host_scores[_lib.METRIC_ROWS[m]].copy() for m in metrics}
+
+
+def _device_draws_from(ws, N, n_rep, stride):
+    """The indices the kernel drew, read back from the head of its workspace (behind the 64-byte status block)."""
+    e = N * int(n_rep) * stride
+    ints = ws[64:64 + (2 * e + N) * 4].view(torch.int32).cpu().numpy()
+    return {'borji_neg': ints[:e].reshape(N, n_rep, stride), 'shuf_neg': ints[e:2 * e].reshape(N, n_rep, stride),
+            'shuf_cnt': ints[2 * e:], 'neg_stride': stride}
+
+
 def saliency_scores_single(pred, gt, fix, other, metrics, draws='device', seed=0, offset=0, n_rep=100, step_size=0.1,
                            jitter=True, max_fix=None, device=None, return_draws=False):
     """Per-frame scores {metric: f64 [N]} of N frames in one launch (``evaluation_metrics.saliency_score_single`` for
@@ -209,20 +270,13 @@ def saliency_scores_single(pred, gt, fix, other, metrics, draws='device', seed=0
         device = next((t.device for t in (pred, gt, fix) if _is_tensor(t) and t.is_cuda), torch.device('cuda:0'))
     dev = torch.device(device)
 
-    flags, packed = 0, None
-    if isinstance(draws, dict) or draws == 'reference':
-        if not isinstance(draws, dict):
-            host_fix = fix.cpu().numpy() if _is_tensor(fix) else fix
-            host_other = other.cpu().numpy() if _is_tensor(other) else other
-            draws = draw_reference_samples(host_fix, host_other, metrics, n_rep=n_rep, jitter=jitter)
-        packed = draws
+    def reference():
+        host_fix = fix.cpu().numpy() if _is_tensor(fix) else fix
+        host_other = other.cpu().numpy() if _is_tensor(other) else other
+        return draw_reference_samples(host_fix, host_other, metrics, n_rep=n_rep, jitter=jitter)
+    flags, packed = _resolve_draws(draws, metrics, other, jitter, reference)
+    if packed is not None:
         stride = int(packed['neg_stride'])
-    elif draws == 'device':
-        flags |= _lib.RGP_METRICS_DEVICE_DRAWS | (0 if jitter else _lib.RGP_METRICS_NO_JITTER)
-        if 'AUC_shuffled' in metrics and other is None:
-            raise ValueError('other_map_union required')
-    else:
-        raise ValueError("draws must be 'device', 'reference' or the result of draw_reference_samples")
 
     if packed is None and max_fix is None and not _is_tensor(fix):
         max_fix = int((np.asarray(fix) > 0.5).reshape(N, -1).sum(1).max())
@@ -246,46 +300,18 @@ def saliency_scores_single(pred, gt, fix, other, metrics, draws='device', seed=0
             elif tuple(d_other.shape) != (H, W):
                 raise ValueError('other_map.shape != fixation_map.shape')
 
-    def up(key, dtype):
-        a = packed.get(key) if packed is not None else None
-        return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype)).to(dev)
-    d_jit, d_borji = up('judd_jitter', np.float64), up('borji_neg', np.int32)
-    d_shuf, d_cnt = up('shuf_neg', np.int32), up('shuf_cnt', np.int32)
-
+    d_draws = _upload_draws(packed, dev)
     lib = _lib.load()
-    bits = 0
-    for m in metrics:
-        bits |= _lib.METRIC_BITS[m]
-    ws_bytes = int(lib.rgp_metrics_workspace_bytes(N, n_rep, stride, flags))
-    ws = torch.empty(max(ws_bytes, 64), dtype=torch.uint8, device=dev)
-    scores = torch.full((_lib.RGP_METRICS_COUNT, N), float('nan'), dtype=torch.float64, device=dev)
-
-    def ptr(t):
-        return None if t is None else t.data_ptr()
-    args = _lib.MetricsArgs(pred=ptr(d_pred), gt=ptr(d_gt), fix=ptr(d_fix), other=ptr(d_other), other_stride=other_stride,
-                            n_frames=N, height=H, width=W, metrics=bits, flags=flags, n_rep=int(n_rep), neg_stride=stride,
-                            step_size=float(step_size), judd_jitter=ptr(d_jit), borji_neg=ptr(d_borji), shuf_neg=ptr(d_shuf),
-                            shuf_cnt=ptr(d_cnt), seed=int(seed) & (2 ** 64 - 1), offset=int(offset), workspace=ws.data_ptr(),
-                            workspace_bytes=ws.numel(), scores=scores.data_ptr())
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.rgp_saliency_scores(ctypes.byref(args), stream)
-        if rc == 0:
-            rc = lib.rgp_metrics_status(ws.data_ptr(), stream)
-    if rc == -1:
-        raise ValueError('%s; %s' % (lib.rgp_last_error().decode(), _HOST))
-    _lib.check(rc)
-    host_scores = scores.cpu().numpy()
-    out = {m: host_scores[_lib.METRIC_ROWS[m]].copy() for m in metrics}
+    ws, scores = _score_buffers(lib.rgp_metrics_workspace_bytes(N, n_rep, stride, flags), N, dev)
+    args = _lib.MetricsArgs(pred=_ptr(d_pred), gt=_ptr(d_gt), fix=_ptr(d_fix), other=_ptr(d_other), other_stride=other_stride,
+                            n_frames=N, height=H, width=W, metrics=_metric_bits(metrics), flags=flags, n_rep=int(n_rep),
+                            neg_stride=stride, step_size=float(step_size), seed=int(seed) & (2 ** 64 - 1), offset=int(offset),
+                            workspace=ws.data_ptr(), workspace_bytes=ws.numel(), scores=scores.data_ptr(),
+                            **{k: _ptr(t) for k, t in d_draws.items()})
+    out = _launch_scores(lib.rgp_saliency_scores, args, ws, scores, metrics, dev)
     if return_draws:
-        if packed is not None:
-            out['draws'] = packed
-        else:
-            e = N * int(n_rep) * stride
-            ints = ws[64:64 + (2 * e + N) * 4].view(torch.int32).cpu().numpy()
-            out['draws'] = {'borji_neg': ints[:e].reshape(N, n_rep, stride), 'shuf_neg': ints[e:2 * e].reshape(N, n_rep, stride),
-                            'shuf_cnt': ints[2 * e:], 'neg_stride': stride,
-                            'n_fix': (d_fix > 0.5).reshape(N, -1).sum(1).to(torch.int32).cpu().numpy()}
+        out['draws'] = packed if packed is not None else dict(
+            _device_draws_from(ws, N, n_rep, stride), n_fix=(d_fix > 0.5).reshape(N, -1).sum(1).to(torch.int32).cpu().numpy())
     return out
 
 
@@ -411,27 +437,22 @@ def saliency_scores_resized(pred, gt, fix, other, metrics, draws='device', seed=
             raise ValueError('other_map.shape != fixation_map.shape')
         shared = len(other[0]) == 2 and N != 1
 
-    flags, packed = (_lib.RGP_METRICS_SCALED_OTHER_SHARED if shared else 0), None
-    if isinstance(draws, dict) or draws == 'reference':
-        if not isinstance(draws, dict):
-            draws = draw_reference_samples_points(_host_points(fix), None if other is None else _host_points(other), (H, W),
-                                                  metrics, n_rep=n_rep, jitter=jitter)
-        packed = draws
+    def reference():
+        return draw_reference_samples_points(_host_points(fix), None if other is None else _host_points(other), (H, W),
+                                             metrics, n_rep=n_rep, jitter=jitter)
+    flags, packed = _resolve_draws(draws, metrics, other, jitter, reference)
+    flags |= _lib.RGP_METRICS_SCALED_OTHER_SHARED if shared else 0
+    if packed is not None:
         stride = int(packed['neg_stride'])
         for key, want in (('judd_jitter', (N, H * W)), ('borji_neg', (N, int(n_rep), stride)), ('shuf_neg', (N, int(n_rep), stride)),
                           ('shuf_cnt', (N,))):                       # the kernel reads them by these extents
             if packed.get(key) is not None and tuple(np.shape(packed[key])) != want:
                 raise ValueError('draws[%r] has shape %s, expected %s' % (key, tuple(np.shape(packed[key])), want))
-    elif draws == 'device':
-        flags |= _lib.RGP_METRICS_DEVICE_DRAWS | (0 if jitter else _lib.RGP_METRICS_NO_JITTER)
-        if 'AUC_shuffled' in metrics and other is None:
-            raise ValueError('other_map_union required')
+    else:
         if max_fix is None:
             counts = fix[0][1:] - fix[0][:-1]
             max_fix = int(counts.max().item() if _is_tensor(counts) else counts.max(initial=0))
         stride = max(1, int(max_fix))
-    else:
-        raise ValueError("draws must be 'device', 'reference' or the result of draw_reference_samples")
     if stride > MAX_FIX:
         raise ValueError('a frame has %d fixations, more than RGP_METRICS_MAX_FIX = %d; %s' % (stride, MAX_FIX, _HOST))
 
@@ -441,47 +462,19 @@ def saliency_scores_resized(pred, gt, fix, other, metrics, draws='device', seed=
     d_fptr, d_fidx, fix_len = _device_points(fix, dev)
     d_optr, d_oidx, other_len = (None, None, 0) if other is None else _device_points(other, dev)
 
-    def up(key, dtype):
-        a = packed.get(key) if packed is not None else None
-        return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype)).to(dev)
-    d_jit, d_borji = up('judd_jitter', np.float64), up('borji_neg', np.int32)
-    d_shuf, d_cnt = up('shuf_neg', np.int32), up('shuf_cnt', np.int32)
-
+    d_draws = _upload_draws(packed, dev)
     lib = _lib.load()
-    bits = 0
-    for m in metrics:
-        bits |= _lib.METRIC_BITS[m]
-    ws_bytes = int(lib.rgp_metrics_scaled_workspace_bytes(N, n_rep, stride, H, W, flags))
-    ws = torch.empty(max(ws_bytes, 64), dtype=torch.uint8, device=dev)
-    scores = torch.full((_lib.RGP_METRICS_COUNT, N), float('nan'), dtype=torch.float64, device=dev)
-
-    def ptr(t):
-        return None if t is None else t.data_ptr()
-    args = _lib.MetricsScaledArgs(pred=ptr(d_pred), gt=ptr(d_gt), fix_ptr=ptr(d_fptr), fix_idx=ptr(d_fidx), other_ptr=ptr(d_optr),
-                                  other_idx=ptr(d_oidx), fix_len=fix_len, other_len=other_len, n_frames=N, height=h, width=w,
-                                  target_height=H, target_width=W, metrics=bits, flags=flags, n_rep=int(n_rep), neg_stride=stride,
-                                  step_size=float(step_size), judd_jitter=ptr(d_jit), borji_neg=ptr(d_borji), shuf_neg=ptr(d_shuf),
-                                  shuf_cnt=ptr(d_cnt), seed=int(seed) & (2 ** 64 - 1), offset=int(offset), workspace=ws.data_ptr(),
-                                  workspace_bytes=ws.numel(), scores=scores.data_ptr())
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.rgp_saliency_scores_scaled(ctypes.byref(args), stream)
-        if rc == 0:
-            rc = lib.rgp_metrics_status(ws.data_ptr(), stream)
-    if rc == -1:
-        raise ValueError('%s; %s' % (lib.rgp_last_error().decode(), _HOST))
-    _lib.check(rc)
-    host_scores = scores.cpu().numpy()
-    out = {m: host_scores[_lib.METRIC_ROWS[m]].copy() for m in metrics}
+    ws, scores = _score_buffers(lib.rgp_metrics_scaled_workspace_bytes(N, n_rep, stride, H, W, flags), N, dev)
+    args = _lib.MetricsScaledArgs(pred=_ptr(d_pred), gt=_ptr(d_gt), fix_ptr=_ptr(d_fptr), fix_idx=_ptr(d_fidx), other_ptr=_ptr(d_optr),
+                                  other_idx=_ptr(d_oidx), fix_len=fix_len, other_len=other_len, n_frames=N, height=h, width=w,
+                                  target_height=H, target_width=W, metrics=_metric_bits(metrics), flags=flags, n_rep=int(n_rep),
+                                  neg_stride=stride, step_size=float(step_size), seed=int(seed) & (2 ** 64 - 1), offset=int(offset),
+                                  workspace=ws.data_ptr(), workspace_bytes=ws.numel(), scores=scores.data_ptr(),
+                                  **{k: _ptr(t) for k, t in d_draws.items()})
+    out = _launch_scores(lib.rgp_saliency_scores_scaled, args, ws, scores, metrics, dev)
     if return_draws:
-        if packed is not None:
-            out['draws'] = packed
-        else:
-            e = N * int(n_rep) * stride
-            ints = ws[64:64 + (2 * e + N) * 4].view(torch.int32).cpu().numpy()
-            out['draws'] = {'borji_neg': ints[:e].reshape(N, n_rep, stride), 'shuf_neg': ints[e:2 * e].reshape(N, n_rep, stride),
-                            'shuf_cnt': ints[2 * e:], 'neg_stride': stride,
-                            'n_fix': np.diff(_host_points(fix)[0]).astype(np.int32)}
+        out['draws'] = packed if packed is not None else dict(
+            _device_draws_from(ws, N, n_rep, stride), n_fix=np.diff(_host_points(fix)[0]).astype(np.int32))
     return out
 
 

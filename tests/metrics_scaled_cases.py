@@ -21,6 +21,7 @@ CASES = {
     'mid64': ((49, 49), (90, 160), 12, np.float64, 7200),
     'mid32': ((49, 49), (90, 160), 12, np.float32, 7300),
     'frame': ((49, 49), (405, 720), 2, np.float32, 7400),
+    'wide': ((7, 7), (3, 1600), 6, np.float64, 7500),      # H + W > 1536: the kernel reads its tap tables from global memory
 }
 
 

@@ -31,7 +31,7 @@ def nan_equal(a, b):
 # ------------------------------------------------------------------ the resize, bit for bit
 @pytest.mark.parametrize('src_dtype', [np.float32, np.float64])
 @pytest.mark.parametrize('src, dst', [((7, 7), (23, 31)), ((49, 49), (90, 160)), ((14, 14), (17, 40)), ((49, 49), (7, 9)),
-                                      ((2, 3), (5, 4))])
+                                      ((2, 3), (5, 4)), ((7, 7), (3, 1600))])
 def test_resize_equals_the_oracle_bit_for_bit(gpu, src, dst, src_dtype):
     x = np.random.RandomState(src[0] * 100 + dst[1]).rand(3, *src).astype(src_dtype)
     want = np.stack([spline_ref.resize(m, dst) for m in x])
