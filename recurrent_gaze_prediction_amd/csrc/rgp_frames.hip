@@ -21,14 +21,14 @@
 #include <climits>
 #include <cstdint>
 
-#include "rgp_host.h"
+#include "image_shared.hip.h"
 
 using namespace rgp;
+using namespace rgp::img;
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kStatusBytes = 64;
 constexpr int kStageBytes = RGP_FRAMES_STAGE_BYTES;
 constexpr int kStageSlack = 64;                       // reads of the last taps' dwords run a few bytes past a chunk
 constexpr int kPrefetch = kStageBytes / (kThreads * 16);
@@ -53,8 +53,6 @@ struct Layout {
   int bands, band_rows, mid_rows, pitch_mid, kt_rows;
   int off_mid, off_kt, off_bh, off_kv, off_bv, total;
 };
-
-inline int align_i(int v, int a) { return (v + a - 1) / a * a; }
 
 // LDS of a workgroup when the out_h rows are cut into nb bands; false if the band's output image exceeds the staging area
 bool layout_for(int fh, int fw, int out_h, int out_w, int ksize_h, int ksize_v, int nb, Layout* L) {
@@ -108,11 +106,7 @@ bool plan(int fh, int fw, int out_h, int out_w, int ksize_h, int ksize_v, int n_
   return false;
 }
 
-__device__ __forceinline__ float quiet_nanf() { return __int_as_float(0x7fc00000); }
-
 __device__ __forceinline__ int band_of_row(int r, int nb, int out_h) { return ((r + 1) * nb - 1) / out_h; }
-
-__device__ __forceinline__ int clip8(int acc) { return min(max((acc + (1 << 21)) >> 22, 0), 255); }
 
 __device__ __forceinline__ int mad24(unsigned byte, int k, int acc) { return __mul24((int)byte, k) + acc; }
 
@@ -122,17 +116,7 @@ __device__ __forceinline__ void store_band(const FramesParams& p, const unsigned
     float* dst = p.images + e0;
     for (int e = tid; e < n_bytes; e += kThreads) dst[e] = src ? (float)src[e] * 0.003921569f : quiet_nanf();
   }
-  if (p.images_u8) {
-    unsigned char* dst = p.images_u8 + e0;
-    const int head = min((int)((0 - (uintptr_t)dst) & 3), n_bytes), words = (n_bytes - head) >> 2;
-    for (int e = tid; e < head; e += kThreads) dst[e] = src ? src[e] : 0;
-    unsigned* dst32 = (unsigned*)(dst + head);
-    for (int i = tid; i < words; i += kThreads) {
-      const unsigned char* s = src + head + 4 * i;
-      dst32[i] = src ? (unsigned)s[0] | (unsigned)s[1] << 8 | (unsigned)s[2] << 16 | (unsigned)s[3] << 24 : 0u;
-    }
-    for (int e = head + 4 * words + tid; e < n_bytes; e += kThreads) dst[e] = src ? src[e] : 0;
-  }
+  if (p.images_u8) store_lds_bytes<kThreads>(p.images_u8 + e0, src, n_bytes, tid);
 }
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -183,18 +167,15 @@ __global__ __launch_bounds__(kThreads) void frame_images_kernel(const FramesPara
   const int src = p.frame_index ? p.frame_index[f] : f;
   bool bad = src < 0 || src >= p.n_frames;
   if (hpass)
-    for (int xx = tid; xx < out_w; xx += kThreads) {
-      int xmin = p.bh[2 * xx], n = p.bh[2 * xx + 1];
-      if (xmin < 0 || n < 0 || n > p.ksize_h || xmin > fw - n) { bad = true; xmin = 0; n = 0; }
-      sBh[xx] = make_int2(xmin, n);
-    }
+    for (int xx = tid; xx < out_w; xx += kThreads) sBh[xx] = checked_bounds(p.bh, xx, p.ksize_h, fw, bad);
   if (vpass)
     for (int r = tid; r < out_h; r += kThreads) {
-      const int ymin = p.bv[2 * r], n = p.bv[2 * r + 1];
-      if (ymin < 0 || n < 0 || n > p.ksize_v || ymin > fh - n) { bad = true; continue; }
+      bool row_bad = false;
+      const int2 by = checked_bounds(p.bv, r, p.ksize_v, fh, row_bad);
+      if (row_bad) { bad = true; continue; }
       const int b = band_of_row(r, nb, out_h);
-      atomicMin(&sLo[b], ymin);
-      atomicMax(&sHi[b], ymin + n);
+      atomicMin(&sLo[b], by.x);
+      atomicMax(&sHi[b], by.x + by.y);
     }
   if (bad) atomicOr(sBad, 1);
   __syncthreads();
@@ -211,13 +192,7 @@ __global__ __launch_bounds__(kThreads) void frame_images_kernel(const FramesPara
   const int rows_in = max(yb - ya, 0);
 
   // ---- the tables of this band
-  if (hpass) {
-    const int kt_rows = (p.ksize_h + 3) & ~3;
-    for (int i = tid; i < kt_rows * out_w; i += kThreads) {
-      const int xx = i / kt_rows, t = i - xx * kt_rows;
-      sKT[t * out_w + xx] = t < sBh[xx].y ? p.kh[xx * p.ksize_h + t] : 0;
-    }
-  }
+  if (hpass) stage_weights_transposed<kThreads>(sKT, p.kh, sBh, out_w, p.ksize_h, (p.ksize_h + 3) & ~3, tid);   // four taps a step
   if (vpass) {
     for (int rr = tid; rr < br; rr += kThreads) sBv[rr] = make_int2(p.bv[2 * (r0 + rr)] - ya, p.bv[2 * (r0 + rr) + 1]);
     for (int i = tid; i < br * p.ksize_v; i += kThreads) {
@@ -369,16 +344,9 @@ int rgp_frame_images(const rgp_frames_args* a, rgp_stream_t stream) {
   RGP_REQUIRE(a->out_w >= 1 && a->out_w <= RGP_FRAMES_MAX_OUT, "rgp_frame_images: out_w = %d must be in [1, RGP_FRAMES_MAX_OUT = %d]",
               a->out_w, RGP_FRAMES_MAX_OUT);
   const bool hpass = a->fw != a->out_w, vpass = a->fh != a->out_h;
-  if (hpass) {
-    RGP_REQUIRE(a->ksize_h >= 1 && a->ksize_h <= RGP_FRAMES_MAX_KSIZE,
-                "rgp_frame_images: ksize_h = %d must be in [1, RGP_FRAMES_MAX_KSIZE = %d]", a->ksize_h, RGP_FRAMES_MAX_KSIZE);
-    RGP_REQUIRE(a->kh && a->bh, "rgp_frame_images: kh or bh is NULL and fw = %d differs from out_w = %d", a->fw, a->out_w);
-  }
-  if (vpass) {
-    RGP_REQUIRE(a->ksize_v >= 1 && a->ksize_v <= RGP_FRAMES_MAX_KSIZE,
-                "rgp_frame_images: ksize_v = %d must be in [1, RGP_FRAMES_MAX_KSIZE = %d]", a->ksize_v, RGP_FRAMES_MAX_KSIZE);
-    RGP_REQUIRE(a->kv && a->bv, "rgp_frame_images: kv or bv is NULL and fh = %d differs from out_h = %d", a->fh, a->out_h);
-  }
+  const char* cap = "RGP_FRAMES_MAX_KSIZE";
+  if (hpass) RGP_TRY(require_pass("rgp_frame_images", 'h', a->ksize_h, a->kh, a->bh, "fw", a->fw, a->out_w, cap, RGP_FRAMES_MAX_KSIZE));
+  if (vpass) RGP_TRY(require_pass("rgp_frame_images", 'v', a->ksize_v, a->kv, a->bv, "fh", a->fh, a->out_h, cap, RGP_FRAMES_MAX_KSIZE));
   RGP_REQUIRE(a->bands >= 0 && a->bands <= a->out_h, "rgp_frame_images: bands = %d must be in [0, out_h = %d]", a->bands, a->out_h);
   RGP_REQUIRE(a->images || a->images_u8, "rgp_frame_images: images and images_u8 are both NULL: nothing to compute");
   RGP_REQUIRE((long long)a->n_frames * a->fh * a->fw * 3 < RGP_FRAMES_MAX_BYTES,
@@ -388,9 +356,7 @@ int rgp_frame_images(const rgp_frames_args* a, rgp_stream_t stream) {
   RGP_REQUIRE(a->frames != nullptr, "rgp_frame_images: frames is NULL");
   RGP_REQUIRE(a->n_frames >= 1, "rgp_frame_images: n_frames = 0 and n_out = %d", a->n_out);
   RGP_REQUIRE(((size_t)a->images & 3) == 0, "rgp_frame_images: images must be 4-byte aligned");
-  RGP_REQUIRE(a->workspace && a->workspace_bytes >= (size_t)kStatusBytes && ((size_t)a->workspace & 7) == 0,
-              "rgp_frame_images: workspace missing, misaligned or too small (%zu < %d bytes)",
-              a->workspace ? a->workspace_bytes : (size_t)0, kStatusBytes);
+  RGP_TRY(require_workspace("rgp_frame_images", a->workspace, a->workspace_bytes, kStatusBytes));
   Layout L;
   RGP_REQUIRE(plan(a->fh, a->fw, a->out_h, a->out_w, hpass ? a->ksize_h : 0, vpass ? a->ksize_v : 0, a->n_out, a->bands, &L),
               "rgp_frame_images: %d x %d -> %d x %d with ksize_h = %d, ksize_v = %d: not even one output row per band fits "
@@ -409,19 +375,15 @@ int rgp_frame_images(const rgp_frames_args* a, rgp_stream_t stream) {
   p.off_mid = L.off_mid; p.off_kt = L.off_kt; p.off_bh = L.off_bh; p.off_kv = L.off_kv; p.off_bv = L.off_bv;
   hipStream_t s = (hipStream_t)stream;
   RGP_TRY(ensure_dyn_smem((const void*)frame_images_kernel, RGP_FRAMES_LDS_BYTES));
-  RGP_HIP(hipMemsetAsync(a->workspace, 0, kStatusBytes, s));
+  RGP_TRY(clear_status(a->workspace, s));
   hipLaunchKernelGGL(frame_images_kernel, dim3(a->n_out * L.bands), dim3(kThreads), L.total, s, p);
   RGP_HIP(hipGetLastError());
   return RGP_OK;
 }
 
 int rgp_frames_status(const void* workspace, int* refused_out, rgp_stream_t stream) {
-  RGP_REQUIRE(workspace != nullptr, "rgp_frames_status: workspace is NULL");
-  hipStream_t s = (hipStream_t)stream;
-  int refused = 0;
-  RGP_HIP(hipMemcpyAsync(&refused, workspace, sizeof(int), hipMemcpyDeviceToHost, s));
-  RGP_HIP(hipStreamSynchronize(s));
-  if (refused_out) *refused_out = refused;
+  int refused;
+  RGP_TRY(read_status("rgp_frames_status", workspace, refused_out, stream, &refused));
   RGP_REQUIRE(refused == 0,
               "rgp_frame_images: %d output frame(s) refused (a frame_index entry outside [0, n_frames), or a bounds table entry "
               "out of range): NaN in images, 0 in images_u8", refused);

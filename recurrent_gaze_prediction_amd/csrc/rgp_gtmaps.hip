@@ -20,16 +20,16 @@
 // behind `labels` has an order of its own (fixed: the same bits on every launch geometry).
 #include <cmath>
 
-#include "rgp_host.h"
+#include "image_shared.hip.h"
 
 using namespace rgp;
+using namespace rgp::img;
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxPix = RGP_GTMAPS_MAX_PIX;
 constexpr int kMaxRadius = RGP_GTMAPS_MAX_RADIUS;
-constexpr int kStatusBytes = 64;
 
 struct GtmapsParams {
   const int *frame_ptr, *samples;
@@ -38,17 +38,6 @@ struct GtmapsParams {
   float *gaze, *fix, *labels;
   int* status;
 };
-
-__device__ __forceinline__ float quiet_nanf() { return __int_as_float(0x7fc00000); }
-
-// scipy's `reflect` (d c b a | a b c d | d c b a) at any distance from the line of n entries
-__device__ __forceinline__ int reflect(int j, int n) {
-  if ((unsigned)j < (unsigned)n) return j;
-  const int period = 2 * n;
-  int m = j % period;
-  if (m < 0) m += period;
-  return m < n ? m : period - 1 - m;
-}
 
 // one output of correlate1d with a symmetric kernel: entry l of the line src[base + k*stride], k < n
 __device__ __forceinline__ float filter_tap_sum(const float* src, int base, int stride, int l, int n, const double* w, int r) {
@@ -65,7 +54,7 @@ __global__ __launch_bounds__(kThreads) void gazemaps_from_fixations_kernel(const
   __shared__ float sA[kMaxPix], sB[kMaxPix];
   __shared__ double sW[2 * kMaxRadius + 1];
   __shared__ double sRed[4];
-  __shared__ float sMin[4], sMax[4];
+  __shared__ float sMinMax[2 * (kThreads / 64)];
   __shared__ int sBad;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -79,14 +68,14 @@ __global__ __launch_bounds__(kThreads) void gazemaps_from_fixations_kernel(const
 
   // ---- scatter: every value is checked before it addresses LDS
   const int beg = p.frame_ptr[n], end = p.frame_ptr[n + 1];
-  if (beg < 0 || end < beg) {
+  if (frame_ptr_bad(beg, end)) {
     if (tid == 0) sBad = 1;
   } else {
     const double f1 = (double)S1 - 1.0, g1 = (double)p.d1 - 1.0, f2 = (double)S2 - 1.0, g2 = (double)p.d2 - 1.0;
     for (int i = beg + tid; i < end; i += kThreads) {
       const int* row = p.samples + (long long)i * 3;
       const int u = row[0], a = row[1], b = row[2];
-      if (u < 0 || u >= p.n_obs || a < 0 || a >= p.d1 || b < 0 || b >= p.d2) { atomicOr(&sBad, 1); continue; }
+      if (sample_bad(u, a, b, p.n_obs, p.d1, p.d2)) { atomicOr(&sBad, 1); continue; }
       const int a_ = (int)(rint((double)a * f1 / g1) + 1e-9);
       const int b_ = (int)(rint((double)b * f2 / g2) + 1e-9);
       if (a_ < 0 || a_ >= S1 || b_ < 0 || b_ >= S2) { atomicOr(&sBad, 1); continue; }   // cannot happen for a, b in range
@@ -121,7 +110,7 @@ __global__ __launch_bounds__(kThreads) void gazemaps_from_fixations_kernel(const
     sB[c] = filter_tap_sum(sA, x, S1, y, S2, sW, r);
   }
   __syncthreads();
-  float mn = INFINITY, mx = -INFINITY;
+  float mn = pos_inf(), mx = neg_inf();
   for (int c = tid; c < n_pix; c += kThreads) {
     const int y = c / S1, x = c - y * S1;
     const float g = filter_tap_sum(sB, y * S1, 1, x, S1, sW, r);
@@ -129,15 +118,7 @@ __global__ __launch_bounds__(kThreads) void gazemaps_from_fixations_kernel(const
     mn = fminf(mn, g);
     mx = fmaxf(mx, g);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, o));
-    mx = fmaxf(mx, __shfl_xor(mx, o));
-  }
-  if (lane == 0) { sMin[wave] = mn; sMax[wave] = mx; }
-  __syncthreads();
-  mn = fminf(fminf(sMin[0], sMin[1]), fminf(sMin[2], sMin[3]));
-  mx = fmaxf(fmaxf(sMax[0], sMax[1]), fmaxf(sMax[2], sMax[3]));
+  block_minmax<kThreads / 64>(mn, mx, sMinMax);
 
   // ---- g -= min(g); g /= max(g) unless the frame sums to 0.  The filtered values are sums of products of
   // non-negative numbers, so their fp32 sum is 0 exactly when the largest of them is.
@@ -190,9 +171,7 @@ int rgp_gazemaps_from_fixations(const rgp_gtmaps_args* a, rgp_stream_t stream) {
               a->out_s2, a->out_s1, RGP_GTMAPS_MAX_PIX);
   RGP_REQUIRE(a->radius >= 0 && a->radius <= RGP_GTMAPS_MAX_RADIUS,
               "rgp_gazemaps_from_fixations: radius = %d must be in [0, RGP_GTMAPS_MAX_RADIUS = %d]", a->radius, RGP_GTMAPS_MAX_RADIUS);
-  RGP_REQUIRE(a->workspace && a->workspace_bytes >= (size_t)kStatusBytes && ((size_t)a->workspace & 7) == 0,
-              "rgp_gazemaps_from_fixations: workspace missing, misaligned or too small (%zu < %d bytes)",
-              a->workspace ? a->workspace_bytes : (size_t)0, kStatusBytes);
+  RGP_TRY(require_workspace("rgp_gazemaps_from_fixations", a->workspace, a->workspace_bytes, kStatusBytes));
 
   GtmapsParams p{};
   p.frame_ptr = a->frame_ptr; p.samples = a->samples; p.weights = a->weights;
@@ -201,18 +180,15 @@ int rgp_gazemaps_from_fixations(const rgp_gtmaps_args* a, rgp_stream_t stream) {
   p.gaze = a->gazemaps; p.fix = a->fixationmaps; p.labels = a->labels;
   p.status = (int*)a->workspace;
   hipStream_t s = (hipStream_t)stream;
-  RGP_HIP(hipMemsetAsync(a->workspace, 0, kStatusBytes, s));
+  RGP_TRY(clear_status(a->workspace, s));
   hipLaunchKernelGGL(gazemaps_from_fixations_kernel, dim3(a->n_frames), dim3(kThreads), 0, s, p);
   RGP_HIP(hipGetLastError());
   return RGP_OK;
 }
 
 int rgp_gtmaps_status(const void* workspace, rgp_stream_t stream) {
-  RGP_REQUIRE(workspace != nullptr, "rgp_gtmaps_status: workspace is NULL");
-  hipStream_t s = (hipStream_t)stream;
-  int refused = 0;
-  RGP_HIP(hipMemcpyAsync(&refused, workspace, sizeof(int), hipMemcpyDeviceToHost, s));
-  RGP_HIP(hipStreamSynchronize(s));
+  int refused;
+  RGP_TRY(read_status("rgp_gtmaps_status", workspace, nullptr, stream, &refused));
   RGP_REQUIRE(refused == 0,
               "rgp_gazemaps_from_fixations: %d frame(s) refused (a sample's observer, a or b out of range, or a bad frame_ptr "
               "pair): their outputs are NaN", refused);

@@ -37,14 +37,14 @@
 #include <climits>
 #include <cmath>
 
-#include "rgp_host.h"
+#include "image_shared.hip.h"
 
 using namespace rgp;
+using namespace rgp::img;
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kStatusBytes = 64;
 constexpr int kLdsRadius = RGP_GTMAPS_FULL_LDS_RADIUS;
 constexpr int kP1Cols = 64, kP1Rows = 64;       // pass 1: 64 columns x 64 rows per workgroup, (64 + 2 * 76) x 64 staged
 constexpr int kP2Cols = 64, kP2Rows = 64;       // pass 2 in LDS: 64 rows x 64 columns, 64 x (64 + 2 * 76) staged
@@ -67,17 +67,6 @@ struct FullParams {
   float* plane;                                                // [N][d2 * d1], between the passes
 };
 
-__device__ __forceinline__ float quiet_nanf() { return __int_as_float(0x7fc00000); }
-
-// scipy's `reflect` (d c b a | a b c d | d c b a) at any distance from the line of n entries
-__device__ __forceinline__ int reflect(int j, int n) {
-  if ((unsigned)j < (unsigned)n) return j;
-  const int period = 2 * n;
-  int m = j % period;
-  if (m < 0) m += period;
-  return m < n ? m : period - 1 - m;
-}
-
 __device__ __forceinline__ bool column_has_sample(const unsigned* bits, int x) { return (bits[x >> 5] >> (x & 31)) & 1u; }
 
 // ---- 1. scatter: every value is checked before it addresses memory
@@ -87,7 +76,7 @@ __global__ __launch_bounds__(kThreads) void gtmaps_full_scatter_kernel(const Ful
   if (tid == 0) sBad = 0;
   __syncthreads();
   const int beg = p.frame_ptr[n], end = p.frame_ptr[n + 1];
-  if (beg < 0 || end < beg) {
+  if (frame_ptr_bad(beg, end)) {
     if (tid == 0) sBad = 1;
   } else {
     unsigned* mask = p.mask + (long long)n * p.d1 * p.d2;
@@ -95,7 +84,7 @@ __global__ __launch_bounds__(kThreads) void gtmaps_full_scatter_kernel(const Ful
     for (int i = beg + tid; i < end; i += kThreads) {
       const int* row = p.samples + (long long)i * 3;
       const int u = row[0], a = row[1], b = row[2];
-      if (u < 0 || u >= p.n_obs || a < 0 || a >= p.d1 || b < 0 || b >= p.d2) { atomicOr(&sBad, 1); continue; }
+      if (sample_bad(u, a, b, p.n_obs, p.d1, p.d2)) { atomicOr(&sBad, 1); continue; }
       atomicOr(&mask[b * p.d1 + a], 1u << u);
       atomicOr(&cols[a >> 5], 1u << (a & 31));
     }
@@ -198,7 +187,7 @@ __global__ __launch_bounds__(kThreads) void gtmaps_full_pass2_lds_kernel(const F
   __shared__ float sB[kP2Rows * kPitchMax];
   __shared__ float sOut[kP2Rows * kOutPitch];
   __shared__ unsigned sCol[kP2Cols + 2 * kLdsRadius];
-  __shared__ float sMin[kThreads / 64], sMax[kThreads / 64];
+  __shared__ float sMinMax[2 * (kThreads / 64)];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   constexpr int kWaves = kThreads / 64;
   const int tiles = tiles_x * tiles_y;
@@ -247,7 +236,7 @@ __global__ __launch_bounds__(kThreads) void gtmaps_full_pass2_lds_kernel(const F
     sOut[lane * kOutPitch + j] = (float)tmp;
   }
   __syncthreads();
-  float mn = INFINITY, mx = 0.0f;
+  float mn = pos_inf(), mx = 0.0f;
   if (lane < x_end)
     for (int ry = wave; ry < y_end; ry += kWaves) {
       const float g = sOut[ry * kOutPitch + lane];
@@ -255,16 +244,8 @@ __global__ __launch_bounds__(kThreads) void gtmaps_full_pass2_lds_kernel(const F
       mn = fminf(mn, g);
       mx = fmaxf(mx, g);
     }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, o));
-    mx = fmaxf(mx, __shfl_xor(mx, o));
-  }
-  if (lane == 0) { sMin[wave] = mn; sMax[wave] = mx; }
-  __syncthreads();
+  block_minmax<kThreads / 64>(mn, mx, sMinMax);
   if (tid == 0) {   // every tile holds at least one cell, so mn is finite here
-    mn = fminf(fminf(sMin[0], sMin[1]), fminf(sMin[2], sMin[3]));
-    mx = fmaxf(fmaxf(sMax[0], sMax[1]), fmaxf(sMax[2], sMax[3]));
     atomicMax(&p.max_bits[n], __float_as_uint(mx));
     atomicMax(&p.negmin_bits[n], ~__float_as_uint(mn));
   }
@@ -312,8 +293,8 @@ __global__ __launch_bounds__(kThreads) void gtmaps_full_pass1_direct_kernel(cons
 
 // ---- 3'. pass 2 at a radius above kLdsRadius; a tile none of whose taps' columns has a sample is +0
 __global__ __launch_bounds__(kThreads) void gtmaps_full_pass2_direct_kernel(const FullParams p, int tiles_x, int tiles_y) {
-  __shared__ float sMin[kThreads / 64], sMax[kThreads / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tx = tid & (kDirCols - 1), tg = tid / kDirCols;
+  __shared__ float sMinMax[2 * (kThreads / 64)];
+  const int tid = threadIdx.x, tx = tid & (kDirCols - 1), tg = tid / kDirCols;
   constexpr int kRowStep = kThreads / kDirCols;
   const int tiles = tiles_x * tiles_y;
   const int n = blockIdx.x / tiles, t = blockIdx.x - n * tiles;
@@ -334,7 +315,7 @@ __global__ __launch_bounds__(kThreads) void gtmaps_full_pass2_direct_kernel(cons
   }
   const float* plane = p.plane + fo;
   const double* __restrict__ w = p.weights;
-  float mn = INFINITY, mx = 0.0f;
+  float mn = pos_inf(), mx = 0.0f;
   if (x < D1)
     for (int ry = tg; ry < y_end; ry += kRowStep) {
       const float* line = plane + (y0 + ry) * D1;
@@ -345,16 +326,8 @@ __global__ __launch_bounds__(kThreads) void gtmaps_full_pass2_direct_kernel(cons
       mn = fminf(mn, g);
       mx = fmaxf(mx, g);
     }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, o));
-    mx = fmaxf(mx, __shfl_xor(mx, o));
-  }
-  if (lane == 0) { sMin[wave] = mn; sMax[wave] = mx; }
-  __syncthreads();
+  block_minmax<kThreads / 64>(mn, mx, sMinMax);
   if (tid == 0) {
-    mn = fminf(fminf(sMin[0], sMin[1]), fminf(sMin[2], sMin[3]));
-    mx = fmaxf(fmaxf(sMax[0], sMax[1]), fmaxf(sMax[2], sMax[3]));
     atomicMax(&p.max_bits[n], __float_as_uint(mx));
     atomicMax(&p.negmin_bits[n], ~__float_as_uint(mn));
   }
@@ -432,9 +405,7 @@ int rgp_gazemaps_full_from_fixations(const rgp_gtmaps_full_args* a, rgp_stream_t
               RGP_GTMAPS_FULL_MAX_RADIUS);
   const int N = a->n_frames, D1 = a->raw_d1, D2 = a->raw_d2;
   const size_t need = rgp_gtmaps_full_workspace_bytes(N, D1, D2);
-  RGP_REQUIRE(a->workspace && a->workspace_bytes >= need && ((size_t)a->workspace & 7) == 0,
-              "rgp_gazemaps_full_from_fixations: workspace missing, misaligned or too small (%zu < %zu bytes)",
-              a->workspace ? a->workspace_bytes : (size_t)0, need);
+  RGP_TRY(require_workspace("rgp_gazemaps_full_from_fixations", a->workspace, a->workspace_bytes, need));
   const bool lds = a->radius <= kLdsRadius;
   const int p2c = lds ? kP2Cols : kDirCols, p2r = lds ? kP2Rows : kDirRows;
   const int t1x = (D1 + kP1Cols - 1) / kP1Cols, t1y = (D2 + kP1Rows - 1) / kP1Rows;
@@ -476,12 +447,8 @@ int rgp_gazemaps_full_from_fixations(const rgp_gtmaps_full_args* a, rgp_stream_t
 }
 
 int rgp_gtmaps_full_status(const void* workspace, int* refused_out, rgp_stream_t stream) {
-  RGP_REQUIRE(workspace != nullptr, "rgp_gtmaps_full_status: workspace is NULL");
-  hipStream_t s = (hipStream_t)stream;
-  int refused = 0;
-  RGP_HIP(hipMemcpyAsync(&refused, workspace, sizeof(int), hipMemcpyDeviceToHost, s));
-  RGP_HIP(hipStreamSynchronize(s));
-  if (refused_out) *refused_out = refused;
+  int refused;
+  RGP_TRY(read_status("rgp_gtmaps_full_status", workspace, refused_out, stream, &refused));
   RGP_REQUIRE(refused == 0,
               "rgp_gazemaps_full_from_fixations: %d frame(s) refused (a sample's observer, a or b out of range, or a bad "
               "frame_ptr pair): their outputs are NaN", refused);

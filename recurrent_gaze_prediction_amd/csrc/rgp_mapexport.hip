@@ -3,10 +3,8 @@
 // (evaluate_gaze.py:148-152), for n fp32 maps [n, H, W] in ONE launch.
 //
 // Per map (scipy <= 1.2, a NumPy before NEP 50):
-//   bytescale   cmin, cmax fp32; cscale = cmax - cmin in fp32, 1 if that is 0; scale = float32(255.0 / float64(cscale));
-//               b = (a - cmin) * scale, an fp32 subtract and an fp32 multiply; u = uint8(trunc(clip(b, 0, 255) + 0.5f)).
-//               A NaN b (0 * inf, when 255 / cscale overflows fp32) gives byte 0, as the x86 conversion does.
-//   imresize    Pillow's 8-bit resample of one channel with host-made 22-bit tables (frames.resample_coeffs):
+//   bytescale   between the map's own fp32 min and max: image_shared.hip.h states the rule (bytescale_scale / _byte).
+//   imresize   Pillow's 8-bit resample of one channel with host-made 22-bit tables (frames.resample_coeffs):
 //               horizontal, then vertical on the 8-bit intermediate; a pass with in == out is skipped.
 //   normalise   p = float64(resized) / float64(sum of the resized bytes): an exact integer sum and one IEEE division;
 //               a zero sum gives NaN in every cell, as NumPy's 0 / 0 does.
@@ -17,19 +15,19 @@
 // a map of H * W * 4 bytes starts at no better alignment), keeps it in LDS while the lanes reduce min, max and the
 // finite test across the wave, writes the bytes to LDS, resamples from LDS to LDS and divides.  DS operations of one
 // wave execute in order, so a wave barrier that only stops the compiler from reordering separates the phases.  Byte
-// outputs leave as aligned dwords with single bytes at the two ends.  No scratch, no float atomics.
+// outputs leave as aligned dwords with single bytes at the two ends (store_bytes).  No scratch, no float atomics.
 #include <climits>
 #include <cstdint>
 
-#include "rgp_host.h"
+#include "image_shared.hip.h"
 
 using namespace rgp;
+using namespace rgp::img;
 
 namespace {
 
 constexpr int kWaves = 4;
 constexpr int kThreads = 64 * kWaves;
-constexpr int kStatusBytes = 64;
 constexpr int kHeadBytes = 16;                         // the flag of the bounds check
 constexpr int kMaxSide = RGP_MAPEXPORT_MAX_SIDE;
 
@@ -48,8 +46,6 @@ struct MapExportParams {
 struct Layout {
   int taps_h, taps_v, off_kv, off_bh, off_bv, off_wave, wave_bytes, off_bytes, off_mid, off_out, total;
 };
-
-inline int align_i(int v, int a) { return (v + a - 1) / a * a; }
 
 // resize: pooled or pooled_u8 is wanted.  A table row holds ksize entries of which the first n <= min(ksize, in) count.
 Layout layout_for(int h, int w, int out_h, int out_w, int ksize_h, int ksize_v, bool resize) {
@@ -83,10 +79,6 @@ static_assert(kHeadBytes + 2 * kMaxSide * kMaxSide * 4 + 2 * kMaxSide * 8 + 16 +
               kWaves * (kMaxSide * kMaxSide * 4 + 3 * kMaxSide * kMaxSide) <= RGP_MAPEXPORT_LDS_BYTES, "the worst case fits");
 static_assert(RGP_MAPEXPORT_LDS_BYTES <= 160 * 1024, "LDS of a CU");
 
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-__device__ __forceinline__ int clip8(unsigned acc) { return min(max(((int)acc + (1 << 21)) >> 22, 0), 255); }
-
 // DS operations of one wave execute in order; the compiler must not move LDS reads above the other lanes' writes
 __device__ __forceinline__ void wave_sync() {
   asm volatile("" ::: "memory");
@@ -94,7 +86,8 @@ __device__ __forceinline__ void wave_sync() {
   asm volatile("" ::: "memory");
 }
 
-// n_bytes of one map's byte output from the wave's LDS bytes `src` (null: a refused map, 0)
+// store_lds_bytes (image_shared.hip.h) for one wave, the ends as loops: with `if (lane < head)` there the launch of 1024
+// maps measured 0.3 us (1.5 %) above the parent's, with loops it is equal (profiles/image_shared_ab.txt)
 __device__ __forceinline__ void store_bytes(unsigned char* dst, const unsigned char* src, int n_bytes, int lane) {
   const int head = min((int)((0 - (uintptr_t)dst) & 3), n_bytes), words = (n_bytes - head) >> 2;
   for (int e = lane; e < head; e += 64) dst[e] = src ? src[e] : 0;
@@ -125,28 +118,14 @@ __global__ __launch_bounds__(kThreads) void mapexport_kernel(const MapExportPara
     __syncthreads();
     bool bad = false;
     if (hpass)
-      for (int xx = tid; xx < out_w; xx += kThreads) {
-        int xmin = p.bh[2 * xx], n = p.bh[2 * xx + 1];
-        if (xmin < 0 || n < 0 || n > p.ksize_h || xmin > w - n) { bad = true; xmin = 0; n = 0; }
-        sBh[xx] = make_int2(xmin, n);
-      }
+      for (int xx = tid; xx < out_w; xx += kThreads) sBh[xx] = checked_bounds(p.bh, xx, p.ksize_h, w, bad);
     if (vpass)
-      for (int yy = tid; yy < out_h; yy += kThreads) {
-        int ymin = p.bv[2 * yy], n = p.bv[2 * yy + 1];
-        if (ymin < 0 || n < 0 || n > p.ksize_v || ymin > h - n) { bad = true; ymin = 0; n = 0; }
-        sBv[yy] = make_int2(ymin, n);
-      }
+      for (int yy = tid; yy < out_h; yy += kThreads) sBv[yy] = checked_bounds(p.bv, yy, p.ksize_v, h, bad);
     if (bad) atomicOr(sBad, 1);
     __syncthreads();
     // n <= ksize and xmin + n <= in: n <= taps = min(ksize, in), the rows the LDS table has
-    for (int i = tid; i < out_w * p.taps_h; i += kThreads) {
-      const int xx = i / p.taps_h, t = i - xx * p.taps_h;
-      sKh[t * out_w + xx] = t < sBh[xx].y ? p.kh[xx * p.ksize_h + t] : 0;
-    }
-    for (int i = tid; i < out_h * p.taps_v; i += kThreads) {
-      const int yy = i / p.taps_v, t = i - yy * p.taps_v;
-      sKv[t * out_h + yy] = t < sBv[yy].y ? p.kv[yy * p.ksize_v + t] : 0;
-    }
+    stage_weights_transposed<kThreads>(sKh, p.kh, sBh, out_w, p.ksize_h, p.taps_h, tid);
+    stage_weights_transposed<kThreads>(sKv, p.kv, sBv, out_h, p.ksize_v, p.taps_v, tid);
     __syncthreads();
   }
 
@@ -160,20 +139,17 @@ __global__ __launch_bounds__(kThreads) void mapexport_kernel(const MapExportPara
   unsigned char* sOut = area + p.off_out;
 
   const float* g = p.maps + m * HW;
-  float mn = __int_as_float(0x7f800000), mx = __int_as_float(0xff800000);
+  float mn = pos_inf(), mx = neg_inf();
   bool finite = true;
 #pragma unroll 8
   for (int i = lane; i < HW; i += 64) {
     const float v = g[i];
     sMap[i] = v;
-    finite = finite && (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u;
+    finite = finite && finite_f(v);
     mn = fminf(mn, v);
     mx = fmaxf(mx, v);
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, o));
-    mx = fmaxf(mx, __shfl_xor(mx, o));
-  }
+  wave_minmax(mn, mx);
   const bool refused = __ballot(!finite) != 0ull || ((hpass || vpass) && *sBad != 0);
   if (refused) {   // a NaN or an Inf in the map, or a bounds table entry out of range: NaN and 0, counted
     if (p.pooled)
@@ -185,15 +161,8 @@ __global__ __launch_bounds__(kThreads) void mapexport_kernel(const MapExportPara
   }
 
   // ---- 3. bytescale: every lane reads back the cells it wrote
-  float cscale = mx - mn;
-  if (cscale == 0.f) cscale = 1.f;
-  const float scale = (float)(255.0 / (double)cscale);
-  for (int i = lane; i < HW; i += 64) {
-    float b = (sMap[i] - mn) * scale;
-    if (!(b >= 0.f)) b = 0.f;              // below 0, and NaN = 0 * inf
-    if (b > 255.f) b = 255.f;
-    sBytes[i] = (unsigned char)(int)(b + 0.5f);
-  }
+  const float scale = bytescale_scale(mn, mx);
+  for (int i = lane; i < HW; i += 64) sBytes[i] = bytescale_byte(sMap[i], mn, scale);
   wave_sync();
   if (p.bytes) store_bytes(p.bytes + m * HW, sBytes, HW, lane);
   if (!resize) return;
@@ -207,7 +176,7 @@ __global__ __launch_bounds__(kThreads) void mapexport_kernel(const MapExportPara
       const unsigned char* s = sBytes + y * w + bx.x;
       unsigned acc = 0;
       for (int t = 0; t < bx.y; ++t) acc += (unsigned)s[t] * (unsigned)sKh[t * out_w + xx];
-      sMid[item] = (unsigned char)clip8(acc);
+      sMid[item] = (unsigned char)clip8((int)acc);
     }
     wave_sync();
     src = sMid;
@@ -219,7 +188,7 @@ __global__ __launch_bounds__(kThreads) void mapexport_kernel(const MapExportPara
       const unsigned char* s = src + by.x * out_w + xx;
       unsigned acc = 0;
       for (int t = 0; t < by.y; ++t) acc += (unsigned)s[t * out_w] * (unsigned)sKv[t * out_h + yy];
-      sOut[item] = (unsigned char)clip8(acc);
+      sOut[item] = (unsigned char)clip8((int)acc);
     }
     wave_sync();
     src = sOut;
@@ -255,22 +224,13 @@ int rgp_mapexport(const rgp_mapexport_args* a, rgp_stream_t stream) {
     RGP_REQUIRE(a->out_h >= 1 && a->out_h <= a->h, "rgp_mapexport: out_h = %d must be in [1, h = %d]", a->out_h, a->h);
     RGP_REQUIRE(a->out_w >= 1 && a->out_w <= a->w, "rgp_mapexport: out_w = %d must be in [1, w = %d]", a->out_w, a->w);
   }
-  if (hpass) {
-    RGP_REQUIRE(a->ksize_h >= 1 && a->ksize_h <= RGP_MAPEXPORT_MAX_KSIZE,
-                "rgp_mapexport: ksize_h = %d must be in [1, RGP_MAPEXPORT_MAX_KSIZE = %d]", a->ksize_h, RGP_MAPEXPORT_MAX_KSIZE);
-    RGP_REQUIRE(a->kh && a->bh, "rgp_mapexport: kh or bh is NULL and w = %d differs from out_w = %d", a->w, a->out_w);
-  }
-  if (vpass) {
-    RGP_REQUIRE(a->ksize_v >= 1 && a->ksize_v <= RGP_MAPEXPORT_MAX_KSIZE,
-                "rgp_mapexport: ksize_v = %d must be in [1, RGP_MAPEXPORT_MAX_KSIZE = %d]", a->ksize_v, RGP_MAPEXPORT_MAX_KSIZE);
-    RGP_REQUIRE(a->kv && a->bv, "rgp_mapexport: kv or bv is NULL and h = %d differs from out_h = %d", a->h, a->out_h);
-  }
+  const char* cap = "RGP_MAPEXPORT_MAX_KSIZE";
+  if (hpass) RGP_TRY(require_pass("rgp_mapexport", 'h', a->ksize_h, a->kh, a->bh, "w", a->w, a->out_w, cap, RGP_MAPEXPORT_MAX_KSIZE));
+  if (vpass) RGP_TRY(require_pass("rgp_mapexport", 'v', a->ksize_v, a->kv, a->bv, "h", a->h, a->out_h, cap, RGP_MAPEXPORT_MAX_KSIZE));
   RGP_REQUIRE(a->maps != nullptr, "rgp_mapexport: maps is NULL");
   RGP_REQUIRE(((size_t)a->maps & 3) == 0, "rgp_mapexport: maps must be 4-byte aligned");
   RGP_REQUIRE(((size_t)a->pooled & 7) == 0, "rgp_mapexport: pooled must be 8-byte aligned");
-  RGP_REQUIRE(a->workspace && a->workspace_bytes >= (size_t)kStatusBytes && ((size_t)a->workspace & 7) == 0,
-              "rgp_mapexport: workspace missing, misaligned or too small (%zu < %d bytes)",
-              a->workspace ? a->workspace_bytes : (size_t)0, kStatusBytes);
+  RGP_TRY(require_workspace("rgp_mapexport", a->workspace, a->workspace_bytes, kStatusBytes));
   const Layout L = layout_for(a->h, a->w, resize ? a->out_h : a->h, resize ? a->out_w : a->w, hpass ? a->ksize_h : 0,
                               vpass ? a->ksize_v : 0, resize);
   RGP_REQUIRE(L.total <= RGP_MAPEXPORT_LDS_BYTES, "rgp_mapexport: %d bytes of LDS, above RGP_MAPEXPORT_LDS_BYTES = %d", L.total,
@@ -289,19 +249,15 @@ int rgp_mapexport(const rgp_mapexport_args* a, rgp_stream_t stream) {
   p.wave_bytes = L.wave_bytes; p.off_bytes = L.off_bytes; p.off_mid = L.off_mid; p.off_out = L.off_out;
   hipStream_t s = (hipStream_t)stream;
   RGP_TRY(ensure_dyn_smem((const void*)mapexport_kernel, RGP_MAPEXPORT_LDS_BYTES));
-  RGP_HIP(hipMemsetAsync(a->workspace, 0, kStatusBytes, s));
+  RGP_TRY(clear_status(a->workspace, s));
   hipLaunchKernelGGL(mapexport_kernel, dim3((a->n - 1) / kWaves + 1), dim3(kThreads), L.total, s, p);
   RGP_HIP(hipGetLastError());
   return RGP_OK;
 }
 
 int rgp_mapexport_status(const void* workspace, int* refused_out, rgp_stream_t stream) {
-  RGP_REQUIRE(workspace != nullptr, "rgp_mapexport_status: workspace is NULL");
-  hipStream_t s = (hipStream_t)stream;
-  int refused = 0;
-  RGP_HIP(hipMemcpyAsync(&refused, workspace, sizeof(int), hipMemcpyDeviceToHost, s));
-  RGP_HIP(hipStreamSynchronize(s));
-  if (refused_out) *refused_out = refused;
+  int refused;
+  RGP_TRY(read_status("rgp_mapexport_status", workspace, refused_out, stream, &refused));
   RGP_REQUIRE(refused == 0,
               "rgp_mapexport: %d map(s) refused (a NaN or an Inf in the map, or a bounds table entry out of range): NaN in "
               "pooled, 0 in pooled_u8 and bytes", refused);

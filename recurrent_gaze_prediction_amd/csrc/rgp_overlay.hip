@@ -2,9 +2,8 @@
 // [n_src, H, W, 3] that are already in device memory, in the arithmetic the host libraries use, bit for bit:
 //   resize     the order-3 spline of rgp_spline_resize (spline.hip.h; fp64 prefilter and taps, rounded once to fp32);
 //              (h, w) == (H, W) takes the map as it is, as the host's resize does
-//   bytescale  scipy's, as rgp_mapexport.hip states it: cmin, cmax fp32 (of the RESIZED map, or the caller's limits);
-//              cscale = cmax - cmin, 1 if that is 0; scale = float32(255.0 / float64(cscale)); b = (v - cmin) * scale, an
-//              fp32 subtract and an fp32 multiply; u = uint8(trunc(clip(b, 0, 255) + 0.5f)); a NaN b (0 * inf) gives 0
+//   bytescale  scipy's, as image_shared.hip.h states it, between the fp32 min and max of the RESIZED map or the caller's
+//              limits
 //   colour     c = lut[u], the caller's [256, 3] table (matplotlib's cmap(u8, bytes=True)[..., :3])
 //   blend      PIL.Image.blend per byte: alpha 0 the frame's byte, alpha 1 the colour's, otherwise
 //              uint8(trunc(float(f) + alpha * float(c - f))), one fp32 multiply and one fp32 add, NOT fused
@@ -38,10 +37,11 @@
 #include <climits>
 #include <cstdint>
 
-#include "rgp_host.h"
+#include "image_shared.hip.h"
 #include "spline.hip.h"
 
 using namespace rgp;
+using namespace rgp::img;
 
 namespace {
 
@@ -50,7 +50,6 @@ constexpr int kChunk = 4096;          // pixels whose heat bytes wait in LDS bet
 constexpr int kCols = 3, kStrip = 64 * kCols;   // columns per lane / per wave: 4 strips cover 768 columns
 constexpr int kMaxBands = 128;
 constexpr int kBlocksWanted = 3072;   // workgroups aimed at: four rounds of 256 CUs x 3; every one prefilters its map again, so no more (measured: 1024 and 8192 are slower)
-constexpr int kStatusBytes = 64;
 
 struct OverlayParams {
   const unsigned char* frames;
@@ -66,10 +65,6 @@ struct OverlayParams {
   int n, n_src, h, w, H, W, bands, rows_per_band, identity, shared;
   SplineConsts sc;
 };
-
-__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-__device__ __forceinline__ float pos_inf() { return __int_as_float(0x7f800000); }
-__device__ __forceinline__ float neg_inf() { return __int_as_float(0xff800000); }
 
 // map m as fp64 in sC, turned into B-spline coefficients in place; false (for the whole workgroup, and sC is then
 // undefined) if the map holds a NaN or an Inf
@@ -149,22 +144,6 @@ __device__ __forceinline__ void wave_strips(const OverlayParams& p, const double
   }
 }
 
-// min and max over the workgroup, to every thread
-__device__ __forceinline__ void block_minmax(float& mn, float& mx, float* sRed) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, o));
-    mx = fmaxf(mx, __shfl_xor(mx, o));
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) { sRed[wave * 2] = mn; sRed[wave * 2 + 1] = mx; }
-  __syncthreads();
-  mn = sRed[0]; mx = sRed[1];
-#pragma unroll
-  for (int wv = 1; wv < kWaves; ++wv) { mn = fminf(mn, sRed[wv * 2]); mx = fmaxf(mx, sRed[wv * 2 + 1]); }
-}
-
 __device__ __forceinline__ bool frame_index_ok(const OverlayParams& p, long long m, int* fi) {
   *fi = p.frame_idx ? p.frame_idx[m] : (int)m;
   return *fi >= 0 && *fi < p.n_src;
@@ -200,7 +179,7 @@ __global__ __launch_bounds__(kThreads) void overlay_minmax_kernel(const OverlayP
       mx = fmaxf(mx, v);
     });
   }
-  block_minmax(mn, mx, sRed);
+  block_minmax<kWaves>(mn, mx, sRed);
   if (tid == 0) {
     float* q = p.partial + 4ll * blockIdx.x;
     q[0] = good ? mn : pos_inf();
@@ -208,18 +187,6 @@ __global__ __launch_bounds__(kThreads) void overlay_minmax_kernel(const OverlayP
     q[2] = good ? 1.f : 0.f;
     q[3] = 0.f;
   }
-}
-
-// n_bytes at dst by the workgroup: aligned dwords from word_at(e) (bytes e .. e + 3), single bytes from byte_at(e) at the ends
-template <class F1, class F4>
-__device__ __forceinline__ void store_run(unsigned char* dst, int n_bytes, F1&& byte_at, F4&& word_at) {
-  const int tid = threadIdx.x;
-  const int head = min((int)((0 - (uintptr_t)dst) & 3), n_bytes), words = (n_bytes - head) >> 2;
-  if (tid < head) dst[tid] = byte_at(tid);
-  unsigned* dst32 = (unsigned*)(dst + head);
-  for (int i = tid; i < words; i += kThreads) dst32[i] = word_at(head + 4 * i);
-  const int tail = head + 4 * words;
-  if (tid < n_bytes - tail) dst[tail + tid] = byte_at(tail + tid);
 }
 
 // PIL.Image.blend on one byte; mode 0: alpha == 0, 1: alpha == 1
@@ -270,7 +237,7 @@ __global__ __launch_bounds__(kThreads) void overlay_render_kernel(const OverlayP
         }
         if (all) { mn = fminf(mn, lo); mx = fmaxf(mx, hi); }
       }
-      block_minmax(mn, mx, sRed);
+      block_minmax<kWaves>(mn, mx, sRed);
     }
   }
   if (p.limits) {
@@ -279,9 +246,7 @@ __global__ __launch_bounds__(kThreads) void overlay_render_kernel(const OverlayP
     good = good && finite_f(mn) && finite_f(mx) && mx >= mn;
   }
   const bool refused = !good;
-  float cscale = mx - mn;
-  if (cscale == 0.f) cscale = 1.f;
-  const float scale = (float)(255.0 / (double)cscale);
+  const float scale = bytescale_scale(mn, mx);
   const float alpha = p.alpha;
   const int mode = alpha == 0.f ? 0 : (alpha == 1.f ? 1 : 2);
 
@@ -289,23 +254,17 @@ __global__ __launch_bounds__(kThreads) void overlay_render_kernel(const OverlayP
   const int p1 = y1 * p.W;
   const float* g = p.maps + m * HW;                                  // read by the identity path only
   const unsigned char* fr = idx_ok && p.out ? p.frames + (long long)fi * HW * 3 : nullptr;
-  auto heat_byte = [&](float v) -> unsigned char {
-    float b = (v - mn) * scale;
-    if (!(b >= 0.f)) b = 0.f;                                         // below 0, and NaN = 0 * inf
-    if (b > 255.f) b = 255.f;
-    return (unsigned char)(int)(b + 0.5f);
-  };
   const int step = p.W <= kChunk ? kChunk / p.W * p.W : kChunk;       // whole rows where a row fits
   unsigned long long tags = kNoRows;
   __syncthreads();                                                    // sLut
   for (int c0 = y0 * p.W; c0 < p1; c0 += step) {
     const int cn = min(step, p1 - c0);
     if (!refused && p.identity) {
-      for (int i = tid; i < cn; i += kThreads) sU[i] = heat_byte(g[c0 + i]);
+      for (int i = tid; i < cn; i += kThreads) sU[i] = bytescale_byte(g[c0 + i], mn, scale);
     } else if (!refused) {
       auto put = [&](int Y, int X, float v) {
         const int i = Y * p.W + X - c0;
-        if ((unsigned)i < (unsigned)cn) sU[i] = heat_byte(v);
+        if ((unsigned)i < (unsigned)cn) sU[i] = bytescale_byte(v, mn, scale);
       };
       const int Ya = c0 / p.W, Yb = (c0 + cn - 1) / p.W + 1;
       if (p.W <= kChunk) {                                            // whole rows, every strip
@@ -318,16 +277,10 @@ __global__ __launch_bounds__(kThreads) void overlay_render_kernel(const OverlayP
       }
     }
     __syncthreads();
-    if (p.heat)
-      store_run(p.heat + m * HW + c0, cn,
-                [&](int e) -> unsigned char { return refused ? 0 : sU[e]; },
-                [&](int e) -> unsigned {
-                  if (refused) return 0u;
-                  return (unsigned)sU[e] | (unsigned)sU[e + 1] << 8 | (unsigned)sU[e + 2] << 16 | (unsigned)sU[e + 3] << 24;
-                });
+    if (p.heat) store_lds_bytes<kThreads>(p.heat + m * HW + c0, refused ? nullptr : sU, cn, tid);
     if (p.out) {
       const unsigned char* frb = fr ? fr + 3ll * c0 : nullptr;        // byte e of the chunk's output is byte e from here
-      store_run(p.out + (m * HW + c0) * 3, cn * 3,
+      store_run<kThreads>(p.out + (m * HW + c0) * 3, cn * 3, tid,
                 [&](int e) -> unsigned char {
                   const unsigned f = frb ? frb[e] : 0u;
                   if (refused) return (unsigned char)f;
@@ -418,9 +371,7 @@ int rgp_overlay(const rgp_overlay_args* a, void* workspace, size_t workspace_byt
     RGP_REQUIRE(o1 <= f0 || f1 <= o0, "%s: out must not alias frames", fn);
   }
   const size_t need = rgp_overlay_workspace_bytes(n, h, w, H, W);
-  if (!workspace || workspace_bytes < need || ((size_t)workspace & 7) != 0)
-    return set_err(RGP_EWORKSPACE, "%s: workspace missing, misaligned or too small (%zu < %zu bytes)", fn,
-                   workspace ? workspace_bytes : (size_t)0, need);
+  RGP_TRY(require_workspace(fn, workspace, workspace_bytes, need, RGP_EWORKSPACE));
 
   OverlayParams p{};
   p.frames = a->frames; p.frame_idx = a->frame_idx; p.maps = a->maps; p.limits = a->limits; p.lut = a->lut;
@@ -440,7 +391,7 @@ int rgp_overlay(const rgp_overlay_args* a, void* workspace, size_t workspace_byt
   // the caller's limits and a resize: every workgroup of the render sees the whole source map, no first launch
   const bool first = identity || !a->limits;
   p.partial = first ? (float*)(ws + off) : nullptr;
-  RGP_HIP(hipMemsetAsync(workspace, 0, kStatusBytes, s));
+  RGP_TRY(clear_status(workspace, s));
   const dim3 grid((unsigned)(n * B.bands));
   const size_t smem = identity ? 0 : (size_t)h * w * sizeof(double);      // the coefficients: at most 32 KiB
   if (first) {
@@ -453,12 +404,8 @@ int rgp_overlay(const rgp_overlay_args* a, void* workspace, size_t workspace_byt
 }
 
 int rgp_overlay_status(const void* workspace, int* refused_out, rgp_stream_t stream) {
-  RGP_REQUIRE(workspace != nullptr, "rgp_overlay_status: workspace is NULL");
-  hipStream_t s = (hipStream_t)stream;
-  int refused = 0;
-  RGP_HIP(hipMemcpyAsync(&refused, workspace, sizeof(int), hipMemcpyDeviceToHost, s));
-  RGP_HIP(hipStreamSynchronize(s));
-  if (refused_out) *refused_out = refused;
+  int refused;
+  RGP_TRY(read_status("rgp_overlay_status", workspace, refused_out, stream, &refused));
   RGP_REQUIRE(refused == 0,
               "rgp_overlay: %d map(s) refused (a NaN or an Inf in the map, limits that are not finite or descend, or a frame "
               "index out of range): the frame unchanged in out, 0 in heat_u8", refused);

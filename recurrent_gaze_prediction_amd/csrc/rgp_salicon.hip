@@ -11,7 +11,7 @@
 #include <algorithm>
 #include <cstdint>
 
-#include "rgp_host.h"
+#include "image_shared.hip.h"
 #include "kernels_misc.hip.h"
 
 using namespace rgp;
@@ -34,8 +34,6 @@ struct SaliconParams {
   int* status;
   int n, hw, band_rows, bands;
 };
-
-__device__ __forceinline__ float quiet_nanf() { return __int_as_float(0x7fc00000); }
 
 // One job = a run of whole rows of one sample (a band of its image, or its whole map): `nbytes` contiguous source bytes
 // become `nbytes` contiguous floats.  The source run is copied to LDS at the same offset within a 16-byte unit it has in
@@ -60,7 +58,7 @@ __device__ __forceinline__ void salicon_job(const unsigned char* __restrict__ sr
   const int pixels = row / C;
   // the byte of output element e: the same place, or the mirrored pixel of its row with the channel order kept
   auto pick = [&](int e) -> float {
-    if (!src) return quiet_nanf();
+    if (!src) return img::quiet_nanf();
     int at = e;
     if (flipped) {
       const int r = e / row, c = e - r * row;
@@ -202,12 +200,8 @@ int rgp_salicon_batch(const rgp_salicon_batch_args* a, rgp_stream_t stream) {
 }
 
 int rgp_salicon_status(const void* workspace, int* refused_out, rgp_stream_t stream) {
-  RGP_REQUIRE(workspace != nullptr, "rgp_salicon_status: workspace is NULL");
-  hipStream_t s = (hipStream_t)stream;
-  int refused = 0;
-  RGP_HIP(hipMemcpyAsync(&refused, workspace, sizeof(int), hipMemcpyDeviceToHost, s));
-  RGP_HIP(hipStreamSynchronize(s));
-  if (refused_out) *refused_out = refused;
+  int refused;
+  RGP_TRY(img::read_status("rgp_salicon_status", workspace, refused_out, stream, &refused));
   RGP_REQUIRE(refused == 0, "rgp_salicon_batch: %d sample(s) refused (an index entry outside [0, n)): NaN in images and maps", refused);
   return RGP_OK;
 }

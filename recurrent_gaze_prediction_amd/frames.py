@@ -22,7 +22,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _image, _lib
 
 PRECISION_BITS = 22
 FILTER_SUPPORT = {'lanczos': 3.0, 'bilinear': 1.0, 'bicubic': 2.0}
@@ -133,21 +133,8 @@ def frame_images(frames, out_hw=(98, 98), frame_index=None, filter='lanczos', ou
     if filter not in FILTER_SUPPORT:
         raise ValueError('filter = %r: choose from %s' % (filter, sorted(FILTER_SUPPORT)))
     oh, ow = (int(v) for v in out_hw)
-    if torch.is_tensor(frames):
-        if frames.dtype != torch.uint8 or frames.dim() != 4:
-            raise ValueError('frames must be uint8 [N, H, W, 3]')
-        if frames.is_cuda and not frames.is_contiguous():
-            raise ValueError('a device tensor of frames must be contiguous')
-        dev = frames.device if frames.is_cuda else torch.device('cuda:0' if device is None else device)
-        x = frames.contiguous().to(dev)
-    else:
-        a = np.asarray(frames)
-        if a.dtype != np.uint8 or a.ndim != 4:
-            raise ValueError('frames must be uint8 [N, H, W, 3]')
-        dev = torch.device('cuda:0' if device is None else device)
-        x = None
-    shape = tuple(frames.shape)
-    N, H, W, C = (int(v) for v in shape)
+    N, H, W, C = _image.host_check(frames, 'frames', torch.uint8, 4, text='frames must be uint8 [N, H, W, 3]')
+    dev = _image.own_device(frames, device)
     if C != 3:
         raise ValueError('frames of %d channels: the kernel covers 3' % C)
     if not (1 <= oh <= MAX_OUT and 1 <= ow <= MAX_OUT):
@@ -179,8 +166,7 @@ def frame_images(frames, out_hw=(98, 98), frame_index=None, filter='lanczos', ou
         kh, bh, ksh = _device_tables(dev, W, ow, filter)
     if H != oh:
         kv, bv, ksv = _device_tables(dev, H, oh, filter)
-    if x is None:
-        x = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    x = _image.to_device(frames, dev)
     f32 = torch.empty((n, oh, ow, 3), dtype=torch.float32, device=dev) if out in ('float32', 'both') else None
     u8 = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev) if out in ('uint8', 'both') else None
     result = f32 if out == 'float32' else u8 if out == 'uint8' else (f32, u8)
@@ -188,23 +174,12 @@ def frame_images(frames, out_hw=(98, 98), frame_index=None, filter='lanczos', ou
         return result
     d_idx = idx.to(torch.int32).to(dev).contiguous() if idx is not None else None
     lib = _lib.load()
-    ws = torch.empty(max(int(lib.rgp_frames_workspace_bytes()), 64), dtype=torch.uint8, device=dev)
-
-    def ptr(t):
-        return t.data_ptr() if t is not None else None
+    ws, ptr = _image.workspace(lib.rgp_frames_workspace_bytes(), dev), _image.ptr
     args = _lib.FramesArgs(frames=x.data_ptr(), n_frames=N, fh=H, fw=W, frame_index=ptr(d_idx), n_out=n, out_h=oh, out_w=ow,
                            kh=ptr(kh), bh=ptr(bh), ksize_h=ksh, kv=ptr(kv), bv=ptr(bv), ksize_v=ksv, bands=int(bands or 0),
                            images=ptr(f32), images_u8=ptr(u8), workspace=ws.data_ptr(), workspace_bytes=ws.numel())
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.rgp_frame_images(ctypes.byref(args), stream)
-        if rc == 0:
-            rc = lib.rgp_frames_status(ws.data_ptr(), None, stream)
-    try:
-        _lib.check(rc)
-    except _lib.RgpError as err:
-        err.outputs = result
-        raise
+    _image.launch(dev, lambda s: lib.rgp_frame_images(ctypes.byref(args), s),
+                  lambda s: lib.rgp_frames_status(ws.data_ptr(), None, s), result)
     return result
 
 

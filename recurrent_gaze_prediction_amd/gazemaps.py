@@ -28,7 +28,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _image, _lib
 
 # (S1, S2) -> sigma (crc_input_data_seq.py:225-236)
 SIGMA_FOR_SHAPE = {(49, 49): 2.0, (48, 48): 2.0, (14, 14): 0.6, (7, 7): 0.3}
@@ -139,6 +139,30 @@ def pack_fixations(observers, raw_shape, frames='reference', fill_missing=False)
     return PackedFixations(frame_ptr.astype(np.int32), samples, len(obs), (D1, D2))
 
 
+def _check_packed(packed):
+    """-> (frame_ptr int32 [N + 1], samples int32 [n, 3], n_observers, (D1, D2), N) of packed fixations; the refusals
+    the host can make about them, which both fixation entries share."""
+    frame_ptr, samples, n_observers, raw_shape = packed
+    D1, D2 = (int(v) for v in raw_shape)
+    if D1 < 2 or D2 < 2:
+        raise ValueError('raw_shape %s: both extents must be at least 2' % ((D1, D2),))
+    n_observers = int(n_observers)
+    if not 1 <= n_observers <= MAX_OBSERVERS:
+        raise ValueError('%d observers: must be in [1, RGP_GTMAPS_MAX_OBSERVERS = %d]' % (n_observers, MAX_OBSERVERS))
+    frame_ptr = np.ascontiguousarray(frame_ptr, np.int32).reshape(-1)
+    samples = np.ascontiguousarray(samples, np.int32).reshape(-1, 3)
+    N = len(frame_ptr) - 1
+    if N < 0 or frame_ptr[0] != 0 or np.any(np.diff(frame_ptr) < 0) or frame_ptr[-1] != len(samples):
+        raise ValueError('frame_ptr must start at 0, not decrease and end at len(samples)')
+    return frame_ptr, samples, n_observers, (D1, D2), N
+
+
+def _upload(frame_ptr, samples, w, dev):
+    """-> the three inputs of a fixation entry on the device (a row of zeros stands in for no samples at all)."""
+    return (torch.from_numpy(frame_ptr).to(dev), torch.from_numpy(samples if len(samples) else np.zeros((1, 3), np.int32)).to(dev),
+            torch.from_numpy(np.ascontiguousarray(w, np.float64)).to(dev))
+
+
 def gazemaps_from_fixations(packed, out_shape=(49, 49), sigma=None, want=('gazemaps', 'fixationmaps'), device=None):
     """Packed fixations -> {name: device tensor fp32 [N, S2, S1]} for the names in ``want`` (of ``OUTPUTS``), one launch.
 
@@ -148,12 +172,11 @@ def gazemaps_from_fixations(packed, out_shape=(49, 49), sigma=None, want=('gazem
     ``normalize_probability_map`` of the gaze maps (what the xentropy / KLD models train on).
     Raises ValueError for what the kernel does not cover and ``_lib.RgpError`` if the device refused a frame (a sample
     out of range: that frame is NaN; the error carries the tensors as ``.outputs``)."""
-    frame_ptr, samples, n_observers, raw_shape = packed
     want = (want,) if isinstance(want, str) else tuple(want)
     if not want or any(w not in OUTPUTS for w in want):
         raise ValueError('want = %r: choose from %s' % (want, OUTPUTS))
     S1, S2 = (int(v) for v in out_shape)
-    D1, D2 = (int(v) for v in raw_shape)
+    frame_ptr, samples, n_observers, (D1, D2), N = _check_packed(packed)
     if sigma is None:
         if (S1, S2) not in SIGMA_FOR_SHAPE:
             raise ValueError('no default sigma for maps of %s; pass sigma' % ((S1, S2),))
@@ -164,42 +187,22 @@ def gazemaps_from_fixations(packed, out_shape=(49, 49), sigma=None, want=('gazem
                          % (S1, S2, MAX_PIX))
     if r > MAX_RADIUS:
         raise ValueError('sigma = %g: filter radius %d above RGP_GTMAPS_MAX_RADIUS = %d' % (sigma, r, MAX_RADIUS))
-    n_observers = int(n_observers)
-    if not 1 <= n_observers <= MAX_OBSERVERS:
-        raise ValueError('%d observers: must be in [1, RGP_GTMAPS_MAX_OBSERVERS = %d]' % (n_observers, MAX_OBSERVERS))
-    if D1 < 2 or D2 < 2:
-        raise ValueError('raw_shape %s: both extents must be at least 2' % ((D1, D2),))
-    frame_ptr = np.ascontiguousarray(frame_ptr, np.int32).reshape(-1)
-    samples = np.ascontiguousarray(samples, np.int32).reshape(-1, 3)
-    N = len(frame_ptr) - 1
-    if N < 0 or frame_ptr[0] != 0 or np.any(np.diff(frame_ptr) < 0) or frame_ptr[-1] != len(samples):
-        raise ValueError('frame_ptr must start at 0, not decrease and end at len(samples)')
     dev = torch.device('cuda:0' if device is None else device)
     out = {name: torch.empty((N, S2, S1), dtype=torch.float32, device=dev) for name in want}
     if N == 0:
         return out
-    d_ptr = torch.from_numpy(frame_ptr).to(dev)
-    d_samples = torch.from_numpy(samples if len(samples) else np.zeros((1, 3), np.int32)).to(dev)
-    d_w = torch.from_numpy(np.ascontiguousarray(w, np.float64)).to(dev)
+    d_ptr, d_samples, d_w = _upload(frame_ptr, samples, w, dev)
     lib = _lib.load()
-    ws = torch.empty(max(int(lib.rgp_gtmaps_workspace_bytes()), 64), dtype=torch.uint8, device=dev)
+    ws = _image.workspace(lib.rgp_gtmaps_workspace_bytes(), dev)
 
     def ptr(name):
-        return out[name].data_ptr() if name in out else None
+        return _image.ptr(out.get(name))
     args = _lib.GtmapsArgs(frame_ptr=d_ptr.data_ptr(), samples=d_samples.data_ptr(), weights=d_w.data_ptr(), n_frames=N,
                            n_observers=n_observers, raw_d1=D1, raw_d2=D2, out_s1=S1, out_s2=S2, radius=r,
                            gazemaps=ptr('gazemaps'), fixationmaps=ptr('fixationmaps'), labels=ptr('labels'),
                            workspace=ws.data_ptr(), workspace_bytes=ws.numel())
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.rgp_gazemaps_from_fixations(ctypes.byref(args), stream)
-        if rc == 0:
-            rc = lib.rgp_gtmaps_status(ws.data_ptr(), stream)
-    try:
-        _lib.check(rc)
-    except _lib.RgpError as err:
-        err.outputs = out
-        raise
+    _image.launch(dev, lambda s: lib.rgp_gazemaps_from_fixations(ctypes.byref(args), s),
+                  lambda s: lib.rgp_gtmaps_status(ws.data_ptr(), s), out)
     return out
 
 
@@ -214,26 +217,15 @@ def gazemaps_original_scale(packed, sigma=SIGMA_ORIGINAL_SCALE, want=OUTPUTS_ORI
     independent, so the split changes no bit.  Raises ValueError for what the entry does not cover (``labels`` among
     it) and ``_lib.RgpError`` if the device refused a frame (a sample out of range: that frame is NaN; the error carries
     the tensors as ``.outputs``)."""
-    frame_ptr, samples, n_observers, raw_shape = packed
     want = (want,) if isinstance(want, str) else tuple(want)
     if not want or any(w not in OUTPUTS_ORIGINAL_SCALE for w in want):
         raise ValueError('want = %r: choose from %s (the original-scale path has no labels)' % (want, OUTPUTS_ORIGINAL_SCALE))
-    D1, D2 = (int(v) for v in raw_shape)
+    frame_ptr, samples, n_observers, (D1, D2), N = _check_packed(packed)
     w, r = gaussian_weights(sigma)
-    if D1 < 2 or D2 < 2:
-        raise ValueError('raw_shape %s: both extents must be at least 2' % ((D1, D2),))
     if D1 * D2 > FULL_MAX_PIX:
         raise ValueError('frames of %d x %d cells: more than RGP_GTMAPS_FULL_MAX_PIX = %d' % (D1, D2, FULL_MAX_PIX))
     if r > FULL_MAX_RADIUS:
         raise ValueError('sigma = %g: filter radius %d above RGP_GTMAPS_FULL_MAX_RADIUS = %d' % (sigma, r, FULL_MAX_RADIUS))
-    n_observers = int(n_observers)
-    if not 1 <= n_observers <= MAX_OBSERVERS:
-        raise ValueError('%d observers: must be in [1, RGP_GTMAPS_MAX_OBSERVERS = %d]' % (n_observers, MAX_OBSERVERS))
-    frame_ptr = np.ascontiguousarray(frame_ptr, np.int32).reshape(-1)
-    samples = np.ascontiguousarray(samples, np.int32).reshape(-1, 3)
-    N = len(frame_ptr) - 1
-    if N < 0 or frame_ptr[0] != 0 or np.any(np.diff(frame_ptr) < 0) or frame_ptr[-1] != len(samples):
-        raise ValueError('frame_ptr must start at 0, not decrease and end at len(samples)')
     if frames_per_call is None:
         frames_per_call = max(1, FULL_WORKSPACE_TARGET // (8 * D1 * D2 + 4 * (3 + (D1 + 31) // 32)))
     frames_per_call = int(frames_per_call)
@@ -243,9 +235,7 @@ def gazemaps_original_scale(packed, sigma=SIGMA_ORIGINAL_SCALE, want=OUTPUTS_ORI
     out = {name: torch.empty((N, D2, D1), dtype=torch.float32, device=dev) for name in want}
     if N == 0:
         return out
-    d_ptr = torch.from_numpy(frame_ptr).to(dev)
-    d_samples = torch.from_numpy(samples if len(samples) else np.zeros((1, 3), np.int32)).to(dev)
-    d_w = torch.from_numpy(np.ascontiguousarray(w, np.float64)).to(dev)
+    d_ptr, d_samples, d_w = _upload(frame_ptr, samples, w, dev)
     lib = _lib.load()
     per_call = min(frames_per_call, N)
     ws = torch.empty(int(lib.rgp_gtmaps_full_workspace_bytes(per_call, D1, D2)), dtype=torch.uint8, device=dev)
@@ -256,7 +246,7 @@ def gazemaps_original_scale(packed, sigma=SIGMA_ORIGINAL_SCALE, want=OUTPUTS_ORI
             n = min(per_call, N - lo)
 
             def ptr(name):
-                return out[name][lo:].data_ptr() if name in out else None
+                return _image.ptr(out[name][lo:] if name in out else None)
             # frame_ptr holds absolute rows of `samples`: a later chunk takes the same samples and a shifted frame_ptr
             args = _lib.GtmapsFullArgs(frame_ptr=d_ptr[lo:].data_ptr(), samples=d_samples.data_ptr(), weights=d_w.data_ptr(),
                                        n_frames=n, n_observers=n_observers, raw_d1=D1, raw_d2=D2, radius=r,
@@ -275,11 +265,7 @@ def gazemaps_original_scale(packed, sigma=SIGMA_ORIGINAL_SCALE, want=OUTPUTS_ORI
                             'b out of range, or a bad frame_ptr pair): their outputs are NaN' % refused_total)
         err.code, err.outputs = -1, out
         raise err
-    try:
-        _lib.check(rc)
-    except _lib.RgpError as err:
-        err.outputs = out
-        raise
+    _image.check(rc, out)
     return out
 
 

@@ -23,7 +23,7 @@ import os
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _image, _lib
 from ..frames import FILTER_SUPPORT, _device_tables
 
 log = logging.getLogger('rgp')
@@ -50,29 +50,16 @@ def bytescale(data):
 
 
 def _check_maps(maps, device):
-    """-> (numpy array or None, device tensor or None, torch.device, (n, h, w)); every refusal the host can make about
-    the maps themselves."""
-    if torch.is_tensor(maps):
-        if maps.dtype != torch.float32 or maps.dim() != 3:
-            raise ValueError('maps must be float32 [n, H, W]')
-        if maps.is_cuda and not maps.is_contiguous():
-            raise ValueError('a device tensor of maps must be contiguous')
-        dev = maps.device if maps.is_cuda else torch.device('cuda:0' if device is None else device)
-        a, x = (None, maps) if maps.is_cuda else (maps.contiguous().numpy(), None)
-    else:
-        a = np.asarray(maps)
-        if a.dtype != np.float32 or a.ndim != 3:
-            raise ValueError('maps must be float32 [n, H, W]')
-        dev, x = torch.device('cuda:0' if device is None else device), None
-    n, h, w = (int(v) for v in maps.shape)
+    """-> (torch.device, (n, h, w)); every refusal the host can make about the maps themselves."""
+    n, h, w = _image.host_check(maps, 'maps', torch.float32, 3, text='maps must be float32 [n, H, W]')
     if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
         raise ValueError('maps of %d x %d: both sides must be in [1, RGP_MAPEXPORT_MAX_SIDE = %d]' % (h, w, MAX_SIDE))
-    return a, x, dev, (n, h, w)
+    return _image.own_device(maps, device), (n, h, w)
 
 
 def _export(maps, out_shape, interp, want, device):
     """One launch of rgp_mapexport.  want: a subset of ('pooled', 'pooled_u8', 'bytes') -> {name: device tensor}."""
-    a, x, dev, (n, h, w) = _check_maps(maps, device)
+    dev, (n, h, w) = _check_maps(maps, device)
     resize = 'pooled' in want or 'pooled_u8' in want
     oh, ow, ksh, ksv = h, w, 0, 0
     if resize:
@@ -92,8 +79,7 @@ def _export(maps, out_shape, interp, want, device):
         kh, bh, ksh = _device_tables(dev, w, ow, interp)
     if resize and h != oh:
         kv, bv, ksv = _device_tables(dev, h, oh, interp)
-    if x is None:
-        x = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    x = _image.to_device(maps, dev)
     out = {}
     if 'pooled' in want:
         out['pooled'] = torch.empty((n, oh, ow), dtype=torch.float64, device=dev)
@@ -104,24 +90,13 @@ def _export(maps, out_shape, interp, want, device):
     if n == 0:
         return out
     lib = _lib.load()
-    ws = torch.empty(max(int(lib.rgp_mapexport_workspace_bytes()), 64), dtype=torch.uint8, device=dev)
-
-    def ptr(t):
-        return t.data_ptr() if t is not None else None
+    ws, ptr = _image.workspace(lib.rgp_mapexport_workspace_bytes(), dev), _image.ptr
     args = _lib.MapExportArgs(maps=x.data_ptr(), n=n, h=h, w=w, out_h=oh, out_w=ow, kh=ptr(kh), bh=ptr(bh), ksize_h=ksh,
                               kv=ptr(kv), bv=ptr(bv), ksize_v=ksv, pooled=ptr(out.get('pooled')),
                               pooled_u8=ptr(out.get('pooled_u8')), bytes=ptr(out.get('bytes')), workspace=ws.data_ptr(),
                               workspace_bytes=ws.numel())
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.rgp_mapexport(ctypes.byref(args), stream)
-        if rc == 0:
-            rc = lib.rgp_mapexport_status(ws.data_ptr(), None, stream)
-    try:
-        _lib.check(rc)
-    except _lib.RgpError as err:
-        err.outputs = out
-        raise
+    _image.launch(dev, lambda s: lib.rgp_mapexport(ctypes.byref(args), s),
+                  lambda s: lib.rgp_mapexport_status(ws.data_ptr(), None, s), out)
     return out
 
 

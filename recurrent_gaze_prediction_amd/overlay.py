@@ -16,7 +16,8 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _image, _lib
+from ._image import host_check as _host_check, to_device as _to_device
 
 MAX_PIX, SCALED_MAX_PIX = _lib.RGP_METRICS_MAX_PIX, _lib.RGP_METRICS_SCALED_MAX_PIX
 
@@ -61,39 +62,6 @@ def colormap_lut(name_or_table):
     except KeyError:
         raise ValueError("unknown colormap %r (built in: 'jet' and 'gray'; others by matplotlib's names)" % (name_or_table,))
     return np.ascontiguousarray(cmap(np.arange(256, dtype=np.uint8), bytes=True)[:, :3])
-
-
-def _pick_device(device, *xs):
-    if device is not None:
-        device = torch.device(device)
-        return torch.device('cuda', 0 if device.index is None else device.index) if device.type == 'cuda' else device
-    for x in xs:
-        if torch.is_tensor(x) and x.is_cuda:
-            return x.device
-    return torch.device('cuda:0')
-
-
-def _host_check(x, what, dtype, ndim, last=None):
-    """The refusals the host can make about an array or tensor; -> its shape."""
-    want = {torch.uint8: np.uint8, torch.float32: np.float32, torch.int32: np.int32}[dtype]
-    if torch.is_tensor(x):
-        ok = x.dtype == dtype
-        if x.is_cuda and not x.is_contiguous():
-            raise ValueError('a device tensor of %s must be contiguous' % what)
-    else:
-        ok = np.asarray(x).dtype == want
-    shape = tuple(int(v) for v in x.shape)
-    if not ok or len(shape) != ndim or (last is not None and shape[-1] != last):
-        raise ValueError('%s must be %s with %d axes%s' % (what, np.dtype(want).name, ndim, '' if last is None else ', the last of %d' % last))
-    return shape
-
-
-def _to_device(x, dev):
-    """A contiguous tensor on ``dev``: a tensor that is there already as it is, anything else (a host tensor, numpy, a
-    tensor on another device) copied there."""
-    if torch.is_tensor(x):
-        return x if x.device == dev else x.contiguous().to(dev)
-    return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
 
 
 def overlay_maps(frames, maps, alpha=0.4, colormap='jet', frame_idx=None, limits=None, want_heat=False, device=None,
@@ -145,7 +113,7 @@ def overlay_maps(frames, maps, alpha=0.4, colormap='jet', frame_idx=None, limits
             limits = np.ascontiguousarray(np.broadcast_to(np.asarray(limits, np.float32), (n, 2)))
         if _host_check(limits, 'limits', torch.float32, 2, 2) != (n, 2):
             raise ValueError('limits must be [n, 2] = [%d, 2]' % n)
-    dev = _pick_device(device, frames, maps)
+    dev = _image.pick_device(device, frames, maps)
     if out is not None:
         if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
                 and tuple(out.shape) == (n, H, W, 3)):
@@ -164,23 +132,12 @@ def overlay_maps(frames, maps, alpha=0.4, colormap='jet', frame_idx=None, limits
         res['heat'] = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
     if n > 0:
         lib = _lib.load()
-        ws = torch.empty(max(int(lib.rgp_overlay_workspace_bytes(n, h, w, H, W)), 64), dtype=torch.uint8, device=dev)
-
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
+        ws, ptr = _image.workspace(lib.rgp_overlay_workspace_bytes(n, h, w, H, W), dev), _image.ptr
         args = _lib.OverlayArgs(frames=frames_d.data_ptr(), frame_idx=ptr(idx_d), maps=maps_d.data_ptr(), limits=ptr(lim_d),
                                 lut=lut_d.data_ptr(), alpha=alpha, flags=flags, out=ptr(res.get('out')), heat_u8=ptr(res.get('heat')),
                                 n=n, n_src=n_src, h=h, w=w, H=H, W=W)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = lib.rgp_overlay(ctypes.byref(args), ws.data_ptr(), ws.numel(), stream)
-            if rc == 0:
-                rc = lib.rgp_overlay_status(ws.data_ptr(), None, stream)      # waits: the workspace is released on return
-        try:
-            _lib.check(rc)
-        except _lib.RgpError as err:
-            err.outputs = res
-            raise
+        _image.launch(dev, lambda s: lib.rgp_overlay(ctypes.byref(args), ws.data_ptr(), ws.numel(), s),
+                      lambda s: lib.rgp_overlay_status(ws.data_ptr(), None, s), res)
     if want_out and want_heat:
         return res['out'], res['heat']
     return res['out'] if want_out else res['heat']
