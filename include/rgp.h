@@ -567,6 +567,24 @@ int rgp_cascade_set_weights(rgp_cascade_t* plan, const rgp_cascade_weights* w, r
  * (predicted_gazemaps of gaze_grcn_cascade.py:423, trained with loss_type l2). */
 int rgp_cascade_forward(rgp_cascade_t* plan, const float* frame_images, const float* c3d_input, float* gazemaps,
                         rgp_stream_t stream);
+/* Streaming inference, as rgp_grcn_forward_stream without bn_phase (the bottom level's batch-norm is the identity for
+ * every step) and without a rows entry: BOTH recurrent states are carried across calls.
+ *   state      one flat fp32 buffer (16-byte aligned): the bottom state [B][49][256], which is what rgp_grcn_state_elems of
+ *              the sub-plan describes, then the top state [B][49][49][3], the dense layout of "gaze_rcn_outputs"
+ *   state_in   NULL = zeros for both; never written
+ *   state_out  may be NULL; must not alias state_in; receives both states behind step n_valid
+ *   n_valid    1..T.  All T steps are computed; the outputs of later steps are unspecified; their inputs, frame images
+ *              included, are read, but influence neither the first n_valid maps nor state_out
+ * rgp_cascade_forward_stream(.., NULL, state_out, T, ..) computes exactly what rgp_cascade_forward computes.  Argument
+ * errors are RGP_EINVAL and are reported ahead of the plan's bound / weights state.  Inference and training plans both
+ * accept the call; behind it rgp_cascade_backward returns RGP_ESTATE (no truncated BPTT) until a plain forward has run.
+ * Every recurrence launch of this plan is a per-step launch: there is no time-out path.  Streaming inside a stream
+ * capture is not supported: RGP_EINVAL if `stream` is capturing.  This one refusal asks the runtime about the stream, so it
+ * comes BEHIND the bound / weights checks (an unbound plan on a capturing stream reports RGP_EWORKSPACE).
+ * rgp_cascade_state_elems: B*(49*256 + 2401*3), the fp32 elements of a state; host-only, works on an unbound plan. */
+size_t rgp_cascade_state_elems(const rgp_cascade_t* plan);
+int rgp_cascade_forward_stream(rgp_cascade_t* plan, const float* frame_images, const float* c3d_input, const float* state_in,
+                               float* state_out, int n_valid, float* gazemaps, rgp_stream_t stream);
 /* Training (BASELINE config 5).  rgp_cascade_create_ex(save_for_backward = 1) keeps the gates, states and
  * maxout masks of the forward.  rgp_cascade_backward differentiates the l2 loss of gaze_grcn_cascade.py:428-441
  * (sum_t 0.5 ||maps - gt||^2 / (B*T)) w.r.t. every non-ShallowNet variable (the ShallowNet has learning rate

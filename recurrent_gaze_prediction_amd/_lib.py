@@ -258,6 +258,8 @@ SIGNATURES = {
     'rgp_cascade_bind_workspace': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     'rgp_cascade_set_weights': (c_int, [c_void_p, ctypes.POINTER(CascadeWeights), c_void_p]),
     'rgp_cascade_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rgp_cascade_state_elems': (c_size_t, [c_void_p]),
+    'rgp_cascade_forward_stream': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'rgp_cascade_read_buffer': (c_int, [c_void_p, c_char_p, c_void_p, c_void_p]),
     'rgp_cascade_create_ex': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int]),
     'rgp_cascade_backward': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(CascadeWeights), c_void_p, c_void_p]),

@@ -101,6 +101,24 @@ __global__ __launch_bounds__(256) void compact_units_kernel(const T* __restrict_
   }
 }
 
+// Streaming: the top cell's h_0 from a caller's state.  src [B][2401][3] fp32 (null: zeros) -> h0 [B][2401][kSt] fp32 (slot 0
+// of the state snapshots) and the interior of the 53x53xkSt operand image of step 0, clip b at pad + b * pad_img_stride,
+// converted as EpiGruC converts hp_out: a cut stream reads the bits an uncut recurrence has.  Channels 3..15 are zeros; the
+// halo is not touched (zero from the bind on).  7203 floats per clip are no multiple of four: scalar reads.
+template <typename T>
+__global__ __launch_bounds__(256) void top_seed_kernel(const float* __restrict__ src, float* __restrict__ h0, T* __restrict__ pad,
+                                                       long long pad_img_stride, int B) {
+  const int total = B * 2401 * kSt;                      // (B <= 2^31 / 38416)
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int c = i % kSt, row = i / kSt;                // row = 2401 b + p
+    const int b = row / 2401, p = row - b * 2401;
+    const float v = (src && c < 3) ? src[(long long)row * 3 + c] : 0.f;
+    h0[i] = v;
+    const int y = p / 49, x = p - y * 49;
+    pad[b * pad_img_stride + ((y + 2) * kHp + x + 2) * kSt + c] = Elem<T>::to(v);
+  }
+}
+
 __global__ void interleave2_kernel(const float* __restrict__ b, float* __restrict__ out, int half) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j < half) { out[2 * j] = b[j]; out[2 * j + 1] = b[j + half]; }
@@ -188,11 +206,15 @@ int forward_impl(rgp_cascade* g, const float* frames, const float* c3d_input, fl
     RGP_HIP(hipStreamWaitEvent(sc_odd, g->ev_join2, 0));
   }
   g->bottom->step_ev = pipe ? g->ev_b.data() : nullptr;
+  // (a streaming call: the bottom recurrence seeds itself from the first part of the state, batch-norm slot 0 = the identity)
+  g->bottom->st_on = g->st_on; g->bottom->st_in = g->st_in; g->bottom->st_phase = 0;
   int rc = rgp_proj_fwd(g->bottom, c3d_input, rs);
   if (rc == RGP_OK) rc = rgp_convgru_xconv_fwd(g->bottom, rs);
   if (rc == RGP_OK) rc = rgp_convgru_seq_fwd(g->bottom, rs);
   g->bottom->step_ev = nullptr;
+  g->bottom->st_on = false; g->bottom->st_in = nullptr;
   RGP_TRY(rc);
+  if (g->st_on) RGP_TRY(grcn_copy_state(g->bottom, g->st_out, g->st_nvalid, s));
   const int es_ = (int)sizeof(T);
   const long long up_in_img = 81LL * 256, xtop_img = (long long)kHp * kHp * kCt, xpre_img = 2401LL * 3 * kSt;
   // (3) 7x7x256 -> 49x49x64 into channels 0..63 of the top cell's input; saliency into channel 64
@@ -230,11 +252,27 @@ int forward_impl(rgp_cascade* g, const float* frames, const float* c3d_input, fl
   const size_t st = (size_t)B * 2401 * kSt;
   const long long img16 = (long long)kHp * kHp * kSt;
   // inference: two state snapshots and one operand image per role; training: every step's states, gates and
-  // operand images are kept (hp_all slot (b, t) = h_{t-1} of step t, slot (b, 0) is never written = h_0 = 0)
+  // operand images are kept (hp_all slot (b, t) = h_{t-1} of step t, slot (b, 0) is written by a streaming seed only = h_0 = 0)
   const bool save = g->save;
-  if (!save) RGP_HIP(hipMemsetAsync(ws + g->hp, 0, (size_t)B * img16 * sizeof(T), st2));
   float* hall = (float*)(ws + (save ? g->hall_t : g->hall));
-  RGP_HIP(hipMemsetAsync(hall, 0, st * 4, st2));
+  // h_0: zeros, or (a streaming call with a state) its second part, [B][2401][3], in one launch instead of the memsets.  A
+  // training plan's first zero-state call behind such a seed puts the zeros back into slot (b, 0) of hp_all.
+  const bool carry = g->st_on && g->st_in;
+  auto seed = [&](const float* src) -> int {
+    top_seed_kernel<T><<<(B * 2401 * kSt + 255) / 256, 256, 0, st2>>>(src, hall, (T*)(ws + (save ? g->hp_all : g->hp)),
+                                                                     save ? (long long)(T_ + 1) * img16 : img16, B);
+    RGP_HIP(hipGetLastError());
+    return RGP_OK;
+  };
+  if (carry) {
+    RGP_TRY(seed(g->st_in + (size_t)B * 49 * 256));
+  } else {
+    if (!save) RGP_HIP(hipMemsetAsync(ws + g->hp, 0, (size_t)B * img16 * sizeof(T), st2));
+    RGP_HIP(hipMemsetAsync(hall, 0, st * 4, st2));
+    // (only for slot (b, 0) of hp_all, which no memset of the parent's covers; slot 0 of hall_t is zero already by then)
+    if (save && g->top_seeded) RGP_TRY(seed(nullptr));
+  }
+  g->top_seeded = carry;
   for (int t = 0; t < T_; ++t) {
     if (pipe) {
       hipStream_t sf = (t & 1) ? sc_odd : sc;
@@ -279,6 +317,14 @@ int forward_impl(rgp_cascade* g, const float* frames, const float* c3d_input, fl
     IgemmParams pc = make_params(g->c, rh_buf, ws, B);
     pc.in_img_stride = rh_stride;
     RGP_TRY((launch_igemm<T, G16, 1, EpiGruC<T>>(pc, e, s)));
+    // streaming: the top state behind step n_valid, directly behind the step that wrote it (an inference plan's two snapshots
+    // ping-pong: the next step overwrites it) and, being on the top cell's stream, ahead of the join below
+    if (g->st_on && g->st_out && t + 1 == g->st_nvalid) {
+      const long long tot = (long long)B * 2401 * 3;
+      unpad_kernel<float><<<(int)((tot + 255) / 256), 256, 0, s>>>(e.h_next, g->st_out + (size_t)B * 49 * 256,
+                                                                  (const int*)(ws + g->c.out_tab_off), 2401, 3, 2401LL * kSt, tot);
+      RGP_HIP(hipGetLastError());
+    }
   }
   if (pipe) {
     RGP_HIP(hipEventRecord(g->ev_join2, st2));
@@ -307,6 +353,7 @@ int forward_impl(rgp_cascade* g, const float* frames, const float* c3d_input, fl
     if (save) e.argmax = (unsigned char*)(ws + g->mask2);
     RGP_TRY((launch_igemm<T, 1, 1, EpiReluMaxout<float>>(p, e, s)));
   }
+  g->streamed = g->st_on;
   return RGP_OK;
 }
 
@@ -408,6 +455,7 @@ int rgp_cascade_bind_workspace(rgp_cascade_t* g, void* workspace, size_t bytes, 
   hipStream_t s = (hipStream_t)stream;
   g->ws = (char*)workspace;
   g->weights_set = false;
+  g->top_seeded = g->streamed = false;       // the workspace is zeroed below: no seeded slot, no streamed activations
   RGP_HIP(hipMemsetAsync(g->ws, 0, g->ws_bytes, s));
   RGP_TRY(rgp_grcn_bind_workspace(g->bottom, g->ws + g->off_bottom, rgp_grcn_workspace_bytes(g->bottom), stream));
   RGP_TRY(rgp_shallownet_bind_workspace(g->shallow, g->ws + g->off_shallow, rgp_shallownet_workspace_bytes(g->shallow), stream));
@@ -454,6 +502,31 @@ int rgp_cascade_forward(rgp_cascade_t* g, const float* frame_images, const float
   hipStream_t s = (hipStream_t)stream;
   return g->dtype == RGP_BF16 ? forward_impl<bf16_t>(g, frame_images, c3d_input, gazemaps, s)
                               : forward_impl<float>(g, frame_images, c3d_input, gazemaps, s);
+}
+
+size_t rgp_cascade_state_elems(const rgp_cascade_t* g) { return g ? (size_t)g->B * (49 * 256 + 2401 * 3) : 0; }
+
+int rgp_cascade_forward_stream(rgp_cascade_t* g, const float* frame_images, const float* c3d_input, const float* state_in,
+                               float* state_out, int n_valid, float* gazemaps, rgp_stream_t stream) {
+  static const char* fn = "rgp_cascade_forward_stream";
+  RGP_REQUIRE(g, "%s: null plan", fn);
+  RGP_REQUIRE(frame_images, "%s: null frame_images", fn);
+  RGP_REQUIRE(c3d_input, "%s: null c3d_input", fn);
+  RGP_REQUIRE(gazemaps, "%s: null gazemaps", fn);
+  RGP_TRY(check_stream_args(fn, g->T, c3d_input, nullptr, state_in, state_out, n_valid, 0, gazemaps));
+  if (!g->ws) return set_err(RGP_EWORKSPACE, "rgp_cascade: workspace not bound");
+  if (!g->weights_set) return set_err(RGP_ESTATE, "rgp_cascade: weights not set");
+  hipStream_t s = (hipStream_t)stream;
+  // (asks the runtime, so it comes behind the host-only checks above: an unbound plan is refused without a device)
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  RGP_REQUIRE(hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone,
+              "%s: the stream is capturing (streaming inside a stream capture is not supported)", fn);
+  g->st_on = true; g->st_in = state_in; g->st_out = state_out; g->st_nvalid = n_valid;
+  const int rc = g->dtype == RGP_BF16 ? forward_impl<bf16_t>(g, frame_images, c3d_input, gazemaps, s)
+                                      : forward_impl<float>(g, frame_images, c3d_input, gazemaps, s);
+  g->st_on = false; g->st_in = nullptr; g->st_out = nullptr; g->st_nvalid = 0;
+  if (rc != RGP_OK) g->streamed = true;          // (a call that failed half-way: the saved activations are not a plain forward's)
+  return rc;
 }
 
 int rgp_cascade_read_buffer(rgp_cascade_t* g, const char* name, float* dst, rgp_stream_t stream) {

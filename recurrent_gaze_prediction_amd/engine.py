@@ -966,6 +966,40 @@ class CascadeEngine(object):
                                                     _stream_ptr(self.device)))
         return maps
 
+    @property
+    def state_elems(self):
+        """fp32 elements of the state forward_stream carries (rgp_cascade_state_elems): per clip the bottom state 49*256,
+        then the top state 49*49*3, each part [B, ...]."""
+        return int(self.lib.rgp_cascade_state_elems(self._h))
+
+    def forward_stream(self, frame_images, c3d_input, state=None, n_valid=None, train=False):
+        """One call of a stream (rgp_cascade_forward_stream): the graph of forward() with both recurrent states started
+        from `state` instead of zeros.  Inputs as for forward(), always at the full plan size; the recurrence is defined for
+        the first n_valid (default T) steps, later maps are unspecified.  state: fp32 device tensor of state_elems elements
+        from an earlier call, or None = the zero state; never modified.  Returns (maps, new_state); new_state is a fresh
+        tensor on every call: both states behind step n_valid."""
+        B, T = self.batch, self.n_steps
+        if train == 'keep':
+            pass
+        elif train:
+            self.dropout.draw()
+        else:
+            self.dropout.off()
+        assert frame_images.is_cuda and frame_images.dtype == torch.float32 and frame_images.is_contiguous()
+        assert c3d_input.is_cuda and c3d_input.dtype == torch.float32 and c3d_input.is_contiguous()
+        assert tuple(frame_images.shape) == (B, T, self.image_hw, self.image_hw, 3), tuple(frame_images.shape)
+        assert tuple(c3d_input.shape) == (B, T, 1024, 7, 7), tuple(c3d_input.shape)
+        n_valid = T if n_valid is None else int(n_valid)
+        if state is not None:
+            assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous()
+            assert state.numel() == self.state_elems, (state.numel(), self.state_elems)
+        maps = torch.empty(B, T, 49, 49, device=self.device)
+        new_state = torch.empty(self.state_elems, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_cascade_forward_stream(self._h, _ptr(frame_images), _ptr(c3d_input), _ptr(state),
+                                                           _ptr(new_state), n_valid, _ptr(maps), _stream_ptr(self.device)))
+        return maps, new_state
+
     BUFFERS = {'frm_sal': lambda B, T: (B, T, 49, 49), 'rcn_outputs': lambda B, T: (B, T, 7, 7, 256),
                'rcn_upsampled_outputs': lambda B, T: (B, T, 49, 49, 64), 'gaze_rcn_outputs': lambda B, T: (B, T, 49, 49, 3)}
 

@@ -186,7 +186,12 @@ def predict_long_clip(model, c3d, frames=None, pool_to_7x7=False, carry_state=Fa
     writes to <clip>.gazemap.npy: extract_map.avg_pool of every map (scipy's imresize to 7x7 over its sum, float64, NaN
     where the resized bytes sum to 0), made on the device from the maps predict() left there.
     carry_state=False is the reference's evaluation: every chunk starts from the zero state (extract_map.py:65).
-    carry_state=True runs the clip as ONE recurrence (stream.predict_long_clips; the conv-recurrent models only)."""
+    carry_state=True runs the clip as ONE recurrence (stream.predict_long_clips; the conv-recurrent models only).
+    frames means a different array on the two branches, and only the cascade reads it (every other model ignores it on both):
+      carry_state=False  one batch [B,T,hw,hw,3], handed to every predict() call as it is (the chunks' own images are not cut
+                         out of a clip here);
+      carry_state=True   the clip's images [N,hw,hw,3], one per step, cut, padded and trimmed beside the features; for the
+                         cascade any other shape is a ValueError."""
     if isinstance(pool_to_7x7, str) and pool_to_7x7 != 'imresize':
         raise ValueError("pool_to_7x7 must be False, True or 'imresize', got %r" % (pool_to_7x7,))
     imresize = isinstance(pool_to_7x7, str)
@@ -194,7 +199,12 @@ def predict_long_clip(model, c3d, frames=None, pool_to_7x7=False, carry_state=Fa
     n, T, B = len(c3d), model.n_lstm_steps, model.batch_size
     if carry_state:
         from ..stream import predict_long_clips
-        maps = predict_long_clips(model, [c3d])[0]
+        if frames is not None and getattr(model, 'NEEDS_FRAMES', False):
+            shape = tuple(frames.shape) if hasattr(frames, 'shape') else np.shape(frames)
+            if len(shape) != 4 or shape[0] != n:
+                raise ValueError('predict_long_clip(carry_state=True): frames must be the clip\'s images [N = %d, hw, hw, 3], one per '
+                                 'step, got %s (the [B,T,hw,hw,3] batch belongs to carry_state=False)' % (n, shape))
+        maps = predict_long_clips(model, [c3d], frames=None if frames is None else [frames])[0]
         if imresize:
             from .extract_map import avg_pool
             return avg_pool(np.ascontiguousarray(maps, np.float32), device=model.session.device)

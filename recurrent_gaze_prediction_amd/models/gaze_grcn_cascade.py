@@ -85,18 +85,31 @@ class _CascadeAdapter(object):
         from ..engine import clip_step_multi
         return clip_step_multi([self.net], step, lr, max_grad_norm, method)
 
-    def forward(self, c3d, want_probs=False, train=False):
+    def _frame_images(self):
         m = self.model
         assert self.frames is not None, 'the cascade needs frame_images (predict(c3d, frames))'
         x = self.frames if torch.is_tensor(self.frames) else torch.as_tensor(np.asarray(self.frames, np.float32))
-        x = x.to(m.session.device, torch.float32).reshape(m.batch_size, m.n_lstm_steps, self.net.image_hw,
-                                                          self.net.image_hw, 3).contiguous()
+        return x.to(m.session.device, torch.float32).reshape(m.batch_size, m.n_lstm_steps, self.net.image_hw,
+                                                             self.net.image_hw, 3).contiguous()
+
+    @staticmethod
+    def _probs(maps, want_probs):
+        if not want_probs:
+            return None
+        from ..engine import softmax_xent
+        return softmax_xent(maps.contiguous())[0]
+
+    def forward(self, c3d, want_probs=False, train=False):
+        x = self._frame_images()
         maps = self.net.forward(x, c3d, train=train)     # train: fc1's dropout draws a mask (gaze_grcn_cascade.py:401-402)
-        probs = None
-        if want_probs:
-            from ..engine import softmax_xent
-            probs = softmax_xent(maps.contiguous())[0]
-        return maps, probs
+        return maps, self._probs(maps, want_probs)
+
+    STREAM_BN_PHASE = False     # the bottom level's batch-norm is the identity for every step
+
+    def forward_stream(self, c3d, state=None, n_valid=None, want_probs=False):
+        """The streaming contract of GazePredictionGRU.predict_stream -> (maps, probs, new_state), on the adapter's frames."""
+        maps, new_state = self.net.forward_stream(self._frame_images(), c3d, state=state, n_valid=n_valid)
+        return maps, self._probs(maps, want_probs), new_state
 
 
 class GazePredictionGRCN(GazePredictionGRU):
@@ -140,3 +153,17 @@ class GazePredictionGRCN(GazePredictionGRU):
     def predict(self, c3d, frames=None, train=False):
         self.engine.frames = frames
         return super(GazePredictionGRCN, self).predict(c3d, frames, train=train)
+
+    # Both recurrent states are carried (rgp_cascade_forward_stream): per lane the bottom state [49, 256], then the top
+    # state [49, 49, 3].  The parts differ in size, so a lane is not one slice of a [parts, B, -1] view (stream.GazeStream.reset)
+    STREAMS = True
+    STATE_LANE_ELEMS = (49 * 256, 2401 * 3)
+    NEEDS_FRAMES = True
+
+    def predict_stream(self, c3d, state=None, n_valid=None, position=0, frames=None):
+        """As GazePredictionGRU.predict_stream, with the frame images [B,T,hw,hw,3] of the same T steps (predict()'s
+        `frames`).  position is accepted and unused: no stage of this graph depends on the step's index."""
+        if frames is None:
+            raise ValueError('predict_stream: the cascade needs the frame images of the call\'s steps (frames=[B,T,hw,hw,3])')
+        self.engine.frames = frames
+        return super(GazePredictionGRCN, self).predict_stream(c3d, state=state, n_valid=n_valid, position=position)

@@ -280,8 +280,9 @@ class GazePredictionGRU(ModelBase):
         of step 0; gaze_grcn's per-timestep batch-norm uses slot (position + t) % T for step t.
         -> (maps [B,T,GH,GW] device tensor, valid for the first n_valid steps; new_state, a fresh tensor)."""
         if not self.STREAMS:
-            raise NotImplementedError('predict_stream: GazePredictionGRCN (gaze_grcn), GazePredictionGRCN77 (gaze_grcn77) and '
-                                      'GazePredictionLSTM (gaze_lstm) stream; %s has no carried state' % type(self).__name__)
+            raise NotImplementedError('predict_stream: GazePredictionGRCN (gaze_grcn), GazePredictionGRCN77 (gaze_grcn77), '
+                                      'GazePredictionLSTM (gaze_lstm) and the cascade (gaze_grcn_cascade.GazePredictionGRCN) '
+                                      'stream; %s has no carried state' % type(self).__name__)
         x = torch.as_tensor(np.asarray(c3d, dtype=np.float32) if not torch.is_tensor(c3d) else c3d)
         x = x.to(self.session.device, torch.float32).reshape(self.batch_size, self.n_lstm_steps, 1024, 7, 7).contiguous()
         want_probs = self.config.loss_type in ('xentropy', 'KLD')
