@@ -308,6 +308,35 @@ int rgp_fcgru_backward(rgp_fcgru_t* plan, const float* logits, const float* prob
  * by every following forward AND backward until changed; keep_prob = 1 or mask = NULL switches the site off
  * (inference, the default). */
 int rgp_fcgru_set_dropout(rgp_fcgru_t* plan, float keep_prob, const unsigned char* mask);
+
+/* rgp_fcgru_create with flags (rgp_fcgru_create = flags 0, rgp_fcgru_create_ex = RGP_FCGRU_SAVE_FOR_BACKWARD or 0):
+ *   RGP_FCGRU_SAVE_FOR_BACKWARD  training plan (gates, states and operand rows of every step kept for rgp_fcgru_backward);
+ *   RGP_FCGRU_PER_STEP           run the recurrence as two launches per timestep (what every plan did so far);
+ *   RGP_FCGRU_PERSISTENT         run all T steps of the recurrence in ONE persistent launch with the h-side kernels
+ *                                resident in registers (csrc/fcgru_seq.hip.h).  Refused with RGP_EINVAL, the reason in
+ *                                rgp_last_error(): f32 plans, batch > 64, n_steps > 16384, and -- asked of the current
+ *                                device at create -- a device with fewer CUs than the launch has workgroups (203).
+ * With neither path flag the library's choice is per step.  Unknown bits and RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT
+ * are RGP_EINVAL.  Both paths fill the same buffers in the same layouts: rgp_fcgru_backward runs behind either. */
+#define RGP_FCGRU_SAVE_FOR_BACKWARD 1
+#define RGP_FCGRU_PER_STEP 2
+#define RGP_FCGRU_PERSISTENT 4
+int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_h, int gazemap_w, int dtype, int flags);
+/* Workgroups (= CUs) a persistent recurrence launch of this plan occupies; 0: the plan runs per-step launches. */
+int rgp_fcgru_persistent_workgroups(const rgp_fcgru_t* plan);
+/* Time-out of the persistent launch, as for the other recurrent families: all its workgroups must be resident together
+ * (keep ONE such launch in flight per device).  A launch that waits about a second for a missing member stops waiting,
+ * NaN-poisons the h rows of every step and clip (NaN logits) and the fp32 states, and sets the plan's error word: the
+ * next rgp_fcgru_forward, or rgp_fcgru_status, which first waits for `stream`, returns RGP_ETIMEOUT once.  RGP_OK on
+ * per-step plans. */
+int rgp_fcgru_status(rgp_fcgru_t* plan, rgp_stream_t stream);
+/* Intermediates of the last forward of a TRAINING plan as fp32 (padding columns dropped, bf16 buffers widened), either
+ * recurrence path: "xpre" [B,T,3,1617] hoisted x parts + biases, column blocks u, r, c; "h" [T+1,B,1617] fp32 states,
+ * slot 0 = h_0; "u", "r", "c" [T,B,1617] gates; "hp" [B,T+1,1617] the operand rows of h (slot t = h_{t-1} of step t);
+ * "rh" [B,T,1617] the operand rows r * h_{t-1}.  rgp_fcgru_buffer_elems: their sizes (0: unknown name, or an inference
+ * plan).  Errors: RGP_EINVAL for an unknown name; RGP_ESTATE on an inference plan or before the first forward. */
+int rgp_fcgru_read_buffer(rgp_fcgru_t* plan, const char* name, float* dst_fp32, rgp_stream_t stream);
+size_t rgp_fcgru_buffer_elems(const rgp_fcgru_t* plan, const char* name);
 /* ------------------------------------------------------------------ gaze_c3d_conv (the no-recurrence baseline) */
 typedef struct rgp_c3dconv rgp_c3dconv_t;
 

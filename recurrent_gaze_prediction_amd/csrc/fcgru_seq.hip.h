@@ -1,0 +1,294 @@
+// Persistent fc-GRU sequence kernel (gfx950, bf16 operands): ALL T steps of the TF-1.x GRUCell(1617) of gaze_rnn /
+// gaze_rnn77 in ONE launch.  The per-step path (rgp_fcgru.hip forward_impl) runs 2 T dependent launches, each of which
+// re-streams the h-side kernels ([1664 x 3328] + [1664 x 1664] bf16 = 16.6 MB) from L2 / Infinity Cache for at most 64 rows;
+// here the kernels never move and only the state does.
+//
+// Decomposition.  Work is split by hidden unit, so a unit's gate math is local to one workgroup.  Member j (one
+// 256-thread workgroup, 4 waves) owns units [8j, 8j + 8) of the padded 1664: the 8 u, 8 r and 8 c rows of the packed
+// kernels (g->zr rows [u | r], g->c; set_weights_impl), resident in REGISTERS for the whole sequence: wave kq keeps K steps
+// [13 kq, 13 kq + 13) of the 52, i.e. 2 x 13 B fragments = 104 VGPRs per lane.  Members that would own padding only (units
+// >= 1624) are not launched: 203 members.  Per step:
+//   phase A  [u(8) | r(8)] = one 16x16x32 column block per K step on the bf16 rows of h_{t-1};
+//            u = sigmoid(. + xpre_u), r = sigmoid(. + xpre_r); publish bf16(r * h_{t-1}) (fp32 product, rounded once:
+//            EpiGruZR); rendezvous
+//   phase B  c block (columns 8..15 of the tile multiply zeros) on the r.h rows; c = tanh(. + xpre_c),
+//            h_t = u h_{t-1} + (1 - u) c (EpiGruC, identity batch-norm); publish bf16(h_t); rendezvous
+// The rows are the clips: NF = (B + 15) / 16 fragments of 16, a template parameter, no run-time guards in the MFMA loops.
+// Rows >= B of the last fragment lie behind the end of the exchange buffer and read zeros (buffer bounds); MFMA rows are
+// independent, and nothing is stored for them.  The 4 K-quarter partial tiles are summed through LDS by thread b of wave 0,
+// which owns clip b: its 8 fp32 h and u stay in its registers across phases and steps, and it publishes the member's
+// 8 units x bf16 = ONE 16-byte row per clip and phase.
+//
+// Exchange buffers: the plan's own row-major operand rows, so the per-step consumers read what they always read.
+//   h:   hrows, row b T + t -- the rows the output projection reads.  Every step has its own row: nothing is overwritten
+//        while it is still read.  (Training plans also get hp_all, plain stores: the backward reads it, not this kernel.)
+//   r.h: training plans rh_all, a row per (clip, step), as above.  Inference plans the single rh buffer [B][np], and that
+//        is safe (write-after-read): a member publishes r.h of step t + 1 only behind the phase-B rendezvous of step t, and
+//        every member arrives at that rendezvous only after its phase-B MFMAs, i.e. after it has read r.h of step t.
+// A wave's A-fragment load of one K step is 16 rows x 64 bytes; all 13 x NF loads of a phase are issued before the first
+// MFMA (>= 13 sixteen-byte loads per lane in flight).  That order is pinned by a scheduling barrier in fcs_gemm and checked
+// in the assembly by scripts/check_isa_waits.py: without it the compiler keeps 2 - 3 loads in flight.
+//
+// Rendezvous: the protocol of seq_group.hip.h with every member of the launch as the group -- payload as 16-byte sc1
+// stores, vmcnt(0), workgroup barrier, one lane adds to the phase's monotonic counter, wave 0 polls it (relaxed,
+// agent scope, s_sleep) against the s_memrealtime deadline, barrier, payload read with sc1 loads only.  2 T counters,
+// each sharded 8 ways (fcs_wait_phase; measured against one counter, before the loads were pinned: 0.494 vs 0.539 ms per
+// forward at 64x16, 0.506 vs 0.610 at 8x35), zeroed ahead of the launch; the last phase needs none (the kernel boundary
+// orders it).  No fence per phase.
+//
+// Padding: units 1617 .. 1623 of member 202 have zero kernel rows and zero xpre, so u = 1/2, c = 0 and h stays 0.
+// Time-out: a member whose wait passes the deadline stops waiting, sets the plan's error word and NaN-poisons its units of
+// every h row (all steps, all clips) and of the fp32 states: the logits are NaN, never finite and wrong.
+#pragma once
+#include "seq_group.hip.h"
+
+namespace rgp {
+
+constexpr int FCS_NP = 1664;                         // padded state (a multiple of 64)
+constexpr int FCS_UNITS = 8;                         // units per member
+constexpr int FCS_MEMBERS = (1617 + FCS_UNITS - 1) / FCS_UNITS;      // 203
+constexpr int FCS_KW = FCS_NP / 32 / 4;              // K steps per wave: 13
+constexpr int FCS_SHARDS = 8;                        // counters per phase (a power of two), 64 bytes apart; member j adds to shard j % 8
+constexpr int FCS_CNT_STRIDE = 16;                   // unsigned per shard
+constexpr int FCS_PITCH = 80;                        // bytes per row of a partial tile in LDS: 16 fp32 + 4 (bank rotation)
+static_assert(FCS_KW * 4 * 32 == FCS_NP, "K split");
+
+struct FcSeqParams {
+  const bf16_t* w_zr;        // packed [2 np][np]: rows [0, np) u, [np, 2 np) r
+  const bf16_t* w_c;         // packed [np][np]
+  const float* xpre;         // [B T][3 np] hoisted x parts + biases, columns [u | r | c]
+  bf16_t* hrows;             // [B T][np] bf16 h_t, row b T + t: exchange rows of h and the output projection's input
+  bf16_t* rh;                // training: rh_all [B T][np]; inference: rh [B][np]
+  float* hall;               // training: hall_t [T+1][B][np] (slot 0 = h_0 = 0); inference: [2][B][np], h_t in slot (t+1) & 1
+  float* uall;               // training [T][B][np] (else null) ...
+  float* rall;
+  float* call;
+  bf16_t* hp_all;            // training [B][T+1][np], slot (b, 0) untouched
+  unsigned* cnt;             // [2 T][FCS_SHARDS][FCS_CNT_STRIDE] phase counters, zeroed ahead of the launch
+  unsigned* err;             // the plan's pinned error word
+  int B, T;
+};
+
+// A fragments of this wave's K quarter from exchange rows (sc1), then the MFMAs of one resident column block on them.
+// off0: the lane's byte offset at fragment 0, K step 0; fragments are fstride bytes apart, K steps 64.
+template <int NF>
+__device__ __forceinline__ void fcs_gemm(const void* base, unsigned bytes, unsigned off0, unsigned fstride, const f32x4 (&b)[FCS_KW],
+                                         f32x4 (&acc)[NF]) {
+  u32x4 a[NF][FCS_KW];
+#pragma unroll
+  for (int f = 0; f < NF; ++f)
+#pragma unroll
+    for (int i = 0; i < FCS_KW; ++i) a[f][i] = seq_ld_sc1(base, bytes, off0 + (unsigned)f * fstride + (unsigned)i * 64u);
+  // The scheduler must not sink the loads between the MFMAs: left alone it re-uses 2 - 4 A registers under vmcnt(1..2), a
+  // chain of dependent round trips per phase (scripts/check_isa_waits.py counts the loads in front of the first MFMA).
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < FCS_KW; ++i)
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+      acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(s16x8, a[f][i]), __builtin_bit_cast(s16x8, b[i]), acc[f], 0, 0, 0);
+}
+
+// Wait of a whole wave for a phase whose arrivals are spread over FCS_SHARDS counters (a phase counter that all 203
+// members add to is 203 atomics on one address, served one after the other: the fan-in the price list puts at 3 - 4.5 us).
+// Lane l < FCS_SHARDS polls shard l; the counters only grow, so their sum, read at different times, never overstates the
+// arrivals.  The deadline is seq_wait_phase's.  One shard: the single-lane wait of seq_group.hip.h.
+__device__ __forceinline__ bool fcs_wait_phase(const unsigned* cnt, unsigned n, int lane) {
+  if (FCS_SHARDS == 1) {
+    int ok = 1;
+    if (lane == 0) ok = seq_wait_phase_n(cnt, n) ? 1 : 0;
+    return __builtin_amdgcn_readfirstlane(ok) != 0;
+  }
+  const unsigned* mine = cnt + (lane & (FCS_SHARDS - 1)) * FCS_CNT_STRIDE;
+  auto arrived = [&]() {
+    unsigned v = lane < FCS_SHARDS ? __hip_atomic_load(mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+#pragma unroll
+    for (int m = 1; m < FCS_SHARDS; m <<= 1) v += (unsigned)__shfl_xor((int)v, m);
+    return (unsigned)__builtin_amdgcn_readfirstlane((int)v) >= n;
+  };
+  if (arrived()) return true;
+  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+  for (unsigned spins = 1;; ++spins) {
+    __builtin_amdgcn_s_sleep(2);
+    if (arrived()) return true;
+    if ((spins & 63u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > SEQ_DEADLINE_TICKS) return false;
+  }
+}
+
+__device__ __forceinline__ u32x4 fcs_pack8(const float (&v)[8]) {
+  u32x4 q;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) q[i] = (unsigned)f2bf(v[2 * i]) | ((unsigned)f2bf(v[2 * i + 1]) << 16);
+  return q;
+}
+
+template <int NF, bool SAVE>
+static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const FcSeqParams p) {
+  __shared__ __attribute__((aligned(16))) char red[4 * NF * 16 * FCS_PITCH];   // [K quarter][row][16 columns]
+  __shared__ int s_timeout;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int kq = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int frow = lane & 15, fk = lane >> 4;
+  const int j = blockIdx.x, u0 = FCS_UNITS * j;          // member, its first unit
+  const int np = FCS_NP, T_ = p.T, B = p.B;
+  const unsigned members = gridDim.x;
+  if (tid == 0) s_timeout = 0;
+
+  // ---- resident B fragments: K steps [13 kq, 13 kq + 13) of columns [u(8) | r(8)] and [c(8) | 0]
+  f32x4 bzr[FCS_KW], bc[FCS_KW];
+  {
+    const bf16_t* wz = p.w_zr + (long long)((frow < 8 ? 0 : np) + u0 + (frow & 7)) * np;
+    const bf16_t* wc = p.w_c + (long long)(u0 + (frow & 7)) * np;
+#pragma unroll
+    for (int i = 0; i < FCS_KW; ++i) {
+      const int k = (kq * FCS_KW + i) * 32 + fk * 8;
+      bzr[i] = *(const f32x4*)(wz + k);
+      const f32x4 c = *(const f32x4*)(wc + k);
+      bc[i] = frow < 8 ? c : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  // thread b of wave 0 finalises clip b: its fp32 state and update gate live here for the whole sequence
+  const int b = tid;
+  const bool red_row = tid < NF * 16;                      // (rows >= B are summed and dropped)
+  const bool own = red_row && b < B;
+  float h[8], u[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { h[i] = 0.f; u[i] = 0.f; }
+  const unsigned hbytes = (unsigned)B * (unsigned)T_ * (unsigned)np * 2u;
+  const unsigned rbytes = SAVE ? hbytes : (unsigned)B * (unsigned)np * 2u;
+  const unsigned koff = (unsigned)((kq * FCS_KW * 32 + fk * 8) * 2);     // the lane's K offset in a row, bytes
+  const long long st = (long long)B * np;
+  __syncthreads();                                         // flag cleared
+
+  // this wave's partial tiles -> LDS; the sum over the 4 quarters of row `tid` (16 columns)
+  auto store_partials = [&](const f32x4 (&acc)[NF]) {
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) *(float*)(red + ((kq * NF + f) * 16 + fk * 4 + r) * FCS_PITCH + frow * 4) = acc[f][r];
+  };
+  auto reduce_row = [&](float (&s)[16]) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v += *(const f32x4*)(red + (q * NF * 16 + tid) * FCS_PITCH + c * 16);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[4 * c + e] = v[e];
+    }
+  };
+  // rendezvous of phase ph: this member's rows are published; all members' are
+  auto rendezvous = [&](int ph) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its write-through stores
+    __syncthreads();
+    unsigned* c = p.cnt + (long long)ph * (FCS_SHARDS * FCS_CNT_STRIDE);
+    if (tid == 0) __hip_atomic_fetch_add(c + (j & (FCS_SHARDS - 1)) * FCS_CNT_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (kq == 0 && !s_timeout) {                           // (a member that timed out once stops waiting)
+      if (!fcs_wait_phase(c, members, lane) && lane == 0) s_timeout = 1;
+    }
+    __syncthreads();
+  };
+  auto store8f = [&](float* dst, const float (&v)[8]) {
+    *(f32x4*)dst = (f32x4){v[0], v[1], v[2], v[3]};
+    *(f32x4*)(dst + 4) = (f32x4){v[4], v[5], v[6], v[7]};
+  };
+
+  for (int t = 0; t < T_; ++t) {
+    // the step's xpre slice of this clip, ahead of the waits: 3 x 8 fp32
+    f32x4 x[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) x[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (own) {
+      const float* xp = p.xpre + ((long long)b * T_ + t) * (3 * np) + u0;
+#pragma unroll
+      for (int g3 = 0; g3 < 3; ++g3) { x[2 * g3] = *(const f32x4*)(xp + g3 * np); x[2 * g3 + 1] = *(const f32x4*)(xp + g3 * np + 4); }
+    }
+
+    // ---- phase A: [u | r] on the rows of h_{t-1} (h_0 = 0: nothing to multiply at t = 0)
+    {
+      f32x4 acc[NF];
+#pragma unroll
+      for (int f = 0; f < NF; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (t > 0)
+        fcs_gemm<NF>(p.hrows, hbytes, ((unsigned)frow * (unsigned)T_ + (unsigned)(t - 1)) * (unsigned)(np * 2) + koff,
+                     16u * (unsigned)T_ * (unsigned)(np * 2), bzr, acc);
+      store_partials(acc);
+    }
+    __syncthreads();
+    float rg[8];
+    if (red_row) {
+      float s[16], rh[8];
+      reduce_row(s);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        u[i] = sigmoidf_(s[i] + x[i >> 2][i & 3]);
+        rg[i] = sigmoidf_(s[8 + i] + x[2 + (i >> 2)][i & 3]);
+        rh[i] = rg[i] * h[i];
+      }
+      if (own) {
+        const unsigned row = SAVE ? (unsigned)b * (unsigned)T_ + (unsigned)t : (unsigned)b;
+        seq_st_sc1(p.rh, rbytes, (row * (unsigned)np + (unsigned)u0) * 2u, fcs_pack8(rh));
+      }
+    }
+    rendezvous(2 * t);
+    // (plain outputs behind the hand-off, under the next phase's loads: in front of it they sit in the queue its drain waits for)
+    if (SAVE && own) {
+      const long long off = (long long)t * st + (long long)b * np + u0;
+      store8f(p.uall + off, u);
+      store8f(p.rall + off, rg);
+    }
+
+    // ---- phase B: c on the rows of r.h, blend
+    {
+      f32x4 acc[NF];
+#pragma unroll
+      for (int f = 0; f < NF; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (SAVE)
+        fcs_gemm<NF>(p.rh, rbytes, ((unsigned)frow * (unsigned)T_ + (unsigned)t) * (unsigned)(np * 2) + koff,
+                     16u * (unsigned)T_ * (unsigned)(np * 2), bc, acc);
+      else
+        fcs_gemm<NF>(p.rh, rbytes, (unsigned)frow * (unsigned)(np * 2) + koff, 16u * (unsigned)(np * 2), bc, acc);
+      store_partials(acc);
+    }
+    __syncthreads();
+    float cg[8];
+    if (red_row) {
+      float s[16];
+      reduce_row(s);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        cg[i] = tanhf_(s[i] + x[4 + (i >> 2)][i & 3]);
+        h[i] = u[i] * h[i] + (1.f - u[i]) * cg[i];
+      }
+      if (own) seq_st_sc1(p.hrows, hbytes, (((unsigned)b * (unsigned)T_ + (unsigned)t) * (unsigned)np + (unsigned)u0) * 2u, fcs_pack8(h));
+    }
+    if (t + 1 < T_) rendezvous(2 * t + 1);
+    if (own) {
+      const long long off = (long long)b * np + u0;
+      store8f(p.hall + (long long)(SAVE ? t + 1 : ((t + 1) & 1)) * st + off, h);
+      if (SAVE) {
+        store8f(p.call + (long long)t * st + off, cg);
+        *(u32x4*)(p.hp_all + ((long long)b * (T_ + 1) + t + 1) * np + u0) = fcs_pack8(h);
+      }
+    }
+  }
+  // a launch that lost a member must not look like a result
+  __syncthreads();
+  if (s_timeout) {
+    if (tid == 0 && p.err) { *(volatile unsigned*)p.err = 1u; __threadfence_system(); }
+    if (own) {
+      const u32x4 qnan = (u32x4){0x7FC07FC0u, 0x7FC07FC0u, 0x7FC07FC0u, 0x7FC07FC0u};
+      float fnan[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) fnan[i] = __builtin_nanf("");
+      const long long off = (long long)b * np + u0;
+      for (int t = 0; t < T_; ++t) {
+        seq_st_sc1(p.hrows, hbytes, (((unsigned)b * (unsigned)T_ + (unsigned)t) * (unsigned)np + (unsigned)u0) * 2u, qnan);
+        if (SAVE) store8f(p.hall + (long long)(t + 1) * st + off, fnan);
+      }
+      if (!SAVE) { store8f(p.hall + off, fnan); store8f(p.hall + st + off, fnan); }
+    }
+  }
+}
+
+}  // namespace rgp

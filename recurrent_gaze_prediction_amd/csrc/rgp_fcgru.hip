@@ -12,9 +12,15 @@
 // Backward (tf.gradients of the loss of gaze_rnn.py:363-408, base.py:278-281): BPTT with two input-gradient
 // GEMMs per step; every weight gradient is hoisted over all T steps and computed by wgrad_kernel
 // (rows = frames, transposing LDS reads) on the operand rows the forward kept.
+// Recurrence, two implementations: per step (every plan; the library's choice), and -- RGP_FCGRU_PERSISTENT, bf16 plans of
+// at most 64 clips -- all T steps in one persistent launch with the h-side kernels resident in registers
+// (fcgru_seq.hip.h).  Both write the same buffers in the same layouts, so the backward runs unchanged behind either.
 #include <algorithm>
 
+#include <string>
+
 #include "wgrad_launch.h"
+#include "fcgru_seq.hip.h"
 
 using namespace rgp;
 
@@ -43,6 +49,10 @@ struct rgp_fcgru {
   size_t dxpre = 0;                                   // T [F+1][3np]  [du_pre | dr_pre | dc_pre], row 0 zero
   size_t dE = 0;                                      // T [F+1][Kx]   row 0 zero
   size_t dwx = 0, dwh = 0, dwc = 0;                   // fp32 [Kx][3np], [np][2np], [np][np]
+  // ---- persistent recurrence (RGP_FCGRU_PERSISTENT)
+  bool persistent = false, fwd_done = false;
+  size_t seq_cnt = 0;                                 // [2 T][FCS_SHARDS][FCS_CNT_STRIDE] phase counters
+  PinnedErrWord err;                                  // set by a launch that lost a member (allocated at bind, persistent plans only)
 };
 
 namespace rgp {
@@ -113,6 +123,42 @@ __global__ void fill_kernel(float* p, float v, int n) {
   if (i < n) p[i] = v;
 }
 
+// All T steps in one persistent launch (fcgru_seq.hip.h)
+template <bool SAVE>
+int seq_persistent(rgp_fcgru* g, hipStream_t s) {
+  char* ws = g->ws;
+  RGP_HIP(hipMemsetAsync(ws + g->seq_cnt, 0, (size_t)2 * g->T * FCS_SHARDS * FCS_CNT_STRIDE * 4, s));         // phase counters: zeroed EVERY call
+  FcSeqParams p;
+  p.w_zr = (const bf16_t*)(ws + g->zr.w_off);
+  p.w_c = (const bf16_t*)(ws + g->c.w_off);
+  p.xpre = (const float*)(ws + g->xpre);
+  p.hrows = (bf16_t*)(ws + g->hrows);
+  p.rh = (bf16_t*)(ws + (SAVE ? g->rh_all : g->rh));
+  p.hall = (float*)(ws + (SAVE ? g->hall_t : g->hall));
+  p.uall = SAVE ? (float*)(ws + g->uall) : nullptr;
+  p.rall = SAVE ? (float*)(ws + g->rall) : nullptr;
+  p.call = SAVE ? (float*)(ws + g->call) : nullptr;
+  p.hp_all = SAVE ? (bf16_t*)(ws + g->hp_all) : nullptr;
+  p.cnt = (unsigned*)(ws + g->seq_cnt);
+  p.err = g->err.host;
+  p.B = g->B; p.T = g->T;
+  RGP_REQUIRE(g->np == FCS_NP && g->zr.K == FCS_NP && g->c.K == FCS_NP && g->zr.chunk_major == 0 && g->c.chunk_major == 0,
+              "fcgru_seq: unexpected filter packing");
+  void (*kern)(FcSeqParams) = nullptr;
+  switch ((g->B + 15) / 16) {
+    case 1: kern = fcgru_seq_kernel<1, SAVE>; break;
+    case 2: kern = fcgru_seq_kernel<2, SAVE>; break;
+    case 3: kern = fcgru_seq_kernel<3, SAVE>; break;
+    case 4: kern = fcgru_seq_kernel<4, SAVE>; break;
+    default: return set_err(RGP_EINVAL, "fcgru_seq: batch %d", g->B);
+  }
+  PersistentLaunch guard(s);
+  RGP_TRY(guard.status());
+  kern<<<FCS_MEMBERS, SEQ_NT, 0, s>>>(p);
+  RGP_HIP(hipGetLastError());
+  return guard.commit();
+}
+
 template <typename T>
 int forward_impl(rgp_fcgru* g, const float* c3d_input, float* logits, float* probs, hipStream_t s) {
   char* ws = g->ws;
@@ -138,7 +184,14 @@ int forward_impl(rgp_fcgru* g, const float* c3d_input, float* logits, float* pro
   if (!save) RGP_HIP(hipMemsetAsync(ws + g->hp, 0, st * sizeof(T), s));
   float* hall = (float*)(ws + (save ? g->hall_t : g->hall));
   RGP_HIP(hipMemsetAsync(hall, 0, st * 4, s));
-  for (int t = 0; t < T_; ++t) {
+  bool one_launch = false;
+  if constexpr (sizeof(T) == 2) {
+    if (g->persistent) {
+      RGP_TRY(save ? seq_persistent<true>(g, s) : seq_persistent<false>(g, s));
+      one_launch = true;
+    }
+  }
+  for (int t = 0; t < T_ && !one_launch; ++t) {
     // training keeps every step's states, gates and operand rows (slot (b, 0) of hp_all is never written = h_0)
     char* hp_in = save ? ws + g->hp_all + (size_t)t * np * sizeof(T) : ws + g->hp;
     char* hp_out = save ? ws + g->hp_all + (size_t)(t + 1) * np * sizeof(T) : ws + g->hp;
@@ -183,7 +236,36 @@ int forward_impl(rgp_fcgru* g, const float* c3d_input, float* logits, float* pro
     RGP_TRY((launch_igemm<T, 1, 1, EpiStore<float, true, false>>(p, e, s)));
   }
   if (probs) RGP_TRY(rgp_softmax_xent_fwd(logits, nullptr, probs, nullptr, nullptr, F, g->G, (rgp_stream_t)s));
+  g->fwd_done = true;
   return RGP_OK;
+}
+
+int fcgru_check_error(rgp_fcgru* g) {
+  return g->err.check("rgp_fcgru: a persistent fc-GRU launch of this plan lost a member (another launch was resident on "
+                         "the device?): its outputs were NaN-poisoned");
+}
+
+// rgp_fcgru_read_buffer: rows of `np` elements at `off`, the first n columns of each are kept
+struct FcView { size_t off; long long rows; bool operand; };
+
+bool find_view(const rgp_fcgru* g, const char* name, FcView& v) {
+  const std::string n(name ? name : "");
+  const long long B = g->B, T_ = g->T;
+  if (n == "xpre") v = {g->xpre, B * T_ * 3, false};
+  else if (n == "h") v = {g->hall_t, (T_ + 1) * B, false};
+  else if (n == "u") v = {g->uall, T_ * B, false};
+  else if (n == "r") v = {g->rall, T_ * B, false};
+  else if (n == "c") v = {g->call, T_ * B, false};
+  else if (n == "hp") v = {g->hp_all, B * (T_ + 1), true};
+  else if (n == "rh") v = {g->rh_all, B * T_, true};
+  else return false;
+  return true;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void fc_read_rows_kernel(const T* __restrict__ src, float* __restrict__ dst, int n, int np, long long total) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256)
+    dst[i] = Elem<T>::from(src[(i / n) * np + (i % n)]);
 }
 
 // ---------------------------------------------------------------- backward kernels
@@ -421,13 +503,34 @@ int rgp_fcgru_create(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_h, 
 }
 
 int rgp_fcgru_create_ex(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_h, int gazemap_w, int dtype, int save_for_backward) {
+  return rgp_fcgru_create_flags(plan, batch, n_steps, gazemap_h, gazemap_w, dtype, save_for_backward ? RGP_FCGRU_SAVE_FOR_BACKWARD : 0);
+}
+
+int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_h, int gazemap_w, int dtype, int flags) {
   RGP_REQUIRE(plan && batch > 0 && n_steps > 0, "rgp_fcgru_create: bad arguments");
+  RGP_REQUIRE((flags & ~(RGP_FCGRU_SAVE_FOR_BACKWARD | RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT)) == 0,
+              "rgp_fcgru_create: unknown flags 0x%x", flags);
+  RGP_REQUIRE((flags & (RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT)) != (RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT),
+              "rgp_fcgru_create: flags name both recurrence paths");
   RGP_REQUIRE((gazemap_h == 49 && gazemap_w == 49) || (gazemap_h == 7 && gazemap_w == 7),
               "rgp_fcgru_create: gaze map %dx%d (reference uses 49x49 or 7x7)", gazemap_h, gazemap_w);
   RGP_REQUIRE(dtype == RGP_F32 || dtype == RGP_BF16, "rgp_fcgru_create: dtype %d", dtype);
+  if (flags & RGP_FCGRU_PERSISTENT) {
+    // the arguments first (no device needed to refuse them), then the device
+    RGP_REQUIRE(dtype == RGP_BF16, "rgp_fcgru_create: the persistent kernel (flags) takes bf16 plans, dtype is %d", dtype);
+    RGP_REQUIRE(batch <= 64, "rgp_fcgru_create: the persistent kernel (flags) takes at most 64 clips, batch is %d", batch);
+    // the kernel addresses its exchange rows with 32-bit byte offsets, those of the up to 64 rows of the last row fragment
+    // included: 64 * T * np * 2 bytes must stay below 2^32 (T < 20 165)
+    RGP_REQUIRE(n_steps <= 16384, "rgp_fcgru_create: the persistent kernel (flags) takes at most 16384 steps, n_steps is %d", n_steps);
+    int n_cu = 0;
+    RGP_TRY(device_cu_count(&n_cu));
+    RGP_REQUIRE(n_cu >= FCS_MEMBERS, "rgp_fcgru_create: the persistent kernel (flags) needs %d CUs resident together, the device has %d",
+                FCS_MEMBERS, n_cu);
+  }
   rgp_fcgru* g = new rgp_fcgru();
   g->B = batch; g->T = n_steps; g->F = batch * n_steps; g->G = gazemap_h * gazemap_w; g->dtype = dtype;
-  g->save = save_for_backward != 0;
+  g->save = (flags & RGP_FCGRU_SAVE_FOR_BACKWARD) != 0;
+  g->persistent = (flags & RGP_FCGRU_PERSISTENT) != 0;                       // (neither flag: the library's choice is per step)
   g->Gp = (int)align_up(g->G, 128);
   g->Kx = (int)align_up(g->nx, 64);
   g->np = (int)align_up(g->n, 64);
@@ -453,6 +556,7 @@ int rgp_fcgru_create_ex(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_
   g->xbias = a.take((size_t)3 * np * 4);
   g->ones = a.take((size_t)np * 4);
   g->zeros = a.take((size_t)np * 4);
+  if (g->persistent) g->seq_cnt = a.take((size_t)2 * n_steps * FCS_SHARDS * FCS_CNT_STRIDE * 4);
   if (g->save) {
     const size_t st = (size_t)batch * np;
     gemm_desc(g->b_out, np, g->Gp, g->Gp, np, dtype);
@@ -484,6 +588,7 @@ int rgp_fcgru_create_ex(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_
 }
 
 int rgp_fcgru_destroy(rgp_fcgru_t* plan) {
+  if (plan) plan->err.release();
   delete plan;
   return RGP_OK;
 }
@@ -495,8 +600,10 @@ int rgp_fcgru_bind_workspace(rgp_fcgru_t* g, void* workspace, size_t bytes, rgp_
   if (bytes < g->ws_bytes) return set_err(RGP_EWORKSPACE, "workspace %zu < required %zu bytes", bytes, g->ws_bytes);
   RGP_REQUIRE(((size_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
+  if (g->persistent) RGP_TRY(g->err.alloc());
   g->ws = (char*)workspace;
   g->weights_set = false;
+  g->fwd_done = false;
   RGP_HIP(hipMemsetAsync(g->ws, 0, g->ws_bytes, s));
   for (ConvDesc* d : {&g->proj, &g->xg, &g->zr, &g->c, &g->out}) RGP_TRY(upload_desc(*d, g->ws, s));
   if (g->save) for (ConvDesc* d : {&g->b_out, &g->b_c, &g->b_zr, &g->b_x}) RGP_TRY(upload_desc(*d, g->ws, s));
@@ -519,6 +626,7 @@ int rgp_fcgru_forward(rgp_fcgru_t* g, const float* c3d_input, float* logits, flo
   RGP_REQUIRE(g && c3d_input && logits, "rgp_fcgru_forward: null argument");
   if (!g->ws) return set_err(RGP_EWORKSPACE, "rgp_fcgru: workspace not bound");
   if (!g->weights_set) return set_err(RGP_ESTATE, "rgp_fcgru: weights not set");
+  RGP_TRY(fcgru_check_error(g));
   hipStream_t s = (hipStream_t)stream;
   return g->dtype == RGP_BF16 ? forward_impl<bf16_t>(g, c3d_input, logits, probs, s)
                               : forward_impl<float>(g, c3d_input, logits, probs, s);
@@ -538,6 +646,36 @@ int rgp_fcgru_backward(rgp_fcgru_t* g, const float* logits, const float* probs, 
   RGP_TRY(g->dtype == RGP_BF16 ? backward_impl<bf16_t>(g, logits, probs, labels, grads, loss_type, s)
                                : backward_impl<float>(g, logits, probs, labels, grads, loss_type, s));
   fc_fold_bias_kernel<<<1, 64, 0, s>>>((const float*)(g->ws + g->dwc), (float*)grads->proj_c3d_b, g->Cp);
+  RGP_HIP(hipGetLastError());
+  return RGP_OK;
+}
+
+int rgp_fcgru_status(rgp_fcgru_t* g, rgp_stream_t stream) {
+  RGP_REQUIRE(g, "rgp_fcgru_status: null plan");
+  RGP_HIP(hipStreamSynchronize((hipStream_t)stream));
+  return fcgru_check_error(g);
+}
+
+int rgp_fcgru_persistent_workgroups(const rgp_fcgru_t* g) { return (g && g->persistent) ? FCS_MEMBERS : 0; }
+
+size_t rgp_fcgru_buffer_elems(const rgp_fcgru_t* g, const char* name) {
+  FcView v;
+  return (g && g->save && find_view(g, name, v)) ? (size_t)v.rows * g->n : 0;
+}
+
+int rgp_fcgru_read_buffer(rgp_fcgru_t* g, const char* name, float* dst, rgp_stream_t stream) {
+  RGP_REQUIRE(g && name && dst, "rgp_fcgru_read_buffer: null argument");
+  FcView v;
+  if (!find_view(g, name, v)) return set_err(RGP_EINVAL, "rgp_fcgru_read_buffer: unknown buffer '%s'", name);
+  if (!g->save) return set_err(RGP_ESTATE, "rgp_fcgru_read_buffer: the plan was created without RGP_FCGRU_SAVE_FOR_BACKWARD");
+  if (!g->ws || !g->fwd_done) return set_err(RGP_ESTATE, "rgp_fcgru_read_buffer: no forward has run on this plan");
+  hipStream_t s = (hipStream_t)stream;
+  const long long total = v.rows * g->n;
+  const int blocks = (int)std::min<long long>((total + 255) / 256, 8192);
+  if (v.operand && g->dtype == RGP_BF16)
+    fc_read_rows_kernel<bf16_t><<<blocks, 256, 0, s>>>((const bf16_t*)(g->ws + v.off), dst, g->n, g->np, total);
+  else
+    fc_read_rows_kernel<float><<<blocks, 256, 0, s>>>((const float*)(g->ws + v.off), dst, g->n, g->np, total);
   RGP_HIP(hipGetLastError());
   return RGP_OK;
 }

@@ -78,11 +78,31 @@ class PersistentLaunch {
   int rc_;
 };
 
+// The error word of a plan with persistent launches: pinned host memory the device writes directly, so the host can test it
+// at the start of any later call without a synchronisation.  A launch that timed out sets it.
+struct PinnedErrWord {
+  unsigned* host = nullptr;
+  int alloc() {
+    if (host) return RGP_OK;
+    void* e = nullptr;
+    RGP_HIP(hipHostMalloc(&e, 64, hipHostMallocMapped));
+    host = (unsigned*)e;
+    *(volatile unsigned*)host = 0u;
+    return RGP_OK;
+  }
+  void release() { if (host) (void)hipHostFree(host); host = nullptr; }
+  int check(const char* msg) {                        // RGP_ETIMEOUT with `msg` (and clears the word) if a launch lost a member
+    if (!host || !*(volatile unsigned*)host) return RGP_OK;
+    *(volatile unsigned*)host = 0u;
+    return set_err(RGP_ETIMEOUT, "%s", msg);
+  }
+};
+
 // Host side of the persistent recurrence kernels (seq_group.hip.h), one per plan: up to 2 clips per group of 8 workgroups
 // and at most 32 groups (= the 256 CUs of the chip), i.e. plans of up to 64 clips.
 struct SeqGroupPlan {
   int nc = 0, groups = 0;           // clips per group / groups (0 = the per-step path)
-  unsigned* err_host = nullptr;     // pinned, device-visible error word: a persistent launch that timed out sets it
+  PinnedErrWord err;                // a persistent launch that timed out sets it
   int fault = 0;                    // fault injection: the next launch that owns a set bit loses a member of group 0
   void size(int batch) { nc = (batch + 31) / 32; groups = (batch + nc - 1) / nc; }
   // All workgroups (8 per group, one per CU) fit on the current device together, `reserve` CUs left over.  A plan without
@@ -92,24 +112,11 @@ struct SeqGroupPlan {
     if (groups <= 0 || device_cu_count(&n_cu) != RGP_OK) return if_none;
     return groups * 8 <= n_cu - reserve;
   }
-  // The error word is pinned host memory the device writes directly, so the host can test it at the start of any later
-  // call without a synchronisation.
-  int alloc_err() {
-    if (groups <= 0 || err_host) return RGP_OK;
-    void* e = nullptr;
-    RGP_HIP(hipHostMalloc(&e, 64, hipHostMallocMapped));
-    err_host = (unsigned*)e;
-    *(volatile unsigned*)err_host = 0u;
-    return RGP_OK;
-  }
-  void free_err() { if (err_host) (void)hipHostFree(err_host); err_host = nullptr; }
-  int check_err(const char* msg) {                    // RGP_ETIMEOUT with `msg` (and clears the word) if a launch lost a member
-    if (!err_host || !*(volatile unsigned*)err_host) return RGP_OK;
-    *(volatile unsigned*)err_host = 0u;
-    return set_err(RGP_ETIMEOUT, "%s", msg);
-  }
+  int alloc_err() { return groups <= 0 ? RGP_OK : err.alloc(); }      // (plans without groups never need the word)
+  void free_err() { err.release(); }
+  int check_err(const char* msg) { return err.check(msg); }
   SeqGroupArgs args(int batch, unsigned* cnt, int fault_bit) {    // of the next launch; consumes its fault bit
-    SeqGroupArgs a{cnt, err_host, batch, nc, groups, (fault & fault_bit) ? 7 : -1};
+    SeqGroupArgs a{cnt, err.host, batch, nc, groups, (fault & fault_bit) ? 7 : -1};
     fault &= ~fault_bit;
     return a;
   }

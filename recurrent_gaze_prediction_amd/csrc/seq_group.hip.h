@@ -63,6 +63,17 @@ __device__ __forceinline__ bool seq_wait_phase(const unsigned* cnt) {      // tr
     if ((spins & 63u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > SEQ_DEADLINE_TICKS) return false;
   }
 }
+// The same wait for a rendezvous of `n` members (fcgru_seq.hip.h: every workgroup of the launch).  A sibling, not a
+// parameter of the function above: the conv-recurrent kernels keep the code they were measured with.
+__device__ __forceinline__ bool seq_wait_phase_n(const unsigned* cnt, unsigned n) {
+  if (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n) return true;
+  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+  for (unsigned spins = 1;; ++spins) {
+    __builtin_amdgcn_s_sleep(2);
+    if (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n) return true;
+    if ((spins & 63u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > SEQ_DEADLINE_TICKS) return false;
+  }
+}
 
 // pixel of position r49 = 7 y + x in a halo-padded 9x9 image
 __device__ __forceinline__ int seq_pad_pix(int r49) { return (r49 / 7 + 1) * 9 + (r49 % 7 + 1); }

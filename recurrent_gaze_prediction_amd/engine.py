@@ -688,19 +688,33 @@ def softmax_xent(logits, labels=None, want_probs=True):
 
 
 class FcGruEngine(object):
-    """fc-GRU gaze model (models/gaze_rnn.py:211-360, BASELINE config 2) at fixed (B, T, GH, GW)."""
+    """fc-GRU gaze model (models/gaze_rnn.py:211-360, BASELINE config 2) at fixed (B, T, GH, GW).
 
-    def __init__(self, batch, n_steps, gazemap_hw=(49, 49), dtype='f32', device='cuda:0', save_for_backward=False):
+    per_step=True names the per-timestep recurrence (RGP_FCGRU_PER_STEP: two launches per step), persistent=True the
+    one-launch recurrence with resident kernels (RGP_FCGRU_PERSISTENT, csrc/fcgru_seq.hip.h: bf16 plans of at most 64
+    clips on a device with at least 203 CUs, refused otherwise); with both False the library chooses (per step).
+    read_buffer (training plans, after a forward; fp32): 'xpre' [B,T,3,1617], 'h' [T+1,B,1617], 'u', 'r', 'c'
+    [T,B,1617], 'hp' [B,T+1,1617], 'rh' [B,T,1617]."""
+
+    BUFFER_SHAPES = {'xpre': lambda B, T: (B, T, 3, 1617), 'h': lambda B, T: (T + 1, B, 1617), 'u': lambda B, T: (T, B, 1617),
+                     'r': lambda B, T: (T, B, 1617), 'c': lambda B, T: (T, B, 1617), 'hp': lambda B, T: (B, T + 1, 1617),
+                     'rh': lambda B, T: (B, T, 1617)}
+
+    def __init__(self, batch, n_steps, gazemap_hw=(49, 49), dtype='f32', device='cuda:0', save_for_backward=False,
+                 per_step=False, persistent=False):
         self.lib = _lib.load()
         self.device = _require_gpu(device)
         self.B, self.T, self.GH, self.GW = int(batch), int(n_steps), int(gazemap_hw[0]), int(gazemap_hw[1])
         self.dtype = dtype
         self.save_for_backward = bool(save_for_backward)
+        self.per_step = bool(per_step)
         self.flat_params = self.flat_grads = self.grads = self.adam_m = self.adam_v = None
         self._h = ctypes.c_void_p()
+        flags = (_lib.RGP_FCGRU_SAVE_FOR_BACKWARD if save_for_backward else 0) | (_lib.RGP_FCGRU_PER_STEP if per_step else 0) | \
+            (_lib.RGP_FCGRU_PERSISTENT if persistent else 0)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_fcgru_create_ex(ctypes.byref(self._h), self.B, self.T, self.GH, self.GW,
-                                                    _lib.DTYPES[dtype], int(self.save_for_backward)))
+            _lib.check(self.lib.rgp_fcgru_create_flags(ctypes.byref(self._h), self.B, self.T, self.GH, self.GW,
+                                                       _lib.DTYPES[dtype], flags))
             nbytes = self.lib.rgp_fcgru_workspace_bytes(self._h)
             self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             _lib.check(self.lib.rgp_fcgru_bind_workspace(self._h, _ptr(self.workspace), nbytes, _stream_ptr(self.device)))
@@ -748,6 +762,32 @@ class FcGruEngine(object):
 
     def adam_step(self, step, lr, max_grad_norm=10.0, method='adam'):
         return clip_step_multi([self], step, lr, max_grad_norm, method)
+
+    def status(self):
+        """Wait for the current stream and raise RgpError (RGP_ETIMEOUT) if a persistent launch of this plan lost a
+        member since the last check (its outputs are NaN)."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_fcgru_status(self._h, _stream_ptr(self.device)))
+
+    @property
+    def persistent_workgroups(self):
+        """CUs the persistent recurrence launch of this plan occupies (0: per-timestep launches)."""
+        return int(self.lib.rgp_fcgru_persistent_workgroups(self._h))
+
+    @property
+    def persistent(self):
+        return self.persistent_workgroups > 0
+
+    def read_buffer(self, name):
+        """An intermediate of the last forward of a training plan (rgp_fcgru_read_buffer), fp32, shaped as the class
+        docstring lists."""
+        if name not in self.BUFFER_SHAPES:
+            raise _lib.RgpError('unknown intermediate %r' % name)
+        shape = self.BUFFER_SHAPES[name](self.B, self.T)
+        out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_fcgru_read_buffer(self._h, name.encode(), _ptr(out), _stream_ptr(self.device)))
+        return out
 
     def forward(self, c3d_input, want_probs=True, train=False):
         """train=True draws a fresh dropout mask when dropout.configure(keep < 1) was called (single_step feeds

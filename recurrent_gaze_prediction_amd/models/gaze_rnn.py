@@ -42,6 +42,9 @@ class GRUModelConfig(BaseModelConfig):
         self.init_seed = 0
         self.flip_seed = None          # None: derived from init_seed and the rank (recorded in the log / checkpoint)
         self.train_keep_prob = 0.5     # keep_prob single_step feeds when training (gaze_rnn.py:529)
+        # recurrence path of the fc-GRU engine: None (the library's choice: per step), 'per_step' or 'persistent' (all T
+        # steps in one launch, csrc/fcgru_seq.hip.h: bf16, at most 64 clips; gaze_rnn77 inherits it)
+        self.fcgru_path = None
 
 
 DROPOUT_RANK_STRIDE = 0x9E3779B1     # key offset between data-parallel ranks (also used by the checkpoint loader)
@@ -132,9 +135,12 @@ class GazePredictionGRU(ModelBase):
         assert model is not None
         if net is None:
             net = {}
+        path = getattr(model.config, 'fcgru_path', None)
+        assert path in (None, 'persistent', 'per_step'), path
         engine = FcGruEngine(model.batch_size, model.n_lstm_steps, (model.gazemap_height, model.gazemap_width),
                              dtype=getattr(model.config, 'compute_dtype', 'f32'), device=model.session.device,
-                             save_for_backward=getattr(model.config, 'trainable', True))
+                             save_for_backward=getattr(model.config, 'trainable', True),
+                             per_step=path == 'per_step', persistent=path == 'persistent')
         model.variables = synthetic.fcgru_params(getattr(model.config, 'init_seed', 0), model.gazemap_height,
                                                  model.gazemap_width)
         engine.set_weights(model.variables)
@@ -317,8 +323,30 @@ class GazePredictionGRU(ModelBase):
             return True
 
     def _recover_from_timeout(self):
-        """Models whose engine has a time-out-free variant override this (GazePredictionGRCN)."""
-        return False
+        """The fc-GRU model (this class, gaze_rnn77): a persistent recurrence launch lost a member (include/rgp.h) --
+        continue on a plan that runs the recurrence as per-timestep launches (RGP_FCGRU_PER_STEP).  A new engine object in
+        this process; master weights, optimizer slots and the dropout site move over; the caller recomputes the poisoned
+        batch.  Same shape as models/gaze_lstm.py.  The models of the other families override this; one that does not,
+        and whose engine is not the fc-GRU's, has no fallback (False)."""
+        from .. import engine as _engine
+        old = self.engine
+        if not isinstance(old, _engine.FcGruEngine) or getattr(old, 'per_step', False):
+            return False
+        log.warning('persistent fc-GRU launch timed out (RGP_ETIMEOUT): switching this model to per-timestep launches')
+        new = _engine.FcGruEngine(old.B, old.T, (old.GH, old.GW), dtype=old.dtype, device=old.device,
+                                  save_for_backward=old.save_for_backward, per_step=True)
+        new.set_weights(old.weights)
+        for k in _engine.OPT_STATE_KEYS:
+            if getattr(old, k, None) is not None:
+                setattr(new, k, getattr(old, k).clone())
+        if getattr(old, 'dropout', None) is not None and getattr(new, 'dropout', None) is not None:
+            # the site's key AND its draw counter: the mask sequence goes on where it was (the recomputed batch draws the
+            # mask after the one the poisoned forward used), it does not start again from the seed
+            new.dropout.configure(old.dropout.keep_prob, seed=old.dropout.seed)
+            new.dropout.draws = old.dropout.draws
+        self.engine = new
+        self.config.fcgru_path = 'per_step'
+        return True
 
     def _has_dropout(self):
         e = getattr(self.engine, 'net', self.engine)

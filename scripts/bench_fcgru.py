@@ -1,0 +1,130 @@
+#!/usr/bin/env python
+"""Time the fc-GRU (gaze_rnn, gaze_rnn77): the persistent recurrence (RGP_FCGRU_PERSISTENT, csrc/fcgru_seq.hip.h) against the
+per-step path, forward and training step.
+
+Shapes (B x T, map side): 64x16 (BASELINE config 2, 7x7), 8x35 (49x49) and 7x35 (gaze_rnn77's, 7x7), bf16.  For each shape
+one 'per_step' and one 'persistent' plan with the same weights are built in ONE process on one device, all are warmed
+first, and the two paths ALTERNATE: a window is --calls calls of one path between two device synchronisations (host
+clock), --windows windows per path; the figure is the median window divided by the calls, the spread is (max - min) /
+median of the windows (the protocol of bench_stream.py).  The training step is forward + backward + clipped Adam + re-pack
+on two training plans per shape, alternating the same way.
+
+--forward-only: the inference forward alone, and of the per-step path alone on a build whose engine has no `persistent`
+argument: for build-to-build A/Bs of the default path (run it on both builds, alternating).
+Writes one JSON document (--out) and prints it.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SHAPES = ((64, 16, 7), (8, 35, 49), (7, 35, 7))
+
+
+def window(fn, calls, sync):
+    sync()
+    t0 = time.perf_counter()
+    for _ in range(calls):
+        fn()
+    sync()
+    return (time.perf_counter() - t0) * 1e3 / calls
+
+
+def summarise(ms):
+    med = float(np.median(ms))
+    return {'ms_median': med, 'ms_min': float(np.min(ms)), 'ms_max': float(np.max(ms)),
+            'spread': float((np.max(ms) - np.min(ms)) / med), 'windows': len(ms)}
+
+
+def compare(entry, a, b):
+    entry['persistent_over_per_step'] = entry[a]['ms_median'] / entry[b]['ms_median']
+    entry['persistent_faster'] = bool(entry[a]['ms_max'] < entry[b]['ms_min'])       # every window, not just the medians
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--calls', type=int, default=50, help='calls per timed window')
+    ap.add_argument('--windows', type=int, default=7, help='windows per path')
+    ap.add_argument('--forward-only', action='store_true')
+    ap.add_argument('--out', default=os.path.join('profiles', 'fcgru_bench.json'))
+    a = ap.parse_args()
+
+    import inspect
+    import torch
+    from recurrent_gaze_prediction_amd import synthetic as syn
+    from recurrent_gaze_prediction_amd.engine import FcGruEngine
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_fcgru.py needs a GPU: timings taken elsewhere say nothing about it')
+    dev = torch.device('cuda:0')
+    sync = torch.cuda.synchronize
+    has_paths = 'persistent' in inspect.signature(FcGruEngine.__init__).parameters
+    paths = ('per_step', 'persistent') if has_paths else ('per_step',)
+
+    def make(B, T, GH, path, train):
+        kw = {path: True} if has_paths else {}
+        eng = FcGruEngine(B, T, (GH, GH), dtype='bf16', device=dev, save_for_backward=train, **kw)
+        eng.set_weights(syn.fcgru_params(0, GH, GH))
+        assert not has_paths or eng.persistent == (path == 'persistent')
+        return eng
+
+    result = {'device': torch.cuda.get_device_name(0), 'calls_per_window': a.calls, 'windows': a.windows, 'dtype': 'bf16',
+              'method': 'host clock around windows of calls between device synchronisations; paths alternate; median window / calls',
+              'forward_only': bool(a.forward_only), 'paths': list(paths), 'shapes': {}}
+    for B, T, GH in SHAPES:
+        x = torch.tensor(syn.c3d_features(1, B, T), device=dev)
+        engs = {p: make(B, T, GH, p, False) for p in paths}
+        for e in engs.values():
+            for _ in range(3):
+                e.forward(x)
+        sync()
+        ms = {p: [] for p in paths}
+        for _ in range(a.windows):
+            for p in paths:
+                ms[p].append(window(lambda: engs[p].forward(x), a.calls, sync))
+        entry = {'frames': B * T, 'map': GH, 'forward': {p: summarise(v) for p, v in ms.items()}}
+        if has_paths:
+            engs['persistent'].status()
+            compare(entry['forward'], 'persistent', 'per_step')
+        result['shapes']['%dx%d' % (B, T)] = entry
+        del engs
+        if a.forward_only:
+            continue
+        g = syn.gaze_maps(2, B, T, hw=GH)[0]
+        labels = torch.tensor(g / g.reshape(B, T, -1).sum(-1)[..., None, None], device=dev).contiguous()
+        engs = {p: make(B, T, GH, p, True) for p in paths}
+        step = [0]
+
+        def train(eng):
+            logits, probs = eng.forward(x)
+            eng.backward(logits, probs, labels)
+            eng.adam_step(step[0], 1e-4)
+            step[0] += 1
+        for e in engs.values():
+            for _ in range(3):
+                train(e)
+        sync()
+        ms = {p: [] for p in paths}
+        for _ in range(a.windows):
+            for p in paths:
+                ms[p].append(window(lambda: train(engs[p]), max(a.calls // 5, 1), sync))
+        entry['train_step'] = {p: summarise(v) for p, v in ms.items()}
+        if has_paths:
+            engs['persistent'].status()
+            compare(entry['train_step'], 'persistent', 'per_step')
+        del engs
+    if has_paths:
+        result['default_of_eligible_plans'] = 'persistent' if FcGruEngine(2, 2, (7, 7), dtype='bf16', device=dev).persistent else 'per_step'
+    text = json.dumps(result, indent=1, sort_keys=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as fp:
+        fp.write(text + '\n')
+    print(text)
+
+
+if __name__ == '__main__':
+    main()

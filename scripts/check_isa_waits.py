@@ -7,7 +7,10 @@ adds a draining `s_waitcnt vmcnt(0)` before the fragment reads depends on its re
 (a global load consumed only under a condition leaves "maybe pending" registers; re-using one of them inside the loop
 forces the wait) -- it appeared and disappeared with unrelated edits during round 1.  Run after touching
 igemm_stagger.hip.h / igemm_wide.hip.h / igemm.hip.h epilogues:   python scripts/check_isa_waits.py
-Also checks the wgrad_patch.hip.h kernels (no scratch access between their MFMAs, accumulation in place).
+Also checks the wgrad_patch.hip.h kernels (no scratch access between their MFMAs, accumulation in place), and the
+persistent fc-GRU kernel (fcgru_seq.hip.h): in each of its two phases all 13 x NF sixteen-byte exchange loads of a wave
+must stand in front of the phase's first MFMA (the scheduler, left alone, sinks them between the MFMAs and re-uses 2 - 4
+registers: 2 - 3 loads in flight instead of the >= 8 the hand-off needs), and nothing may spill.
 """
 import os, subprocess, sys, tempfile
 
@@ -93,8 +96,48 @@ def patch_faults(name, body):
     return faults
 
 
+def fcgru_kernels(asm):
+    lines = asm.split('\n')
+    for st, l in enumerate(lines):
+        if l.startswith('_ZN3rgpL16fcgru_seq_kernel') and '@' in l:
+            end = next(i for i in range(st, len(lines)) if 's_endpgm' in lines[i])
+            yield l.split(':')[0], lines[st:end]
+
+
+def fcgru_faults(name, body):
+    """Runs of sc1 exchange loads and of MFMAs, in program order: exactly [13 NF loads, 13 NF MFMAs] twice."""
+    nf = int(name.split('fcgru_seq_kernelILi')[1][0])
+    runs = []
+    for l in body:
+        k = 'L' if ('buffer_load_dwordx4' in l and 'sc1' in l) else 'M' if 'v_mfma' in l else None
+        if k and runs and runs[-1][0] == k:
+            runs[-1][1] += 1
+        elif k:
+            runs.append([k, 1])
+    faults = []
+    if runs != [['L', 13 * nf], ['M', 13 * nf]] * 2:
+        faults.append('loads / MFMAs interleaved: ' + ' '.join('%s%d' % (k, n) for k, n in runs))
+    if any('scratch_' in l for l in body):
+        faults.append('scratch access')
+    return faults
+
+
 def main():
     rc = 0
+    with tempfile.NamedTemporaryFile(suffix='.s') as tf:
+        subprocess.run(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-I' + os.path.join(ROOT, 'include'),
+                        '-I' + CSRC, '-S', '--cuda-device-only', '-o', tf.name, os.path.join(CSRC, 'rgp_fcgru.hip')], check=True,
+                       stderr=subprocess.DEVNULL)
+        asm = open(tf.name).read()
+    n = nbad = 0
+    for name, body in fcgru_kernels(asm):
+        n += 1
+        faults = fcgru_faults(name, body)
+        if faults:
+            nbad += 1
+            print('FCGRU_SEQ', name[:100], faults)
+    print('rgp_fcgru.hip: %d fcgru_seq kernels, %d with exchange loads not in front of their MFMAs, or spills' % (n, nbad))
+    rc |= nbad > 0 or n != 8
     with tempfile.NamedTemporaryFile(suffix='.s') as tf:
         subprocess.run(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-I' + os.path.join(ROOT, 'include'),
                         '-I' + CSRC, '-S', '--cuda-device-only', '-o', tf.name, os.path.join(CSRC, 'rgp_conv_patch.hip')], check=True,
