@@ -337,6 +337,23 @@ int rgp_fcgru_status(rgp_fcgru_t* plan, rgp_stream_t stream);
  * plan).  Errors: RGP_EINVAL for an unknown name; RGP_ESTATE on an inference plan or before the first forward. */
 int rgp_fcgru_read_buffer(rgp_fcgru_t* plan, const char* name, float* dst_fp32, rgp_stream_t stream);
 size_t rgp_fcgru_buffer_elems(const rgp_fcgru_t* plan, const char* name);
+/* Streaming inference, as rgp_grcn_forward_stream without bn_phase (this graph has no per-timestep batch-norm) and without
+ * a rows entry.  Streaming is a call, not a plan property: any plan takes it, on either recurrence path.
+ *   state_in   fp32 [B][1617], dense (the layout of a slot of "h" above, not the padded 1664); NULL = the zero state;
+ *              never written
+ *   state_out  may be NULL; must not be state_in; receives h behind step n_valid
+ *   n_valid    1..T.  All T steps are computed; the outputs of steps behind n_valid are unspecified, their inputs are read
+ *              but reach nothing the caller keeps (projection, x-GEMM, read-out and softmax are per frame, the recurrence
+ *              is causal)
+ * rgp_fcgru_forward_stream(.., NULL, state_out, T, ..) computes exactly what rgp_fcgru_forward computes.  Argument errors
+ * are RGP_EINVAL, name the argument, and come ahead of the bound / weights checks.  The dropout site behaves as in
+ * rgp_fcgru_forward (it is frame-local).  A training plan accepts the call; rgp_fcgru_backward then returns RGP_ESTATE
+ * (no truncated BPTT) until a plain forward has run.  A persistent launch that times out NaN-poisons state_out along with
+ * what it poisons anyway; state_in being read-only, the caller repeats the call.
+ * rgp_fcgru_state_elems: B*1617, the fp32 elements of a state; host-only, works on an unbound plan. */
+size_t rgp_fcgru_state_elems(const rgp_fcgru_t* plan);
+int rgp_fcgru_forward_stream(rgp_fcgru_t* plan, const float* c3d_input, const float* state_in, float* state_out, int n_valid,
+                             float* logits, float* probs, rgp_stream_t stream);
 /* ------------------------------------------------------------------ gaze_c3d_conv (the no-recurrence baseline) */
 typedef struct rgp_c3dconv rgp_c3dconv_t;
 

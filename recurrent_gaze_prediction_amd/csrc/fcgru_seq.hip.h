@@ -39,6 +39,19 @@
 // Padding: units 1617 .. 1623 of member 202 have zero kernel rows and zero xpre, so u = 1/2, c = 0 and h stays 0.
 // Time-out: a member whose wait passes the deadline stops waiting, sets the plan's error word and NaN-poisons its units of
 // every h row (all steps, all clips) and of the fp32 states: the logits are NaN, never finite and wrong.
+//
+// Streaming (rgp_fcgru_forward_stream), template argument STREAM.  STREAM = false is the kernel above (one expression apart: the
+// blend is now spelled as one rounded product and one fma, see there -- both instantiations must round alike), and is what
+// zero-state calls over all T steps launch.  STREAM = true starts from a caller's state: fcgru_seed_kernel
+// (rgp_fcgru.hip) has put fp32 h_{-1} into slot 0 of hall and its bf16 rows into the plan's operand row of step 0 -- hp
+// (row b, stride np) on inference plans, slot (b, 0) of hp_all (stride (T + 1) np) on training plans -- so thread b loads its
+// 8 fp32 h from slot 0 ahead of the step loop (it alone writes those 8 floats later: no race), and phase A of step 0 runs
+// the same fcs_gemm on the seeded rows instead of skipping; base and strides are selected per step, so the phase still is ONE
+// run of loads in front of ONE run of MFMAs.  No new exchange buffer.  Write-after-read: the seeded rows are only READ, in
+// phase A of step 0, and never written by this kernel (h_t goes to hrows, and to slots >= 1 of hp_all): nothing to order.
+// State out: inference hall is a two-slot ping-pong, so h behind step n_valid < T does not survive the launch; on inference
+// plans thread b stores its 8 fp32 h behind step n_valid - 1 into hsnap [B][np] (training plans: the host reads slot n_valid
+// of hall_t).  A timed-out launch NaN-poisons hsnap with the rest.
 #pragma once
 #include "seq_group.hip.h"
 
@@ -67,6 +80,14 @@ struct FcSeqParams {
   unsigned* cnt;             // [2 T][FCS_SHARDS][FCS_CNT_STRIDE] phase counters, zeroed ahead of the launch
   unsigned* err;             // the plan's pinned error word
   int B, T;
+};
+// STREAM = true takes these on top (the STREAM = false instantiations keep the parameter block they were measured with)
+struct FcSeqStreamParams : FcSeqParams {
+  const bf16_t* seed;        // bf16 rows of h_{-1}: inference hp [B][np]; training hp_all, slot (b, 0)
+  unsigned seed_bytes;       // extent of that buffer (rows >= B lie behind it and read zeros)
+  unsigned seed_stride;      // bytes from clip b to clip b + 1: np * 2, or (T + 1) * np * 2
+  float* hsnap;              // inference: [B][np] fp32 h behind step n_valid - 1; training: null
+  int n_valid;
 };
 
 // A fragments of this wave's K quarter from exchange rows (sc1), then the MFMAs of one resident column block on them.
@@ -122,8 +143,11 @@ __device__ __forceinline__ u32x4 fcs_pack8(const float (&v)[8]) {
   return q;
 }
 
-template <int NF, bool SAVE>
-static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const FcSeqParams p) {
+template <bool STREAM> struct FcSeqParamsOf { typedef FcSeqParams type; };
+template <> struct FcSeqParamsOf<true> { typedef FcSeqStreamParams type; };
+
+template <int NF, bool SAVE, bool STREAM>
+static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const typename FcSeqParamsOf<STREAM>::type p) {
   __shared__ __attribute__((aligned(16))) char red[4 * NF * 16 * FCS_PITCH];   // [K quarter][row][16 columns]
   __shared__ int s_timeout;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -158,6 +182,14 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const FcSeqPar
   const unsigned rbytes = SAVE ? hbytes : (unsigned)B * (unsigned)np * 2u;
   const unsigned koff = (unsigned)((kq * FCS_KW * 32 + fk * 8) * 2);     // the lane's K offset in a row, bytes
   const long long st = (long long)B * np;
+  if constexpr (STREAM) {                                  // the caller's state: slot 0 of hall (fcgru_seed_kernel)
+    if (own) {
+      const float* h0 = p.hall + (long long)b * np + u0;
+      const f32x4 lo = *(const f32x4*)h0, hi = *(const f32x4*)(h0 + 4);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { h[i] = lo[i]; h[4 + i] = hi[i]; }
+    }
+  }
   __syncthreads();                                         // flag cleared
 
   // this wave's partial tiles -> LDS; the sum over the 4 quarters of row `tid` (16 columns)
@@ -209,7 +241,12 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const FcSeqPar
       f32x4 acc[NF];
 #pragma unroll
       for (int f = 0; f < NF; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (t > 0)
+      if constexpr (STREAM) {                              // step 0: the seeded rows of h_{-1}
+        const bool first = t == 0;
+        const unsigned rstride = first ? p.seed_stride : (unsigned)T_ * (unsigned)(np * 2);
+        fcs_gemm<NF>(first ? (const void*)p.seed : (const void*)p.hrows, first ? p.seed_bytes : hbytes,
+                     (unsigned)frow * rstride + (first ? 0u : (unsigned)(t - 1) * (unsigned)(np * 2)) + koff, 16u * rstride, bzr, acc);
+      } else if (t > 0)
         fcs_gemm<NF>(p.hrows, hbytes, ((unsigned)frow * (unsigned)T_ + (unsigned)(t - 1)) * (unsigned)(np * 2) + koff,
                      16u * (unsigned)T_ * (unsigned)(np * 2), bzr, acc);
       store_partials(acc);
@@ -258,7 +295,11 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const FcSeqPar
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         cg[i] = tanhf_(s[i] + x[4 + (i >> 2)][i & 3]);
-        h[i] = u[i] * h[i] + (1.f - u[i]) * cg[i];
+        // The blend with its roundings spelled out: ONE product rounded, then one fused multiply-add.  Written as
+        // u h + (1 - u) c the compiler is free to fuse either product into the add, and it chose differently from unit to unit
+        // and from instantiation to instantiation (STREAM = false / true differed in rare last bits, measured at B = 64): a
+        // stream cut between a zero-state launch and a seeded one must give the bits of the uncut recurrence.
+        h[i] = __builtin_fmaf(u[i], h[i], (1.f - u[i]) * cg[i]);
       }
       if (own) seq_st_sc1(p.hrows, hbytes, (((unsigned)b * (unsigned)T_ + (unsigned)t) * (unsigned)np + (unsigned)u0) * 2u, fcs_pack8(h));
     }
@@ -269,6 +310,9 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const FcSeqPar
       if (SAVE) {
         store8f(p.call + (long long)t * st + off, cg);
         *(u32x4*)(p.hp_all + ((long long)b * (T_ + 1) + t + 1) * np + u0) = fcs_pack8(h);
+      }
+      if constexpr (STREAM && !SAVE) {
+        if (t + 1 == p.n_valid) store8f(p.hsnap + off, h);
       }
     }
   }
@@ -287,6 +331,7 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const FcSeqPar
         if (SAVE) store8f(p.hall + (long long)(t + 1) * st + off, fnan);
       }
       if (!SAVE) { store8f(p.hall + off, fnan); store8f(p.hall + st + off, fnan); }
+      if constexpr (STREAM && !SAVE) store8f(p.hsnap + off, fnan);
     }
   }
 }

@@ -15,6 +15,9 @@
 // Recurrence, two implementations: per step (every plan; the library's choice), and -- RGP_FCGRU_PERSISTENT, bf16 plans of
 // at most 64 clips -- all T steps in one persistent launch with the h-side kernels resident in registers
 // (fcgru_seq.hip.h).  Both write the same buffers in the same layouts, so the backward runs unchanged behind either.
+// Streaming (rgp_fcgru_forward_stream): the same forward started from a caller's h_{-1} [B][1617] instead of zeros, on either
+// path and on inference and training plans.  Way in: fcgru_seed_kernel, one launch in place of the two memsets.  Way out: one
+// strided copy of the fp32 state behind step n_valid.  Nothing else in the per-step loop changes.
 #include <algorithm>
 
 #include <string>
@@ -53,6 +56,15 @@ struct rgp_fcgru {
   bool persistent = false, fwd_done = false;
   size_t seq_cnt = 0;                                 // [2 T][FCS_SHARDS][FCS_CNT_STRIDE] phase counters
   PinnedErrWord err;                                  // set by a launch that lost a member (allocated at bind, persistent plans only)
+  size_t hsnap = 0;                                   // fp32 [B][np]: h behind step n_valid of a streaming launch (persistent inference plans)
+  // ---- streaming (rgp_fcgru_forward_stream): set around one call's forward_impl
+  bool st_on = false;
+  const float* st_in = nullptr;                       // [B][n] dense, null = zeros
+  float* st_out = nullptr;                            // [B][n] dense, or null
+  int st_nvalid = 0;
+  bool slot0_seeded = false;                          // training plans: slot (b, 0) of hp_all holds a caller's state, not the zeros of the
+                                                      // bind -- the next zero-state forward clears it first
+  bool streamed_last = false;                         // the buffers are a streaming call's: no backward (no truncated BPTT)
 };
 
 namespace rgp {
@@ -123,12 +135,54 @@ __global__ void fill_kernel(float* p, float v, int n) {
   if (i < n) p[i] = v;
 }
 
-// All T steps in one persistent launch (fcgru_seq.hip.h)
-template <bool SAVE>
+// rows of `np` elements, the first n columns of each kept, widened to fp32 and stored dense: rgp_fcgru_read_buffer, and the
+// state a streaming call hands out
+template <typename T>
+__global__ __launch_bounds__(256) void fc_read_rows_kernel(const T* __restrict__ src, float* __restrict__ dst, int n, int np, long long total) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256)
+    dst[i] = Elem<T>::from(src[(i / n) * np + (i % n)]);
+}
+
+// Streaming calls: the state a recurrence starts from, where each path reads its step -1 (as seq_seed_kernel does for the
+// conv-recurrent families).  h_in [B][n] dense fp32, or null = zeros -> fp32 h0 [B][np] (slot 0 of hall / hall_t) and the
+// operand rows, row b at rows + b * row_stride: hp (stride np) on inference plans, slot (b, 0) of hp_all (stride (T + 1) np)
+// on training plans.  Columns >= n are written as zeros.  The conversion is the epilogues' (Elem<T>::to = f2bf: EpiGruC,
+// fcs_pack8), so the operand row of a cut stream is bit for bit the row an uncut recurrence publishes at that step.
+template <typename T>
+__global__ __launch_bounds__(256) void fcgru_seed_kernel(const float* __restrict__ h_in, float* __restrict__ h0, T* __restrict__ rows,
+                                                         long long row_stride, int B, int n, int np) {
+  const int total = B * np;                              // (B * 1664 < 2^31 for every plan that fits a device)
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int b = i / np, j = i - b * np;
+    const float v = (h_in && j < n) ? h_in[(long long)b * n + j] : 0.f;
+    h0[i] = v;
+    rows[(long long)b * row_stride + j] = Elem<T>::to(v);
+  }
+}
+
+// the dense [B][n] state behind a step, from its padded fp32 rows: one strided copy
+int state_out_copy(rgp_fcgru* g, const float* src, hipStream_t s) {
+  if (!g->st_out) return RGP_OK;
+  const long long total = (long long)g->B * g->n;
+  fc_read_rows_kernel<float><<<(int)std::min<long long>((total + 255) / 256, 8192), 256, 0, s>>>(src, g->st_out, g->n, g->np, total);
+  RGP_HIP(hipGetLastError());
+  return RGP_OK;
+}
+
+// All T steps in one persistent launch (fcgru_seq.hip.h).  STREAM: from the seeded state (fcgru_seed_kernel has run), and --
+// inference plans -- with the snapshot behind step n_valid.
+template <bool SAVE, bool STREAM>
 int seq_persistent(rgp_fcgru* g, hipStream_t s) {
   char* ws = g->ws;
   RGP_HIP(hipMemsetAsync(ws + g->seq_cnt, 0, (size_t)2 * g->T * FCS_SHARDS * FCS_CNT_STRIDE * 4, s));         // phase counters: zeroed EVERY call
-  FcSeqParams p;
+  typename FcSeqParamsOf<STREAM>::type p;
+  if constexpr (STREAM) {
+    p.seed = (const bf16_t*)(ws + (SAVE ? g->hp_all : g->hp));
+    p.seed_stride = (unsigned)((SAVE ? g->T + 1 : 1) * g->np * 2);
+    p.seed_bytes = (unsigned)g->B * p.seed_stride;       // (B <= 64, T <= 16384: below 2^32, as hbytes)
+    p.hsnap = SAVE ? nullptr : (float*)(ws + g->hsnap);
+    p.n_valid = g->st_nvalid;
+  }
   p.w_zr = (const bf16_t*)(ws + g->zr.w_off);
   p.w_c = (const bf16_t*)(ws + g->c.w_off);
   p.xpre = (const float*)(ws + g->xpre);
@@ -144,12 +198,12 @@ int seq_persistent(rgp_fcgru* g, hipStream_t s) {
   p.B = g->B; p.T = g->T;
   RGP_REQUIRE(g->np == FCS_NP && g->zr.K == FCS_NP && g->c.K == FCS_NP && g->zr.chunk_major == 0 && g->c.chunk_major == 0,
               "fcgru_seq: unexpected filter packing");
-  void (*kern)(FcSeqParams) = nullptr;
+  void (*kern)(typename FcSeqParamsOf<STREAM>::type) = nullptr;
   switch ((g->B + 15) / 16) {
-    case 1: kern = fcgru_seq_kernel<1, SAVE>; break;
-    case 2: kern = fcgru_seq_kernel<2, SAVE>; break;
-    case 3: kern = fcgru_seq_kernel<3, SAVE>; break;
-    case 4: kern = fcgru_seq_kernel<4, SAVE>; break;
+    case 1: kern = fcgru_seq_kernel<1, SAVE, STREAM>; break;
+    case 2: kern = fcgru_seq_kernel<2, SAVE, STREAM>; break;
+    case 3: kern = fcgru_seq_kernel<3, SAVE, STREAM>; break;
+    case 4: kern = fcgru_seq_kernel<4, SAVE, STREAM>; break;
     default: return set_err(RGP_EINVAL, "fcgru_seq: batch %d", g->B);
   }
   PersistentLaunch guard(s);
@@ -181,18 +235,36 @@ int forward_impl(rgp_fcgru* g, const float* c3d_input, float* logits, float* pro
     RGP_TRY((launch_igemm<T, 1, 1, EpiStore<float, true, false>>(p, e, s)));
   }
   const size_t st = (size_t)B * np;
-  if (!save) RGP_HIP(hipMemsetAsync(ws + g->hp, 0, st * sizeof(T), s));
   float* hall = (float*)(ws + (save ? g->hall_t : g->hall));
-  RGP_HIP(hipMemsetAsync(hall, 0, st * 4, s));
+  // h_{-1}: zeros, or a streaming call's state.  The seed launch stands in for the two memsets when there is a state to put
+  // in place, and -- training plans -- once when the call before left one in slot (b, 0) of hp_all.
+  const float* h_in = g->st_on ? g->st_in : nullptr;
+  if (h_in || g->slot0_seeded) {
+    T* rows = (T*)(ws + (save ? g->hp_all : g->hp));
+    fcgru_seed_kernel<T><<<(int)std::min<size_t>((st + 255) / 256, 4096), 256, 0, s>>>(h_in, hall, rows, save ? (long long)(T_ + 1) * np : np, B,
+                                                                                    g->n, np);
+    RGP_HIP(hipGetLastError());
+    g->slot0_seeded = save && h_in != nullptr;
+  } else {
+    if (!save) RGP_HIP(hipMemsetAsync(ws + g->hp, 0, st * sizeof(T), s));
+    RGP_HIP(hipMemsetAsync(hall, 0, st * 4, s));
+  }
+  const int n_valid = g->st_on ? g->st_nvalid : T_;
   bool one_launch = false;
   if constexpr (sizeof(T) == 2) {
     if (g->persistent) {
-      RGP_TRY(save ? seq_persistent<true>(g, s) : seq_persistent<false>(g, s));
+      // STREAM = false: zero state (and, inference plans, every step kept: the ping-pong then ends on h behind step T)
+      const bool stream_kernel = h_in || (!save && n_valid < T_);
+      if (stream_kernel) RGP_TRY(save ? (seq_persistent<true, true>(g, s)) : (seq_persistent<false, true>(g, s)));
+      else RGP_TRY(save ? (seq_persistent<true, false>(g, s)) : (seq_persistent<false, false>(g, s)));
+      if (g->st_on)
+        RGP_TRY(state_out_copy(g, save ? hall + (size_t)n_valid * st : stream_kernel ? (const float*)(ws + g->hsnap) : hall + (size_t)(T_ & 1) * st, s));
       one_launch = true;
     }
   }
   for (int t = 0; t < T_ && !one_launch; ++t) {
-    // training keeps every step's states, gates and operand rows (slot (b, 0) of hp_all is never written = h_0)
+    // training keeps every step's states, gates and operand rows (slot (b, 0) of hp_all is h_{-1}: the zeros of the bind, unless a
+    // streaming call seeded it -- slot0_seeded above)
     char* hp_in = save ? ws + g->hp_all + (size_t)t * np * sizeof(T) : ws + g->hp;
     char* hp_out = save ? ws + g->hp_all + (size_t)(t + 1) * np * sizeof(T) : ws + g->hp;
     char* rh_buf = save ? ws + g->rh_all + (size_t)t * np * sizeof(T) : ws + g->rh;
@@ -228,6 +300,7 @@ int forward_impl(rgp_fcgru* g, const float* c3d_input, float* logits, float* pro
     IgemmParams pc = make_params(g->c, rh_buf, ws, B);
     pc.in_img_stride = rh_stride;
     RGP_TRY((launch_igemm<T, 1, 1, EpiGruC<T>>(pc, e, s)));
+    if (g->st_on && t + 1 == n_valid) RGP_TRY(state_out_copy(g, e.h_next, s));       // (the ping-pong slot is rewritten two steps on)
   }
   {  // output projection (gaze_rnn.py:346-349)
     IgemmParams p = make_params(g->out, ws + g->hrows, ws, F);
@@ -237,6 +310,7 @@ int forward_impl(rgp_fcgru* g, const float* c3d_input, float* logits, float* pro
   }
   if (probs) RGP_TRY(rgp_softmax_xent_fwd(logits, nullptr, probs, nullptr, nullptr, F, g->G, (rgp_stream_t)s));
   g->fwd_done = true;
+  g->streamed_last = g->st_on;
   return RGP_OK;
 }
 
@@ -260,12 +334,6 @@ bool find_view(const rgp_fcgru* g, const char* name, FcView& v) {
   else if (n == "rh") v = {g->rh_all, B * T_, true};
   else return false;
   return true;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void fc_read_rows_kernel(const T* __restrict__ src, float* __restrict__ dst, int n, int np, long long total) {
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256)
-    dst[i] = Elem<T>::from(src[(i / n) * np + (i % n)]);
 }
 
 // ---------------------------------------------------------------- backward kernels
@@ -557,6 +625,7 @@ int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazem
   g->ones = a.take((size_t)np * 4);
   g->zeros = a.take((size_t)np * 4);
   if (g->persistent) g->seq_cnt = a.take((size_t)2 * n_steps * FCS_SHARDS * FCS_CNT_STRIDE * 4);
+  if (g->persistent && !g->save) g->hsnap = a.take((size_t)batch * np * 4);
   if (g->save) {
     const size_t st = (size_t)batch * np;
     gemm_desc(g->b_out, np, g->Gp, g->Gp, np, dtype);
@@ -604,6 +673,7 @@ int rgp_fcgru_bind_workspace(rgp_fcgru_t* g, void* workspace, size_t bytes, rgp_
   g->ws = (char*)workspace;
   g->weights_set = false;
   g->fwd_done = false;
+  g->slot0_seeded = g->streamed_last = false;
   RGP_HIP(hipMemsetAsync(g->ws, 0, g->ws_bytes, s));
   for (ConvDesc* d : {&g->proj, &g->xg, &g->zr, &g->c, &g->out}) RGP_TRY(upload_desc(*d, g->ws, s));
   if (g->save) for (ConvDesc* d : {&g->b_out, &g->b_c, &g->b_zr, &g->b_x}) RGP_TRY(upload_desc(*d, g->ws, s));
@@ -632,6 +702,26 @@ int rgp_fcgru_forward(rgp_fcgru_t* g, const float* c3d_input, float* logits, flo
                               : forward_impl<float>(g, c3d_input, logits, probs, s);
 }
 
+size_t rgp_fcgru_state_elems(const rgp_fcgru_t* g) { return g ? (size_t)g->B * g->n : 0; }
+
+int rgp_fcgru_forward_stream(rgp_fcgru_t* g, const float* c3d_input, const float* state_in, float* state_out, int n_valid,
+                             float* logits, float* probs, rgp_stream_t stream) {
+  RGP_REQUIRE(g, "rgp_fcgru_forward_stream: null plan");
+  RGP_REQUIRE(c3d_input, "rgp_fcgru_forward_stream: null c3d_input");
+  RGP_REQUIRE(n_valid >= 1 && n_valid <= g->T, "rgp_fcgru_forward_stream: n_valid=%d must be in 1..%d", n_valid, g->T);
+  RGP_REQUIRE(!state_out || state_out != state_in, "rgp_fcgru_forward_stream: state_out must not alias state_in");
+  RGP_REQUIRE(logits, "rgp_fcgru_forward_stream: null logits");
+  if (!g->ws) return set_err(RGP_EWORKSPACE, "rgp_fcgru: workspace not bound");
+  if (!g->weights_set) return set_err(RGP_ESTATE, "rgp_fcgru: weights not set");
+  RGP_TRY(fcgru_check_error(g));
+  hipStream_t s = (hipStream_t)stream;
+  g->st_on = true; g->st_in = state_in; g->st_out = state_out; g->st_nvalid = n_valid;
+  const int rc = g->dtype == RGP_BF16 ? forward_impl<bf16_t>(g, c3d_input, logits, probs, s)
+                                      : forward_impl<float>(g, c3d_input, logits, probs, s);
+  g->st_on = false; g->st_in = nullptr; g->st_out = nullptr; g->st_nvalid = 0;
+  return rc;
+}
+
 int rgp_fcgru_backward(rgp_fcgru_t* g, const float* logits, const float* probs, const float* labels,
                        const rgp_fcgru_weights* grads, int loss_type, rgp_stream_t stream) {
   RGP_REQUIRE(g && logits && labels && grads, "rgp_fcgru_backward: null argument");
@@ -642,6 +732,8 @@ int rgp_fcgru_backward(rgp_fcgru_t* g, const float* logits, const float* probs, 
   const float* const* ptrs = (const float* const*)grads;
   for (size_t i = 0; i < sizeof(rgp_fcgru_weights) / sizeof(float*); ++i)
     RGP_REQUIRE(ptrs[i], "rgp_fcgru_backward: gradient pointer %zu is null", i);
+  if (g->streamed_last)
+    return set_err(RGP_ESTATE, "rgp_fcgru_backward: the last forward was a streaming call (no truncated BPTT): run rgp_fcgru_forward first");
   hipStream_t s = (hipStream_t)stream;
   RGP_TRY(g->dtype == RGP_BF16 ? backward_impl<bf16_t>(g, logits, probs, labels, grads, loss_type, s)
                                : backward_impl<float>(g, logits, probs, labels, grads, loss_type, s));

@@ -807,6 +807,36 @@ class FcGruEngine(object):
             _lib.check(self.lib.rgp_fcgru_forward(self._h, _ptr(x), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
         return logits, probs
 
+    STREAM_BN_PHASE = False     # this graph has no per-timestep batch-norm
+
+    @property
+    def state_elems(self):
+        """fp32 elements of the recurrent state forward_stream carries (rgp_fcgru_state_elems): B * 1617, h per clip."""
+        return int(self.lib.rgp_fcgru_state_elems(self._h))
+
+    def forward_stream(self, c3d_input, state=None, n_valid=None, want_probs=True):
+        """One call of a stream (rgp_fcgru_forward_stream): the graph of forward() started from `state` instead of zeros, on
+        either recurrence path and on inference and training plans (backward() is refused behind it until a plain forward).
+        c3d_input [B,T,1024,7,7] fp32 at the full plan size; the recurrence is defined for the first n_valid (default T)
+        steps, later outputs are unspecified.  state: fp32 device tensor of state_elems elements ([B, 1617], one slot of
+        read_buffer('h')) from an earlier call, or None = the zero state; never modified.  The dropout site is off.
+        Returns (logits, probs, new_state); new_state is a fresh tensor on every call: h behind step n_valid."""
+        x = c3d_input
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        assert tuple(x.shape) == (self.B, self.T, 1024, 7, 7), tuple(x.shape)
+        n_valid = self.T if n_valid is None else int(n_valid)
+        if state is not None:
+            assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous()
+            assert state.numel() == self.state_elems, (state.numel(), self.state_elems)
+        self.dropout.off()
+        logits = torch.empty(self.B, self.T, self.GH, self.GW, device=self.device)
+        probs = torch.empty_like(logits) if want_probs else None
+        new_state = torch.empty(self.state_elems, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_fcgru_forward_stream(self._h, _ptr(x), _ptr(state), _ptr(new_state), n_valid, _ptr(logits),
+                                                         _ptr(probs), _stream_ptr(self.device)))
+        return logits, probs, new_state
+
 
 class ShallowNetEngine(object):
     """Frame-wise ShallowNet (models/saliency_shallownet.py:74-216, BASELINE config 1)."""

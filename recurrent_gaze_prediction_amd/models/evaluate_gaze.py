@@ -186,7 +186,8 @@ def predict_long_clip(model, c3d, frames=None, pool_to_7x7=False, carry_state=Fa
     writes to <clip>.gazemap.npy: extract_map.avg_pool of every map (scipy's imresize to 7x7 over its sum, float64, NaN
     where the resized bytes sum to 0), made on the device from the maps predict() left there.
     carry_state=False is the reference's evaluation: every chunk starts from the zero state (extract_map.py:65).
-    carry_state=True runs the clip as ONE recurrence (stream.predict_long_clips; the conv-recurrent models only).
+    carry_state=True runs the clip as ONE recurrence (stream.predict_long_clips; every recurrent model of the family, the
+    fc-GRU models gaze_rnn / gaze_rnn77 included; gaze_c3d_conv has no state and refuses).
     frames means a different array on the two branches, and only the cascade reads it (every other model ignores it on both):
       carry_state=False  one batch [B,T,hw,hw,3], handed to every predict() call as it is (the chunks' own images are not cut
                          out of a clip here);

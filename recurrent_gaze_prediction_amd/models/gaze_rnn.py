@@ -131,21 +131,30 @@ class GazePredictionGRU(ModelBase):
         is an op of the engine: off at inference, keep = config.train_keep_prob (0.5, :529) with a fresh
         device-drawn mask per training step."""
         from .. import synthetic
-        from ..engine import FcGruEngine
         assert model is not None
         if net is None:
             net = {}
         path = getattr(model.config, 'fcgru_path', None)
         assert path in (None, 'persistent', 'per_step'), path
-        engine = FcGruEngine(model.batch_size, model.n_lstm_steps, (model.gazemap_height, model.gazemap_width),
-                             dtype=getattr(model.config, 'compute_dtype', 'f32'), device=model.session.device,
-                             save_for_backward=getattr(model.config, 'trainable', True),
-                             per_step=path == 'per_step', persistent=path == 'persistent')
+        engine = model._new_fcgru_engine(model.batch_size, model.n_lstm_steps, (model.gazemap_height, model.gazemap_width),
+                                         dtype=getattr(model.config, 'compute_dtype', 'f32'), device=model.session.device,
+                                         save_for_backward=getattr(model.config, 'trainable', True),
+                                         per_step=path == 'per_step', persistent=path == 'persistent')
         model.variables = synthetic.fcgru_params(getattr(model.config, 'init_seed', 0), model.gazemap_height,
                                                  model.gazemap_width)
         engine.set_weights(model.variables)
         engine.dropout.configure(getattr(model.config, 'train_keep_prob', 0.5), seed=dropout_seed(model.config, 0x5bd1e995))
         net['variables'] = model.variables
+        return engine
+
+    def _new_fcgru_engine(self, batch, n_steps, gazemap_hw, **kw):
+        """The one place that builds this model's FcGruEngine (the graph above, and the per-step plan _recover_from_timeout
+        falls back to).  The engine carries a recurrent state across calls (FcGruEngine.forward_stream), so the INSTANCE
+        streams; the class attribute STREAMS stays False: subclasses with other graphs (gaze_c3d_conv) and objects without
+        an engine refuse predict_stream."""
+        from ..engine import FcGruEngine
+        engine = FcGruEngine(batch, n_steps, gazemap_hw, **kw)
+        self.STREAMS = True
         return engine
 
     def state_dict(self):
@@ -276,7 +285,8 @@ class GazePredictionGRU(ModelBase):
         self.predicted_gazemaps = probs if want_probs else logits
         return self.predicted_gazemaps
 
-    # the conv-recurrent models whose engines carry a recurrent state across calls (engine.forward_stream)
+    # the models whose engines carry a recurrent state across calls (engine.forward_stream): the conv-recurrent classes set
+    # this on the class; the fc-GRU graph of THIS class sets it on the instance, where its engine is built (_new_fcgru_engine)
     STREAMS = False
     STATE_PARTS = 1             # tensors of [B, ...] the engine's flat state holds one after the other (gaze_lstm: h, c)
 
@@ -287,8 +297,9 @@ class GazePredictionGRU(ModelBase):
         -> (maps [B,T,GH,GW] device tensor, valid for the first n_valid steps; new_state, a fresh tensor)."""
         if not self.STREAMS:
             raise NotImplementedError('predict_stream: GazePredictionGRCN (gaze_grcn), GazePredictionGRCN77 (gaze_grcn77), '
-                                      'GazePredictionLSTM (gaze_lstm) and the cascade (gaze_grcn_cascade.GazePredictionGRCN) '
-                                      'stream; %s has no carried state' % type(self).__name__)
+                                      'GazePredictionLSTM (gaze_lstm), the cascade (gaze_grcn_cascade.GazePredictionGRCN) and the '
+                                      'fc-GRU models (GazePredictionGRU of gaze_rnn / gaze_rnn77, once their engine is built) '
+                                      'stream; this %s has no carried state' % type(self).__name__)
         x = torch.as_tensor(np.asarray(c3d, dtype=np.float32) if not torch.is_tensor(c3d) else c3d)
         x = x.to(self.session.device, torch.float32).reshape(self.batch_size, self.n_lstm_steps, 1024, 7, 7).contiguous()
         want_probs = self.config.loss_type in ('xentropy', 'KLD')
@@ -333,8 +344,8 @@ class GazePredictionGRU(ModelBase):
         if not isinstance(old, _engine.FcGruEngine) or getattr(old, 'per_step', False):
             return False
         log.warning('persistent fc-GRU launch timed out (RGP_ETIMEOUT): switching this model to per-timestep launches')
-        new = _engine.FcGruEngine(old.B, old.T, (old.GH, old.GW), dtype=old.dtype, device=old.device,
-                                  save_for_backward=old.save_for_backward, per_step=True)
+        new = self._new_fcgru_engine(old.B, old.T, (old.GH, old.GW), dtype=old.dtype, device=old.device,
+                                     save_for_backward=old.save_for_backward, per_step=True)
         new.set_weights(old.weights)
         for k in _engine.OPT_STATE_KEYS:
             if getattr(old, k, None) is not None:

@@ -1,6 +1,7 @@
-"""Streaming gaze prediction: a conv-recurrent model run on a video longer than its plan as ONE recurrence, the state
-carried from call to call (engine.forward_stream, include/rgp.h rgp_*_forward_stream), instead of the reference's
-T-step chunks that each start from zeros (extract_map.py:65; SURVEY "State is not carried between chunks")."""
+"""Streaming gaze prediction: a recurrent model of the family (the conv-recurrent ones, the cascade and the fc-GRU models
+gaze_rnn / gaze_rnn77) run on a video longer than its plan as ONE recurrence, the state carried from call to call
+(engine.forward_stream, include/rgp.h rgp_*_forward_stream), instead of the reference's T-step chunks that each start from
+zeros (extract_map.py:65; SURVEY "State is not carried between chunks")."""
 import numpy as np
 import torch
 
@@ -8,7 +9,8 @@ import torch
 class GazeStream(object):
     """B lanes, one clip per lane, all at the same stream position.
 
-    model: GazePredictionGRCN / GazePredictionGRCN77 / GazePredictionLSTM / the cascade's GazePredictionGRCN (anything
+    model: GazePredictionGRCN / GazePredictionGRCN77 / GazePredictionLSTM / the cascade's GazePredictionGRCN / the fc-GRU
+    GazePredictionGRU of gaze_rnn and gaze_rnn77, whose state is one [B, 1617] part (anything
     with predict_stream, batch_size, n_lstm_steps; the cascade also takes the steps' frame images).  c3d_engine: a C3DEngine of the model's operand dtype for push_windows.
     `position` is the stream position of the next step; gaze_grcn's per-timestep batch-norm slot is position % T, so the
     maps do not depend on how the stream is cut into calls."""
@@ -70,7 +72,7 @@ class GazeStream(object):
         """video [B*T, 16, 112, 112, 3] fp32 device tensor (window b*T + t = step t of lane b, the full plan size) -> maps
         [B, T, GH, GW].  C3D conv5b rows go straight into the recurrent engine (C3DEngine.forward(want_rows=True), the rows
         variant of forward_stream): frames to maps without leaving the device.  A model whose engine has no rows entry (the
-        cascade) gets the C3D features instead, through predict_stream with frame_images [B, T, hw, hw, 3]."""
+        cascade, the fc-GRU models) gets the C3D features instead, through predict_stream with frame_images [B, T, hw, hw, 3]."""
         assert self.c3d_engine is not None, 'GazeStream(model, c3d_engine=...) for push_windows'
         model, T = self.model, self.T
         n_valid = T if n_valid is None else int(n_valid)

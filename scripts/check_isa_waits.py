@@ -10,7 +10,8 @@ igemm_stagger.hip.h / igemm_wide.hip.h / igemm.hip.h epilogues:   python scripts
 Also checks the wgrad_patch.hip.h kernels (no scratch access between their MFMAs, accumulation in place), and the
 persistent fc-GRU kernel (fcgru_seq.hip.h): in each of its two phases all 13 x NF sixteen-byte exchange loads of a wave
 must stand in front of the phase's first MFMA (the scheduler, left alone, sinks them between the MFMAs and re-uses 2 - 4
-registers: 2 - 3 loads in flight instead of the >= 8 the hand-off needs), and nothing may spill.
+registers: 2 - 3 loads in flight instead of the >= 8 the hand-off needs), and nothing may spill.  Sixteen instantiations
+<NF, SAVE, STREAM>: the eight STREAM = false ones as before, and the eight streaming ones (step 0 of phase A on the seeded rows).
 """
 import os, subprocess, sys, tempfile
 
@@ -129,15 +130,20 @@ def main():
                         '-I' + CSRC, '-S', '--cuda-device-only', '-o', tf.name, os.path.join(CSRC, 'rgp_fcgru.hip')], check=True,
                        stderr=subprocess.DEVNULL)
         asm = open(tf.name).read()
-    n = nbad = 0
+    n = nbad = n_stream = 0
     for name, body in fcgru_kernels(asm):
         n += 1
+        # <NF, SAVE, STREAM>: the streaming instantiations (rgp_fcgru_forward_stream) run phase A of step 0 on the seeded rows
+        # through the same fcs_gemm call, so the same two [loads, MFMAs] runs are expected of them
+        n_stream += name.split('fcgru_seq_kernelILi')[1][1:].startswith('ELb0ELb1E') or \
+            name.split('fcgru_seq_kernelILi')[1][1:].startswith('ELb1ELb1E')
         faults = fcgru_faults(name, body)
         if faults:
             nbad += 1
             print('FCGRU_SEQ', name[:100], faults)
-    print('rgp_fcgru.hip: %d fcgru_seq kernels, %d with exchange loads not in front of their MFMAs, or spills' % (n, nbad))
-    rc |= nbad > 0 or n != 8
+    print('rgp_fcgru.hip: %d fcgru_seq kernels (%d streaming), %d with exchange loads not in front of their MFMAs, or spills' %
+          (n, n_stream, nbad))
+    rc |= nbad > 0 or n != 16 or n_stream != 8
     with tempfile.NamedTemporaryFile(suffix='.s') as tf:
         subprocess.run(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-I' + os.path.join(ROOT, 'include'),
                         '-I' + CSRC, '-S', '--cuda-device-only', '-o', tf.name, os.path.join(CSRC, 'rgp_conv_patch.hip')], check=True,
