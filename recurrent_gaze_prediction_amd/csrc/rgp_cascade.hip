@@ -18,6 +18,7 @@
 #include <string>
 
 #include "rgp_cascade_plan.h"
+#include "gru_steps.h"
 
 using namespace rgp;
 
@@ -98,24 +99,6 @@ __global__ __launch_bounds__(256) void compact_units_kernel(const T* __restrict_
     const int p = (int)((i / 3) % 2401);
     const long long f = i / (3 * 2401);
     rows[f * Kfc + p * 3 + c] = h[(f * 2401 + p) * kSt + c];
-  }
-}
-
-// Streaming: the top cell's h_0 from a caller's state.  src [B][2401][3] fp32 (null: zeros) -> h0 [B][2401][kSt] fp32 (slot 0
-// of the state snapshots) and the interior of the 53x53xkSt operand image of step 0, clip b at pad + b * pad_img_stride,
-// converted as EpiGruC converts hp_out: a cut stream reads the bits an uncut recurrence has.  Channels 3..15 are zeros; the
-// halo is not touched (zero from the bind on).  7203 floats per clip are no multiple of four: scalar reads.
-template <typename T>
-__global__ __launch_bounds__(256) void top_seed_kernel(const float* __restrict__ src, float* __restrict__ h0, T* __restrict__ pad,
-                                                       long long pad_img_stride, int B) {
-  const int total = B * 2401 * kSt;                      // (B <= 2^31 / 38416)
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    const int c = i % kSt, row = i / kSt;                // row = 2401 b + p
-    const int b = row / 2401, p = row - b * 2401;
-    const float v = (src && c < 3) ? src[(long long)row * 3 + c] : 0.f;
-    h0[i] = v;
-    const int y = p / 49, x = p - y * 49;
-    pad[b * pad_img_stride + ((y + 2) * kHp + x + 2) * kSt + c] = Elem<T>::to(v);
   }
 }
 
@@ -206,15 +189,16 @@ int forward_impl(rgp_cascade* g, const float* frames, const float* c3d_input, fl
     RGP_HIP(hipStreamWaitEvent(sc_odd, g->ev_join2, 0));
   }
   g->bottom->step_ev = pipe ? g->ev_b.data() : nullptr;
-  // (a streaming call: the bottom recurrence seeds itself from the first part of the state, batch-norm slot 0 = the identity)
-  g->bottom->st_on = g->st_on; g->bottom->st_in = g->st_in; g->bottom->st_phase = 0;
-  int rc = rgp_proj_fwd(g->bottom, c3d_input, rs);
-  if (rc == RGP_OK) rc = rgp_convgru_xconv_fwd(g->bottom, rs);
-  if (rc == RGP_OK) rc = rgp_convgru_seq_fwd(g->bottom, rs);
-  g->bottom->step_ev = nullptr;
-  g->bottom->st_on = false; g->bottom->st_in = nullptr;
-  RGP_TRY(rc);
-  if (g->st_on) RGP_TRY(grcn_copy_state(g->bottom, g->st_out, g->st_nvalid, s));
+  {  // (a streaming call: the bottom recurrence seeds itself from the first part of the state, batch-norm slot 0 = the identity,
+     // and hands the first part of the new one out)
+    StreamScope sub(g->bottom->stream, g->stream);
+    int rc = rgp_proj_fwd(g->bottom, c3d_input, rs);
+    if (rc == RGP_OK) rc = rgp_convgru_xconv_fwd(g->bottom, rs);
+    if (rc == RGP_OK) rc = rgp_convgru_seq_fwd(g->bottom, rs);
+    g->bottom->step_ev = nullptr;
+    RGP_TRY(rc);
+    RGP_TRY(grcn_state_out(g->bottom, s));
+  }
   const int es_ = (int)sizeof(T);
   const long long up_in_img = 81LL * 256, xtop_img = (long long)kHp * kHp * kCt, xpre_img = 2401LL * 3 * kSt;
   // (3) 7x7x256 -> 49x49x64 into channels 0..63 of the top cell's input; saliency into channel 64
@@ -254,78 +238,40 @@ int forward_impl(rgp_cascade* g, const float* frames, const float* c3d_input, fl
   // inference: two state snapshots and one operand image per role; training: every step's states, gates and
   // operand images are kept (hp_all slot (b, t) = h_{t-1} of step t, slot (b, 0) is written by a streaming seed only = h_0 = 0)
   const bool save = g->save;
-  float* hall = (float*)(ws + (save ? g->hall_t : g->hall));
-  // h_0: zeros, or (a streaming call with a state) its second part, [B][2401][3], in one launch instead of the memsets.  A
-  // training plan's first zero-state call behind such a seed puts the zeros back into slot (b, 0) of hp_all.
-  const bool carry = g->st_on && g->st_in;
-  auto seed = [&](const float* src) -> int {
-    top_seed_kernel<T><<<(B * 2401 * kSt + 255) / 256, 256, 0, st2>>>(src, hall, (T*)(ws + (save ? g->hp_all : g->hp)),
-                                                                     save ? (long long)(T_ + 1) * img16 : img16, B);
-    RGP_HIP(hipGetLastError());
+  GruSteps d;
+  d.zr = &g->zr; d.c = &g->c;
+  d.B = B; d.T = T_; d.S = kSt; d.rows = 2401;
+  d.xpre = (const float*)(ws + g->xpre);
+  d.hall = (float*)(ws + (save ? g->hall_t : g->hall)); d.h_ring = save ? 0 : 2;
+  d.u = (float*)(ws + (save ? g->uall : g->u)); d.gate_step = save ? st : 0;
+  d.r = save ? (float*)(ws + g->rall) : nullptr;
+  d.cand = save ? (float*)(ws + g->call) : nullptr;
+  d.hp = ws + (save ? g->hp_all : g->hp); d.rh = ws + (save ? g->rhp_all : g->rh);
+  d.hp_step = d.rh_step = save ? img16 * sizeof(T) : 0;
+  d.hp_img = save ? (long long)(T_ + 1) * img16 : img16; d.rh_img = save ? (long long)T_ * img16 : img16;
+  d.zr_out_tab = d.c_out_tab = (const int*)(ws + g->o_pad53_t);
+  d.out2 = ws + g->hrows; d.out2_img = 2401LL * kSt;     // dense [2401][kSt] rows: c's own table
+  d.bn_gamma = (const float*)(ws + g->ones); d.bn_beta = (const float*)(ws + g->zeros);
+  // h_0: zeros, or (a streaming call with a state) its second part, [B][2401][3]
+  StreamCall& call = g->stream;
+  const size_t bottom_part = (size_t)B * 49 * 256;
+  RGP_TRY(gru_seed_or_zero<T>(call, call.carry() ? call.in + bottom_part : nullptr, d, 3, d.zr_out_tab, save, st2));
+  auto before = [&](int t) -> int {
+    if (!pipe) return RGP_OK;
+    hipStream_t sf = (t & 1) ? sc_odd : sc;
+    RGP_HIP(hipStreamWaitEvent(sf, g->ev_b[t], 0));           // the bottom state of step t
+    RGP_TRY(feed(t, sf));
+    RGP_HIP(hipEventRecord(g->ev_x[t], sf));
+    RGP_HIP(hipStreamWaitEvent(st2, g->ev_x[t], 0));          // the x-part of step t's gates
     return RGP_OK;
   };
-  if (carry) {
-    RGP_TRY(seed(g->st_in + (size_t)B * 49 * 256));
-  } else {
-    if (!save) RGP_HIP(hipMemsetAsync(ws + g->hp, 0, (size_t)B * img16 * sizeof(T), st2));
-    RGP_HIP(hipMemsetAsync(hall, 0, st * 4, st2));
-    // (only for slot (b, 0) of hp_all, which no memset of the parent's covers; slot 0 of hall_t is zero already by then)
-    if (save && g->top_seeded) RGP_TRY(seed(nullptr));
-  }
-  g->top_seeded = carry;
-  for (int t = 0; t < T_; ++t) {
-    if (pipe) {
-      hipStream_t sf = (t & 1) ? sc_odd : sc;
-      RGP_HIP(hipStreamWaitEvent(sf, g->ev_b[t], 0));           // the bottom state of step t
-      RGP_TRY(feed(t, sf));
-      RGP_HIP(hipEventRecord(g->ev_x[t], sf));
-      RGP_HIP(hipStreamWaitEvent(st2, g->ev_x[t], 0));          // the x-part of step t's gates
-    }
-    hipStream_t s = st2;
-    char* hp_in = save ? ws + g->hp_all + (size_t)t * img16 * sizeof(T) : ws + g->hp;
-    char* hp_out = save ? ws + g->hp_all + (size_t)(t + 1) * img16 * sizeof(T) : ws + g->hp;
-    char* rh_buf = save ? ws + g->rhp_all + (size_t)t * img16 * sizeof(T) : ws + g->rh;
-    const long long hp_stride = save ? (long long)(T_ + 1) * img16 : img16, rh_stride = save ? (long long)T_ * img16 : img16;
-    EpiParams e = make_epi(g->zr, rh_buf, ws);
-    e.out_tab = (const int*)(ws + g->o_pad53_t);
-    e.out_img_stride = rh_stride;
-    e.xpre = (const float*)(ws + g->xpre) + (size_t)t * 2401 * 3 * kSt;
-    e.xpre_img_stride = (long long)T_ * 2401 * 3 * kSt;
-    e.xpre_ld = 3 * kSt;
-    e.xpre_col = 0;
-    e.S = kSt;
-    e.state_rows = 2401;
-    e.h_prev = hall + (size_t)(save ? t : (t & 1)) * st;
-    e.h_next = hall + (size_t)(save ? t + 1 : ((t + 1) & 1)) * st;
-    e.u_gate = save ? (float*)(ws + g->uall) + (size_t)t * st : (float*)(ws + g->u);
-    e.r_save = save ? (float*)(ws + g->rall) + (size_t)t * st : nullptr;
-    e.c_save = save ? (float*)(ws + g->call) + (size_t)t * st : nullptr;
-    IgemmParams p = make_params(g->zr, hp_in, ws, B);
-    p.in_img_stride = hp_stride;
-    RGP_TRY((launch_igemm<T, G16, 1, EpiGruZR<T>>(p, e, s)));
-    e.out = hp_out;
-    e.out_img_stride = hp_stride;
-    e.xpre_col = 2 * kSt;
-    e.out2 = ws + g->hrows;
-    e.out2_tab = (const int*)(ws + g->c.out_tab_off);      // dense [2401][kSt] rows
-    e.out2_img_stride = 2401LL * kSt;
-    e.out2_img_mul = T_;
-    e.out2_img_add = t;
-    e.bn_gamma = (const float*)(ws + g->ones);
-    e.bn_beta = (const float*)(ws + g->zeros);
-    e.bn_inv_std = 1.0f;
-    IgemmParams pc = make_params(g->c, rh_buf, ws, B);
-    pc.in_img_stride = rh_stride;
-    RGP_TRY((launch_igemm<T, G16, 1, EpiGruC<T>>(pc, e, s)));
-    // streaming: the top state behind step n_valid, directly behind the step that wrote it (an inference plan's two snapshots
-    // ping-pong: the next step overwrites it) and, being on the top cell's stream, ahead of the join below
-    if (g->st_on && g->st_out && t + 1 == g->st_nvalid) {
-      const long long tot = (long long)B * 2401 * 3;
-      unpad_kernel<float><<<(int)((tot + 255) / 256), 256, 0, s>>>(e.h_next, g->st_out + (size_t)B * 49 * 256,
-                                                                  (const int*)(ws + g->c.out_tab_off), 2401, 3, 2401LL * kSt, tot);
-      RGP_HIP(hipGetLastError());
-    }
-  }
+  // streaming: the top state behind step n_valid, directly behind the step that wrote it (an inference plan's two snapshots
+  // ping-pong: the next step overwrites it) and, being on the top cell's stream, ahead of the join below
+  auto after = [&](int t, const float* h_next) -> int {
+    if (!call.on || !call.out || t + 1 != call.n_valid) return RGP_OK;
+    return gru_state_out(h_next, call.out + bottom_part, (const int*)(ws + g->c.out_tab_off), d, 3, st2);
+  };
+  RGP_TRY((run_gru_steps<T, G16>(d, ws, st2, before, after)));
   if (pipe) {
     RGP_HIP(hipEventRecord(g->ev_join2, st2));
     RGP_HIP(hipStreamWaitEvent(s, g->ev_join2, 0));
@@ -353,7 +299,7 @@ int forward_impl(rgp_cascade* g, const float* frames, const float* c3d_input, fl
     if (save) e.argmax = (unsigned char*)(ws + g->mask2);
     RGP_TRY((launch_igemm<T, 1, 1, EpiReluMaxout<float>>(p, e, s)));
   }
-  g->streamed = g->st_on;
+  g->stream.streamed = g->stream.on;
   return RGP_OK;
 }
 
@@ -455,7 +401,7 @@ int rgp_cascade_bind_workspace(rgp_cascade_t* g, void* workspace, size_t bytes, 
   hipStream_t s = (hipStream_t)stream;
   g->ws = (char*)workspace;
   g->weights_set = false;
-  g->top_seeded = g->streamed = false;       // the workspace is zeroed below: no seeded slot, no streamed activations
+  g->stream = StreamCall();                  // the workspace is zeroed below: no seeded slot, no streamed activations
   RGP_HIP(hipMemsetAsync(g->ws, 0, g->ws_bytes, s));
   RGP_TRY(rgp_grcn_bind_workspace(g->bottom, g->ws + g->off_bottom, rgp_grcn_workspace_bytes(g->bottom), stream));
   RGP_TRY(rgp_shallownet_bind_workspace(g->shallow, g->ws + g->off_shallow, rgp_shallownet_workspace_bytes(g->shallow), stream));
@@ -521,12 +467,9 @@ int rgp_cascade_forward_stream(rgp_cascade_t* g, const float* frame_images, cons
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   RGP_REQUIRE(hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone,
               "%s: the stream is capturing (streaming inside a stream capture is not supported)", fn);
-  g->st_on = true; g->st_in = state_in; g->st_out = state_out; g->st_nvalid = n_valid;
-  const int rc = g->dtype == RGP_BF16 ? forward_impl<bf16_t>(g, frame_images, c3d_input, gazemaps, s)
-                                      : forward_impl<float>(g, frame_images, c3d_input, gazemaps, s);
-  g->st_on = false; g->st_in = nullptr; g->st_out = nullptr; g->st_nvalid = 0;
-  if (rc != RGP_OK) g->streamed = true;          // (a call that failed half-way: the saved activations are not a plain forward's)
-  return rc;
+  StreamScope call(g->stream, state_in, state_out, n_valid);
+  return g->dtype == RGP_BF16 ? forward_impl<bf16_t>(g, frame_images, c3d_input, gazemaps, s)
+                              : forward_impl<float>(g, frame_images, c3d_input, gazemaps, s);
 }
 
 int rgp_cascade_read_buffer(rgp_cascade_t* g, const char* name, float* dst, rgp_stream_t stream) {

@@ -440,7 +440,7 @@ int rgp_cascade_backward(rgp_cascade_t* g, const float* gazemaps, const float* g
   RGP_REQUIRE(g && gazemaps && gt_gazemap && grads, "rgp_cascade_backward: null argument");
   if (!g->save) return set_err(RGP_ESTATE, "rgp_cascade_backward: plan was created without save_for_backward");
   if (!g->ws || !g->weights_set) return set_err(RGP_ESTATE, "rgp_cascade_backward: workspace/weights not set");
-  if (g->streamed) return set_err(RGP_ESTATE, "rgp_cascade_backward: the last forward was a streaming call (no truncated BPTT)");
+  if (g->stream.streamed) return set_err(RGP_ESTATE, "rgp_cascade_backward: the last forward was a streaming call (no truncated BPTT)");
   const float* const* ptrs = (const float* const*)grads;
   for (size_t i = 0; i < 19; ++i) RGP_REQUIRE(ptrs[i], "rgp_cascade_backward: gradient pointer %zu is null", i);
   hipStream_t s = (hipStream_t)stream;

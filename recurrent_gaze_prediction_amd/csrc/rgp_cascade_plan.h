@@ -31,21 +31,15 @@ struct rgp_cascade {
   // training-time dropout on fc1 (gaze_grcn_cascade.py:401-402): caller-owned keep bytes [F][4802], null = off
   const unsigned char* drop_mask = nullptr;
   float drop_keep = 1.0f;
-  // Streaming (rgp_cascade_forward_stream): set around one call's forward_impl.  The state is [bottom B*49*256 | top B*2401*3]
-  // fp32; st_in null = zeros, st_out null = not wanted.  top_seeded: the last call wrote a state into slot 0 of hall_t and
-  // slot (b, 0) of hp_all, which a zero-state call relies on being zero: the next one writes zeros there again (training plans;
-  // an inference plan clears its one operand image on every zero-state call anyway).
-  bool st_on = false, top_seeded = false;
-  const float* st_in = nullptr;
-  float* st_out = nullptr;
-  int st_nvalid = 0;
-  bool streamed = false;   // the last forward was a streaming call: rgp_cascade_backward -> RGP_ESTATE (no truncated BPTT)
+  // rgp_cascade_forward_stream: the state is [bottom B*49*256 | top B*2401*3] fp32; `seeded` is the top cell's (slot 0 of hall_t
+  // and slot (b, 0) of hp_all on training plans), the bottom level goes through its sub-plan's
+  rgp::StreamCall stream;
 
   // ---- training (save_for_backward) ----
   bool save = false;
   // forward state kept for BPTT of the top cell: fp32 [T(+1)][B][2401][kSt]; operand images of every step
   size_t hall_t = 0, uall = 0, rall = 0, call = 0;
-  size_t hp_all = 0;         // T  [B][T+1][53*53][kSt]   h_{t-1} of step t in slot (b, t); slot (b, 0) is zero (top_seeded)
+  size_t hp_all = 0;         // T  [B][T+1][53*53][kSt]   h_{t-1} of step t in slot (b, t); slot (b, 0) is zero (stream.seeded)
   size_t rhp_all = 0;        // T  [B][T][53*53][kSt]     r (.) h_{t-1}
   size_t mask1 = 0, mask2 = 0;   // bytes [F][2401]: winning half of each maxout unit (0 = ReLU-gated)
   // backward operands

@@ -16,13 +16,14 @@
 // at most 64 clips -- all T steps in one persistent launch with the h-side kernels resident in registers
 // (fcgru_seq.hip.h).  Both write the same buffers in the same layouts, so the backward runs unchanged behind either.
 // Streaming (rgp_fcgru_forward_stream): the same forward started from a caller's h_{-1} [B][1617] instead of zeros, on either
-// path and on inference and training plans.  Way in: fcgru_seed_kernel, one launch in place of the two memsets.  Way out: one
-// strided copy of the fp32 state behind step n_valid.  Nothing else in the per-step loop changes.
+// path and on inference and training plans.  Way in: gru_seed_or_zero (gru_steps.h), one launch in place of the two memsets.
+// Way out: one strided copy of the fp32 state behind step n_valid.  Nothing else in the per-step loop changes.
 #include <algorithm>
 
 #include <string>
 
 #include "wgrad_launch.h"
+#include "gru_steps.h"
 #include "fcgru_seq.hip.h"
 
 using namespace rgp;
@@ -57,14 +58,7 @@ struct rgp_fcgru {
   size_t seq_cnt = 0;                                 // [2 T][FCS_SHARDS][FCS_CNT_STRIDE] phase counters
   PinnedErrWord err;                                  // set by a launch that lost a member (allocated at bind, persistent plans only)
   size_t hsnap = 0;                                   // fp32 [B][np]: h behind step n_valid of a streaming launch (persistent inference plans)
-  // ---- streaming (rgp_fcgru_forward_stream): set around one call's forward_impl
-  bool st_on = false;
-  const float* st_in = nullptr;                       // [B][n] dense, null = zeros
-  float* st_out = nullptr;                            // [B][n] dense, or null
-  int st_nvalid = 0;
-  bool slot0_seeded = false;                          // training plans: slot (b, 0) of hp_all holds a caller's state, not the zeros of the
-                                                      // bind -- the next zero-state forward clears it first
-  bool streamed_last = false;                         // the buffers are a streaming call's: no backward (no truncated BPTT)
+  StreamCall stream;                                  // rgp_fcgru_forward_stream: the state is [B][n] dense; slot 0 = slot (b, 0) of hp_all
 };
 
 namespace rgp {
@@ -135,41 +129,14 @@ __global__ void fill_kernel(float* p, float v, int n) {
   if (i < n) p[i] = v;
 }
 
-// rows of `np` elements, the first n columns of each kept, widened to fp32 and stored dense: rgp_fcgru_read_buffer, and the
-// state a streaming call hands out
+// rows of `np` elements, the first n columns of each kept, widened to fp32 and stored dense: rgp_fcgru_read_buffer
 template <typename T>
 __global__ __launch_bounds__(256) void fc_read_rows_kernel(const T* __restrict__ src, float* __restrict__ dst, int n, int np, long long total) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256)
     dst[i] = Elem<T>::from(src[(i / n) * np + (i % n)]);
 }
 
-// Streaming calls: the state a recurrence starts from, where each path reads its step -1 (as seq_seed_kernel does for the
-// conv-recurrent families).  h_in [B][n] dense fp32, or null = zeros -> fp32 h0 [B][np] (slot 0 of hall / hall_t) and the
-// operand rows, row b at rows + b * row_stride: hp (stride np) on inference plans, slot (b, 0) of hp_all (stride (T + 1) np)
-// on training plans.  Columns >= n are written as zeros.  The conversion is the epilogues' (Elem<T>::to = f2bf: EpiGruC,
-// fcs_pack8), so the operand row of a cut stream is bit for bit the row an uncut recurrence publishes at that step.
-template <typename T>
-__global__ __launch_bounds__(256) void fcgru_seed_kernel(const float* __restrict__ h_in, float* __restrict__ h0, T* __restrict__ rows,
-                                                         long long row_stride, int B, int n, int np) {
-  const int total = B * np;                              // (B * 1664 < 2^31 for every plan that fits a device)
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    const int b = i / np, j = i - b * np;
-    const float v = (h_in && j < n) ? h_in[(long long)b * n + j] : 0.f;
-    h0[i] = v;
-    rows[(long long)b * row_stride + j] = Elem<T>::to(v);
-  }
-}
-
-// the dense [B][n] state behind a step, from its padded fp32 rows: one strided copy
-int state_out_copy(rgp_fcgru* g, const float* src, hipStream_t s) {
-  if (!g->st_out) return RGP_OK;
-  const long long total = (long long)g->B * g->n;
-  fc_read_rows_kernel<float><<<(int)std::min<long long>((total + 255) / 256, 8192), 256, 0, s>>>(src, g->st_out, g->n, g->np, total);
-  RGP_HIP(hipGetLastError());
-  return RGP_OK;
-}
-
-// All T steps in one persistent launch (fcgru_seq.hip.h).  STREAM: from the seeded state (fcgru_seed_kernel has run), and --
+// All T steps in one persistent launch (fcgru_seq.hip.h).  STREAM: from the seeded state (gru_seed_kernel has run), and --
 // inference plans -- with the snapshot behind step n_valid.
 template <bool SAVE, bool STREAM>
 int seq_persistent(rgp_fcgru* g, hipStream_t s) {
@@ -181,7 +148,7 @@ int seq_persistent(rgp_fcgru* g, hipStream_t s) {
     p.seed_stride = (unsigned)((SAVE ? g->T + 1 : 1) * g->np * 2);
     p.seed_bytes = (unsigned)g->B * p.seed_stride;       // (B <= 64, T <= 16384: below 2^32, as hbytes)
     p.hsnap = SAVE ? nullptr : (float*)(ws + g->hsnap);
-    p.n_valid = g->st_nvalid;
+    p.n_valid = g->stream.n_valid;
   }
   p.w_zr = (const bf16_t*)(ws + g->zr.w_off);
   p.w_c = (const bf16_t*)(ws + g->c.w_off);
@@ -234,74 +201,43 @@ int forward_impl(rgp_fcgru* g, const float* c3d_input, float* logits, float* pro
     e.bias = (const float*)(ws + g->xbias);
     RGP_TRY((launch_igemm<T, 1, 1, EpiStore<float, true, false>>(p, e, s)));
   }
+  // training keeps every step's states, gates and operand rows (slot (b, 0) of hp_all is h_{-1}: the zeros of the bind, unless a
+  // streaming call seeded it); inference: the two-slot ring of states and one operand row per role
   const size_t st = (size_t)B * np;
-  float* hall = (float*)(ws + (save ? g->hall_t : g->hall));
-  // h_{-1}: zeros, or a streaming call's state.  The seed launch stands in for the two memsets when there is a state to put
-  // in place, and -- training plans -- once when the call before left one in slot (b, 0) of hp_all.
-  const float* h_in = g->st_on ? g->st_in : nullptr;
-  if (h_in || g->slot0_seeded) {
-    T* rows = (T*)(ws + (save ? g->hp_all : g->hp));
-    fcgru_seed_kernel<T><<<(int)std::min<size_t>((st + 255) / 256, 4096), 256, 0, s>>>(h_in, hall, rows, save ? (long long)(T_ + 1) * np : np, B,
-                                                                                    g->n, np);
-    RGP_HIP(hipGetLastError());
-    g->slot0_seeded = save && h_in != nullptr;
-  } else {
-    if (!save) RGP_HIP(hipMemsetAsync(ws + g->hp, 0, st * sizeof(T), s));
-    RGP_HIP(hipMemsetAsync(hall, 0, st * 4, s));
-  }
-  const int n_valid = g->st_on ? g->st_nvalid : T_;
+  const int* lin = (const int*)(ws + g->c.out_tab_off);        // one row per clip: the identity table
+  GruSteps d;
+  d.zr = &g->zr; d.c = &g->c;
+  d.B = B; d.T = T_; d.S = np; d.rows = 1;
+  d.xpre = (const float*)(ws + g->xpre);
+  d.hall = (float*)(ws + (save ? g->hall_t : g->hall)); d.h_ring = save ? 0 : 2;
+  d.u = (float*)(ws + (save ? g->uall : g->u)); d.gate_step = save ? st : 0;
+  d.r = save ? (float*)(ws + g->rall) : nullptr;
+  d.cand = save ? (float*)(ws + g->call) : nullptr;
+  d.hp = ws + (save ? g->hp_all : g->hp); d.rh = ws + (save ? g->rh_all : g->rh);
+  d.hp_step = d.rh_step = save ? np * sizeof(T) : 0;
+  d.hp_img = save ? (long long)(T_ + 1) * np : np; d.rh_img = save ? (long long)T_ * np : np;
+  d.out2 = ws + g->hrows; d.out2_img = np;
+  d.bn_gamma = (const float*)(ws + g->ones); d.bn_beta = (const float*)(ws + g->zeros);
+  StreamCall& sc = g->stream;
+  RGP_TRY(gru_seed_or_zero<T>(sc, sc.in, d, g->n, nullptr, save, s));
+  const int n_valid = sc.on ? sc.n_valid : T_;
   bool one_launch = false;
   if constexpr (sizeof(T) == 2) {
     if (g->persistent) {
       // STREAM = false: zero state (and, inference plans, every step kept: the ping-pong then ends on h behind step T)
-      const bool stream_kernel = h_in || (!save && n_valid < T_);
+      const bool stream_kernel = sc.carry() || (!save && n_valid < T_);
       if (stream_kernel) RGP_TRY(save ? (seq_persistent<true, true>(g, s)) : (seq_persistent<false, true>(g, s)));
       else RGP_TRY(save ? (seq_persistent<true, false>(g, s)) : (seq_persistent<false, false>(g, s)));
-      if (g->st_on)
-        RGP_TRY(state_out_copy(g, save ? hall + (size_t)n_valid * st : stream_kernel ? (const float*)(ws + g->hsnap) : hall + (size_t)(T_ & 1) * st, s));
+      if (sc.on)
+        RGP_TRY(gru_state_out(save ? d.hall + (size_t)n_valid * st : stream_kernel ? (const float*)(ws + g->hsnap) : d.hall + (size_t)(T_ & 1) * st,
+                              sc.out, lin, d, g->n, s));
       one_launch = true;
     }
   }
-  for (int t = 0; t < T_ && !one_launch; ++t) {
-    // training keeps every step's states, gates and operand rows (slot (b, 0) of hp_all is h_{-1}: the zeros of the bind, unless a
-    // streaming call seeded it -- slot0_seeded above)
-    char* hp_in = save ? ws + g->hp_all + (size_t)t * np * sizeof(T) : ws + g->hp;
-    char* hp_out = save ? ws + g->hp_all + (size_t)(t + 1) * np * sizeof(T) : ws + g->hp;
-    char* rh_buf = save ? ws + g->rh_all + (size_t)t * np * sizeof(T) : ws + g->rh;
-    const long long hp_stride = save ? (long long)(T_ + 1) * np : np, rh_stride = save ? (long long)T_ * np : np;
-    EpiParams e = make_epi(g->zr, rh_buf, ws);
-    e.out_img_stride = rh_stride;
-    e.xpre = (const float*)(ws + g->xpre) + (size_t)t * 3 * np;
-    e.xpre_img_stride = (long long)T_ * 3 * np;
-    e.xpre_ld = 3 * np;
-    e.xpre_col = 0;
-    e.S = np;
-    e.state_rows = 1;
-    e.h_prev = hall + (size_t)(save ? t : (t & 1)) * st;
-    e.h_next = hall + (size_t)(save ? t + 1 : ((t + 1) & 1)) * st;
-    e.u_gate = save ? (float*)(ws + g->uall) + (size_t)t * st : (float*)(ws + g->u);
-    e.r_save = save ? (float*)(ws + g->rall) + (size_t)t * st : nullptr;
-    e.c_save = save ? (float*)(ws + g->call) + (size_t)t * st : nullptr;
-    IgemmParams p = make_params(g->zr, hp_in, ws, B);
-    p.in_img_stride = hp_stride;
-    RGP_TRY((launch_igemm<T, 1, 1, EpiGruZR<T>>(p, e, s)));
-    e.out = hp_out;
-    e.out_tab = (const int*)(ws + g->c.out_tab_off);
-    e.out_img_stride = hp_stride;
-    e.xpre_col = 2 * np;
-    e.out2 = ws + g->hrows;
-    e.out2_tab = (const int*)(ws + g->c.out_tab_off);
-    e.out2_img_stride = np;
-    e.out2_img_mul = T_;
-    e.out2_img_add = t;
-    e.bn_gamma = (const float*)(ws + g->ones);
-    e.bn_beta = (const float*)(ws + g->zeros);
-    e.bn_inv_std = 1.0f;
-    IgemmParams pc = make_params(g->c, rh_buf, ws, B);
-    pc.in_img_stride = rh_stride;
-    RGP_TRY((launch_igemm<T, 1, 1, EpiGruC<T>>(pc, e, s)));
-    if (g->st_on && t + 1 == n_valid) RGP_TRY(state_out_copy(g, e.h_next, s));       // (the ping-pong slot is rewritten two steps on)
-  }
+  if (!one_launch)
+    RGP_TRY((run_gru_steps<T, 1>(d, ws, s, [](int) { return RGP_OK; }, [&](int t, const float* h_next) -> int {
+      return sc.on && t + 1 == n_valid ? gru_state_out(h_next, sc.out, lin, d, g->n, s) : RGP_OK;   // (the ring slot is rewritten two steps on)
+    })));
   {  // output projection (gaze_rnn.py:346-349)
     IgemmParams p = make_params(g->out, ws + g->hrows, ws, F);
     EpiParams e = make_epi(g->out, logits, ws);
@@ -310,7 +246,7 @@ int forward_impl(rgp_fcgru* g, const float* c3d_input, float* logits, float* pro
   }
   if (probs) RGP_TRY(rgp_softmax_xent_fwd(logits, nullptr, probs, nullptr, nullptr, F, g->G, (rgp_stream_t)s));
   g->fwd_done = true;
-  g->streamed_last = g->st_on;
+  g->stream.streamed = g->stream.on;
   return RGP_OK;
 }
 
@@ -673,7 +609,7 @@ int rgp_fcgru_bind_workspace(rgp_fcgru_t* g, void* workspace, size_t bytes, rgp_
   g->ws = (char*)workspace;
   g->weights_set = false;
   g->fwd_done = false;
-  g->slot0_seeded = g->streamed_last = false;
+  g->stream = StreamCall();
   RGP_HIP(hipMemsetAsync(g->ws, 0, g->ws_bytes, s));
   for (ConvDesc* d : {&g->proj, &g->xg, &g->zr, &g->c, &g->out}) RGP_TRY(upload_desc(*d, g->ws, s));
   if (g->save) for (ConvDesc* d : {&g->b_out, &g->b_c, &g->b_zr, &g->b_x}) RGP_TRY(upload_desc(*d, g->ws, s));
@@ -708,18 +644,14 @@ int rgp_fcgru_forward_stream(rgp_fcgru_t* g, const float* c3d_input, const float
                              float* logits, float* probs, rgp_stream_t stream) {
   RGP_REQUIRE(g, "rgp_fcgru_forward_stream: null plan");
   RGP_REQUIRE(c3d_input, "rgp_fcgru_forward_stream: null c3d_input");
-  RGP_REQUIRE(n_valid >= 1 && n_valid <= g->T, "rgp_fcgru_forward_stream: n_valid=%d must be in 1..%d", n_valid, g->T);
-  RGP_REQUIRE(!state_out || state_out != state_in, "rgp_fcgru_forward_stream: state_out must not alias state_in");
-  RGP_REQUIRE(logits, "rgp_fcgru_forward_stream: null logits");
+  RGP_TRY(check_stream_args("rgp_fcgru_forward_stream", g->T, c3d_input, nullptr, state_in, state_out, n_valid, 0, logits, false));
   if (!g->ws) return set_err(RGP_EWORKSPACE, "rgp_fcgru: workspace not bound");
   if (!g->weights_set) return set_err(RGP_ESTATE, "rgp_fcgru: weights not set");
   RGP_TRY(fcgru_check_error(g));
   hipStream_t s = (hipStream_t)stream;
-  g->st_on = true; g->st_in = state_in; g->st_out = state_out; g->st_nvalid = n_valid;
-  const int rc = g->dtype == RGP_BF16 ? forward_impl<bf16_t>(g, c3d_input, logits, probs, s)
-                                      : forward_impl<float>(g, c3d_input, logits, probs, s);
-  g->st_on = false; g->st_in = nullptr; g->st_out = nullptr; g->st_nvalid = 0;
-  return rc;
+  StreamScope call(g->stream, state_in, state_out, n_valid);
+  return g->dtype == RGP_BF16 ? forward_impl<bf16_t>(g, c3d_input, logits, probs, s)
+                              : forward_impl<float>(g, c3d_input, logits, probs, s);
 }
 
 int rgp_fcgru_backward(rgp_fcgru_t* g, const float* logits, const float* probs, const float* labels,
@@ -732,7 +664,7 @@ int rgp_fcgru_backward(rgp_fcgru_t* g, const float* logits, const float* probs, 
   const float* const* ptrs = (const float* const*)grads;
   for (size_t i = 0; i < sizeof(rgp_fcgru_weights) / sizeof(float*); ++i)
     RGP_REQUIRE(ptrs[i], "rgp_fcgru_backward: gradient pointer %zu is null", i);
-  if (g->streamed_last)
+  if (g->stream.streamed)
     return set_err(RGP_ESTATE, "rgp_fcgru_backward: the last forward was a streaming call (no truncated BPTT): run rgp_fcgru_forward first");
   hipStream_t s = (hipStream_t)stream;
   RGP_TRY(g->dtype == RGP_BF16 ? backward_impl<bf16_t>(g, logits, probs, labels, grads, loss_type, s)

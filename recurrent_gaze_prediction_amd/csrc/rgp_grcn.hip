@@ -5,6 +5,7 @@
 #include <map>
 
 #include "rgp_grcn_plan.h"
+#include "gru_steps.h"
 #include "convgru_seq.hip.h"
 #include "head_logits.hip.h"
 
@@ -124,7 +125,7 @@ namespace {
 int seq_persistent(rgp_grcn* g, hipStream_t s) {
   const int B = g->B, T_ = g->T, S = g->S;
   const size_t st = (size_t)B * 49 * S;
-  const bool carry = g->st_on && g->st_in;                                   // a streaming call with a state
+  const bool carry = g->stream.carry();                                      // a streaming call with a state
   {
     ZeroBatch z(s);
     if (!carry) RGP_TRY(z.add(g->ws + g->hall.off, st * 4));                 // h_0 = 0 (gaze_grcn.py:262)
@@ -132,7 +133,7 @@ int seq_persistent(rgp_grcn* g, hipStream_t s) {
     RGP_TRY(z.flush());
   }
   if (carry) {                                                               // h_0 = the state: slot 0 + the groups' exchange image
-    SeqSeedArgs a{g->st_in, nullptr, (float*)(g->ws + g->hall.off), nullptr, nullptr, 0, (bf16_t*)(g->ws + g->xch_h.off), 0, g->sg.nc, B, S};
+    SeqSeedArgs a{g->stream.in, nullptr, (float*)(g->ws + g->hall.off), nullptr, nullptr, 0, (bf16_t*)(g->ws + g->xch_h.off), 0, g->sg.nc, B, S};
     RGP_TRY(launch_seq_seed<bf16_t>(a, s));
   }
   SeqParams p;
@@ -152,7 +153,7 @@ int seq_persistent(rgp_grcn* g, hipStream_t s) {
   p.g = g->sg.args(B, (unsigned*)(g->ws + g->seq_cnt.off), RGP_FAULT_SEQ_LOST_MEMBER);
   p.T = T_; p.K = g->gzr.K;
   p.carry = carry ? 1 : 0;
-  p.bn_phase = g->st_on ? g->st_phase : 0;
+  p.bn_phase = g->stream.bn_phase;
   RGP_REQUIRE(g->gzr.K == 9 * S && g->gc.K == 9 * S && g->gzr.chunk_major == 0, "convgru_seq: unexpected filter packing");
   if (p.carry || p.bn_phase) return launch_seq_group(g->sg, convgru_seq_kernel<4, true>, convgru_seq_kernel<7, true>, p, SEQ_SMEM, s);
   return launch_seq_group(g->sg, convgru_seq_kernel<4, false>, convgru_seq_kernel<7, false>, p, SEQ_SMEM, s);
@@ -163,51 +164,29 @@ int seq_impl(rgp_grcn* g, hipStream_t s) {
   const int B = g->B, T_ = g->T, S = g->S;
   if (sizeof(T) == 2 && g->sg.resident() && dev_knob("RGP_SEQ", 1)) return seq_persistent(g, s);
   const size_t st = (size_t)B * 49 * S;  // fp32 elements per state snapshot
-  const int phase = g->st_on ? g->st_phase : 0;
-  if (g->st_on && g->st_in) {                                         // streaming call: h_0 = the state, copied and padded
-    SeqSeedArgs a{g->st_in, nullptr, (float*)(g->ws + g->hall.off), nullptr, g->ws + g->hp.off, 81LL * S, nullptr, 0, 1, B, S};
+  if (g->stream.carry()) {                                            // streaming call: h_0 = the state, copied and padded
+    SeqSeedArgs a{g->stream.in, nullptr, (float*)(g->ws + g->hall.off), nullptr, g->ws + g->hp.off, 81LL * S, nullptr, 0, 1, B, S};
     RGP_TRY(launch_seq_seed<T>(a, s));
   } else {
     RGP_HIP(hipMemsetAsync(g->ws + g->hp.off, 0, g->hp.bytes, s));    // h_0 = 0 (gaze_grcn.py:262)
     RGP_HIP(hipMemsetAsync(g->ws + g->hall.off, 0, st * 4, s));
   }
-  float* hall = (float*)(g->ws + g->hall.off);
-  float* uall = (float*)(g->ws + g->uall.off);
-  float* rall = g->save ? (float*)(g->ws + g->rall.off) : nullptr;
-  float* call = g->save ? (float*)(g->ws + g->call.off) : nullptr;
-  for (int t = 0; t < T_; ++t) {
-    EpiParams e = make_epi(g->gzr, g->ws + g->rhp.off, g->ws);
-    e.xpre = (const float*)(g->ws + g->xpre.off) + (size_t)t * 49 * 3 * S;
-    e.xpre_img_stride = (long long)T_ * 49 * 3 * S;
-    e.xpre_ld = 3 * S;
-    e.xpre_col = 0;
-    e.S = S;
-    e.state_rows = 49;
-    e.h_prev = hall + (size_t)t * st;
-    e.h_next = hall + (size_t)(t + 1) * st;
-    e.u_gate = uall + (size_t)t * st;
-    e.r_save = rall ? rall + (size_t)t * st : nullptr;
-    e.c_save = call ? call + (size_t)t * st : nullptr;
-    IgemmParams p = make_params(g->gzr, g->ws + g->hp.off, g->ws, B);
-    RGP_TRY((launch_igemm<T, 1, 1, EpiGruZR<T>>(p, e, s)));
-    // candidate conv on r*h, blend, BN -> next operand + head image b*T+t
-    e.out = g->ws + g->hp.off;
-    e.out_tab = (const int*)(g->ws + g->gc.out_tab_off);
-    e.out_img_stride = g->gc.out_img_stride;
-    e.xpre_col = 2 * S;
-    e.out2 = g->ws + g->hbn.off;
-    e.out2_tab = (const int*)(g->ws + g->gc.out_tab_off);
-    e.out2_img_stride = 81LL * S;
-    e.out2_img_mul = T_;
-    e.out2_img_add = t;
-    e.bn_gamma = g->bn_gamma + (size_t)((t + phase) % T_) * S;
-    e.bn_beta = g->bn_beta + (size_t)((t + phase) % T_) * S;
-    e.bn_inv_std = 1.0f / sqrtf(1.0f + 1e-3f);  // moving mean 0 / var 1, eps 1e-3
-    IgemmParams pc = make_params(g->gc, g->ws + g->rhp.off, g->ws, B);
-    RGP_TRY((launch_igemm<T, 1, 1, EpiGruC<T>>(pc, e, s)));
+  GruSteps d;                                   // every state and gate kept (T + 1 / T slots), one operand image per role
+  d.zr = &g->gzr; d.c = &g->gc;
+  d.B = B; d.T = T_; d.S = S; d.rows = 49;
+  d.xpre = (const float*)(g->ws + g->xpre.off);
+  d.hall = (float*)(g->ws + g->hall.off);
+  d.u = (float*)(g->ws + g->uall.off); d.gate_step = st;
+  d.r = g->save ? (float*)(g->ws + g->rall.off) : nullptr;
+  d.cand = g->save ? (float*)(g->ws + g->call.off) : nullptr;
+  d.hp = g->ws + g->hp.off; d.rh = g->ws + g->rhp.off; d.hp_img = d.rh_img = 81LL * S;
+  d.out2 = g->ws + g->hbn.off; d.out2_img = 81LL * S;             // the head's image b*T+t
+  d.bn_gamma = g->bn_gamma; d.bn_beta = g->bn_beta; d.bn_step = S; d.bn_phase = g->stream.bn_phase;
+  d.bn_inv_std = 1.0f / sqrtf(1.0f + 1e-3f);    // moving mean 0 / var 1, eps 1e-3
+  return run_gru_steps<T, 1>(d, g->ws, s, [](int) { return RGP_OK; }, [&](int t, const float*) -> int {
     if (g->step_ev) RGP_HIP(hipEventRecord(g->step_ev[t], s));
-  }
-  return RGP_OK;
+    return RGP_OK;
+  });
 }
 
 template <typename T>
@@ -510,7 +489,7 @@ int rgp_convgru_seq_fwd(rgp_grcn_t* g, rgp_stream_t stream) {
   const int pid = g->prof.begin(2, s);
   const int rc = RGP_BY_DTYPE(g->dtype, seq_impl, g, s);
   g->prof.end(pid, s);
-  g->streamed = g->st_on;
+  g->stream.streamed = g->stream.on;
   return rc;
 }
 
@@ -559,22 +538,13 @@ int rgp_grcn_forward_stream(rgp_grcn_t* g, const float* c3d_input, const void* c
   RGP_TRY(check_stream_args("rgp_grcn_forward_stream", g->T, c3d_input, c3d_rows, state_in, state_out, n_valid, bn_phase, logits));
   RGP_TRY(check_ready(g));
   hipStream_t s = (hipStream_t)stream;
-  g->st_on = true; g->st_in = state_in; g->st_phase = bn_phase;
-  int rc = c3d_input ? rgp_proj_fwd(g, c3d_input, stream) : grcn_proj_rows_fwd(g, c3d_rows, s);
-  if (rc == RGP_OK) rc = grcn_tail(g, logits, probs, stream);
-  g->st_on = false; g->st_in = nullptr; g->st_phase = 0;
-  RGP_TRY(rc);
-  return grcn_copy_state(g, state_out, n_valid, s);
+  StreamScope call(g->stream, state_in, state_out, n_valid, bn_phase);
+  RGP_TRY(c3d_input ? rgp_proj_fwd(g, c3d_input, stream) : grcn_proj_rows_fwd(g, c3d_rows, s));
+  RGP_TRY(grcn_tail(g, logits, probs, stream));
+  return grcn_state_out(g, s);
 }
 
 }  // extern "C"
-
-int grcn_copy_state(rgp_grcn* g, float* state_out, int n_valid, hipStream_t s) {
-  if (!state_out) return RGP_OK;
-  const size_t st = (size_t)g->B * 49 * g->S * 4;
-  RGP_HIP(hipMemcpyAsync(state_out, g->ws + g->hall.off + (size_t)n_valid * st, st, hipMemcpyDeviceToDevice, s));
-  return RGP_OK;
-}
 
 // rgp_grcn_forward_rows' projection alone (no ABI symbol: for plans that own a sub-plan and run its stages, rgp_grcn77.hip)
 int grcn_proj_rows_fwd(rgp_grcn* g, const void* c3d_rows, hipStream_t s) {

@@ -58,7 +58,7 @@ const float* plan_states(const rgp_grcn77* g) {
 int tail(rgp_grcn77* g, float* logits, float* probs, rgp_stream_t stream) {
   RGP_TRY(rgp_convgru_xconv_fwd(g->inner, stream));
   RGP_TRY(rgp_convgru_seq_fwd(g->inner, stream));
-  g->fwd_done = true;
+  g->fwd_done = !g->inner->stream.on;
   g->bwd_done = false;
   return launch_head_fwd(plan_states(g), 49LL * rgp_grcn77::S, (long long)g->B * 49 * rgp_grcn77::S, g, logits, probs,
                          (hipStream_t)stream);
@@ -166,13 +166,11 @@ int rgp_grcn77_forward_stream(rgp_grcn77_t* g, const float* c3d_input, const voi
   RGP_TRY(check_stream_args("rgp_grcn77_forward_stream", g->T, c3d_input, c3d_rows, state_in, state_out, n_valid, 0, logits));
   RGP_TRY(check_ready(g));
   rgp_grcn* in = g->inner;
-  in->st_on = true; in->st_in = state_in; in->st_phase = 0;
-  int rc = c3d_input ? rgp_proj_fwd(in, c3d_input, stream) : grcn_proj_rows_fwd(in, c3d_rows, (hipStream_t)stream);
-  if (rc == RGP_OK) rc = tail(g, logits, probs, stream);
-  in->st_on = false; in->st_in = nullptr;
-  g->fwd_done = false;                                     // no backward behind a streaming call (RGP_ESTATE)
-  RGP_TRY(rc);
-  return grcn_copy_state(in, state_out, n_valid, (hipStream_t)stream);
+  StreamScope call(in->stream, state_in, state_out, n_valid);
+  g->fwd_done = false;                                     // no backward behind a started streaming call (RGP_ESTATE)
+  RGP_TRY(c3d_input ? rgp_proj_fwd(in, c3d_input, stream) : grcn_proj_rows_fwd(in, c3d_rows, (hipStream_t)stream));
+  RGP_TRY(tail(g, logits, probs, stream));
+  return grcn_state_out(in, (hipStream_t)stream);
 }
 
 int rgp_grcn77_head_fwd(rgp_grcn77_t* g, const float* states, float* logits, float* probs, rgp_stream_t stream) {

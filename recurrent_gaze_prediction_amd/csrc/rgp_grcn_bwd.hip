@@ -622,7 +622,7 @@ int rgp_grcn_backward(rgp_grcn_t* g, const float* logits, const float* probs, co
   if (!g->ws) return set_err(RGP_EWORKSPACE, "rgp_grcn: workspace not bound");
   if (!g->save || !g->bwd) return set_err(RGP_ESTATE, "rgp_grcn_backward: plan was created without save_for_backward");
   if (!g->weights_set) return set_err(RGP_ESTATE, "rgp_grcn: weights not set");
-  if (g->streamed) return set_err(RGP_ESTATE, "rgp_grcn_backward: the last forward was a streaming call (no truncated BPTT)");
+  if (g->stream.streamed) return set_err(RGP_ESTATE, "rgp_grcn_backward: the last forward was a streaming call (no truncated BPTT)");
   RGP_TRY(grcn_check_error(g));
   RGP_REQUIRE(loss_type == 0 || loss_type == 1, "rgp_grcn_backward: loss_type %d (0 xentropy, 1 l2)", loss_type);
   RGP_REQUIRE(loss_type == 1 || probs, "rgp_grcn_backward: xentropy needs the softmax maps");
@@ -634,7 +634,7 @@ int rgp_grcn_backward_from_states(rgp_grcn_t* g, const float* d_states, const rg
   RGP_REQUIRE(g && d_states && grads, "rgp_grcn_backward_from_states: null argument");
   if (!g->ws || !g->save || !g->bwd || !g->weights_set)
     return set_err(RGP_ESTATE, "rgp_grcn_backward_from_states: needs a save_for_backward plan with weights and a forward");
-  if (g->streamed) return set_err(RGP_ESTATE, "rgp_grcn_backward_from_states: the last forward was a streaming call (no truncated BPTT)");
+  if (g->stream.streamed) return set_err(RGP_ESTATE, "rgp_grcn_backward_from_states: the last forward was a streaming call (no truncated BPTT)");
   RGP_TRY(require_pointers(grads, "rgp_grcn_backward_from_states", "gradient"));
   return RGP_BY_DTYPE(g->dtype, backward_impl, g, nullptr, nullptr, nullptr, grads, 0, (hipStream_t)stream, d_states);
 }

@@ -32,13 +32,7 @@ struct rgp_grcn {
   bool weights_set = false;
   const float *bn_gamma = nullptr, *bn_beta = nullptr, *proj_b = nullptr, *out_b = nullptr;
   rgp::StageProfiler prof;
-  // Streaming (rgp_grcn_forward_stream; rgp_grcn77.hip drives the same fields on its sub-plan): set around the stage calls
-  // of one call.  st_in = the caller's state (null: zeros), st_phase = batch-norm slot of step 0.
-  bool st_on = false;
-  const float* st_in = nullptr;
-  int st_phase = 0;
-  bool streamed = false;   // the last recurrence ran inside a streaming call: its saved activations do not start at h_0 = 0 with
-                           // batch-norm slot 0, which is what the backward differentiates -> RGP_ESTATE (no truncated BPTT)
+  rgp::StreamCall stream;   // rgp_grcn_forward_stream, or the call of the plan that owns this one (rgp_grcn77, rgp_cascade)
   struct GrcnBwd* bwd = nullptr;   // backward plan (save_for_backward only), rgp_grcn_bwd.hip
 };
 
@@ -46,8 +40,10 @@ struct rgp_grcn {
 bool grads_top_early(const rgp_grcn* g);
 // rgp_grcn.hip: the projection from conv5b rows as a stage of its own (what rgp_grcn_forward_rows runs first)
 int grcn_proj_rows_fwd(rgp_grcn* g, const void* c3d_rows, hipStream_t s);
-// rgp_grcn.hip: state_out (may be null) = the state behind step n_valid of the last recurrence, i.e. slot n_valid of hall
-int grcn_copy_state(rgp_grcn* g, float* state_out, int n_valid, hipStream_t s);
+// the state behind step n_valid of the plan's streaming call = slot n_valid of hall
+inline int grcn_state_out(rgp_grcn* g, hipStream_t s) {
+  return rgp::stream_state_out(g->stream, {g->ws + g->hall.off}, (size_t)g->B * 49 * g->S * 4, s);
+}
 // rgp_grcn_bwd.hip
 // returns RGP_ETIMEOUT (and clears the word) if a persistent launch of this plan reported a lost group member
 int grcn_check_error(rgp_grcn* g);

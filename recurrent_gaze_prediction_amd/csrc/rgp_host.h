@@ -145,15 +145,64 @@ int launch_seq_seed(const SeqSeedArgs& a, hipStream_t s) {
 
 // Argument rules common to the rgp_*_forward_stream calls (include/rgp.h), checked AHEAD of the plan's bound / ready
 // state.  T = the plan's steps; the families without a per-timestep batch-norm pass bn_phase = 0.
+// align16 = false: a family whose seed and hand-out read scalars (the fc-GRU) has no alignment rule.
 inline int check_stream_args(const char* fn, int T, const void* c3d_input, const void* c3d_rows, const float* state_in,
-                             const float* state_out, int n_valid, int bn_phase, const void* logits) {
+                             const float* state_out, int n_valid, int bn_phase, const void* logits, bool align16 = true) {
   RGP_REQUIRE((c3d_input != nullptr) != (c3d_rows != nullptr), "%s: exactly one of c3d_input and c3d_rows must be set", fn);
   RGP_REQUIRE(n_valid >= 1 && n_valid <= T, "%s: n_valid=%d must be in 1..%d", fn, n_valid, T);
   RGP_REQUIRE(bn_phase >= 0 && bn_phase < T, "%s: bn_phase=%d must be in 0..%d", fn, bn_phase, T - 1);
   RGP_REQUIRE(!state_out || state_out != state_in, "%s: state_out must not alias state_in", fn);
-  RGP_REQUIRE((((size_t)state_in | (size_t)state_out | (size_t)c3d_rows) & 15) == 0,
+  RGP_REQUIRE(!align16 || (((size_t)state_in | (size_t)state_out | (size_t)c3d_rows) & 15) == 0,
               "%s: state_in, state_out and c3d_rows must be 16-byte aligned", fn);
   RGP_REQUIRE(logits, "%s: null logits", fn);
+  return RGP_OK;
+}
+
+// The streaming state of a recurrent plan (rgp_grcn, rgp_lstm, rgp_fcgru, rgp_cascade hold one; rgp_grcn77 and the cascade's
+// bottom level use their rgp_grcn sub-plan's).  The fields of one call are set by a StreamScope and are defaults outside one, so
+// a plain forward reads them as "no call": no state, every step valid, batch-norm slot 0.
+struct StreamCall {
+  bool on = false;
+  const float* in = nullptr;       // the caller's state, null = zeros
+  float* out = nullptr;            // where the state behind step n_valid goes, null = not wanted
+  int n_valid = 0, bn_phase = 0;   // bn_phase: batch-norm slot of step 0 (gaze_grcn; the others have no per-timestep batch-norm)
+  // ... and two flags that outlive the call
+  bool seeded = false;             // slot 0 of the plan's state buffers holds a caller's state, not the zeros of the bind
+  bool streamed = false;           // the saved activations are a streaming call's: they do not start at h_0 = 0 with batch-norm
+                                   // slot 0, which is what the backward differentiates -> RGP_ESTATE (no truncated BPTT)
+  bool carry() const { return on && in; }
+  // The re-zero rule.  Slot 0 is zero from the bind on and no plain forward writes it, so only two kinds of call run a seed
+  // launch: one with a state to put there, and the first zero-state call behind one, which puts the zeros back (a null source).
+  // kept = false: this plan clears slot 0 with its memsets on every zero-state call anyway.
+  bool needs_seed() const { return carry() || seeded; }
+  const float* seed_src() const { return carry() ? in : nullptr; }
+  void seed_done(bool kept = true) { seeded = kept && carry(); }
+};
+
+// One streaming call, from the first launch to the return: arms `c` and marks the plan streamed at once, so a call that fails
+// half-way leaves the backward refused; clears the per-call fields on every return path.  A plain forward clears `streamed`
+// behind its recurrence (c.streamed = c.on).  Second form: a plan that runs a sub-plan's stages hands its own call on, the
+// sub-plan's part of the state first in both buffers (no call: nothing armed).
+struct StreamScope {
+  StreamCall& c;
+  StreamScope(StreamCall& c_, const float* in, float* out, int n_valid, int bn_phase = 0) : c(c_) {
+    c.on = c.streamed = true; c.in = in; c.out = out; c.n_valid = n_valid; c.bn_phase = bn_phase;
+  }
+  StreamScope(StreamCall& sub, const StreamCall& outer) : c(sub) {
+    if (outer.on) { c.on = c.streamed = true; c.in = outer.in; c.out = outer.out; c.n_valid = outer.n_valid; }
+  }
+  ~StreamScope() { c.on = false; c.in = nullptr; c.out = nullptr; c.n_valid = c.bn_phase = 0; }
+};
+
+// The state behind step n_valid of the call: slot n_valid of each of `bufs` (fp32 snapshots of `bytes` each), one behind the
+// other in c.out.  Nothing to do without a call or without a destination.
+inline int stream_state_out(const StreamCall& c, std::initializer_list<const char*> bufs, size_t bytes, hipStream_t s) {
+  if (!c.on || !c.out) return RGP_OK;
+  char* dst = (char*)c.out;
+  for (const char* b : bufs) {
+    RGP_HIP(hipMemcpyAsync(dst, b + (size_t)c.n_valid * bytes, bytes, hipMemcpyDeviceToDevice, s));
+    dst += bytes;
+  }
   return RGP_OK;
 }
 

@@ -28,10 +28,7 @@ using namespace rgp;
 struct rgp_lstm {
   int B = 0, T = 0, P = 512, S = 128, dtype = RGP_BF16, F = 0;
   bool save = false, fwd_done = false, bwd_done = false, weights_set = false;
-  // Streaming (rgp_lstm_forward_stream): set around one call's forward_impl.  slot0_seeded: slot 0 of hall / call / the h
-  // images holds a caller's state, not the zeros the bind left there -- the next zero-state forward clears it first.
-  bool st_on = false, slot0_seeded = false;
-  const float* st_in = nullptr;
+  StreamCall stream;                       // rgp_lstm_forward_stream; slot 0 = that of hall / call / the h images
   Projection pj;                           // gaze_stages.h
   FoldedHead head;                         // on h_t: a GEMM "image" is a clip
   ConvDesc xconv, grec;
@@ -151,16 +148,15 @@ int seq_impl(rgp_lstm* g, hipStream_t s) {
   char* ws = g->ws;
   const int B = g->B, T_ = g->T, S = g->S;
   const bool persistent = sizeof(T) == 2 && g->fwd_persistent && g->sg.resident();
-  const bool carry = g->st_on && g->st_in;
-  // Slot 0 of the states and of the h images is zero from the bind on; a streaming call seeds it with its state (both
-  // paths: [h | c] -> hall, call, the padded h image; the persistent kernel's exchange image of parity 1), and the first
-  // zero-state call behind one seeds zeros again.
-  if (carry || g->slot0_seeded) {
-    const float* si = carry ? g->st_in : nullptr;
+  const bool carry = g->stream.carry();
+  // A streaming call seeds slot 0 with its state (both paths: [h | c] -> hall, call, the padded h image; the persistent
+  // kernel's exchange image of parity 1), by StreamCall's rule
+  if (g->stream.needs_seed()) {
+    const float* si = g->stream.seed_src();
     SeqSeedArgs a{si, si ? si + (size_t)B * 49 * S : nullptr, (float*)(ws + g->hall.off), (float*)(ws + g->call.off), ws + g->hseq.off,
                   (long long)(T_ + 1) * 81 * S, persistent ? (bf16_t*)(ws + g->xch.off) : nullptr, g->sg.groups, std::max(g->sg.nc, 1), B, S};
     RGP_TRY(launch_seq_seed<T>(a, s));
-    g->slot0_seeded = carry;
+    g->stream.seed_done();
   }
   if constexpr (sizeof(T) == 2) {
     if (persistent) return seq_persistent(g, carry, s);
@@ -218,7 +214,7 @@ int forward_impl(rgp_lstm* g, const float* c3d_input, const void* rows, float* l
   RGP_TRY(seq_impl<T>(g, s));
   RGP_TRY(g->head.forward<T>(ws, ws + g->hseq.off, g->B, g->out_b, logits, g->F, s));
   if (probs) RGP_TRY(rgp_softmax_xent_fwd(logits, nullptr, probs, nullptr, nullptr, g->F, 2401, (rgp_stream_t)s));
-  g->fwd_done = !g->st_on;                                    // no backward behind a streaming call (no truncated BPTT)
+  g->fwd_done = !g->stream.on;                                // no backward behind a streaming call (no truncated BPTT)
   g->bwd_done = false;
   return RGP_OK;
 }
@@ -476,7 +472,7 @@ int rgp_lstm_bind_workspace(rgp_lstm_t* g, void* workspace, size_t bytes, rgp_st
   RGP_TRY(g->sg.alloc_err());
   g->ws = (char*)workspace;
   g->weights_set = false;
-  g->slot0_seeded = false;
+  g->stream = StreamCall();
   // zero everything once: the halos of E / h images / dpre, slot 0 of the states and the unused filter rows stay zero,
   // because kernels only ever write interiors and a pack writes the same positions every time
   RGP_HIP(hipMemsetAsync(g->ws, 0, g->ws_bytes, s));
@@ -516,16 +512,10 @@ int rgp_lstm_forward_stream(rgp_lstm_t* g, const float* c3d_input, const void* c
   RGP_TRY(check_stream_args("rgp_lstm_forward_stream", g->T, c3d_input, c3d_rows, state_in, state_out, n_valid, 0, logits));
   RGP_TRY(check_ready(g));
   hipStream_t s = (hipStream_t)stream;
-  g->st_on = true; g->st_in = state_in;
-  const int rc = RGP_BY_DTYPE(g->dtype, forward_impl, g, c3d_input, c3d_rows, logits, probs, s);
-  g->st_on = false; g->st_in = nullptr;
-  RGP_TRY(rc);
-  if (state_out) {                                           // [h | c] behind step n_valid
-    const size_t st = (size_t)g->B * 49 * g->S * 4;
-    RGP_HIP(hipMemcpyAsync(state_out, g->ws + g->hall.off + (size_t)n_valid * st, st, hipMemcpyDeviceToDevice, s));
-    RGP_HIP(hipMemcpyAsync((char*)state_out + st, g->ws + g->call.off + (size_t)n_valid * st, st, hipMemcpyDeviceToDevice, s));
-  }
-  return RGP_OK;
+  StreamScope call(g->stream, state_in, state_out, n_valid);
+  g->fwd_done = false;                                       // ... nor behind one that fails half-way
+  RGP_TRY(RGP_BY_DTYPE(g->dtype, forward_impl, g, c3d_input, c3d_rows, logits, probs, s));
+  return stream_state_out(g->stream, {g->ws + g->hall.off, g->ws + g->call.off}, (size_t)g->B * 49 * g->S * 4, s);   // [h | c]
 }
 
 int rgp_lstm_backward(rgp_lstm_t* g, const float* logits, const float* probs, const float* labels, const rgp_lstm_weights* grads,

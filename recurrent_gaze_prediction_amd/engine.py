@@ -219,6 +219,13 @@ class DropoutSite(object):
     def off(self):
         _lib.check(self._set(ctypes.c_float(1.0), None))
 
+    def arm(self, train):
+        """The site for one forward: True = draw a fresh mask (if configured), 'keep' = leave the mask use() installed as it
+        is, False = site off."""
+        if train == 'keep':
+            return
+        self.draw() if train else self.off()
+
     def draw(self):
         """New mask for this step (counter offset advances by ceil(n/4) blocks per draw)."""
         if self.keep_prob >= 1.0:
@@ -236,6 +243,27 @@ class DropoutSite(object):
         self.mask.copy_(m.reshape(-1).to(self.device, torch.uint8))
         self.keep_prob = float(keep_prob)
         _lib.check(self._set(ctypes.c_float(self.keep_prob), _ptr(self.mask)))
+
+
+def _stream_call(eng, fn, B, T, c3d_input, state, n_valid, args, rows=None):
+    """What the forward_stream methods share: c3d_input (or rows, as forward_rows takes them) and state are checked, n_valid
+    defaults to T, new_state is allocated and fn(plan, *args(state, new_state, n_valid), stream) is called and checked.
+    Returns new_state."""
+    x = c3d_input
+    if x is not None:
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        assert tuple(x.shape) == (B, T, 1024, 7, 7), tuple(x.shape)
+    if rows is not None:
+        assert rows.is_cuda and rows.dtype == eng.torch_dtype and rows.is_contiguous()
+        assert rows.numel() == B * T * 49 * 1024
+    n_valid = T if n_valid is None else int(n_valid)
+    if state is not None:
+        assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous()
+        assert state.numel() == eng.state_elems, (state.numel(), eng.state_elems)
+    new_state = torch.empty(eng.state_elems, dtype=torch.float32, device=eng.device)
+    with torch.cuda.device(eng.device):
+        _lib.check(fn(eng._h, *(args(_ptr(state), _ptr(new_state), n_valid) + (_stream_ptr(eng.device),))))
+    return new_state
 
 
 def _flat_layout(names, shapes, untrained=()):
@@ -428,24 +456,11 @@ class _PersistentEngine(_GazeEngine):
         bn_phase: step t uses batch-norm slot (bn_phase + t) % T (gaze_grcn only; the others have no per-timestep BN).
         Returns (logits, probs, new_state); new_state is a fresh tensor on every call: the state behind step n_valid."""
         assert (c3d_input is None) != (rows is None), 'exactly one of c3d_input and rows'
-        if c3d_input is not None:
-            x = c3d_input
-            assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
-            assert tuple(x.shape) == (self.B, self.T, 1024, 7, 7), tuple(x.shape)
-        else:
-            assert rows.is_cuda and rows.dtype == self.torch_dtype and rows.is_contiguous()
-            assert rows.numel() == self.B * self.T * 49 * 1024
-        n_valid = self.T if n_valid is None else int(n_valid)
-        if state is not None:
-            assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous()
-            assert state.numel() == self.state_elems, (state.numel(), self.state_elems)
         assert self.STREAM_BN_PHASE or bn_phase == 0, 'this family has no per-timestep batch-norm'
         logits, probs = self._outputs(want_probs, None, None)
-        new_state = torch.empty(self.state_elems, dtype=torch.float32, device=self.device)
         phase = (int(bn_phase),) if self.STREAM_BN_PHASE else ()
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['forward_stream'](self._h, _ptr(c3d_input), _ptr(rows), _ptr(state), _ptr(new_state), n_valid,
-                                                 *(phase + (_ptr(logits), _ptr(probs), _stream_ptr(self.device)))))
+        new_state = _stream_call(self, self._f['forward_stream'], self.B, self.T, c3d_input, state, n_valid, lambda si, so, nv: (
+            _ptr(c3d_input), _ptr(rows), si, so, nv) + phase + (_ptr(logits), _ptr(probs)), rows=rows)
         return logits, probs, new_state
 
     def inject_fault(self, kind='seq'):
@@ -795,12 +810,7 @@ class FcGruEngine(object):
         x = c3d_input
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
         assert tuple(x.shape) == (self.B, self.T, 1024, 7, 7), tuple(x.shape)
-        if train == 'keep':
-            pass                                   # a mask installed by dropout.use() stays as it is
-        elif train:
-            self.dropout.draw()
-        else:
-            self.dropout.off()
+        self.dropout.arm(train)
         logits = torch.empty(self.B, self.T, self.GH, self.GW, device=self.device)
         probs = torch.empty_like(logits) if want_probs else None
         with torch.cuda.device(self.device):
@@ -821,20 +831,11 @@ class FcGruEngine(object):
         steps, later outputs are unspecified.  state: fp32 device tensor of state_elems elements ([B, 1617], one slot of
         read_buffer('h')) from an earlier call, or None = the zero state; never modified.  The dropout site is off.
         Returns (logits, probs, new_state); new_state is a fresh tensor on every call: h behind step n_valid."""
-        x = c3d_input
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
-        assert tuple(x.shape) == (self.B, self.T, 1024, 7, 7), tuple(x.shape)
-        n_valid = self.T if n_valid is None else int(n_valid)
-        if state is not None:
-            assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous()
-            assert state.numel() == self.state_elems, (state.numel(), self.state_elems)
         self.dropout.off()
         logits = torch.empty(self.B, self.T, self.GH, self.GW, device=self.device)
         probs = torch.empty_like(logits) if want_probs else None
-        new_state = torch.empty(self.state_elems, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_fcgru_forward_stream(self._h, _ptr(x), _ptr(state), _ptr(new_state), n_valid, _ptr(logits),
-                                                         _ptr(probs), _stream_ptr(self.device)))
+        new_state = _stream_call(self, self.lib.rgp_fcgru_forward_stream, self.B, self.T, c3d_input, state, n_valid,
+                                 lambda si, so, nv: (_ptr(c3d_input), si, so, nv, _ptr(logits), _ptr(probs)))
         return logits, probs, new_state
 
 
@@ -923,12 +924,8 @@ class ShallowNetEngine(object):
         assert tuple(frames.shape[1:]) == (self.image_hw, self.image_hw, 3) and n <= self.max_frames
         if self.dropout is None:
             assert not train, 'create the engine with dropout=True'
-        elif train == 'keep':
-            pass
-        elif train:
-            self.dropout.draw()
         else:
-            self.dropout.off()
+            self.dropout.arm(train)
         sal = torch.empty(n, 49, 49, device=self.device)
         sal7 = torch.empty(n, 7, 7, device=self.device) if want_7x7 else None
         with torch.cuda.device(self.device):
@@ -1020,12 +1017,7 @@ class CascadeEngine(object):
         """frame_images [B,T,H,W,3], c3d_input [B,T,1024,7,7] fp32 device tensors -> maps [B,T,49,49].
         train: True = draw a dropout mask (if configured), 'keep' = leave an installed mask, False = site off."""
         B, T = self.batch, self.n_steps
-        if train == 'keep':
-            pass
-        elif train:
-            self.dropout.draw()
-        else:
-            self.dropout.off()
+        self.dropout.arm(train)
         assert frame_images.is_cuda and frame_images.dtype == torch.float32 and frame_images.is_contiguous()
         assert c3d_input.is_cuda and c3d_input.dtype == torch.float32 and c3d_input.is_contiguous()
         assert tuple(frame_images.shape) == (B, T, self.image_hw, self.image_hw, 3), tuple(frame_images.shape)
@@ -1049,25 +1041,12 @@ class CascadeEngine(object):
         from an earlier call, or None = the zero state; never modified.  Returns (maps, new_state); new_state is a fresh
         tensor on every call: both states behind step n_valid."""
         B, T = self.batch, self.n_steps
-        if train == 'keep':
-            pass
-        elif train:
-            self.dropout.draw()
-        else:
-            self.dropout.off()
+        self.dropout.arm(train)
         assert frame_images.is_cuda and frame_images.dtype == torch.float32 and frame_images.is_contiguous()
-        assert c3d_input.is_cuda and c3d_input.dtype == torch.float32 and c3d_input.is_contiguous()
         assert tuple(frame_images.shape) == (B, T, self.image_hw, self.image_hw, 3), tuple(frame_images.shape)
-        assert tuple(c3d_input.shape) == (B, T, 1024, 7, 7), tuple(c3d_input.shape)
-        n_valid = T if n_valid is None else int(n_valid)
-        if state is not None:
-            assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous()
-            assert state.numel() == self.state_elems, (state.numel(), self.state_elems)
         maps = torch.empty(B, T, 49, 49, device=self.device)
-        new_state = torch.empty(self.state_elems, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_cascade_forward_stream(self._h, _ptr(frame_images), _ptr(c3d_input), _ptr(state),
-                                                           _ptr(new_state), n_valid, _ptr(maps), _stream_ptr(self.device)))
+        new_state = _stream_call(self, self.lib.rgp_cascade_forward_stream, B, T, c3d_input, state, n_valid,
+                                 lambda si, so, nv: (_ptr(frame_images), _ptr(c3d_input), si, so, nv, _ptr(maps)))
         return maps, new_state
 
     BUFFERS = {'frm_sal': lambda B, T: (B, T, 49, 49), 'rcn_outputs': lambda B, T: (B, T, 7, 7, 256),
