@@ -316,25 +316,41 @@ int rgp_fcgru_set_dropout(rgp_fcgru_t* plan, float keep_prob, const unsigned cha
  *                                resident in registers (csrc/fcgru_seq.hip.h).  Refused with RGP_EINVAL, the reason in
  *                                rgp_last_error(): f32 plans, batch > 64, n_steps > 16384, and -- asked of the current
  *                                device at create -- a device with fewer CUs than the launch has workgroups (203).
+ *   RGP_FCGRU_BPTT_PERSISTENT    run the backward-through-time pass of rgp_fcgru_backward in ONE persistent launch with the
+ *                                transposed h-side kernels resident in registers (csrc/fcgru_bptt.hip.h), whatever path the
+ *                                forward takes; without it the pass is four launches per timestep, as on every plan so
+ *                                far.  Refused with RGP_EINVAL, the reason in rgp_last_error(): without
+ *                                RGP_FCGRU_SAVE_FOR_BACKWARD, f32 plans, batch > 64, (batch * n_steps + 1) * 3 * 1664 * 2
+ *                                bytes (the gate-gradient rows, which the kernel addresses with 32-bit offsets; batch
+ *                                rounded up to a multiple of 16) not below 2^32 (batch 64: n_steps <= 6721) -- these four
+ *                                need no device -- and a device with fewer than 203 CUs.
  * With neither path flag the library's choice is per step.  Unknown bits and RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT
  * are RGP_EINVAL.  Both paths fill the same buffers in the same layouts: rgp_fcgru_backward runs behind either. */
 #define RGP_FCGRU_SAVE_FOR_BACKWARD 1
 #define RGP_FCGRU_PER_STEP 2
 #define RGP_FCGRU_PERSISTENT 4
+#define RGP_FCGRU_BPTT_PERSISTENT 8
 int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_h, int gazemap_w, int dtype, int flags);
 /* Workgroups (= CUs) a persistent recurrence launch of this plan occupies; 0: the plan runs per-step launches. */
 int rgp_fcgru_persistent_workgroups(const rgp_fcgru_t* plan);
+/* The same for the persistent BPTT launch of rgp_fcgru_backward: 203, or 0 (plans without RGP_FCGRU_BPTT_PERSISTENT). */
+int rgp_fcgru_bptt_persistent_workgroups(const rgp_fcgru_t* plan);
 /* Time-out of the persistent launch, as for the other recurrent families: all its workgroups must be resident together
  * (keep ONE such launch in flight per device).  A launch that waits about a second for a missing member stops waiting,
  * NaN-poisons the h rows of every step and clip (NaN logits) and the fp32 states, and sets the plan's error word: the
  * next rgp_fcgru_forward, or rgp_fcgru_status, which first waits for `stream`, returns RGP_ETIMEOUT once.  RGP_OK on
- * per-step plans. */
+ * per-step plans.  A persistent BPTT launch that times out NaN-poisons its units of all three parts of every gate-gradient
+ * row ("dxpre" below) and of the final carry ("dh0"): every filter gradient and the projection's input gradient are then
+ * NaN; rgp_fcgru_status, or the next rgp_fcgru_forward / rgp_fcgru_backward of the plan, returns RGP_ETIMEOUT once. */
 int rgp_fcgru_status(rgp_fcgru_t* plan, rgp_stream_t stream);
 /* Intermediates of the last forward of a TRAINING plan as fp32 (padding columns dropped, bf16 buffers widened), either
  * recurrence path: "xpre" [B,T,3,1617] hoisted x parts + biases, column blocks u, r, c; "h" [T+1,B,1617] fp32 states,
  * slot 0 = h_0; "u", "r", "c" [T,B,1617] gates; "hp" [B,T+1,1617] the operand rows of h (slot t = h_{t-1} of step t);
  * "rh" [B,T,1617] the operand rows r * h_{t-1}.  rgp_fcgru_buffer_elems: their sizes (0: unknown name, or an inference
- * plan).  Errors: RGP_EINVAL for an unknown name; RGP_ESTATE on an inference plan or before the first forward. */
+ * plan).  Errors: RGP_EINVAL for an unknown name; RGP_ESTATE on an inference plan or before the first forward.
+ * Of the last BACKWARD, either BPTT path (RGP_ESTATE before the first one): "dxpre" [B,T,3,1617] the gate-gradient operand
+ * rows d loss / d pre-activation, parts [u | r | c] (row 0 of the buffer, all zero, is skipped); "dh_head" [B,T,1617] fp32
+ * d loss / d h_t through the read-out alone; "dh0" [B,1617] fp32 the final carry, d loss / d h_{-1}. */
 int rgp_fcgru_read_buffer(rgp_fcgru_t* plan, const char* name, float* dst_fp32, rgp_stream_t stream);
 size_t rgp_fcgru_buffer_elems(const rgp_fcgru_t* plan, const char* name);
 /* Streaming inference, as rgp_grcn_forward_stream without bn_phase (this graph has no per-timestep batch-norm) and without

@@ -22,7 +22,7 @@ RGP_C3D_SAVE_FOR_BACKWARD, RGP_C3D_KERNELS_IGEMM, RGP_C3D_KERNELS_TILE128, RGP_C
 RGP_C3DCONV_SAVE_FOR_BACKWARD, RGP_C3DCONV_STAGED, RGP_C3DCONV_FUSED = 1, 2, 4
 RGP_LSTM_SAVE_FOR_BACKWARD, RGP_LSTM_PER_STEP, RGP_LSTM_PERSISTENT, RGP_LSTM_BPTT_PERSISTENT = 1, 2, 4, 8
 RGP_GRCN77_SAVE_FOR_BACKWARD, RGP_GRCN77_PER_STEP = 1, 2
-RGP_FCGRU_SAVE_FOR_BACKWARD, RGP_FCGRU_PER_STEP, RGP_FCGRU_PERSISTENT = 1, 2, 4
+RGP_FCGRU_SAVE_FOR_BACKWARD, RGP_FCGRU_PER_STEP, RGP_FCGRU_PERSISTENT, RGP_FCGRU_BPTT_PERSISTENT = 1, 2, 4, 8
 RGP_FAULT_SEQ_LOST_MEMBER, RGP_FAULT_BPTT_LOST_MEMBER = 1, 2
 RGP_ACTION_NN, RGP_ACTION_SVM = 0, 1
 RGP_ACTION_USE_GAZEMAP, RGP_ACTION_SAVE_FOR_BACKWARD, RGP_ACTION_UNFUSED = 1, 2, 4
@@ -202,6 +202,7 @@ SIGNATURES = {
     'rgp_fcgru_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(FcGruWeights), c_int, c_void_p]),
     'rgp_fcgru_create_flags': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int]),
     'rgp_fcgru_persistent_workgroups': (c_int, [c_void_p]),
+    'rgp_fcgru_bptt_persistent_workgroups': (c_int, [c_void_p]),
     'rgp_fcgru_status': (c_int, [c_void_p, c_void_p]),
     'rgp_fcgru_read_buffer': (c_int, [c_void_p, c_char_p, c_void_p, c_void_p]),
     'rgp_fcgru_buffer_elems': (c_size_t, [c_void_p, c_char_p]),

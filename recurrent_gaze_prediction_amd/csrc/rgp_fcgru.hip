@@ -15,6 +15,10 @@
 // Recurrence, two implementations: per step (every plan; the library's choice), and -- RGP_FCGRU_PERSISTENT, bf16 plans of
 // at most 64 clips -- all T steps in one persistent launch with the h-side kernels resident in registers
 // (fcgru_seq.hip.h).  Both write the same buffers in the same layouts, so the backward runs unchanged behind either.
+// BPTT, two implementations as well: per step (every plan; the library's choice: four launches per timestep), and --
+// RGP_FCGRU_BPTT_PERSISTENT, bf16 training plans of at most 64 clips -- all T steps in one persistent launch with the
+// TRANSPOSED h-side kernels resident in registers (fcgru_bptt.hip.h), whatever the forward ran.  Both leave dxpre and the final
+// carry in the same buffers, so the hoisted filter gradients and the projection's input gradient run unchanged behind either.
 // Streaming (rgp_fcgru_forward_stream): the same forward started from a caller's h_{-1} [B][1617] instead of zeros, on either
 // path and on inference and training plans.  Way in: gru_seed_or_zero (gru_steps.h), one launch in place of the two memsets.
 // Way out: one strided copy of the fp32 state behind step n_valid.  Nothing else in the per-step loop changes.
@@ -25,6 +29,7 @@
 #include "wgrad_launch.h"
 #include "gru_steps.h"
 #include "fcgru_seq.hip.h"
+#include "fcgru_bptt.hip.h"
 
 using namespace rgp;
 
@@ -59,6 +64,9 @@ struct rgp_fcgru {
   PinnedErrWord err;                                  // set by a launch that lost a member (allocated at bind, persistent plans only)
   size_t hsnap = 0;                                   // fp32 [B][np]: h behind step n_valid of a streaming launch (persistent inference plans)
   StreamCall stream;                                  // rgp_fcgru_forward_stream: the state is [B][n] dense; slot 0 = slot (b, 0) of hp_all
+  // ---- persistent BPTT (RGP_FCGRU_BPTT_PERSISTENT)
+  bool bptt_persistent = false, bwd_done = false;
+  size_t bptt_cnt = 0;                                // [2 T][FCS_SHARDS][FCS_CNT_STRIDE] phase counters of fcgru_bptt_kernel
 };
 
 namespace rgp {
@@ -256,7 +264,7 @@ int fcgru_check_error(rgp_fcgru* g) {
 }
 
 // rgp_fcgru_read_buffer: rows of `np` elements at `off`, the first n columns of each are kept
-struct FcView { size_t off; long long rows; bool operand; };
+struct FcView { size_t off; long long rows; bool operand; bool bwd = false; };    // bwd: valid only after a backward
 
 bool find_view(const rgp_fcgru* g, const char* name, FcView& v) {
   const std::string n(name ? name : "");
@@ -268,6 +276,9 @@ bool find_view(const rgp_fcgru* g, const char* name, FcView& v) {
   else if (n == "c") v = {g->call, T_ * B, false};
   else if (n == "hp") v = {g->hp_all, B * (T_ + 1), true};
   else if (n == "rh") v = {g->rh_all, B * T_, true};
+  else if (n == "dxpre") v = {g->dxpre + (size_t)3 * g->np * esize(g->dtype), B * T_ * 3, true, true};       // (row 0 of the buffer skipped)
+  else if (n == "dh_head") v = {g->dh_head, B * T_, false, true};
+  else if (n == "dh0") v = {g->carry, B, false, true};
   else return false;
   return true;
 }
@@ -368,6 +379,40 @@ __global__ __launch_bounds__(256) void fc_unpack_kernel(const float* __restrict_
   }
 }
 
+// Step 2 of backward_impl for all T steps in one persistent launch (fcgru_bptt.hip.h)
+int bptt_persistent_launch(rgp_fcgru* g, hipStream_t s) {
+  char* ws = g->ws;
+  RGP_HIP(hipMemsetAsync(ws + g->bptt_cnt, 0, (size_t)2 * g->T * FCS_SHARDS * FCS_CNT_STRIDE * 4, s));        // phase counters: zeroed EVERY call
+  FcBpttParams p;
+  p.b_c = (const bf16_t*)(ws + g->b_c.w_off);
+  p.b_zr = (const bf16_t*)(ws + g->b_zr.w_off);
+  p.dh_head = (const float*)(ws + g->dh_head);
+  p.hall = (const float*)(ws + g->hall_t);
+  p.uall = (const float*)(ws + g->uall);
+  p.rall = (const float*)(ws + g->rall);
+  p.call = (const float*)(ws + g->call);
+  p.dxpre = (bf16_t*)(ws + g->dxpre);
+  p.carry = (float*)(ws + g->carry);
+  p.cnt = (unsigned*)(ws + g->bptt_cnt);
+  p.err = g->err.host;
+  p.B = g->B; p.T = g->T;
+  RGP_REQUIRE(g->np == FCS_NP && g->b_c.K == FCS_NP && g->b_zr.K == 2 * FCS_NP && g->b_c.chunk_major == 0 && g->b_zr.chunk_major == 0,
+              "fcgru_bptt: unexpected filter packing");
+  void (*kern)(FcBpttParams) = nullptr;
+  switch ((g->B + 15) / 16) {
+    case 1: kern = fcgru_bptt_kernel<1>; break;
+    case 2: kern = fcgru_bptt_kernel<2>; break;
+    case 3: kern = fcgru_bptt_kernel<3>; break;
+    case 4: kern = fcgru_bptt_kernel<4>; break;
+    default: return set_err(RGP_EINVAL, "fcgru_bptt: batch %d", g->B);
+  }
+  PersistentLaunch guard(s);
+  RGP_TRY(guard.status());
+  kern<<<FCS_MEMBERS, SEQ_NT, 0, s>>>(p);
+  RGP_HIP(hipGetLastError());
+  return guard.commit();
+}
+
 template <typename T>
 int backward_impl(rgp_fcgru* g, const float* logits, const float* probs, const float* labels, const rgp_fcgru_weights* gr,
                   int loss_l2, hipStream_t s) {
@@ -402,9 +447,16 @@ int backward_impl(rgp_fcgru* g, const float* logits, const float* probs, const f
     EpiParams e = make_epi(g->b_out, Fp(g->dh_head), ws);
     RGP_TRY((launch_igemm<T, 1, 1, EpiStore<float, false, false>>(p, e, s)));
   }
-  // 2. BPTT
+  // 2. BPTT: one persistent launch (RGP_FCGRU_BPTT_PERSISTENT), or four launches per step
   const float* hall = Fp(g->hall_t);
-  for (int t = T_ - 1; t >= 0; --t) {
+  bool one_launch = false;
+  if constexpr (sizeof(T) == 2) {
+    if (g->bptt_persistent) {
+      RGP_TRY(bptt_persistent_launch(g, s));
+      one_launch = true;
+    }
+  }
+  for (int t = one_launch ? -1 : T_ - 1; t >= 0; --t) {
     const float* h_prev = hall + (size_t)t * st;
     fc_bwd1_kernel<T><<<nblk((long long)st), 256, 0, s>>>(Fp(g->dh_head), Fp(g->carry), h_prev, Fp(g->uall) + (size_t)t * st,
                                                          Fp(g->call) + (size_t)t * st, Tp(g->dxpre), Tp(g->dcp), B, T_, t, np, t == T_ - 1);
@@ -512,13 +564,28 @@ int rgp_fcgru_create_ex(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_
 
 int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_h, int gazemap_w, int dtype, int flags) {
   RGP_REQUIRE(plan && batch > 0 && n_steps > 0, "rgp_fcgru_create: bad arguments");
-  RGP_REQUIRE((flags & ~(RGP_FCGRU_SAVE_FOR_BACKWARD | RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT)) == 0,
+  RGP_REQUIRE((flags & ~(RGP_FCGRU_SAVE_FOR_BACKWARD | RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT | RGP_FCGRU_BPTT_PERSISTENT)) == 0,
               "rgp_fcgru_create: unknown flags 0x%x", flags);
   RGP_REQUIRE((flags & (RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT)) != (RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT),
               "rgp_fcgru_create: flags name both recurrence paths");
   RGP_REQUIRE((gazemap_h == 49 && gazemap_w == 49) || (gazemap_h == 7 && gazemap_w == 7),
               "rgp_fcgru_create: gaze map %dx%d (reference uses 49x49 or 7x7)", gazemap_h, gazemap_w);
   RGP_REQUIRE(dtype == RGP_F32 || dtype == RGP_BF16, "rgp_fcgru_create: dtype %d", dtype);
+  if (flags & RGP_FCGRU_BPTT_PERSISTENT) {
+    // the arguments (no device needed to refuse them); the device is asked below, behind the forward's argument checks
+    RGP_REQUIRE(flags & RGP_FCGRU_SAVE_FOR_BACKWARD, "rgp_fcgru_create: the persistent BPTT kernel (flags) needs RGP_FCGRU_SAVE_FOR_BACKWARD");
+    RGP_REQUIRE(dtype == RGP_BF16, "rgp_fcgru_create: the persistent BPTT kernel (flags) takes bf16 plans, dtype is %d", dtype);
+    RGP_REQUIRE(batch <= 64, "rgp_fcgru_create: the persistent BPTT kernel (flags) takes at most 64 clips, batch is %d", batch);
+    // the kernel addresses the dxpre rows with 32-bit byte offsets: (B T + 1) rows of 3 * 1664 * 2 bytes must stay below 2^32
+    // (B = 64: T <= 6721), and so must the offsets of the rows >= B of the last 16-row fragment, which have to land BEHIND the
+    // buffer to read zeros
+    RGP_REQUIRE(((long long)batch * n_steps + 1) * (long long)FCB_ROW < (1LL << 32),
+                "rgp_fcgru_create: the persistent BPTT kernel (flags) addresses (batch * n_steps + 1) * %u bytes with 32-bit offsets: "
+                "batch %d x n_steps %d is past 2^32", FCB_ROW, batch, n_steps);
+    RGP_REQUIRE(((long long)((batch + 15) / 16 * 16) * n_steps + 1) * (long long)FCB_ROW < (1LL << 32),
+                "rgp_fcgru_create: the persistent BPTT kernel (flags) addresses whole 16-clip fragments with 32-bit offsets: "
+                "batch %d (rounded up to 16) x n_steps %d is past 2^32", batch, n_steps);
+  }
   if (flags & RGP_FCGRU_PERSISTENT) {
     // the arguments first (no device needed to refuse them), then the device
     RGP_REQUIRE(dtype == RGP_BF16, "rgp_fcgru_create: the persistent kernel (flags) takes bf16 plans, dtype is %d", dtype);
@@ -531,10 +598,17 @@ int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazem
     RGP_REQUIRE(n_cu >= FCS_MEMBERS, "rgp_fcgru_create: the persistent kernel (flags) needs %d CUs resident together, the device has %d",
                 FCS_MEMBERS, n_cu);
   }
+  if (flags & RGP_FCGRU_BPTT_PERSISTENT) {
+    int n_cu = 0;
+    RGP_TRY(device_cu_count(&n_cu));
+    RGP_REQUIRE(n_cu >= FCS_MEMBERS, "rgp_fcgru_create: the persistent BPTT kernel (flags) needs %d CUs resident together, the device has %d",
+                FCS_MEMBERS, n_cu);
+  }
   rgp_fcgru* g = new rgp_fcgru();
   g->B = batch; g->T = n_steps; g->F = batch * n_steps; g->G = gazemap_h * gazemap_w; g->dtype = dtype;
   g->save = (flags & RGP_FCGRU_SAVE_FOR_BACKWARD) != 0;
   g->persistent = (flags & RGP_FCGRU_PERSISTENT) != 0;                       // (neither flag: the library's choice is per step)
+  g->bptt_persistent = (flags & RGP_FCGRU_BPTT_PERSISTENT) != 0;             // (independent of the forward's path)
   g->Gp = (int)align_up(g->G, 128);
   g->Kx = (int)align_up(g->nx, 64);
   g->np = (int)align_up(g->n, 64);
@@ -586,6 +660,7 @@ int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazem
     g->dwx = a.take((size_t)Kx * 3 * np * 4);
     g->dwh = a.take((size_t)np * 2 * np * 4);
     g->dwc = a.take((size_t)np * np * 4);
+    if (g->bptt_persistent) g->bptt_cnt = a.take((size_t)2 * n_steps * FCS_SHARDS * FCS_CNT_STRIDE * 4);
   }
   g->ws_bytes = a.off;
   *plan = g;
@@ -605,10 +680,11 @@ int rgp_fcgru_bind_workspace(rgp_fcgru_t* g, void* workspace, size_t bytes, rgp_
   if (bytes < g->ws_bytes) return set_err(RGP_EWORKSPACE, "workspace %zu < required %zu bytes", bytes, g->ws_bytes);
   RGP_REQUIRE(((size_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  if (g->persistent) RGP_TRY(g->err.alloc());
+  if (g->persistent || g->bptt_persistent) RGP_TRY(g->err.alloc());
   g->ws = (char*)workspace;
   g->weights_set = false;
   g->fwd_done = false;
+  g->bwd_done = false;
   g->stream = StreamCall();
   RGP_HIP(hipMemsetAsync(g->ws, 0, g->ws_bytes, s));
   for (ConvDesc* d : {&g->proj, &g->xg, &g->zr, &g->c, &g->out}) RGP_TRY(upload_desc(*d, g->ws, s));
@@ -666,11 +742,13 @@ int rgp_fcgru_backward(rgp_fcgru_t* g, const float* logits, const float* probs, 
     RGP_REQUIRE(ptrs[i], "rgp_fcgru_backward: gradient pointer %zu is null", i);
   if (g->stream.streamed)
     return set_err(RGP_ESTATE, "rgp_fcgru_backward: the last forward was a streaming call (no truncated BPTT): run rgp_fcgru_forward first");
+  if (g->bptt_persistent) RGP_TRY(fcgru_check_error(g));
   hipStream_t s = (hipStream_t)stream;
   RGP_TRY(g->dtype == RGP_BF16 ? backward_impl<bf16_t>(g, logits, probs, labels, grads, loss_type, s)
                                : backward_impl<float>(g, logits, probs, labels, grads, loss_type, s));
   fc_fold_bias_kernel<<<1, 64, 0, s>>>((const float*)(g->ws + g->dwc), (float*)grads->proj_c3d_b, g->Cp);
   RGP_HIP(hipGetLastError());
+  g->bwd_done = true;
   return RGP_OK;
 }
 
@@ -681,6 +759,8 @@ int rgp_fcgru_status(rgp_fcgru_t* g, rgp_stream_t stream) {
 }
 
 int rgp_fcgru_persistent_workgroups(const rgp_fcgru_t* g) { return (g && g->persistent) ? FCS_MEMBERS : 0; }
+
+int rgp_fcgru_bptt_persistent_workgroups(const rgp_fcgru_t* g) { return (g && g->bptt_persistent) ? FCS_MEMBERS : 0; }
 
 size_t rgp_fcgru_buffer_elems(const rgp_fcgru_t* g, const char* name) {
   FcView v;
@@ -693,6 +773,7 @@ int rgp_fcgru_read_buffer(rgp_fcgru_t* g, const char* name, float* dst, rgp_stre
   if (!find_view(g, name, v)) return set_err(RGP_EINVAL, "rgp_fcgru_read_buffer: unknown buffer '%s'", name);
   if (!g->save) return set_err(RGP_ESTATE, "rgp_fcgru_read_buffer: the plan was created without RGP_FCGRU_SAVE_FOR_BACKWARD");
   if (!g->ws || !g->fwd_done) return set_err(RGP_ESTATE, "rgp_fcgru_read_buffer: no forward has run on this plan");
+  if (v.bwd && !g->bwd_done) return set_err(RGP_ESTATE, "rgp_fcgru_read_buffer: '%s' is a buffer of the backward, and none has run on this plan", name);
   hipStream_t s = (hipStream_t)stream;
   const long long total = v.rows * g->n;
   const int blocks = (int)std::min<long long>((total + 255) / 256, 8192);

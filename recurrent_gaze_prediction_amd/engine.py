@@ -708,15 +708,20 @@ class FcGruEngine(object):
     per_step=True names the per-timestep recurrence (RGP_FCGRU_PER_STEP: two launches per step), persistent=True the
     one-launch recurrence with resident kernels (RGP_FCGRU_PERSISTENT, csrc/fcgru_seq.hip.h: bf16 plans of at most 64
     clips on a device with at least 203 CUs, refused otherwise); with both False the library chooses (per step).
+    bptt_persistent=True: the backward-through-time pass of backward() as one persistent launch as well
+    (RGP_FCGRU_BPTT_PERSISTENT, csrc/fcgru_bptt.hip.h; bf16 training plans of at most 64 clips), whatever the forward runs;
+    False is the library's choice (four launches per step).
     read_buffer (training plans, after a forward; fp32): 'xpre' [B,T,3,1617], 'h' [T+1,B,1617], 'u', 'r', 'c'
-    [T,B,1617], 'hp' [B,T+1,1617], 'rh' [B,T,1617]."""
+    [T,B,1617], 'hp' [B,T+1,1617], 'rh' [B,T,1617]; after a backward also 'dxpre' [B,T,3,1617] (the gate-gradient operand
+    rows, parts u, r, c), 'dh_head' [B,T,1617] and 'dh0' [B,1617] (the final carry)."""
 
     BUFFER_SHAPES = {'xpre': lambda B, T: (B, T, 3, 1617), 'h': lambda B, T: (T + 1, B, 1617), 'u': lambda B, T: (T, B, 1617),
                      'r': lambda B, T: (T, B, 1617), 'c': lambda B, T: (T, B, 1617), 'hp': lambda B, T: (B, T + 1, 1617),
-                     'rh': lambda B, T: (B, T, 1617)}
+                     'rh': lambda B, T: (B, T, 1617), 'dxpre': lambda B, T: (B, T, 3, 1617), 'dh_head': lambda B, T: (B, T, 1617),
+                     'dh0': lambda B, T: (B, 1617)}
 
     def __init__(self, batch, n_steps, gazemap_hw=(49, 49), dtype='f32', device='cuda:0', save_for_backward=False,
-                 per_step=False, persistent=False):
+                 per_step=False, persistent=False, bptt_persistent=False):
         self.lib = _lib.load()
         self.device = _require_gpu(device)
         self.B, self.T, self.GH, self.GW = int(batch), int(n_steps), int(gazemap_hw[0]), int(gazemap_hw[1])
@@ -726,7 +731,7 @@ class FcGruEngine(object):
         self.flat_params = self.flat_grads = self.grads = self.adam_m = self.adam_v = None
         self._h = ctypes.c_void_p()
         flags = (_lib.RGP_FCGRU_SAVE_FOR_BACKWARD if save_for_backward else 0) | (_lib.RGP_FCGRU_PER_STEP if per_step else 0) | \
-            (_lib.RGP_FCGRU_PERSISTENT if persistent else 0)
+            (_lib.RGP_FCGRU_PERSISTENT if persistent else 0) | (_lib.RGP_FCGRU_BPTT_PERSISTENT if bptt_persistent else 0)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.rgp_fcgru_create_flags(ctypes.byref(self._h), self.B, self.T, self.GH, self.GW,
                                                        _lib.DTYPES[dtype], flags))
@@ -793,8 +798,17 @@ class FcGruEngine(object):
     def persistent(self):
         return self.persistent_workgroups > 0
 
+    @property
+    def bptt_persistent_workgroups(self):
+        """CUs the persistent BPTT launch of this plan's backward occupies (0: four launches per timestep)."""
+        return int(self.lib.rgp_fcgru_bptt_persistent_workgroups(self._h))
+
+    @property
+    def bptt_persistent(self):
+        return self.bptt_persistent_workgroups > 0
+
     def read_buffer(self, name):
-        """An intermediate of the last forward of a training plan (rgp_fcgru_read_buffer), fp32, shaped as the class
+        """An intermediate of the last forward (or backward) of a training plan (rgp_fcgru_read_buffer), fp32, shaped as the class
         docstring lists."""
         if name not in self.BUFFER_SHAPES:
             raise _lib.RgpError('unknown intermediate %r' % name)

@@ -45,6 +45,9 @@ class GRUModelConfig(BaseModelConfig):
         # recurrence path of the fc-GRU engine: None (the library's choice: per step), 'per_step' or 'persistent' (all T
         # steps in one launch, csrc/fcgru_seq.hip.h: bf16, at most 64 clips; gaze_rnn77 inherits it)
         self.fcgru_path = None
+        # BPTT path of the same engine: None (the library's choice: per step), 'per_step' or 'persistent' (the backward-through-
+        # time pass in one launch, csrc/fcgru_bptt.hip.h: bf16 training plans of at most 64 clips), whatever fcgru_path says
+        self.fcgru_bptt_path = None
 
 
 DROPOUT_RANK_STRIDE = 0x9E3779B1     # key offset between data-parallel ranks (also used by the checkpoint loader)
@@ -136,10 +139,13 @@ class GazePredictionGRU(ModelBase):
             net = {}
         path = getattr(model.config, 'fcgru_path', None)
         assert path in (None, 'persistent', 'per_step'), path
+        bptt_path = getattr(model.config, 'fcgru_bptt_path', None)
+        assert bptt_path in (None, 'persistent', 'per_step'), bptt_path
+        kw = {'bptt_persistent': True} if bptt_path == 'persistent' else {}          # (named only when asked for)
         engine = model._new_fcgru_engine(model.batch_size, model.n_lstm_steps, (model.gazemap_height, model.gazemap_width),
                                          dtype=getattr(model.config, 'compute_dtype', 'f32'), device=model.session.device,
                                          save_for_backward=getattr(model.config, 'trainable', True),
-                                         per_step=path == 'per_step', persistent=path == 'persistent')
+                                         per_step=path == 'per_step', persistent=path == 'persistent', **kw)
         model.variables = synthetic.fcgru_params(getattr(model.config, 'init_seed', 0), model.gazemap_height,
                                                  model.gazemap_width)
         engine.set_weights(model.variables)
@@ -334,15 +340,17 @@ class GazePredictionGRU(ModelBase):
             return True
 
     def _recover_from_timeout(self):
-        """The fc-GRU model (this class, gaze_rnn77): a persistent recurrence launch lost a member (include/rgp.h) --
-        continue on a plan that runs the recurrence as per-timestep launches (RGP_FCGRU_PER_STEP).  A new engine object in
-        this process; master weights, optimizer slots and the dropout site move over; the caller recomputes the poisoned
+        """The fc-GRU model (this class, gaze_rnn77): a persistent recurrence or BPTT launch lost a member (include/rgp.h) --
+        continue on a plan that runs the recurrence as per-timestep launches (RGP_FCGRU_PER_STEP) and its BPTT per step too.
+        A new engine object in this process; master weights, optimizer slots and the dropout site move over; the caller recomputes the poisoned
         batch.  Same shape as models/gaze_lstm.py.  The models of the other families override this; one that does not,
         and whose engine is not the fc-GRU's, has no fallback (False)."""
         from .. import engine as _engine
         old = self.engine
-        if not isinstance(old, _engine.FcGruEngine) or getattr(old, 'per_step', False):
+        if not isinstance(old, _engine.FcGruEngine):
             return False
+        if getattr(old, 'per_step', False) and not getattr(old, 'bptt_persistent', False):
+            return False          # nothing persistent about it
         log.warning('persistent fc-GRU launch timed out (RGP_ETIMEOUT): switching this model to per-timestep launches')
         new = self._new_fcgru_engine(old.B, old.T, (old.GH, old.GW), dtype=old.dtype, device=old.device,
                                      save_for_backward=old.save_for_backward, per_step=True)
@@ -357,6 +365,7 @@ class GazePredictionGRU(ModelBase):
             new.dropout.draws = old.dropout.draws
         self.engine = new
         self.config.fcgru_path = 'per_step'
+        self.config.fcgru_bptt_path = 'per_step'
         return True
 
     def _has_dropout(self):

@@ -12,6 +12,9 @@ persistent fc-GRU kernel (fcgru_seq.hip.h): in each of its two phases all 13 x N
 must stand in front of the phase's first MFMA (the scheduler, left alone, sinks them between the MFMAs and re-uses 2 - 4
 registers: 2 - 3 loads in flight instead of the >= 8 the hand-off needs), and nothing may spill.  Sixteen instantiations
 <NF, SAVE, STREAM>: the eight STREAM = false ones as before, and the eight streaming ones (step 0 of phase A on the seeded rows).
+The persistent fc-GRU BPTT kernel (fcgru_bptt.hip.h), four instantiations <NF>: the same rule for each fcs_gemm call of its
+step body -- GEMM C, the u half and the r half of GEMM ZR: three runs of exactly 13 x NF loads in front of 13 x NF MFMAs (no
+phase of any instantiation issues its loads in two runs), and no scratch access.
 """
 import os, subprocess, sys, tempfile
 
@@ -123,6 +126,32 @@ def fcgru_faults(name, body):
     return faults
 
 
+def fcgru_bptt_kernels(asm):
+    lines = asm.split('\n')
+    for st, l in enumerate(lines):
+        if l.startswith('_ZN3rgpL17fcgru_bptt_kernel') and '@' in l:
+            end = next(i for i in range(st, len(lines)) if 's_endpgm' in lines[i])
+            yield l.split(':')[0], lines[st:end]
+
+
+def fcgru_bptt_faults(name, body):
+    """As fcgru_faults, for the three fcs_gemm calls of a BPTT step: exactly [13 NF loads, 13 NF MFMAs] three times."""
+    nf = int(name.split('fcgru_bptt_kernelILi')[1][0])
+    runs = []
+    for l in body:
+        k = 'L' if ('buffer_load_dwordx4' in l and 'sc1' in l) else 'M' if 'v_mfma' in l else None
+        if k and runs and runs[-1][0] == k:
+            runs[-1][1] += 1
+        elif k:
+            runs.append([k, 1])
+    faults = []
+    if runs != [['L', 13 * nf], ['M', 13 * nf]] * 3:
+        faults.append('loads / MFMAs interleaved: ' + ' '.join('%s%d' % (k, n) for k, n in runs))
+    if any('scratch_' in l for l in body):
+        faults.append('scratch access')
+    return faults
+
+
 def main():
     rc = 0
     with tempfile.NamedTemporaryFile(suffix='.s') as tf:
@@ -144,6 +173,15 @@ def main():
     print('rgp_fcgru.hip: %d fcgru_seq kernels (%d streaming), %d with exchange loads not in front of their MFMAs, or spills' %
           (n, n_stream, nbad))
     rc |= nbad > 0 or n != 16 or n_stream != 8
+    n = nbad = 0
+    for name, body in fcgru_bptt_kernels(asm):
+        n += 1
+        faults = fcgru_bptt_faults(name, body)
+        if faults:
+            nbad += 1
+            print('FCGRU_BPTT', name[:100], faults)
+    print('rgp_fcgru.hip: %d fcgru_bptt kernels, %d with exchange loads not in front of their MFMAs, or spills' % (n, nbad))
+    rc |= nbad > 0 or n != 4
     with tempfile.NamedTemporaryFile(suffix='.s') as tf:
         subprocess.run(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-I' + os.path.join(ROOT, 'include'),
                         '-I' + CSRC, '-S', '--cuda-device-only', '-o', tf.name, os.path.join(CSRC, 'rgp_conv_patch.hip')], check=True,
