@@ -324,12 +324,21 @@ int rgp_fcgru_set_dropout(rgp_fcgru_t* plan, float keep_prob, const unsigned cha
  *                                bytes (the gate-gradient rows, which the kernel addresses with 32-bit offsets; batch
  *                                rounded up to a multiple of 16) not below 2^32 (batch 64: n_steps <= 6721) -- these four
  *                                need no device -- and a device with fewer than 203 CUs.
- * With neither path flag the library's choice is per step.  Unknown bits and RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT
- * are RGP_EINVAL.  Both paths fill the same buffers in the same layouts: rgp_fcgru_backward runs behind either. */
+ *   RGP_FCGRU_PERSISTENT_F32     RGP_FCGRU_PERSISTENT for f32 plans: all T steps in ONE persistent launch with the fp32 h-side
+ *                                kernels resident in registers and fp32 MFMAs on the plan's own fp32 operand rows
+ *                                (csrc/fcgru_seq_f32.hip.h).  A flag of its own because RGP_FCGRU_PERSISTENT keeps refusing
+ *                                f32 plans.  Refused with RGP_EINVAL, the reason in rgp_last_error(): plans that are not f32,
+ *                                batch > 64, together with RGP_FCGRU_PER_STEP or RGP_FCGRU_PERSISTENT, n_steps > 8192
+ *                                (64 * n_steps * 1664 * 4 bytes of exchange rows are addressed with 32-bit offsets) -- these
+ *                                need no device -- and a device with fewer than 203 CUs.  The backward behind it is the
+ *                                per-step one (RGP_FCGRU_BPTT_PERSISTENT stays bf16 only).
+ * With no path flag the library's choice is per step.  Unknown bits and two path flags together are RGP_EINVAL.  All
+ * paths fill the same buffers in the same layouts: rgp_fcgru_backward runs behind any of them. */
 #define RGP_FCGRU_SAVE_FOR_BACKWARD 1
 #define RGP_FCGRU_PER_STEP 2
 #define RGP_FCGRU_PERSISTENT 4
 #define RGP_FCGRU_BPTT_PERSISTENT 8
+#define RGP_FCGRU_PERSISTENT_F32 16
 int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_h, int gazemap_w, int dtype, int flags);
 /* Workgroups (= CUs) a persistent recurrence launch of this plan occupies; 0: the plan runs per-step launches. */
 int rgp_fcgru_persistent_workgroups(const rgp_fcgru_t* plan);

@@ -14,7 +14,8 @@
 // (rows = frames, transposing LDS reads) on the operand rows the forward kept.
 // Recurrence, two implementations: per step (every plan; the library's choice), and -- RGP_FCGRU_PERSISTENT, bf16 plans of
 // at most 64 clips -- all T steps in one persistent launch with the h-side kernels resident in registers
-// (fcgru_seq.hip.h).  Both write the same buffers in the same layouts, so the backward runs unchanged behind either.
+// (fcgru_seq.hip.h); RGP_FCGRU_PERSISTENT_F32 is the same for f32 plans (fcgru_seq_f32.hip.h: fp32 MFMAs on the plan's fp32 rows).
+// All write the same buffers in the same layouts, so the backward runs unchanged behind any of them.
 // BPTT, two implementations as well: per step (every plan; the library's choice: four launches per timestep), and --
 // RGP_FCGRU_BPTT_PERSISTENT, bf16 training plans of at most 64 clips -- all T steps in one persistent launch with the
 // TRANSPOSED h-side kernels resident in registers (fcgru_bptt.hip.h), whatever the forward ran.  Both leave dxpre and the final
@@ -29,6 +30,7 @@
 #include "wgrad_launch.h"
 #include "gru_steps.h"
 #include "fcgru_seq.hip.h"
+#include "fcgru_seq_f32.hip.h"
 #include "fcgru_bptt.hip.h"
 
 using namespace rgp;
@@ -188,6 +190,49 @@ int seq_persistent(rgp_fcgru* g, hipStream_t s) {
   return guard.commit();
 }
 
+// The same for f32 plans (RGP_FCGRU_PERSISTENT_F32, fcgru_seq_f32.hip.h): the exchange rows are the plan's fp32 operand rows.
+template <bool SAVE, bool STREAM>
+int seq_persistent_f32(rgp_fcgru* g, hipStream_t s) {
+  char* ws = g->ws;
+  RGP_HIP(hipMemsetAsync(ws + g->seq_cnt, 0, (size_t)2 * g->T * FCS_SHARDS * FCS_CNT_STRIDE * 4, s));         // phase counters: zeroed EVERY call
+  typename FcSeq32ParamsOf<STREAM>::type p;
+  if constexpr (STREAM) {
+    p.seed = (const float*)(ws + (SAVE ? g->hp_all : g->hp));
+    p.seed_stride = (unsigned)((SAVE ? g->T + 1 : 1) * FCS32_ROW);
+    p.seed_bytes = (unsigned)g->B * p.seed_stride;       // (B <= 64, T <= 8192: below 2^32, as hbytes)
+    p.hsnap = SAVE ? nullptr : (float*)(ws + g->hsnap);
+    p.n_valid = g->stream.n_valid;
+  }
+  p.w_zr = (const float*)(ws + g->zr.w_off);
+  p.w_c = (const float*)(ws + g->c.w_off);
+  p.xpre = (const float*)(ws + g->xpre);
+  p.hrows = (float*)(ws + g->hrows);
+  p.rh = (float*)(ws + (SAVE ? g->rh_all : g->rh));
+  p.hall = (float*)(ws + (SAVE ? g->hall_t : g->hall));
+  p.uall = SAVE ? (float*)(ws + g->uall) : nullptr;
+  p.rall = SAVE ? (float*)(ws + g->rall) : nullptr;
+  p.call = SAVE ? (float*)(ws + g->call) : nullptr;
+  p.hp_all = SAVE ? (float*)(ws + g->hp_all) : nullptr;
+  p.cnt = (unsigned*)(ws + g->seq_cnt);
+  p.err = g->err.host;
+  p.B = g->B; p.T = g->T;
+  RGP_REQUIRE(g->np == FCS_NP && g->zr.K == FCS_NP && g->c.K == FCS_NP && g->zr.chunk_major == 0 && g->c.chunk_major == 0,
+              "fcgru_seq_f32: unexpected filter packing");
+  void (*kern)(typename FcSeq32ParamsOf<STREAM>::type) = nullptr;
+  switch ((g->B + 15) / 16) {
+    case 1: kern = fcgru_seq_f32_kernel<1, SAVE, STREAM>; break;
+    case 2: kern = fcgru_seq_f32_kernel<2, SAVE, STREAM>; break;
+    case 3: kern = fcgru_seq_f32_kernel<3, SAVE, STREAM>; break;
+    case 4: kern = fcgru_seq_f32_kernel<4, SAVE, STREAM>; break;
+    default: return set_err(RGP_EINVAL, "fcgru_seq_f32: batch %d", g->B);
+  }
+  PersistentLaunch guard(s);
+  RGP_TRY(guard.status());
+  kern<<<FCS_MEMBERS, SEQ_NT, 0, s>>>(p);
+  RGP_HIP(hipGetLastError());
+  return guard.commit();
+}
+
 template <typename T>
 int forward_impl(rgp_fcgru* g, const float* c3d_input, float* logits, float* probs, hipStream_t s) {
   char* ws = g->ws;
@@ -236,6 +281,16 @@ int forward_impl(rgp_fcgru* g, const float* c3d_input, float* logits, float* pro
       const bool stream_kernel = sc.carry() || (!save && n_valid < T_);
       if (stream_kernel) RGP_TRY(save ? (seq_persistent<true, true>(g, s)) : (seq_persistent<false, true>(g, s)));
       else RGP_TRY(save ? (seq_persistent<true, false>(g, s)) : (seq_persistent<false, false>(g, s)));
+      if (sc.on)
+        RGP_TRY(gru_state_out(save ? d.hall + (size_t)n_valid * st : stream_kernel ? (const float*)(ws + g->hsnap) : d.hall + (size_t)(T_ & 1) * st,
+                              sc.out, lin, d, g->n, s));
+      one_launch = true;
+    }
+  } else {
+    if (g->persistent) {                                   // RGP_FCGRU_PERSISTENT_F32: the same choice of kernel and of state source
+      const bool stream_kernel = sc.carry() || (!save && n_valid < T_);
+      if (stream_kernel) RGP_TRY(save ? (seq_persistent_f32<true, true>(g, s)) : (seq_persistent_f32<false, true>(g, s)));
+      else RGP_TRY(save ? (seq_persistent_f32<true, false>(g, s)) : (seq_persistent_f32<false, false>(g, s)));
       if (sc.on)
         RGP_TRY(gru_state_out(save ? d.hall + (size_t)n_valid * st : stream_kernel ? (const float*)(ws + g->hsnap) : d.hall + (size_t)(T_ & 1) * st,
                               sc.out, lin, d, g->n, s));
@@ -564,10 +619,13 @@ int rgp_fcgru_create_ex(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_
 
 int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_h, int gazemap_w, int dtype, int flags) {
   RGP_REQUIRE(plan && batch > 0 && n_steps > 0, "rgp_fcgru_create: bad arguments");
-  RGP_REQUIRE((flags & ~(RGP_FCGRU_SAVE_FOR_BACKWARD | RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT | RGP_FCGRU_BPTT_PERSISTENT)) == 0,
+  RGP_REQUIRE((flags & ~(RGP_FCGRU_SAVE_FOR_BACKWARD | RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT | RGP_FCGRU_BPTT_PERSISTENT |
+                         RGP_FCGRU_PERSISTENT_F32)) == 0,
               "rgp_fcgru_create: unknown flags 0x%x", flags);
   RGP_REQUIRE((flags & (RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT)) != (RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT),
               "rgp_fcgru_create: flags name both recurrence paths");
+  RGP_REQUIRE(!(flags & RGP_FCGRU_PERSISTENT_F32) || !(flags & (RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT)),
+              "rgp_fcgru_create: flags name both recurrence paths (RGP_FCGRU_PERSISTENT_F32 with another path flag)");
   RGP_REQUIRE((gazemap_h == 49 && gazemap_w == 49) || (gazemap_h == 7 && gazemap_w == 7),
               "rgp_fcgru_create: gaze map %dx%d (reference uses 49x49 or 7x7)", gazemap_h, gazemap_w);
   RGP_REQUIRE(dtype == RGP_F32 || dtype == RGP_BF16, "rgp_fcgru_create: dtype %d", dtype);
@@ -598,6 +656,18 @@ int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazem
     RGP_REQUIRE(n_cu >= FCS_MEMBERS, "rgp_fcgru_create: the persistent kernel (flags) needs %d CUs resident together, the device has %d",
                 FCS_MEMBERS, n_cu);
   }
+  if (flags & RGP_FCGRU_PERSISTENT_F32) {
+    // the arguments first (no device needed to refuse them), then the device
+    RGP_REQUIRE(dtype == RGP_F32, "rgp_fcgru_create: the persistent f32 kernel (flags) takes f32 plans, dtype is %d", dtype);
+    RGP_REQUIRE(batch <= 64, "rgp_fcgru_create: the persistent f32 kernel (flags) takes at most 64 clips, batch is %d", batch);
+    // 32-bit byte offsets into the fp32 exchange rows, those of the up to 64 rows of the last row fragment included:
+    // 64 * T * np * 4 bytes must stay below 2^32 (T <= 10081), rounded down as the bf16 kernel's limit is
+    RGP_REQUIRE(n_steps <= 8192, "rgp_fcgru_create: the persistent f32 kernel (flags) takes at most 8192 steps, n_steps is %d", n_steps);
+    int n_cu = 0;
+    RGP_TRY(device_cu_count(&n_cu));
+    RGP_REQUIRE(n_cu >= FCS_MEMBERS, "rgp_fcgru_create: the persistent f32 kernel (flags) needs %d CUs resident together, the device has %d",
+                FCS_MEMBERS, n_cu);
+  }
   if (flags & RGP_FCGRU_BPTT_PERSISTENT) {
     int n_cu = 0;
     RGP_TRY(device_cu_count(&n_cu));
@@ -607,7 +677,7 @@ int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazem
   rgp_fcgru* g = new rgp_fcgru();
   g->B = batch; g->T = n_steps; g->F = batch * n_steps; g->G = gazemap_h * gazemap_w; g->dtype = dtype;
   g->save = (flags & RGP_FCGRU_SAVE_FOR_BACKWARD) != 0;
-  g->persistent = (flags & RGP_FCGRU_PERSISTENT) != 0;                       // (neither flag: the library's choice is per step)
+  g->persistent = (flags & (RGP_FCGRU_PERSISTENT | RGP_FCGRU_PERSISTENT_F32)) != 0;   // (no path flag: the library's choice is per step)
   g->bptt_persistent = (flags & RGP_FCGRU_BPTT_PERSISTENT) != 0;             // (independent of the forward's path)
   g->Gp = (int)align_up(g->G, 128);
   g->Kx = (int)align_up(g->nx, 64);

@@ -706,8 +706,9 @@ class FcGruEngine(object):
     """fc-GRU gaze model (models/gaze_rnn.py:211-360, BASELINE config 2) at fixed (B, T, GH, GW).
 
     per_step=True names the per-timestep recurrence (RGP_FCGRU_PER_STEP: two launches per step), persistent=True the
-    one-launch recurrence with resident kernels (RGP_FCGRU_PERSISTENT, csrc/fcgru_seq.hip.h: bf16 plans of at most 64
-    clips on a device with at least 203 CUs, refused otherwise); with both False the library chooses (per step).
+    one-launch recurrence with resident kernels: RGP_FCGRU_PERSISTENT for bf16 plans (csrc/fcgru_seq.hip.h),
+    RGP_FCGRU_PERSISTENT_F32 for f32 plans (csrc/fcgru_seq_f32.hip.h: fp32 MFMAs on the plan's fp32 rows); plans of at
+    most 64 clips on a device with at least 203 CUs, refused otherwise.  With both False the library chooses (per step).
     bptt_persistent=True: the backward-through-time pass of backward() as one persistent launch as well
     (RGP_FCGRU_BPTT_PERSISTENT, csrc/fcgru_bptt.hip.h; bf16 training plans of at most 64 clips), whatever the forward runs;
     False is the library's choice (four launches per step).
@@ -731,7 +732,8 @@ class FcGruEngine(object):
         self.flat_params = self.flat_grads = self.grads = self.adam_m = self.adam_v = None
         self._h = ctypes.c_void_p()
         flags = (_lib.RGP_FCGRU_SAVE_FOR_BACKWARD if save_for_backward else 0) | (_lib.RGP_FCGRU_PER_STEP if per_step else 0) | \
-            (_lib.RGP_FCGRU_PERSISTENT if persistent else 0) | (_lib.RGP_FCGRU_BPTT_PERSISTENT if bptt_persistent else 0)
+            ((_lib.RGP_FCGRU_PERSISTENT_F32 if dtype == 'f32' else _lib.RGP_FCGRU_PERSISTENT) if persistent else 0) | \
+            (_lib.RGP_FCGRU_BPTT_PERSISTENT if bptt_persistent else 0)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.rgp_fcgru_create_flags(ctypes.byref(self._h), self.B, self.T, self.GH, self.GW,
                                                        _lib.DTYPES[dtype], flags))

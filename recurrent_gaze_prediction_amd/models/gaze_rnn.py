@@ -43,7 +43,8 @@ class GRUModelConfig(BaseModelConfig):
         self.flip_seed = None          # None: derived from init_seed and the rank (recorded in the log / checkpoint)
         self.train_keep_prob = 0.5     # keep_prob single_step feeds when training (gaze_rnn.py:529)
         # recurrence path of the fc-GRU engine: None (the library's choice: per step), 'per_step' or 'persistent' (all T
-        # steps in one launch, csrc/fcgru_seq.hip.h: bf16, at most 64 clips; gaze_rnn77 inherits it)
+        # steps in one launch: csrc/fcgru_seq.hip.h for compute_dtype 'bf16', csrc/fcgru_seq_f32.hip.h for 'f32'; at most 64
+        # clips; gaze_rnn77 inherits it)
         self.fcgru_path = None
         # BPTT path of the same engine: None (the library's choice: per step), 'per_step' or 'persistent' (the backward-through-
         # time pass in one launch, csrc/fcgru_bptt.hip.h: bf16 training plans of at most 64 clips), whatever fcgru_path says

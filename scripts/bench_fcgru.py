@@ -17,6 +17,10 @@ again behind one forward: it reads what the forward kept) and the training step.
 on 7x7 plans of 8 and 64 clips behind the per-step forward: the difference over 16 is what one more step costs each BPTT path.
 Writes profiles/fcgru_bptt_bench.json unless --out names another file.  --train-only (with a build that has no `persistent`
 argument too): the training step of per-step plans alone, for build-to-build A/Bs of the default path.
+--dtype f32: the same protocol on f32 plans, the f32 persistent recurrence (RGP_FCGRU_PERSISTENT_F32, csrc/fcgru_seq_f32.hip.h)
+against the per-step f32 path; then the inference forward at T = 16 and T = 32 on 7x7 plans of 8 and 64 clips: the difference
+over 16 is what one more step costs each path.  Writes profiles/fcgru_f32_bench.json unless --out names another file.
+--per-step-only: the per-step path alone, whatever the build offers (build-to-build A/Bs of the default path in either dtype).
 Writes one JSON document (--out) and prints it.
 """
 import argparse
@@ -143,10 +147,14 @@ def main():
     ap.add_argument('--forward-only', action='store_true')
     ap.add_argument('--train-only', action='store_true', help='the training step of per-step plans alone (build-to-build A/Bs)')
     ap.add_argument('--bptt', action='store_true', help='per-step against persistent BPTT, behind both forwards')
+    ap.add_argument('--dtype', default='bf16', choices=('bf16', 'f32'), help='operand dtype of the plans (not with --bptt)')
+    ap.add_argument('--per-step-only', action='store_true', help='the per-step path alone (build-to-build A/Bs)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    if a.bptt and a.dtype != 'bf16':
+        raise SystemExit('bench_fcgru.py --bptt: the persistent BPTT takes bf16 plans only')
     if a.out is None:
-        a.out = os.path.join('profiles', 'fcgru_bptt_bench.json' if a.bptt else 'fcgru_bench.json')
+        a.out = os.path.join('profiles', 'fcgru_bptt_bench.json' if a.bptt else 'fcgru_f32_bench.json' if a.dtype == 'f32' else 'fcgru_bench.json')
 
     import inspect
     import torch
@@ -157,7 +165,7 @@ def main():
     dev = torch.device('cuda:0')
     sync = torch.cuda.synchronize
     has_paths = 'persistent' in inspect.signature(FcGruEngine.__init__).parameters
-    paths = ('per_step', 'persistent') if has_paths and not a.train_only else ('per_step',)
+    paths = ('per_step', 'persistent') if has_paths and not a.train_only and not a.per_step_only else ('per_step',)
     if a.bptt:
         result = bptt_mode(a, torch, syn, FcGruEngine, dev, sync)
         text = json.dumps(result, indent=1, sort_keys=True)
@@ -169,12 +177,12 @@ def main():
 
     def make(B, T, GH, path, train):
         kw = {path: True} if has_paths else {}
-        eng = FcGruEngine(B, T, (GH, GH), dtype='bf16', device=dev, save_for_backward=train, **kw)
+        eng = FcGruEngine(B, T, (GH, GH), dtype=a.dtype, device=dev, save_for_backward=train, **kw)
         eng.set_weights(syn.fcgru_params(0, GH, GH))
         assert not has_paths or eng.persistent == (path == 'persistent')
         return eng
 
-    result = {'device': torch.cuda.get_device_name(0), 'calls_per_window': a.calls, 'windows': a.windows, 'dtype': 'bf16',
+    result = {'device': torch.cuda.get_device_name(0), 'calls_per_window': a.calls, 'windows': a.windows, 'dtype': a.dtype,
               'method': 'host clock around windows of calls between device synchronisations; paths alternate; median window / calls',
               'forward_only': bool(a.forward_only), 'paths': list(paths), 'shapes': {}}
     for B, T, GH in SHAPES:
@@ -221,8 +229,30 @@ def main():
             engs['persistent'].status()
             compare(entry['train_step'], 'persistent', 'per_step')
         del engs
-    if has_paths and not a.train_only:
-        result['default_of_eligible_plans'] = 'persistent' if FcGruEngine(2, 2, (7, 7), dtype='bf16', device=dev).persistent else 'per_step'
+    if a.dtype == 'f32' and 'persistent' in paths and not a.train_only:
+        # what one more step costs the forward: T = 16 against T = 32, 7x7 inference plans
+        result['per_step_of_T'] = {}
+        for B in (8, 64):
+            med = {}
+            for T in (16, 32):
+                x = torch.tensor(syn.c3d_features(1, B, T), device=dev)
+                engs = {p: make(B, T, 7, p, False) for p in paths}
+                for e in engs.values():
+                    for _ in range(3):
+                        e.forward(x)
+                sync()
+                ms = {p: [] for p in paths}
+                for _ in range(a.windows):
+                    for p in paths:
+                        ms[p].append(window(lambda: engs[p].forward(x), a.calls, sync))
+                engs['persistent'].status()
+                med[T] = {p: summarise(v) for p, v in ms.items()}
+                del engs
+            result['per_step_of_T'][str(B)] = {
+                'forward_T16': med[16], 'forward_T32': med[32],
+                'us_per_step': {p: (med[32][p]['ms_median'] - med[16][p]['ms_median']) * 1e3 / 16 for p in paths}}
+    if has_paths and not a.train_only and not a.per_step_only:
+        result['default_of_eligible_plans'] = 'persistent' if FcGruEngine(2, 2, (7, 7), dtype=a.dtype, device=dev).persistent else 'per_step'
     text = json.dumps(result, indent=1, sort_keys=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, 'w') as fp:

@@ -15,6 +15,12 @@ registers: 2 - 3 loads in flight instead of the >= 8 the hand-off needs), and no
 The persistent fc-GRU BPTT kernel (fcgru_bptt.hip.h), four instantiations <NF>: the same rule for each fcs_gemm call of its
 step body -- GEMM C, the u half and the r half of GEMM ZR: three runs of exactly 13 x NF loads in front of 13 x NF MFMAs (no
 phase of any instantiation issues its loads in two runs), and no scratch access.
+The f32 persistent fc-GRU kernel (fcgru_seq_f32.hip.h), sixteen instantiations <NF, SAVE, STREAM>: a fragment's A operands are
+26 sixteen-byte exchange loads and 104 MFMAs (v_mfma_f32_16x16x4_f32), and only two fragments' loads fit the register file, so
+each phase issues its loads in GROUPS: fragments 0 and 1 (26 min(NF, 2) loads) in front of the first MFMA, then 26 loads of
+fragment f + 2 behind the 104 MFMAs of fragment f.  Each group must stand in front of the MFMAs that consume it: the runs of a
+phase are exactly [L 26 min(NF, 2), M 104] + [L 26, M 104] x (NF - 3) + [L 26, M 208] (NF <= 2: [L 26 NF, M 104 NF]), twice per
+kernel, every exchange load 16 bytes wide, and no scratch access.
 """
 import os, subprocess, sys, tempfile
 
@@ -126,6 +132,44 @@ def fcgru_faults(name, body):
     return faults
 
 
+def fcgru_f32_kernels(asm):
+    lines = asm.split('\n')
+    for st, l in enumerate(lines):
+        if l.startswith('_ZN3rgpL20fcgru_seq_f32_kernel') and '@' in l:
+            end = next(i for i in range(st, len(lines)) if 's_endpgm' in lines[i])
+            yield l.split(':')[0], lines[st:end]
+
+
+def fcgru_f32_expected(nf):
+    """Runs of one phase: the ring of two fragment buffers of fcs32_gemm."""
+    if nf <= 2:
+        return [['L', 26 * nf], ['M', 104 * nf]]
+    runs = [['L', 52], ['M', 104]]
+    for f in range(1, nf - 1):                          # behind fragment f - 1: the loads of fragment f + 1
+        runs += [['L', 26], ['M', 104 if f < nf - 2 else 208]]
+    return runs
+
+
+def fcgru_f32_faults(name, body):
+    """Runs of sc1 exchange loads and of MFMAs in program order against fcgru_f32_expected, twice (phase A, phase B)."""
+    nf = int(name.split('fcgru_seq_f32_kernelILi')[1][0])
+    runs = []
+    faults = []
+    for l in body:
+        k = 'L' if ('buffer_load_dwordx4' in l and 'sc1' in l) else 'M' if 'v_mfma_f32_16x16x4_f32' in l else None
+        if k is None and 'buffer_load' in l and 'sc1' in l:
+            faults.append('exchange load narrower than 16 bytes: ' + l.strip())
+        if k and runs and runs[-1][0] == k:
+            runs[-1][1] += 1
+        elif k:
+            runs.append([k, 1])
+    if runs != fcgru_f32_expected(nf) * 2:
+        faults.append('load groups not in front of their MFMAs: ' + ' '.join('%s%d' % (k, n) for k, n in runs))
+    if any('scratch_' in l for l in body):
+        faults.append('scratch access')
+    return faults[:3]
+
+
 def fcgru_bptt_kernels(asm):
     lines = asm.split('\n')
     for st, l in enumerate(lines):
@@ -182,6 +226,15 @@ def main():
             print('FCGRU_BPTT', name[:100], faults)
     print('rgp_fcgru.hip: %d fcgru_bptt kernels, %d with exchange loads not in front of their MFMAs, or spills' % (n, nbad))
     rc |= nbad > 0 or n != 4
+    n = nbad = 0
+    for name, body in fcgru_f32_kernels(asm):
+        n += 1
+        faults = fcgru_f32_faults(name, body)
+        if faults:
+            nbad += 1
+            print('FCGRU_SEQ_F32', name[:100], faults)
+    print('rgp_fcgru.hip: %d fcgru_seq_f32 kernels, %d with a load group not in front of its MFMAs, narrow loads or spills' % (n, nbad))
+    rc |= nbad > 0 or n != 16
     with tempfile.NamedTemporaryFile(suffix='.s') as tf:
         subprocess.run(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-I' + os.path.join(ROOT, 'include'),
                         '-I' + CSRC, '-S', '--cuda-device-only', '-o', tf.name, os.path.join(CSRC, 'rgp_conv_patch.hip')], check=True,
