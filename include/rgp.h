@@ -331,7 +331,17 @@ int rgp_fcgru_set_dropout(rgp_fcgru_t* plan, float keep_prob, const unsigned cha
  *                                batch > 64, together with RGP_FCGRU_PER_STEP or RGP_FCGRU_PERSISTENT, n_steps > 8192
  *                                (64 * n_steps * 1664 * 4 bytes of exchange rows are addressed with 32-bit offsets) -- these
  *                                need no device -- and a device with fewer than 203 CUs.  The backward behind it is the
- *                                per-step one (RGP_FCGRU_BPTT_PERSISTENT stays bf16 only).
+ *                                per-step one unless RGP_FCGRU_BPTT_PERSISTENT_F32 is set (RGP_FCGRU_BPTT_PERSISTENT stays
+ *                                bf16 only).
+ *   RGP_FCGRU_BPTT_PERSISTENT_F32  RGP_FCGRU_BPTT_PERSISTENT for f32 plans: the backward-through-time pass in ONE persistent
+ *                                launch with the transposed fp32 h-side kernels resident in registers and LDS and fp32
+ *                                MFMAs on the plan's own fp32 gate-gradient rows (csrc/fcgru_bptt_f32.hip.h), whatever path
+ *                                the forward takes.  A flag of its own because RGP_FCGRU_BPTT_PERSISTENT keeps refusing f32
+ *                                plans.  Refused with RGP_EINVAL, the reason in rgp_last_error(): without
+ *                                RGP_FCGRU_SAVE_FOR_BACKWARD, plans that are not f32, batch > 64, together with
+ *                                RGP_FCGRU_BPTT_PERSISTENT, (batch16 * n_steps + 1) * 3 * 1664 * 4 bytes (batch16 = batch
+ *                                rounded up to a multiple of 16) not below 2^32 (batch 64: n_steps <= 3360) -- these need
+ *                                no device -- and a device with fewer than 203 CUs.
  * With no path flag the library's choice is per step.  Unknown bits and two path flags together are RGP_EINVAL.  All
  * paths fill the same buffers in the same layouts: rgp_fcgru_backward runs behind any of them. */
 #define RGP_FCGRU_SAVE_FOR_BACKWARD 1
@@ -339,10 +349,12 @@ int rgp_fcgru_set_dropout(rgp_fcgru_t* plan, float keep_prob, const unsigned cha
 #define RGP_FCGRU_PERSISTENT 4
 #define RGP_FCGRU_BPTT_PERSISTENT 8
 #define RGP_FCGRU_PERSISTENT_F32 16
+#define RGP_FCGRU_BPTT_PERSISTENT_F32 32
 int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_h, int gazemap_w, int dtype, int flags);
 /* Workgroups (= CUs) a persistent recurrence launch of this plan occupies; 0: the plan runs per-step launches. */
 int rgp_fcgru_persistent_workgroups(const rgp_fcgru_t* plan);
-/* The same for the persistent BPTT launch of rgp_fcgru_backward: 203, or 0 (plans without RGP_FCGRU_BPTT_PERSISTENT). */
+/* The same for the persistent BPTT launch of rgp_fcgru_backward: 203, or 0 (plans without RGP_FCGRU_BPTT_PERSISTENT
+ * or RGP_FCGRU_BPTT_PERSISTENT_F32). */
 int rgp_fcgru_bptt_persistent_workgroups(const rgp_fcgru_t* plan);
 /* Time-out of the persistent launch, as for the other recurrent families: all its workgroups must be resident together
  * (keep ONE such launch in flight per device).  A launch that waits about a second for a missing member stops waiting,

@@ -24,6 +24,7 @@ RGP_LSTM_SAVE_FOR_BACKWARD, RGP_LSTM_PER_STEP, RGP_LSTM_PERSISTENT, RGP_LSTM_BPT
 RGP_GRCN77_SAVE_FOR_BACKWARD, RGP_GRCN77_PER_STEP = 1, 2
 RGP_FCGRU_SAVE_FOR_BACKWARD, RGP_FCGRU_PER_STEP, RGP_FCGRU_PERSISTENT, RGP_FCGRU_BPTT_PERSISTENT = 1, 2, 4, 8
 RGP_FCGRU_PERSISTENT_F32 = 16       # the persistent recurrence of f32 plans (csrc/fcgru_seq_f32.hip.h)
+RGP_FCGRU_BPTT_PERSISTENT_F32 = 32  # the persistent BPTT of f32 plans (csrc/fcgru_bptt_f32.hip.h)
 RGP_FAULT_SEQ_LOST_MEMBER, RGP_FAULT_BPTT_LOST_MEMBER = 1, 2
 RGP_ACTION_NN, RGP_ACTION_SVM = 0, 1
 RGP_ACTION_USE_GAZEMAP, RGP_ACTION_SAVE_FOR_BACKWARD, RGP_ACTION_UNFUSED = 1, 2, 4

@@ -18,7 +18,8 @@
 // All write the same buffers in the same layouts, so the backward runs unchanged behind any of them.
 // BPTT, two implementations as well: per step (every plan; the library's choice: four launches per timestep), and --
 // RGP_FCGRU_BPTT_PERSISTENT, bf16 training plans of at most 64 clips -- all T steps in one persistent launch with the
-// TRANSPOSED h-side kernels resident in registers (fcgru_bptt.hip.h), whatever the forward ran.  Both leave dxpre and the final
+// TRANSPOSED h-side kernels resident in registers (fcgru_bptt.hip.h), whatever the forward ran; RGP_FCGRU_BPTT_PERSISTENT_F32
+// is the same for f32 training plans (fcgru_bptt_f32.hip.h: fp32 MFMAs on the plan's fp32 dxpre rows).  All leave dxpre and the final
 // carry in the same buffers, so the hoisted filter gradients and the projection's input gradient run unchanged behind either.
 // Streaming (rgp_fcgru_forward_stream): the same forward started from a caller's h_{-1} [B][1617] instead of zeros, on either
 // path and on inference and training plans.  Way in: gru_seed_or_zero (gru_steps.h), one launch in place of the two memsets.
@@ -32,6 +33,7 @@
 #include "fcgru_seq.hip.h"
 #include "fcgru_seq_f32.hip.h"
 #include "fcgru_bptt.hip.h"
+#include "fcgru_bptt_f32.hip.h"
 
 using namespace rgp;
 
@@ -66,7 +68,7 @@ struct rgp_fcgru {
   PinnedErrWord err;                                  // set by a launch that lost a member (allocated at bind, persistent plans only)
   size_t hsnap = 0;                                   // fp32 [B][np]: h behind step n_valid of a streaming launch (persistent inference plans)
   StreamCall stream;                                  // rgp_fcgru_forward_stream: the state is [B][n] dense; slot 0 = slot (b, 0) of hp_all
-  // ---- persistent BPTT (RGP_FCGRU_BPTT_PERSISTENT)
+  // ---- persistent BPTT (RGP_FCGRU_BPTT_PERSISTENT on bf16 plans, RGP_FCGRU_BPTT_PERSISTENT_F32 on f32 plans)
   bool bptt_persistent = false, bwd_done = false;
   size_t bptt_cnt = 0;                                // [2 T][FCS_SHARDS][FCS_CNT_STRIDE] phase counters of fcgru_bptt_kernel
 };
@@ -468,6 +470,40 @@ int bptt_persistent_launch(rgp_fcgru* g, hipStream_t s) {
   return guard.commit();
 }
 
+// The same for f32 plans (RGP_FCGRU_BPTT_PERSISTENT_F32, fcgru_bptt_f32.hip.h): the exchange rows are the plan's fp32 dxpre rows.
+int bptt_persistent_f32_launch(rgp_fcgru* g, hipStream_t s) {
+  char* ws = g->ws;
+  RGP_HIP(hipMemsetAsync(ws + g->bptt_cnt, 0, (size_t)2 * g->T * FCS_SHARDS * FCS_CNT_STRIDE * 4, s));        // phase counters: zeroed EVERY call
+  FcBptt32Params p;
+  p.b_c = (const float*)(ws + g->b_c.w_off);
+  p.b_zr = (const float*)(ws + g->b_zr.w_off);
+  p.dh_head = (const float*)(ws + g->dh_head);
+  p.hall = (const float*)(ws + g->hall_t);
+  p.uall = (const float*)(ws + g->uall);
+  p.rall = (const float*)(ws + g->rall);
+  p.call = (const float*)(ws + g->call);
+  p.dxpre = (float*)(ws + g->dxpre);
+  p.carry = (float*)(ws + g->carry);
+  p.cnt = (unsigned*)(ws + g->bptt_cnt);
+  p.err = g->err.host;
+  p.B = g->B; p.T = g->T;
+  RGP_REQUIRE(g->np == FCS_NP && g->b_c.K == FCS_NP && g->b_zr.K == 2 * FCS_NP && g->b_c.chunk_major == 0 && g->b_zr.chunk_major == 0,
+              "fcgru_bptt_f32: unexpected filter packing");
+  void (*kern)(FcBptt32Params) = nullptr;
+  switch ((g->B + 15) / 16) {
+    case 1: kern = fcgru_bptt_f32_kernel<1>; break;
+    case 2: kern = fcgru_bptt_f32_kernel<2>; break;
+    case 3: kern = fcgru_bptt_f32_kernel<3>; break;
+    case 4: kern = fcgru_bptt_f32_kernel<4>; break;
+    default: return set_err(RGP_EINVAL, "fcgru_bptt_f32: batch %d", g->B);
+  }
+  PersistentLaunch guard(s);
+  RGP_TRY(guard.status());
+  kern<<<FCS_MEMBERS, SEQ_NT, 0, s>>>(p);
+  RGP_HIP(hipGetLastError());
+  return guard.commit();
+}
+
 template <typename T>
 int backward_impl(rgp_fcgru* g, const float* logits, const float* probs, const float* labels, const rgp_fcgru_weights* gr,
                   int loss_l2, hipStream_t s) {
@@ -502,12 +538,17 @@ int backward_impl(rgp_fcgru* g, const float* logits, const float* probs, const f
     EpiParams e = make_epi(g->b_out, Fp(g->dh_head), ws);
     RGP_TRY((launch_igemm<T, 1, 1, EpiStore<float, false, false>>(p, e, s)));
   }
-  // 2. BPTT: one persistent launch (RGP_FCGRU_BPTT_PERSISTENT), or four launches per step
+  // 2. BPTT: one persistent launch (RGP_FCGRU_BPTT_PERSISTENT / RGP_FCGRU_BPTT_PERSISTENT_F32), or four launches per step
   const float* hall = Fp(g->hall_t);
   bool one_launch = false;
   if constexpr (sizeof(T) == 2) {
     if (g->bptt_persistent) {
       RGP_TRY(bptt_persistent_launch(g, s));
+      one_launch = true;
+    }
+  } else {
+    if (g->bptt_persistent) {
+      RGP_TRY(bptt_persistent_f32_launch(g, s));
       one_launch = true;
     }
   }
@@ -620,7 +661,7 @@ int rgp_fcgru_create_ex(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_
 int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazemap_h, int gazemap_w, int dtype, int flags) {
   RGP_REQUIRE(plan && batch > 0 && n_steps > 0, "rgp_fcgru_create: bad arguments");
   RGP_REQUIRE((flags & ~(RGP_FCGRU_SAVE_FOR_BACKWARD | RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT | RGP_FCGRU_BPTT_PERSISTENT |
-                         RGP_FCGRU_PERSISTENT_F32)) == 0,
+                         RGP_FCGRU_PERSISTENT_F32 | RGP_FCGRU_BPTT_PERSISTENT_F32)) == 0,
               "rgp_fcgru_create: unknown flags 0x%x", flags);
   RGP_REQUIRE((flags & (RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT)) != (RGP_FCGRU_PER_STEP | RGP_FCGRU_PERSISTENT),
               "rgp_fcgru_create: flags name both recurrence paths");
@@ -629,6 +670,20 @@ int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazem
   RGP_REQUIRE((gazemap_h == 49 && gazemap_w == 49) || (gazemap_h == 7 && gazemap_w == 7),
               "rgp_fcgru_create: gaze map %dx%d (reference uses 49x49 or 7x7)", gazemap_h, gazemap_w);
   RGP_REQUIRE(dtype == RGP_F32 || dtype == RGP_BF16, "rgp_fcgru_create: dtype %d", dtype);
+  if (flags & RGP_FCGRU_BPTT_PERSISTENT_F32) {
+    // the arguments (no device needed to refuse them); the device is asked below
+    RGP_REQUIRE(!(flags & RGP_FCGRU_BPTT_PERSISTENT),
+                "rgp_fcgru_create: flags name both persistent BPTT kernels (RGP_FCGRU_BPTT_PERSISTENT_F32 with RGP_FCGRU_BPTT_PERSISTENT)");
+    RGP_REQUIRE(flags & RGP_FCGRU_SAVE_FOR_BACKWARD, "rgp_fcgru_create: the persistent f32 BPTT kernel (flags) needs RGP_FCGRU_SAVE_FOR_BACKWARD");
+    RGP_REQUIRE(dtype == RGP_F32, "rgp_fcgru_create: the persistent f32 BPTT kernel (flags) takes f32 plans, dtype is %d", dtype);
+    RGP_REQUIRE(batch <= 64, "rgp_fcgru_create: the persistent f32 BPTT kernel (flags) takes at most 64 clips, batch is %d", batch);
+    // the kernel addresses the fp32 dxpre rows with 32-bit byte offsets, those of the rows >= B of the last 16-row fragment
+    // included (they have to land BEHIND the buffer to read zeros, not wrap): (B16 T + 1) rows of 3 * 1664 * 4 bytes must
+    // stay below 2^32 (B = 64: T <= 3360)
+    RGP_REQUIRE(((long long)((batch + 15) / 16 * 16) * n_steps + 1) * (long long)FCB32_ROW < (1LL << 32),
+                "rgp_fcgru_create: the persistent f32 BPTT kernel (flags) addresses (batch16 * n_steps + 1) * %u bytes with 32-bit offsets: "
+                "batch %d (rounded up to 16) x n_steps %d is past 2^32", FCB32_ROW, batch, n_steps);
+  }
   if (flags & RGP_FCGRU_BPTT_PERSISTENT) {
     // the arguments (no device needed to refuse them); the device is asked below, behind the forward's argument checks
     RGP_REQUIRE(flags & RGP_FCGRU_SAVE_FOR_BACKWARD, "rgp_fcgru_create: the persistent BPTT kernel (flags) needs RGP_FCGRU_SAVE_FOR_BACKWARD");
@@ -674,11 +729,17 @@ int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazem
     RGP_REQUIRE(n_cu >= FCS_MEMBERS, "rgp_fcgru_create: the persistent BPTT kernel (flags) needs %d CUs resident together, the device has %d",
                 FCS_MEMBERS, n_cu);
   }
+  if (flags & RGP_FCGRU_BPTT_PERSISTENT_F32) {
+    int n_cu = 0;
+    RGP_TRY(device_cu_count(&n_cu));
+    RGP_REQUIRE(n_cu >= FCS_MEMBERS, "rgp_fcgru_create: the persistent f32 BPTT kernel (flags) needs %d CUs resident together, the device has %d",
+                FCS_MEMBERS, n_cu);
+  }
   rgp_fcgru* g = new rgp_fcgru();
   g->B = batch; g->T = n_steps; g->F = batch * n_steps; g->G = gazemap_h * gazemap_w; g->dtype = dtype;
   g->save = (flags & RGP_FCGRU_SAVE_FOR_BACKWARD) != 0;
   g->persistent = (flags & (RGP_FCGRU_PERSISTENT | RGP_FCGRU_PERSISTENT_F32)) != 0;   // (no path flag: the library's choice is per step)
-  g->bptt_persistent = (flags & RGP_FCGRU_BPTT_PERSISTENT) != 0;             // (independent of the forward's path)
+  g->bptt_persistent = (flags & (RGP_FCGRU_BPTT_PERSISTENT | RGP_FCGRU_BPTT_PERSISTENT_F32)) != 0;   // (independent of the forward's path)
   g->Gp = (int)align_up(g->G, 128);
   g->Kx = (int)align_up(g->nx, 64);
   g->np = (int)align_up(g->n, 64);

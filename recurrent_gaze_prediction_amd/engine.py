@@ -711,7 +711,10 @@ class FcGruEngine(object):
     most 64 clips on a device with at least 203 CUs, refused otherwise.  With both False the library chooses (per step).
     bptt_persistent=True: the backward-through-time pass of backward() as one persistent launch as well
     (RGP_FCGRU_BPTT_PERSISTENT, csrc/fcgru_bptt.hip.h; bf16 training plans of at most 64 clips), whatever the forward runs;
-    False is the library's choice (four launches per step).
+    False is the library's choice (four launches per step).  On an f32 plan that keyword is refused by the library;
+    bptt_persistent_f32=True is the same pass for f32 training plans (RGP_FCGRU_BPTT_PERSISTENT_F32,
+    csrc/fcgru_bptt_f32.hip.h: fp32 MFMAs on the plan's fp32 gate-gradient rows; at most 64 clips), behind any forward path.
+    The bptt_persistent / bptt_persistent_workgroups properties report either.
     read_buffer (training plans, after a forward; fp32): 'xpre' [B,T,3,1617], 'h' [T+1,B,1617], 'u', 'r', 'c'
     [T,B,1617], 'hp' [B,T+1,1617], 'rh' [B,T,1617]; after a backward also 'dxpre' [B,T,3,1617] (the gate-gradient operand
     rows, parts u, r, c), 'dh_head' [B,T,1617] and 'dh0' [B,1617] (the final carry)."""
@@ -722,7 +725,7 @@ class FcGruEngine(object):
                      'dh0': lambda B, T: (B, 1617)}
 
     def __init__(self, batch, n_steps, gazemap_hw=(49, 49), dtype='f32', device='cuda:0', save_for_backward=False,
-                 per_step=False, persistent=False, bptt_persistent=False):
+                 per_step=False, persistent=False, bptt_persistent=False, bptt_persistent_f32=False):
         self.lib = _lib.load()
         self.device = _require_gpu(device)
         self.B, self.T, self.GH, self.GW = int(batch), int(n_steps), int(gazemap_hw[0]), int(gazemap_hw[1])
@@ -733,7 +736,8 @@ class FcGruEngine(object):
         self._h = ctypes.c_void_p()
         flags = (_lib.RGP_FCGRU_SAVE_FOR_BACKWARD if save_for_backward else 0) | (_lib.RGP_FCGRU_PER_STEP if per_step else 0) | \
             ((_lib.RGP_FCGRU_PERSISTENT_F32 if dtype == 'f32' else _lib.RGP_FCGRU_PERSISTENT) if persistent else 0) | \
-            (_lib.RGP_FCGRU_BPTT_PERSISTENT if bptt_persistent else 0)
+            (_lib.RGP_FCGRU_BPTT_PERSISTENT if bptt_persistent else 0) | \
+            (_lib.RGP_FCGRU_BPTT_PERSISTENT_F32 if bptt_persistent_f32 else 0)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.rgp_fcgru_create_flags(ctypes.byref(self._h), self.B, self.T, self.GH, self.GW,
                                                        _lib.DTYPES[dtype], flags))

@@ -47,7 +47,8 @@ class GRUModelConfig(BaseModelConfig):
         # clips; gaze_rnn77 inherits it)
         self.fcgru_path = None
         # BPTT path of the same engine: None (the library's choice: per step), 'per_step' or 'persistent' (the backward-through-
-        # time pass in one launch, csrc/fcgru_bptt.hip.h: bf16 training plans of at most 64 clips), whatever fcgru_path says
+        # time pass in one launch: csrc/fcgru_bptt.hip.h for compute_dtype 'bf16', csrc/fcgru_bptt_f32.hip.h for 'f32'; training
+        # plans of at most 64 clips), whatever fcgru_path says
         self.fcgru_bptt_path = None
 
 
@@ -142,7 +143,9 @@ class GazePredictionGRU(ModelBase):
         assert path in (None, 'persistent', 'per_step'), path
         bptt_path = getattr(model.config, 'fcgru_bptt_path', None)
         assert bptt_path in (None, 'persistent', 'per_step'), bptt_path
-        kw = {'bptt_persistent': True} if bptt_path == 'persistent' else {}          # (named only when asked for)
+        # (named only when asked for; f32 plans have a keyword of their own: bptt_persistent stays refused for them)
+        f32 = getattr(model.config, 'compute_dtype', 'f32') == 'f32'
+        kw = {'bptt_persistent_f32' if f32 else 'bptt_persistent': True} if bptt_path == 'persistent' else {}
         engine = model._new_fcgru_engine(model.batch_size, model.n_lstm_steps, (model.gazemap_height, model.gazemap_width),
                                          dtype=getattr(model.config, 'compute_dtype', 'f32'), device=model.session.device,
                                          save_for_backward=getattr(model.config, 'trainable', True),

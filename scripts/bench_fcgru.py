@@ -20,6 +20,9 @@ argument too): the training step of per-step plans alone, for build-to-build A/B
 --dtype f32: the same protocol on f32 plans, the f32 persistent recurrence (RGP_FCGRU_PERSISTENT_F32, csrc/fcgru_seq_f32.hip.h)
 against the per-step f32 path; then the inference forward at T = 16 and T = 32 on 7x7 plans of 8 and 64 clips: the difference
 over 16 is what one more step costs each path.  Writes profiles/fcgru_f32_bench.json unless --out names another file.
+--dtype f32 --bptt: the --bptt protocol on f32 plans, the f32 persistent BPTT (RGP_FCGRU_BPTT_PERSISTENT_F32,
+csrc/fcgru_bptt_f32.hip.h) against the per-step f32 BPTT behind both f32 forwards.  Writes profiles/fcgru_f32_bptt_bench.json
+unless --out names another file.
 --per-step-only: the per-step path alone, whatever the build offers (build-to-build A/Bs of the default path in either dtype).
 Writes one JSON document (--out) and prints it.
 """
@@ -61,8 +64,8 @@ def bptt_mode(a, torch, syn, FcGruEngine, dev, sync):
     name = lambda c: 'fwd_%s__bptt_%s' % c
 
     def make(B, T, GH, fwd, bptt):
-        eng = FcGruEngine(B, T, (GH, GH), dtype='bf16', device=dev, save_for_backward=True, bptt_persistent=bptt == 'persistent',
-                          **{fwd: True})
+        kw = {'bptt_persistent_f32' if a.dtype == 'f32' else 'bptt_persistent': True} if bptt == 'persistent' else {}
+        eng = FcGruEngine(B, T, (GH, GH), dtype=a.dtype, device=dev, save_for_backward=True, **dict(kw, **{fwd: True}))
         eng.set_weights(syn.fcgru_params(0, GH, GH))
         assert eng.persistent == (fwd == 'persistent') and eng.bptt_persistent == (bptt == 'persistent')
         return eng
@@ -94,7 +97,7 @@ def bptt_mode(a, torch, syn, FcGruEngine, dev, sync):
             entry['persistent_bptt_faster__fwd_' + f] = bool(p['ms_max'] < q['ms_min'])            # every window
             entry['persistent_bptt_slower__fwd_' + f] = bool(p['ms_min'] > q['ms_max'])
 
-    result = {'device': torch.cuda.get_device_name(0), 'calls_per_window': a.calls, 'windows': a.windows, 'dtype': 'bf16',
+    result = {'device': torch.cuda.get_device_name(0), 'calls_per_window': a.calls, 'windows': a.windows, 'dtype': a.dtype,
               'method': 'host clock around windows of calls between device synchronisations; plans alternate; median window / calls',
               'plans': [name(c) for c in combos], 'shapes': {}, 'per_step_of_T': {}}
     for B, T, GH in SHAPES:
@@ -136,7 +139,7 @@ def bptt_mode(a, torch, syn, FcGruEngine, dev, sync):
             'backward_T16': med[16], 'backward_T32': med[32],
             'us_per_step': {k: (med[32][k]['ms_median'] - med[16][k]['ms_median']) * 1e3 / 16 for k in ('per_step', 'persistent')}}
     result['default_bptt_of_eligible_plans'] = \
-        'persistent' if FcGruEngine(2, 2, (7, 7), dtype='bf16', device=dev, save_for_backward=True).bptt_persistent else 'per_step'
+        'persistent' if FcGruEngine(2, 2, (7, 7), dtype=a.dtype, device=dev, save_for_backward=True).bptt_persistent else 'per_step'
     return result
 
 
@@ -147,14 +150,12 @@ def main():
     ap.add_argument('--forward-only', action='store_true')
     ap.add_argument('--train-only', action='store_true', help='the training step of per-step plans alone (build-to-build A/Bs)')
     ap.add_argument('--bptt', action='store_true', help='per-step against persistent BPTT, behind both forwards')
-    ap.add_argument('--dtype', default='bf16', choices=('bf16', 'f32'), help='operand dtype of the plans (not with --bptt)')
+    ap.add_argument('--dtype', default='bf16', choices=('bf16', 'f32'), help='operand dtype of the plans')
     ap.add_argument('--per-step-only', action='store_true', help='the per-step path alone (build-to-build A/Bs)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
-    if a.bptt and a.dtype != 'bf16':
-        raise SystemExit('bench_fcgru.py --bptt: the persistent BPTT takes bf16 plans only')
     if a.out is None:
-        a.out = os.path.join('profiles', 'fcgru_bptt_bench.json' if a.bptt else 'fcgru_f32_bench.json' if a.dtype == 'f32' else 'fcgru_bench.json')
+        a.out = os.path.join('profiles', ('fcgru_f32_bptt_bench.json' if a.dtype == 'f32' else 'fcgru_bptt_bench.json') if a.bptt else 'fcgru_f32_bench.json' if a.dtype == 'f32' else 'fcgru_bench.json')
 
     import inspect
     import torch

@@ -21,6 +21,9 @@ each phase issues its loads in GROUPS: fragments 0 and 1 (26 min(NF, 2) loads) i
 fragment f + 2 behind the 104 MFMAs of fragment f.  Each group must stand in front of the MFMAs that consume it: the runs of a
 phase are exactly [L 26 min(NF, 2), M 104] + [L 26, M 104] x (NF - 3) + [L 26, M 208] (NF <= 2: [L 26 NF, M 104 NF]), twice per
 kernel, every exchange load 16 bytes wide, and no scratch access.
+The f32 persistent fc-GRU BPTT kernel (fcgru_bptt_f32.hip.h), four instantiations <NF>: a step is three fcs32_gemm passes --
+GEMM C (b_c from registers), the u half and the r half of GEMM ZR (both from LDS) -- so the runs of the f32 forward's phase are
+expected exactly THREE times per kernel, every exchange load 16 bytes wide, and no scratch access.
 """
 import os, subprocess, sys, tempfile
 
@@ -170,6 +173,36 @@ def fcgru_f32_faults(name, body):
     return faults[:3]
 
 
+def fcgru_bptt_f32_kernels(asm):
+    lines = asm.split('\n')
+    for st, l in enumerate(lines):
+        if l.startswith('_ZN3rgpL21fcgru_bptt_f32_kernel') and '@' in l:
+            end = next(i for i in range(st, len(lines)) if 's_endpgm' in lines[i])
+            yield l.split(':')[0], lines[st:end]
+
+
+def fcgru_bptt_f32_faults(name, body):
+    """As fcgru_f32_faults, for the three fcs32_gemm passes of a BPTT step: the runs of fcgru_f32_expected three times."""
+    nf = int(name.split('fcgru_bptt_f32_kernelILi')[1][0])
+    runs = []
+    faults = []
+    for l in body:
+        k = 'L' if ('buffer_load_dwordx4' in l and 'sc1' in l) else 'M' if 'v_mfma_f32_16x16x4_f32' in l else None
+        if k is None and 'buffer_load' in l and 'sc1' in l:
+            faults.append('exchange load narrower than 16 bytes: ' + l.strip())
+        if k is None and 'v_mfma' in l:
+            faults.append('an MFMA that is not v_mfma_f32_16x16x4_f32: ' + l.strip())
+        if k and runs and runs[-1][0] == k:
+            runs[-1][1] += 1
+        elif k:
+            runs.append([k, 1])
+    if runs != fcgru_f32_expected(nf) * 3:
+        faults.append('load groups not in front of their MFMAs: ' + ' '.join('%s%d' % (k, n) for k, n in runs))
+    if any('scratch_' in l for l in body):
+        faults.append('scratch access')
+    return faults[:3]
+
+
 def fcgru_bptt_kernels(asm):
     lines = asm.split('\n')
     for st, l in enumerate(lines):
@@ -235,6 +268,15 @@ def main():
             print('FCGRU_SEQ_F32', name[:100], faults)
     print('rgp_fcgru.hip: %d fcgru_seq_f32 kernels, %d with a load group not in front of its MFMAs, narrow loads or spills' % (n, nbad))
     rc |= nbad > 0 or n != 16
+    n = nbad = 0
+    for name, body in fcgru_bptt_f32_kernels(asm):
+        n += 1
+        faults = fcgru_bptt_f32_faults(name, body)
+        if faults:
+            nbad += 1
+            print('FCGRU_BPTT_F32', name[:100], faults)
+    print('rgp_fcgru.hip: %d fcgru_bptt_f32 kernels, %d with a load group not in front of its MFMAs, narrow loads or spills' % (n, nbad))
+    rc |= nbad > 0 or n != 4
     with tempfile.NamedTemporaryFile(suffix='.s') as tf:
         subprocess.run(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-I' + os.path.join(ROOT, 'include'),
                         '-I' + CSRC, '-S', '--cuda-device-only', '-o', tf.name, os.path.join(CSRC, 'rgp_conv_patch.hip')], check=True,
