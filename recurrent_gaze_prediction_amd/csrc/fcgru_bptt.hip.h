@@ -3,11 +3,9 @@
 // input-gradient GEMM, fc_bwd2_kernel, the b_zr GEMM), and both GEMMs re-stream the transposed h-side kernels (16.6 MB in
 // bf16) for at most 64 rows; here the transposed kernels never move and only the gradient rows do.
 //
-// Decomposition: fcgru_seq.hip.h's.  Member j (one 256-thread workgroup, 4 waves; 203 members) owns h units
-// k in [8j, 8j + 8); wave kq holds K steps [13 kq, 13 kq + 13); thread b of wave 0 owns clip b and keeps its 8 fp32 `carry`
-// values (d loss / d h_{t-1} as far as it is known) in registers across the whole sequence.  NF = (B + 15) / 16 is a template
-// parameter: no guards in the MFMA loops, rows >= B lie behind the end of dxpre and read zeros (buffer bounds).
-//
+// Decomposition, exchange, rendezvous, padding and time-out are described in fcgru_member.hip.h (the member owns h units
+// k in [8j, 8j + 8); thread b of wave 0 keeps the clip's 8 fp32 `carry` values, d loss / d h_{t-1} as far as it is known).
+// This kernel's own:
 // Resident B fragments, from the packed images set_weights_impl makes for training plans: rows k of g->b_c (Wc_h
 // transposed, K = 1664) and rows k of g->b_zr ([Wu_h | Wr_h] transposed, K = 2 x 1664, u half first) = 3 x 13 fragments
 // = 156 VGPRs per lane (the forward holds 104).  The tiles are 16x16x32 with columns 8..15 multiplying zeros, as the
@@ -19,72 +17,43 @@
 // row are contiguous, in the K order b_zr was packed with.  (dcp and dzr of the workspace are not used by this path.)
 //
 // Per step t = T - 1 .. 0 (the clip's 8-unit slices of dh_head, hall_t[t], uall[t], call[t], rall[t] are loaded one step
-// ahead, under the previous step's phases):
+// ahead, under the previous step's phases, into a second set of registers):
 //   1. local (fc_bwd1_kernel):  dh = dh_head + carry (no carry at t = T - 1); du = dh (h_prev - c), dc = dh (1 - u),
 //      carry = dh u; du_pre = bf16(du u (1 - u)), dc_pre = bf16(dc (1 - c^2)); publish both (16-byte sc1); rendezvous
 //   2. GEMM C:   drh = dc_pre rows . Wc_h^T on the member's units, K quarters summed through LDS; then fc_bwd2_kernel:
 //      carry += drh r, dr_pre = bf16(drh h_prev r (1 - r)); publish; rendezvous
 //   3. GEMM ZR:  carry += [du_pre | dr_pre] rows . [Wu_h | Wr_h]^T, as two fcs_gemm passes (u half, r half), each 13 NF
 //      loads in front of 13 NF MFMAs.  Step t - 1's local math follows without a rendezvous: the carry is member-local.
-// Two rendezvous per step, 2 T counters [2 T][FCS_SHARDS][FCS_CNT_STRIDE] of its own, zeroed ahead of the launch; none behind
-// the last phase.  Step 0 still runs GEMM ZR and stores the final carry (d loss / d h_{-1}, fp32 [B][np]) into g->carry,
-// where the per-step path leaves the same quantity.
-//
-// Shared with the forward: fcs_gemm, fcs_wait_phase, fcs_pack8, seq_ld_sc1 / seq_st_sc1, SEQ_DEADLINE_TICKS and the LDS
-// pitch.  The forward's partial-tile store / sum are lambdas inside fcgru_seq_kernel (that kernel keeps the code it was
-// measured with), so their 8-column forms for this kernel are the two functions below.
+// 2 T counters of its own; none behind the last phase.  Step 0 still runs GEMM ZR and stores the final carry (d loss / d h_{-1},
+// fp32 [B][np]) into g->carry, where the per-step path leaves the same quantity.
 //
 // Registers: 156 resident + 13 NF x 4 in flight; at NF = 4 that is 364 of the 512 a wave of a 4-wave workgroup may use, and
 // all four instantiations compile without scratch (profiles/fcgru_bptt_kernel_resources.txt): every phase issues its
 // 13 NF loads in ONE run at every NF.
-//
-// Time-out: a member whose wait passes the deadline stops waiting and sets the plan's error word; at the end of the launch
-// it NaN-poisons, for all steps and all clips, its 8 units in all three parts of every dxpre row, and its units of g->carry:
-// every filter gradient and dE is then NaN, never finite and wrong.
 #pragma once
 #include "fcgru_seq.hip.h"
 
 namespace rgp {
 
-constexpr unsigned FCB_ROW = 3u * FCS_NP * 2u;       // bytes per dxpre row
-
-struct FcBpttParams {
-  const bf16_t* b_c;         // packed [np][np]: row k = Wc_h[k][:]
-  const bf16_t* b_zr;        // packed [np][2 np]: row k = [Wu_h[k][:] | Wr_h[k][:]]
+// E: the element type of the plan's operand rows (bf16_t here, float in fcgru_bptt_f32.hip.h)
+template <typename E>
+struct FcBpttParamsT {
+  const E* b_c;              // packed [np][np]: row k = Wc_h[k][:]
+  const E* b_zr;             // packed [np][2 np]: row k = [Wu_h[k][:] | Wr_h[k][:]]
   const float* dh_head;      // [B T][np] d loss / d h_t through the read-out
   const float* hall;         // hall_t [T+1][B][np]: slot t = h_{t-1} of step t
   const float* uall;         // [T][B][np]
   const float* rall;
   const float* call;
-  bf16_t* dxpre;             // [B T + 1][3 np], row 0 zero and untouched
+  E* dxpre;                  // [B T + 1][3 np], row 0 zero and untouched
   float* carry;              // [B][np]: the final carry
   unsigned* cnt;             // [2 T][FCS_SHARDS][FCS_CNT_STRIDE] phase counters, zeroed ahead of the launch
   unsigned* err;             // the plan's pinned error word
   int B, T;
 };
 
-// this wave's partial tiles -> LDS [K quarter][row][16 columns]; the sum over the 4 quarters of columns 0..7 of row `row`
 template <int NF>
-__device__ __forceinline__ void fcb_store_partials(char* red, int kq, int fk, int frow, const f32x4 (&acc)[NF]) {
-#pragma unroll
-  for (int f = 0; f < NF; ++f)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) *(float*)(red + ((kq * NF + f) * 16 + fk * 4 + r) * FCS_PITCH + frow * 4) = acc[f][r];
-}
-template <int NF>
-__device__ __forceinline__ void fcb_reduce_row8(const char* red, int row, float (&s)[8]) {
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) v += *(const f32x4*)(red + (q * NF * 16 + row) * FCS_PITCH + c * 16);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s[4 * c + e] = v[e];
-  }
-}
-
-template <int NF>
-static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_kernel(const FcBpttParams p) {
+static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_kernel(const FcBpttParamsT<bf16_t> p) {
   __shared__ __attribute__((aligned(16))) char red[4 * NF * 16 * FCS_PITCH];   // [K quarter][row][16 columns]
   __shared__ int s_timeout;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -122,43 +91,17 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_kernel(const FcBpttP
   const long long coff = (long long)b * np + u0;                            // the clip's slice in a [B][np] slab
   __syncthreads();                                         // flag cleared
 
-  auto rendezvous = [&](int ph) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its write-through stores
-    __syncthreads();
-    unsigned* c = p.cnt + (long long)ph * (FCS_SHARDS * FCS_CNT_STRIDE);
-    if (tid == 0) __hip_atomic_fetch_add(c + (j & (FCS_SHARDS - 1)) * FCS_CNT_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (kq == 0 && !s_timeout) {                           // (a member that timed out once stops waiting)
-      if (!fcs_wait_phase(c, members, lane) && lane == 0) s_timeout = 1;
-    }
-    __syncthreads();
-  };
-  auto load8 = [&](const float* src, float (&v)[8]) {
-    const f32x4 lo = *(const f32x4*)src, hi = *(const f32x4*)(src + 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[i] = lo[i]; v[4 + i] = hi[i]; }
-  };
-  auto store8f = [&](float* dst, const float (&v)[8]) {
-    *(f32x4*)dst = (f32x4){v[0], v[1], v[2], v[3]};
-    *(f32x4*)(dst + 4) = (f32x4){v[4], v[5], v[6], v[7]};
-  };
-  // the clip's slices of step t: dh_head, h_{t-1}, u, c, r
-  struct Slices { float dh[8], h[8], u[8], c[8], r[8]; };
-  auto load_step = [&](int t, Slices& s) {
-    const long long off = (long long)t * st + coff;
-    load8(p.dh_head + ((long long)b * T_ + t) * np + u0, s.dh);
-    load8(p.hall + off, s.h);
-    load8(p.uall + off, s.u);
-    load8(p.call + off, s.c);
-    load8(p.rall + off, s.r);
-  };
-  // the byte offset of part `part` (0 du_pre, 1 dr_pre, 2 dc_pre) of this thread's clip row / this lane's fragment row
+  const FcRendezvous rendezvous{p.cnt, tid, j, kq, s_timeout, members, lane};
+  // (lambdas that capture the coordinates by reference, as this kernel always had: with the shared functions called directly,
+  // or own_off made one of them, the kernel compiles to other code than the one that was measured)
+  auto load_step = [&](int t, FcbSlices& s) { fcb_load_step(p, b, u0, coff, st, t, s); };
   auto own_off = [&](int t, int part) { return ((unsigned)b * (unsigned)T_ + (unsigned)t + 1u) * FCB_ROW + (unsigned)((part * np + u0) * 2); };
-  auto frag_off = [&](int t, int part) { return ((unsigned)frow * (unsigned)T_ + (unsigned)t + 1u) * FCB_ROW + (unsigned)(part * np * 2) + koff; };
+  auto frag_off = [&](int t, int part) { return fcb_frag_off<bf16_t>(frow, koff, T_, t, part); };
 
   float carry[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) carry[i] = 0.f;
-  Slices cur, nxt;
+  FcbSlices cur, nxt;
 #pragma unroll
   for (int i = 0; i < 8; ++i) cur.dh[i] = cur.h[i] = cur.u[i] = cur.c[i] = cur.r[i] = nxt.dh[i] = nxt.h[i] = nxt.u[i] = nxt.c[i] = nxt.r[i] = 0.f;
   if (own) load_step(T_ - 1, cur);
@@ -177,8 +120,8 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_kernel(const FcBpttP
         dup[i] = du * uu * (1.f - uu);
         dcp[i] = dc * (1.f - cc * cc);
       }
-      seq_st_sc1(p.dxpre, dxbytes, own_off(t, 0), fcs_pack8(dup));
-      seq_st_sc1(p.dxpre, dxbytes, own_off(t, 2), fcs_pack8(dcp));
+      FcExch<bf16_t>::publish8(p.dxpre, dxbytes, own_off(t, 0), dup);
+      FcExch<bf16_t>::publish8(p.dxpre, dxbytes, own_off(t, 2), dcp);
     }
     rendezvous(ph);
     // the next step's slices, under this step's phases (the next rendezvous drains them)
@@ -190,19 +133,19 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_kernel(const FcBpttP
 #pragma unroll
       for (int f = 0; f < NF; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
       fcs_gemm<NF>(p.dxpre, dxbytes, frag_off(t, 2), fstride, bcw, acc);
-      fcb_store_partials<NF>(red, kq, fk, frow, acc);
+      fcm_store_partials<NF>(red, kq, fk, frow, acc);
     }
     __syncthreads();
     if (red_row) {
       float drh[8], drp[8];
-      fcb_reduce_row8<NF>(red, tid, drh);
+      fcm_reduce_row8<NF>(red, tid, drh);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const float rr = cur.r[i];
         carry[i] += drh[i] * rr;
         drp[i] = drh[i] * cur.h[i] * rr * (1.f - rr);
       }
-      if (own) seq_st_sc1(p.dxpre, dxbytes, own_off(t, 1), fcs_pack8(drp));
+      if (own) FcExch<bf16_t>::publish8(p.dxpre, dxbytes, own_off(t, 1), drp);
     }
     rendezvous(ph + 1);
 
@@ -216,12 +159,12 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_kernel(const FcBpttP
       // u half's MFMAs a few at a time, and at NF = 4 re-uses their registers under short counted waits)
       __builtin_amdgcn_sched_barrier(0);
       fcs_gemm<NF>(p.dxpre, dxbytes, frag_off(t, 1), fstride, bzr, acc);
-      fcb_store_partials<NF>(red, kq, fk, frow, acc);
+      fcm_store_partials<NF>(red, kq, fk, frow, acc);
     }
     __syncthreads();
     if (red_row) {
       float s[8];
-      fcb_reduce_row8<NF>(red, tid, s);
+      fcm_reduce_row8<NF>(red, tid, s);
 #pragma unroll
       for (int i = 0; i < 8; ++i) carry[i] += s[i];
     }
@@ -234,7 +177,7 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_kernel(const FcBpttP
   if (s_timeout) {
     if (tid == 0 && p.err) { *(volatile unsigned*)p.err = 1u; __threadfence_system(); }
     if (own) {
-      const u32x4 qnan = (u32x4){0x7FC07FC0u, 0x7FC07FC0u, 0x7FC07FC0u, 0x7FC07FC0u};
+      const u32x4 qnan = (u32x4){FcExch<bf16_t>::QNAN, FcExch<bf16_t>::QNAN, FcExch<bf16_t>::QNAN, FcExch<bf16_t>::QNAN};
       float fnan[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) fnan[i] = __builtin_nanf("");

@@ -3,17 +3,11 @@
 // both of its GEMMs re-stream the transposed fp32 h-side kernels (33.2 MB per step) for at most 64 rows; here they are read
 // from memory once per launch.
 //
-// Decomposition, barriers, rendezvous and time-out are those of fcgru_bptt.hip.h: member j (one 256-thread workgroup, 203
-// members) owns units [8j, 8j + 8), wave kq owns K quarter [416 kq, 416 kq + 416), thread b of wave 0 owns clip b and keeps its
-// 8 fp32 `carry` values in registers across the sequence; two rendezvous per step on 2 T sharded counters zeroed every call.
-// MFMA, operand loads and the K permutation are those of fcgru_seq_f32.hip.h: v_mfma_f32_16x16x4_f32, lane (frow, fk) loads
-// 16 bytes at k = 416 kq + 16 i + 4 fk and component e of chunk i feeds MFMA (i, e), A and B alike, so every product is that
-// of the per-step path and only the fp32 summation order differs (chunk, component, fk per quarter; quarters ascending).
-// The published values are NOT rounded: this is fc_bwd1_kernel<float> / fc_bwd2_kernel<float>.
-//
-// Exchange: the plan's own fp32 dxpre, rows [F + 1][3 np] = [du_pre | dr_pre | dc_pre], row b T + t + 1.  A member publishes
-// 8 units x 4 bytes = TWO 16-byte sc1 stores per clip and part.  Every step has its own row: nothing is overwritten while it
-// is read, and the hoisted filter gradients and the b_x GEMM read what they always read.
+// Decomposition, exchange, rendezvous, padding and time-out are described in fcgru_member.hip.h.  The step, its exchange through the
+// plan's own dxpre and the final carry: fcgru_bptt.hip.h (the same algebra; the published values are NOT
+// rounded here: this is fc_bwd1_kernel<float> / fc_bwd2_kernel<float>).  MFMA, operand loads and the K permutation:
+// fcgru_seq_f32.hip.h, so every product is that of the per-step path and only the fp32 summation order differs (chunk,
+// component, fk per quarter; quarters ascending).  The host refuses sequences whose (B16 T + 1) dxpre rows pass 2^32 bytes.
 //
 // Residency.  Three 8-row blocks of fp32 (b_c and the u and r halves of b_zr), 52 KB each.  A block in registers is 104
 // dwords per lane (columns 8..15 of every tile multiply zeros), the ring of two A-fragment buffers of fcs32_gemm is 208:
@@ -26,43 +20,14 @@
 // GEMM ZR (the longer GEMM phase), straight into the registers step t's slices have just left: at that point u, c and dh_head
 // are dead since the local math and h_prev and r since the r gate, so ONE set of 40 dwords is enough where fcgru_bptt.hip.h
 // holds two.  profiles/fcgru_f32_bptt_kernel_resources.txt: no scratch, no spill at NF = 1 .. 4.
-//
-// Per step t = T - 1 .. 0:
-//   1. local:   dh = dh_head + carry (no carry at T - 1); du_pre = dh (h_prev - c) u (1 - u); dc_pre = dh (1 - u)(1 - c^2);
-//               carry = dh u; publish du_pre, dc_pre; rendezvous
-//   2. GEMM C:  drh = dc_pre rows . Wc_h^T, quarters summed through LDS ascending; carry += drh r;
-//               dr_pre = drh h_prev r (1 - r); publish; rendezvous
-//   3. GEMM ZR: carry += [du_pre | dr_pre] rows . [Wu_h | Wr_h]^T.  No rendezvous behind it: the carry is member-local.
-// Step 0 stores the final carry into g->carry, where the per-step path leaves dh0.
-// Padding: rows >= B of the last fragment lie behind the end of dxpre and read zeros (buffer bounds; the host refuses sequences
-// whose (B16 T + 1) rows pass 2^32 bytes); nothing is stored for them.
-// Time-out: as fcgru_bptt.hip.h.  A member past its deadline stops waiting and sets the plan's error word; at the end of the
-// launch it NaN-poisons its 8 units of all three parts of every dxpre row and of g->carry.
 #pragma once
 #include "fcgru_seq_f32.hip.h"
 #include "fcgru_bptt.hip.h"
 
 namespace rgp {
 
-constexpr unsigned FCB32_ROW = 3u * FCS_NP * 4u;     // bytes per fp32 dxpre row
-
-struct FcBptt32Params {
-  const float* b_c;          // packed [np][np]: row k = Wc_h[k][:]
-  const float* b_zr;         // packed [np][2 np]: row k = [Wu_h[k][:] | Wr_h[k][:]]
-  const float* dh_head;      // [B T][np] d loss / d h_t through the read-out
-  const float* hall;         // hall_t [T+1][B][np]: slot t = h_{t-1} of step t
-  const float* uall;         // [T][B][np]
-  const float* rall;
-  const float* call;
-  float* dxpre;              // [B T + 1][3 np], row 0 zero and untouched
-  float* carry;              // [B][np]: the final carry
-  unsigned* cnt;             // [2 T][FCS_SHARDS][FCS_CNT_STRIDE] phase counters, zeroed ahead of the launch
-  unsigned* err;             // the plan's pinned error word
-  int B, T;
-};
-
 template <int NF>
-static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_f32_kernel(const FcBptt32Params p) {
+static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_f32_kernel(const FcBpttParamsT<float> p) {
   __shared__ __attribute__((aligned(16))) char red[4 * NF * 16 * FCS_PITCH];   // [K quarter][row][16 columns]
   __shared__ __attribute__((aligned(16))) char zw[2 * FCS_UNITS * FCS32_CPITCH];   // [u half | r half][unit][K]
   __shared__ int s_timeout;
@@ -106,49 +71,17 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_f32_kernel(const FcB
   const long long coff = (long long)b * np + u0;                            // the clip's slice in a [B][np] slab
   __syncthreads();                                         // flag cleared, both halves of b_zr in LDS
 
-  auto rendezvous = [&](int ph) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its write-through stores
-    __syncthreads();
-    unsigned* c = p.cnt + (long long)ph * (FCS_SHARDS * FCS_CNT_STRIDE);
-    if (tid == 0) __hip_atomic_fetch_add(c + (j & (FCS_SHARDS - 1)) * FCS_CNT_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (kq == 0 && !s_timeout) {                           // (a member that timed out once stops waiting)
-      if (!fcs_wait_phase(c, members, lane) && lane == 0) s_timeout = 1;
-    }
-    __syncthreads();
-  };
-  auto load8 = [&](const float* src, float (&v)[8]) {
-    const f32x4 lo = *(const f32x4*)src, hi = *(const f32x4*)(src + 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[i] = lo[i]; v[4 + i] = hi[i]; }
-  };
-  auto store8f = [&](float* dst, const float (&v)[8]) {
-    *(f32x4*)dst = (f32x4){v[0], v[1], v[2], v[3]};
-    *(f32x4*)(dst + 4) = (f32x4){v[4], v[5], v[6], v[7]};
-  };
-  // the clip's slices of step t: dh_head, h_{t-1}, u, c, r
-  struct Slices { float dh[8], h[8], u[8], c[8], r[8]; };
-  auto load_step = [&](int t, Slices& s) {
-    const long long off = (long long)t * st + coff;
-    load8(p.dh_head + ((long long)b * T_ + t) * np + u0, s.dh);
-    load8(p.hall + off, s.h);
-    load8(p.uall + off, s.u);
-    load8(p.call + off, s.c);
-    load8(p.rall + off, s.r);
-  };
-  // the member's 8 units of part `part` (0 du_pre, 1 dr_pre, 2 dc_pre) of this thread's clip row: two 16-byte write-through stores
-  auto publish8 = [&](int t, int part, u32x4 lo, u32x4 hi) {
-    const unsigned off = ((unsigned)b * (unsigned)T_ + (unsigned)t + 1u) * FCB32_ROW + (unsigned)((part * np + u0) * 4);
-    seq_st_sc1(p.dxpre, dxbytes, off, lo);
-    seq_st_sc1(p.dxpre, dxbytes, off + 16u, hi);
-  };
-  auto publish8f = [&](int t, int part, const float (&v)[8]) {
-    publish8(t, part, __builtin_bit_cast(u32x4, (f32x4){v[0], v[1], v[2], v[3]}), __builtin_bit_cast(u32x4, (f32x4){v[4], v[5], v[6], v[7]}));
-  };
+  const FcRendezvous rendezvous{p.cnt, tid, j, kq, s_timeout, members, lane};
+  // (lambdas that capture the coordinates by reference, as this kernel always had: DESIGN 34)
+  auto load_step = [&](int t, FcbSlices& s) { fcb_load_step(p, b, u0, coff, st, t, s); };
+  // the member's 8 units of part `part` (0 du_pre, 1 dr_pre, 2 dc_pre) of this thread's clip row
+  auto own_off = [&](int t, int part) { return ((unsigned)b * (unsigned)T_ + (unsigned)t + 1u) * FCB32_ROW + (unsigned)((part * np + u0) * 4); };
+  auto publish8f = [&](int t, int part, const float (&v)[8]) { FcExch<float>::publish8(p.dxpre, dxbytes, own_off(t, part), v); };
   // the byte offset of part `part` of this lane's fragment row, chunk 0
-  auto frag_off = [&](int t, int part) { return ((unsigned)frow * (unsigned)T_ + (unsigned)t + 1u) * FCB32_ROW + (unsigned)(part * np * 4) + koff; };
+  auto frag_off = [&](int t, int part) { return fcb_frag_off<float>(frow, koff, T_, t, part); };
 
   float carry[8];
-  Slices cur;
+  FcbSlices cur;
 #pragma unroll
   for (int i = 0; i < 8; ++i) carry[i] = cur.dh[i] = cur.h[i] = cur.u[i] = cur.c[i] = cur.r[i] = 0.f;
   if (own) load_step(T_ - 1, cur);
@@ -178,12 +111,12 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_f32_kernel(const FcB
 #pragma unroll
       for (int f = 0; f < NF; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
       fcs32_gemm<NF, false>(p.dxpre, dxbytes, frag_off(t, 2), fstride, bcw, nullptr, false, acc);
-      fcb_store_partials<NF>(red, kq, fk, frow, acc);
+      fcm_store_partials<NF>(red, kq, fk, frow, acc);
     }
     __syncthreads();
     if (red_row) {
       float drh[8], drp[8];
-      fcb_reduce_row8<NF>(red, tid, drh);
+      fcm_reduce_row8<NF>(red, tid, drh);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const float rr = cur.r[i];
@@ -206,12 +139,12 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_f32_kernel(const FcB
       // (fcs32_gemm pins its loads in front of ITS MFMAs; this keeps the r half's loads behind the u half's MFMAs)
       __builtin_amdgcn_sched_barrier(0);
       fcs32_gemm<NF, true>(p.dxpre, dxbytes, frag_off(t, 1), fstride, bcw, blr, bzero, acc);
-      fcb_store_partials<NF>(red, kq, fk, frow, acc);
+      fcm_store_partials<NF>(red, kq, fk, frow, acc);
     }
     __syncthreads();
     if (red_row) {
       float s[8];
-      fcb_reduce_row8<NF>(red, tid, s);
+      fcm_reduce_row8<NF>(red, tid, s);
 #pragma unroll
       for (int i = 0; i < 8; ++i) carry[i] += s[i];
     }
@@ -223,12 +156,11 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_f32_kernel(const FcB
   if (s_timeout) {
     if (tid == 0 && p.err) { *(volatile unsigned*)p.err = 1u; __threadfence_system(); }
     if (own) {
-      const u32x4 qnan = (u32x4){0x7FC00000u, 0x7FC00000u, 0x7FC00000u, 0x7FC00000u};
       float fnan[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) fnan[i] = __builtin_nanf("");
       for (int t = 0; t < T_; ++t)
-        for (int part = 0; part < 3; ++part) publish8(t, part, qnan, qnan);
+        for (int part = 0; part < 3; ++part) FcExch<float>::poison8(p.dxpre, dxbytes, own_off(t, part));
       store8f(p.carry + coff, fnan);
     }
   }

@@ -3,21 +3,16 @@
 // re-streams the h-side kernels ([1664 x 3328] + [1664 x 1664] bf16 = 16.6 MB) from L2 / Infinity Cache for at most 64 rows;
 // here the kernels never move and only the state does.
 //
-// Decomposition.  Work is split by hidden unit, so a unit's gate math is local to one workgroup.  Member j (one
-// 256-thread workgroup, 4 waves) owns units [8j, 8j + 8) of the padded 1664: the 8 u, 8 r and 8 c rows of the packed
-// kernels (g->zr rows [u | r], g->c; set_weights_impl), resident in REGISTERS for the whole sequence: wave kq keeps K steps
-// [13 kq, 13 kq + 13) of the 52, i.e. 2 x 13 B fragments = 104 VGPRs per lane.  Members that would own padding only (units
-// >= 1624) are not launched: 203 members.  Per step:
+// Decomposition, exchange, rendezvous, padding and time-out are described in fcgru_member.hip.h.  This kernel's own:
+// Residency.  The member's 8 u, 8 r and 8 c rows of the packed kernels (g->zr rows [u | r], g->c; set_weights_impl) in
+// REGISTERS for the whole sequence: wave kq keeps K steps [13 kq, 13 kq + 13) of the 52, i.e. 2 x 13 B fragments = 104 VGPRs
+// per lane.  Per step:
 //   phase A  [u(8) | r(8)] = one 16x16x32 column block per K step on the bf16 rows of h_{t-1};
 //            u = sigmoid(. + xpre_u), r = sigmoid(. + xpre_r); publish bf16(r * h_{t-1}) (fp32 product, rounded once:
 //            EpiGruZR); rendezvous
 //   phase B  c block (columns 8..15 of the tile multiply zeros) on the r.h rows; c = tanh(. + xpre_c),
 //            h_t = u h_{t-1} + (1 - u) c (EpiGruC, identity batch-norm); publish bf16(h_t); rendezvous
-// The rows are the clips: NF = (B + 15) / 16 fragments of 16, a template parameter, no run-time guards in the MFMA loops.
-// Rows >= B of the last fragment lie behind the end of the exchange buffer and read zeros (buffer bounds); MFMA rows are
-// independent, and nothing is stored for them.  The 4 K-quarter partial tiles are summed through LDS by thread b of wave 0,
-// which owns clip b: its 8 fp32 h and u stay in its registers across phases and steps, and it publishes the member's
-// 8 units x bf16 = ONE 16-byte row per clip and phase.
+// (none behind the last phase: the kernel boundary orders it.)
 //
 // Exchange buffers: the plan's own row-major operand rows, so the per-step consumers read what they always read.
 //   h:   hrows, row b T + t -- the rows the output projection reads.  Every step has its own row: nothing is overwritten
@@ -29,66 +24,53 @@
 // MFMA (>= 13 sixteen-byte loads per lane in flight).  That order is pinned by a scheduling barrier in fcs_gemm and checked
 // in the assembly by scripts/check_isa_waits.py: without it the compiler keeps 2 - 3 loads in flight.
 //
-// Rendezvous: the protocol of seq_group.hip.h with every member of the launch as the group -- payload as 16-byte sc1
-// stores, vmcnt(0), workgroup barrier, one lane adds to the phase's monotonic counter, wave 0 polls it (relaxed,
-// agent scope, s_sleep) against the s_memrealtime deadline, barrier, payload read with sc1 loads only.  2 T counters,
-// each sharded 8 ways (fcs_wait_phase; measured against one counter, before the loads were pinned: 0.494 vs 0.539 ms per
-// forward at 64x16, 0.506 vs 0.610 at 8x35), zeroed ahead of the launch; the last phase needs none (the kernel boundary
-// orders it).  No fence per phase.
-//
-// Padding: units 1617 .. 1623 of member 202 have zero kernel rows and zero xpre, so u = 1/2, c = 0 and h stays 0.
-// Time-out: a member whose wait passes the deadline stops waiting, sets the plan's error word and NaN-poisons its units of
-// every h row (all steps, all clips) and of the fp32 states: the logits are NaN, never finite and wrong.
-//
-// Streaming (rgp_fcgru_forward_stream), template argument STREAM.  STREAM = false is the kernel above (one expression apart: the
-// blend is now spelled as one rounded product and one fma, see there -- both instantiations must round alike), and is what
-// zero-state calls over all T steps launch.  STREAM = true starts from a caller's state: fcgru_seed_kernel
-// (rgp_fcgru.hip) has put fp32 h_{-1} into slot 0 of hall and its bf16 rows into the plan's operand row of step 0 -- hp
-// (row b, stride np) on inference plans, slot (b, 0) of hp_all (stride (T + 1) np) on training plans -- so thread b loads its
-// 8 fp32 h from slot 0 ahead of the step loop (it alone writes those 8 floats later: no race), and phase A of step 0 runs
-// the same fcs_gemm on the seeded rows instead of skipping; base and strides are selected per step, so the phase still is ONE
-// run of loads in front of ONE run of MFMAs.  No new exchange buffer.  Write-after-read: the seeded rows are only READ, in
-// phase A of step 0, and never written by this kernel (h_t goes to hrows, and to slots >= 1 of hp_all): nothing to order.
+// Streaming (rgp_fcgru_forward_stream), template argument STREAM.  STREAM = false is what zero-state calls over all T steps
+// launch.  STREAM = true starts from a caller's state: gru_seed_kernel has put fp32 h_{-1} into slot 0 of hall and its bf16
+// rows into the plan's operand row of step 0 -- hp (row b, stride np) on inference plans, slot (b, 0) of hp_all (stride
+// (T + 1) np) on training plans -- so thread b loads its 8 fp32 h from slot 0 ahead of the step loop (it alone writes those 8
+// floats later: no race), and phase A of step 0 runs the same fcs_gemm on the seeded rows instead of skipping; base and strides
+// are selected per step, so the phase still is ONE run of loads in front of ONE run of MFMAs.  No new exchange buffer.
+// Write-after-read: the seeded rows are only READ, in phase A of step 0, and never written by this kernel (h_t goes to hrows,
+// and to slots >= 1 of hp_all): nothing to order.
 // State out: inference hall is a two-slot ping-pong, so h behind step n_valid < T does not survive the launch; on inference
 // plans thread b stores its 8 fp32 h behind step n_valid - 1 into hsnap [B][np] (training plans: the host reads slot n_valid
-// of hall_t).  A timed-out launch NaN-poisons hsnap with the rest.
+// of hall_t).
 #pragma once
-#include "seq_group.hip.h"
+#include "fcgru_member.hip.h"
 
 namespace rgp {
 
-constexpr int FCS_NP = 1664;                         // padded state (a multiple of 64)
-constexpr int FCS_UNITS = 8;                         // units per member
-constexpr int FCS_MEMBERS = (1617 + FCS_UNITS - 1) / FCS_UNITS;      // 203
 constexpr int FCS_KW = FCS_NP / 32 / 4;              // K steps per wave: 13
-constexpr int FCS_SHARDS = 8;                        // counters per phase (a power of two), 64 bytes apart; member j adds to shard j % 8
-constexpr int FCS_CNT_STRIDE = 16;                   // unsigned per shard
-constexpr int FCS_PITCH = 80;                        // bytes per row of a partial tile in LDS: 16 fp32 + 4 (bank rotation)
 static_assert(FCS_KW * 4 * 32 == FCS_NP, "K split");
 
-struct FcSeqParams {
-  const bf16_t* w_zr;        // packed [2 np][np]: rows [0, np) u, [np, 2 np) r
-  const bf16_t* w_c;         // packed [np][np]
+// E: the element type of the plan's operand rows (bf16_t here, float in fcgru_seq_f32.hip.h)
+template <typename E>
+struct FcSeqParamsT {
+  const E* w_zr;             // packed [2 np][np]: rows [0, np) u, [np, 2 np) r
+  const E* w_c;              // packed [np][np]
   const float* xpre;         // [B T][3 np] hoisted x parts + biases, columns [u | r | c]
-  bf16_t* hrows;             // [B T][np] bf16 h_t, row b T + t: exchange rows of h and the output projection's input
-  bf16_t* rh;                // training: rh_all [B T][np]; inference: rh [B][np]
+  E* hrows;                  // [B T][np] h_t, row b T + t: exchange rows of h and the output projection's input
+  E* rh;                     // training: rh_all [B T][np]; inference: rh [B][np]
   float* hall;               // training: hall_t [T+1][B][np] (slot 0 = h_0 = 0); inference: [2][B][np], h_t in slot (t+1) & 1
   float* uall;               // training [T][B][np] (else null) ...
   float* rall;
   float* call;
-  bf16_t* hp_all;            // training [B][T+1][np], slot (b, 0) untouched
+  E* hp_all;                 // training [B][T+1][np], slot (b, 0) untouched
   unsigned* cnt;             // [2 T][FCS_SHARDS][FCS_CNT_STRIDE] phase counters, zeroed ahead of the launch
   unsigned* err;             // the plan's pinned error word
   int B, T;
 };
 // STREAM = true takes these on top (the STREAM = false instantiations keep the parameter block they were measured with)
-struct FcSeqStreamParams : FcSeqParams {
-  const bf16_t* seed;        // bf16 rows of h_{-1}: inference hp [B][np]; training hp_all, slot (b, 0)
+template <typename E>
+struct FcSeqStreamParamsT : FcSeqParamsT<E> {
+  const E* seed;             // rows of h_{-1}: inference hp [B][np]; training hp_all, slot (b, 0)
   unsigned seed_bytes;       // extent of that buffer (rows >= B lie behind it and read zeros)
-  unsigned seed_stride;      // bytes from clip b to clip b + 1: np * 2, or (T + 1) * np * 2
+  unsigned seed_stride;      // bytes from clip b to clip b + 1: one row, or T + 1 rows
   float* hsnap;              // inference: [B][np] fp32 h behind step n_valid - 1; training: null
   int n_valid;
 };
+template <typename E, bool STREAM> struct FcSeqParamsOf { typedef FcSeqParamsT<E> type; };
+template <typename E> struct FcSeqParamsOf<E, true> { typedef FcSeqStreamParamsT<E> type; };
 
 // A fragments of this wave's K quarter from exchange rows (sc1), then the MFMAs of one resident column block on them.
 // off0: the lane's byte offset at fragment 0, K step 0; fragments are fstride bytes apart, K steps 64.
@@ -110,44 +92,8 @@ __device__ __forceinline__ void fcs_gemm(const void* base, unsigned bytes, unsig
       acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(s16x8, a[f][i]), __builtin_bit_cast(s16x8, b[i]), acc[f], 0, 0, 0);
 }
 
-// Wait of a whole wave for a phase whose arrivals are spread over FCS_SHARDS counters (a phase counter that all 203
-// members add to is 203 atomics on one address, served one after the other: the fan-in the price list puts at 3 - 4.5 us).
-// Lane l < FCS_SHARDS polls shard l; the counters only grow, so their sum, read at different times, never overstates the
-// arrivals.  The deadline is seq_wait_phase's.  One shard: the single-lane wait of seq_group.hip.h.
-__device__ __forceinline__ bool fcs_wait_phase(const unsigned* cnt, unsigned n, int lane) {
-  if (FCS_SHARDS == 1) {
-    int ok = 1;
-    if (lane == 0) ok = seq_wait_phase_n(cnt, n) ? 1 : 0;
-    return __builtin_amdgcn_readfirstlane(ok) != 0;
-  }
-  const unsigned* mine = cnt + (lane & (FCS_SHARDS - 1)) * FCS_CNT_STRIDE;
-  auto arrived = [&]() {
-    unsigned v = lane < FCS_SHARDS ? __hip_atomic_load(mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-#pragma unroll
-    for (int m = 1; m < FCS_SHARDS; m <<= 1) v += (unsigned)__shfl_xor((int)v, m);
-    return (unsigned)__builtin_amdgcn_readfirstlane((int)v) >= n;
-  };
-  if (arrived()) return true;
-  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-  for (unsigned spins = 1;; ++spins) {
-    __builtin_amdgcn_s_sleep(2);
-    if (arrived()) return true;
-    if ((spins & 63u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > SEQ_DEADLINE_TICKS) return false;
-  }
-}
-
-__device__ __forceinline__ u32x4 fcs_pack8(const float (&v)[8]) {
-  u32x4 q;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) q[i] = (unsigned)f2bf(v[2 * i]) | ((unsigned)f2bf(v[2 * i + 1]) << 16);
-  return q;
-}
-
-template <bool STREAM> struct FcSeqParamsOf { typedef FcSeqParams type; };
-template <> struct FcSeqParamsOf<true> { typedef FcSeqStreamParams type; };
-
 template <int NF, bool SAVE, bool STREAM>
-static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const typename FcSeqParamsOf<STREAM>::type p) {
+static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const typename FcSeqParamsOf<bf16_t, STREAM>::type p) {
   __shared__ __attribute__((aligned(16))) char red[4 * NF * 16 * FCS_PITCH];   // [K quarter][row][16 columns]
   __shared__ int s_timeout;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -192,7 +138,8 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const typename
   }
   __syncthreads();                                         // flag cleared
 
-  // this wave's partial tiles -> LDS; the sum over the 4 quarters of row `tid` (16 columns)
+  // this wave's partial tiles -> LDS; the sum over the 4 quarters of row `tid` (16 columns).  This kernel's own text: on
+  // fcm_store_partials and a 16-column fcm_reduce_row its STREAM instantiations compile to other code than the one measured
   auto store_partials = [&](const f32x4 (&acc)[NF]) {
 #pragma unroll
     for (int f = 0; f < NF; ++f)
@@ -209,21 +156,7 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const typename
       for (int e = 0; e < 4; ++e) s[4 * c + e] = v[e];
     }
   };
-  // rendezvous of phase ph: this member's rows are published; all members' are
-  auto rendezvous = [&](int ph) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its write-through stores
-    __syncthreads();
-    unsigned* c = p.cnt + (long long)ph * (FCS_SHARDS * FCS_CNT_STRIDE);
-    if (tid == 0) __hip_atomic_fetch_add(c + (j & (FCS_SHARDS - 1)) * FCS_CNT_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (kq == 0 && !s_timeout) {                           // (a member that timed out once stops waiting)
-      if (!fcs_wait_phase(c, members, lane) && lane == 0) s_timeout = 1;
-    }
-    __syncthreads();
-  };
-  auto store8f = [&](float* dst, const float (&v)[8]) {
-    *(f32x4*)dst = (f32x4){v[0], v[1], v[2], v[3]};
-    *(f32x4*)(dst + 4) = (f32x4){v[4], v[5], v[6], v[7]};
-  };
+  const FcRendezvous rendezvous{p.cnt, tid, j, kq, s_timeout, members, lane};
 
   for (int t = 0; t < T_; ++t) {
     // the step's xpre slice of this clip, ahead of the waits: 3 x 8 fp32
@@ -264,7 +197,7 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const typename
       }
       if (own) {
         const unsigned row = SAVE ? (unsigned)b * (unsigned)T_ + (unsigned)t : (unsigned)b;
-        seq_st_sc1(p.rh, rbytes, (row * (unsigned)np + (unsigned)u0) * 2u, fcs_pack8(rh));
+        FcExch<bf16_t>::publish8(p.rh, rbytes, (row * (unsigned)np + (unsigned)u0) * 2u, rh);
       }
     }
     rendezvous(2 * t);
@@ -301,7 +234,7 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const typename
         // stream cut between a zero-state launch and a seeded one must give the bits of the uncut recurrence.
         h[i] = __builtin_fmaf(u[i], h[i], (1.f - u[i]) * cg[i]);
       }
-      if (own) seq_st_sc1(p.hrows, hbytes, (((unsigned)b * (unsigned)T_ + (unsigned)t) * (unsigned)np + (unsigned)u0) * 2u, fcs_pack8(h));
+      if (own) FcExch<bf16_t>::publish8(p.hrows, hbytes, (((unsigned)b * (unsigned)T_ + (unsigned)t) * (unsigned)np + (unsigned)u0) * 2u, h);
     }
     if (t + 1 < T_) rendezvous(2 * t + 1);
     if (own) {
@@ -321,13 +254,12 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_kernel(const typename
   if (s_timeout) {
     if (tid == 0 && p.err) { *(volatile unsigned*)p.err = 1u; __threadfence_system(); }
     if (own) {
-      const u32x4 qnan = (u32x4){0x7FC07FC0u, 0x7FC07FC0u, 0x7FC07FC0u, 0x7FC07FC0u};
       float fnan[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) fnan[i] = __builtin_nanf("");
       const long long off = (long long)b * np + u0;
       for (int t = 0; t < T_; ++t) {
-        seq_st_sc1(p.hrows, hbytes, (((unsigned)b * (unsigned)T_ + (unsigned)t) * (unsigned)np + (unsigned)u0) * 2u, qnan);
+        FcExch<bf16_t>::poison8(p.hrows, hbytes, (((unsigned)b * (unsigned)T_ + (unsigned)t) * (unsigned)np + (unsigned)u0) * 2u);
         if (SAVE) store8f(p.hall + (long long)(t + 1) * st + off, fnan);
       }
       if (!SAVE) { store8f(p.hall + off, fnan); store8f(p.hall + st + off, fnan); }

@@ -2,13 +2,9 @@
 // gaze_rnn77 in ONE launch, the fp32 form of fcgru_seq.hip.h (DESIGN 28 -> 32).  The per-step f32 path re-streams the h-side
 // kernels ([1664 x 3328] + [1664 x 1664] fp32 = 33.2 MB) every timestep; here they are read from memory once per launch.
 //
-// Decomposition, barriers and rendezvous are those of fcgru_seq.hip.h: member j (one 256-thread workgroup) owns units
-// [8j, 8j + 8) of the padded 1664, 203 members, wave kq owns K quarter [416 kq, 416 kq + 416); phase A is the [u(8) | r(8)]
-// column block on the rows of h_{t-1}, phase B the c block on the rows of r.h; the 4 K-quarter partial tiles are summed through
-// LDS by thread b of wave 0, which owns clip b, keeps its 8 fp32 h and u in registers and does the gate math (the same
-// sigmoidf_ / tanhf_, the blend as one rounded product and one fma, so STREAM = true and STREAM = false round alike).
-//
-// What differs for fp32.
+// Decomposition, exchange, rendezvous, padding and time-out are described in fcgru_member.hip.h.  Phases, exchange buffers, their
+// write-after-read argument and streaming: fcgru_seq.hip.h (the gate math is the same text, so STREAM = true and
+// STREAM = false round alike here too).  What differs for fp32:
 // MFMA: v_mfma_f32_16x16x4_f32, an exact fp32 FMA chain (the instruction of the per-step f32 path, Mma<float>).  Its A and B
 //   operands are ONE dword per lane: A[row = l & 15][k = l >> 4], B[k = l >> 4][col = l & 15].
 // Operand loads: no dword exchange loads.  Lane (frow, fk) loads 16 bytes at k = 416 kq + 16 i + 4 fk, i in [0, 26), and
@@ -26,53 +22,16 @@
 //   assembly.  (Tried first: both blocks in registers, 208 + 208 for the ring, which spilled up to 196 VGPRs at
 //   NF >= 2.  Resident [u | r] 104 + ring 208 + a transient pair of c chunks leaves the gate math of wave 0 its registers:
 //   256 VGPRs + at most 244 AGPRs, no scratch; profiles/fcgru_f32_kernel_resources.txt.)
-// Exchange rows: the plan's own fp32 operand rows -- hrows row b T + t, rh_all (training) / rh (inference) -- no new buffers.
-//   A member publishes 8 units x 4 bytes = TWO 16-byte sc1 stores per clip and phase.  hp_all rows are the fp32 h itself, bit
-//   for bit, and rh is exactly the fp32 product r * h_{t-1}.
-//   Write-after-read of the single inference rh buffer [B][np], as in fcgru_seq.hip.h: a member publishes r.h of step t + 1
-//   only behind the phase-B rendezvous of step t, and every member arrives at that rendezvous only after its phase-B MFMAs,
-//   i.e. after its loads of r.h of step t have landed in its registers.  h has a row per step: nothing is overwritten.
-// Padding: rows >= B of the last fragment lie behind the end of the exchange buffer and read zeros (buffer bounds; 64 rows x T
-//   x 6656 bytes stay below 2^32: the host refuses T > 8192); nothing is stored for them.  Units 1617 .. 1623 of member 202 have
-//   zero kernel rows and zero xpre: u = 1/2, c = 0, h stays 0.
-// Time-out: as fcgru_seq.hip.h -- a member whose wait passes the deadline stops waiting, sets the plan's error word and
-//   NaN-poisons its units of every fp32 h row, of the fp32 states and of hsnap.
-// Streaming (STREAM = true): gru_seed_kernel<float> has put h_{-1} into slot 0 of hall and into the operand row of step 0 (hp on
-//   inference plans, slot (b, 0) of hp_all on training plans); phase A of step 0 runs on those rows, which this kernel only reads.
+// Exchange rows: the plan's own fp32 operand rows; hp_all rows are the fp32 h itself, bit for bit, and rh is exactly the fp32
+//   product r * h_{t-1}.  64 rows x T x 6656 bytes stay below 2^32: the host refuses T > 8192.
 #pragma once
 #include "fcgru_seq.hip.h"
 
 namespace rgp {
 
 constexpr int FCS32_KC = FCS_NP / 16 / 4;            // 16-float chunks per wave: 26
-constexpr int FCS32_ROW = FCS_NP * 4;                // bytes per exchange row
 constexpr int FCS32_CPITCH = (FCS_NP + 4) * 4;       // bytes per row of the c block in LDS
 static_assert(FCS32_KC * 4 * 16 == FCS_NP, "K split");
-
-struct FcSeq32Params {
-  const float* w_zr;         // packed [2 np][np]: rows [0, np) u, [np, 2 np) r
-  const float* w_c;          // packed [np][np]
-  const float* xpre;         // [B T][3 np] hoisted x parts + biases, columns [u | r | c]
-  float* hrows;              // [B T][np] h_t, row b T + t: exchange rows of h and the output projection's input
-  float* rh;                 // training: rh_all [B T][np]; inference: rh [B][np]
-  float* hall;               // training: hall_t [T+1][B][np] (slot 0 = h_0); inference: [2][B][np], h_t in slot (t+1) & 1
-  float* uall;               // training [T][B][np] (else null) ...
-  float* rall;
-  float* call;
-  float* hp_all;             // training [B][T+1][np], slot (b, 0) untouched
-  unsigned* cnt;             // [2 T][FCS_SHARDS][FCS_CNT_STRIDE] phase counters, zeroed ahead of the launch
-  unsigned* err;             // the plan's pinned error word
-  int B, T;
-};
-struct FcSeq32StreamParams : FcSeq32Params {
-  const float* seed;         // rows of h_{-1}: inference hp [B][np]; training hp_all, slot (b, 0)
-  unsigned seed_bytes;       // extent of that buffer (rows >= B lie behind it and read zeros)
-  unsigned seed_stride;      // bytes from clip b to clip b + 1: np * 4, or (T + 1) * np * 4
-  float* hsnap;              // inference: [B][np] h behind step n_valid - 1; training: null
-  int n_valid;
-};
-template <bool STREAM> struct FcSeq32ParamsOf { typedef FcSeq32Params type; };
-template <> struct FcSeq32ParamsOf<true> { typedef FcSeq32StreamParams type; };
 
 // A operands of this wave's K quarter from exchange rows (sc1), then the MFMAs of one resident column block on them.
 // off0: the lane's byte offset at fragment 0, chunk 0; fragments are fstride bytes apart, chunks 64.
@@ -136,7 +95,7 @@ __device__ __forceinline__ void fcs32_gemm(const void* base, unsigned bytes, uns
 }
 
 template <int NF, bool SAVE, bool STREAM>
-static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_f32_kernel(const typename FcSeq32ParamsOf<STREAM>::type p) {
+static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_f32_kernel(const typename FcSeqParamsOf<float, STREAM>::type p) {
   __shared__ __attribute__((aligned(16))) char red[4 * NF * 16 * FCS_PITCH];   // [K quarter][row][16 columns]
   __shared__ __attribute__((aligned(16))) char cw[FCS_UNITS * FCS32_CPITCH];   // the member's c block [unit][K]
   __shared__ int s_timeout;
@@ -174,15 +133,11 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_f32_kernel(const type
   const unsigned koff = (unsigned)((kq * FCS32_KC * 16 + fk * 4) * 4);   // the lane's K offset in a row, bytes
   const long long st = (long long)B * np;
   if constexpr (STREAM) {                                  // the caller's state: slot 0 of hall (gru_seed_kernel)
-    if (own) {
-      const float* h0 = p.hall + (long long)b * np + u0;
-      const f32x4 lo = *(const f32x4*)h0, hi = *(const f32x4*)(h0 + 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { h[i] = lo[i]; h[4 + i] = hi[i]; }
-    }
+    if (own) load8(p.hall + (long long)b * np + u0, h);
   }
   __syncthreads();                                         // flag cleared, c block in LDS
 
+  // (this kernel's own text, as in fcgru_seq.hip.h and for its reason: DESIGN 34)
   auto store_partials = [&](const f32x4 (&acc)[NF]) {
 #pragma unroll
     for (int f = 0; f < NF; ++f)
@@ -199,20 +154,7 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_f32_kernel(const type
       for (int e = 0; e < 4; ++e) s[4 * c + e] = v[e];
     }
   };
-  auto rendezvous = [&](int ph) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its write-through stores
-    __syncthreads();
-    unsigned* c = p.cnt + (long long)ph * (FCS_SHARDS * FCS_CNT_STRIDE);
-    if (tid == 0) __hip_atomic_fetch_add(c + (j & (FCS_SHARDS - 1)) * FCS_CNT_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (kq == 0 && !s_timeout) {                           // (a member that timed out once stops waiting)
-      if (!fcs_wait_phase(c, members, lane) && lane == 0) s_timeout = 1;
-    }
-    __syncthreads();
-  };
-  auto store8f = [&](float* dst, const float (&v)[8]) {
-    *(f32x4*)dst = (f32x4){v[0], v[1], v[2], v[3]};
-    *(f32x4*)(dst + 4) = (f32x4){v[4], v[5], v[6], v[7]};
-  };
+  const FcRendezvous rendezvous{p.cnt, tid, j, kq, s_timeout, members, lane};
   // the member's 8 units of an exchange row: two 16-byte write-through stores
   auto publish8 = [&](float* base, unsigned bytes, unsigned row, const float (&v)[8]) {
     const unsigned off = (row * (unsigned)np + (unsigned)u0) * 4u;
@@ -315,7 +257,7 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_seq_f32_kernel(const type
       for (int i = 0; i < 8; ++i) fnan[i] = __builtin_nanf("");
       const long long off = (long long)b * np + u0;
       for (int t = 0; t < T_; ++t) {
-        publish8(p.hrows, hbytes, (unsigned)b * (unsigned)T_ + (unsigned)t, fnan);
+        publish8(p.hrows, hbytes, (unsigned)b * (unsigned)T_ + (unsigned)t, fnan);   // (on FcExch<float>::poison8 <4, true, *> compile anew)
         if (SAVE) store8f(p.hall + (long long)(t + 1) * st + off, fnan);
       }
       if (!SAVE) { store8f(p.hall + off, fnan); store8f(p.hall + st + off, fnan); }

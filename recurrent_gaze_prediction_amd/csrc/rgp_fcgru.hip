@@ -12,21 +12,21 @@
 // Backward (tf.gradients of the loss of gaze_rnn.py:363-408, base.py:278-281): BPTT with two input-gradient
 // GEMMs per step; every weight gradient is hoisted over all T steps and computed by wgrad_kernel
 // (rows = frames, transposing LDS reads) on the operand rows the forward kept.
-// Recurrence, two implementations: per step (every plan; the library's choice), and -- RGP_FCGRU_PERSISTENT, bf16 plans of
-// at most 64 clips -- all T steps in one persistent launch with the h-side kernels resident in registers
-// (fcgru_seq.hip.h); RGP_FCGRU_PERSISTENT_F32 is the same for f32 plans (fcgru_seq_f32.hip.h: fp32 MFMAs on the plan's fp32 rows).
-// All write the same buffers in the same layouts, so the backward runs unchanged behind any of them.
-// BPTT, two implementations as well: per step (every plan; the library's choice: four launches per timestep), and --
-// RGP_FCGRU_BPTT_PERSISTENT, bf16 training plans of at most 64 clips -- all T steps in one persistent launch with the
-// TRANSPOSED h-side kernels resident in registers (fcgru_bptt.hip.h), whatever the forward ran; RGP_FCGRU_BPTT_PERSISTENT_F32
-// is the same for f32 training plans (fcgru_bptt_f32.hip.h: fp32 MFMAs on the plan's fp32 dxpre rows).  All leave dxpre and the final
-// carry in the same buffers, so the hoisted filter gradients and the projection's input gradient run unchanged behind either.
+// Recurrence and BPTT, two implementations each, chosen independently by the plan's flags:
+//   per step    every plan; the library's choice (two launches per timestep forward, four backward);
+//   persistent: bf16 or f32 by the plan's dtype, at most 64 clips -- all T steps in ONE launch with the h-side kernels (BPTT:
+//               the TRANSPOSED ones, training plans) resident on the device: fcgru_seq.hip.h / fcgru_seq_f32.hip.h,
+//               fcgru_bptt.hip.h / fcgru_bptt_f32.hip.h, on the member layer of fcgru_member.hip.h.  A flag per dtype
+//               (RGP_FCGRU_PERSISTENT / _F32, RGP_FCGRU_BPTT_PERSISTENT / _F32); one launch path here (FcPersist<T>).
+// Both write the same buffers in the same layouts (states, gates and operand rows; dxpre and the final carry), so everything
+// around them -- the backward behind either forward, the hoisted filter gradients, the projection's input gradient -- is one code.
 // Streaming (rgp_fcgru_forward_stream): the same forward started from a caller's h_{-1} [B][1617] instead of zeros, on either
 // path and on inference and training plans.  Way in: gru_seed_or_zero (gru_steps.h), one launch in place of the two memsets.
 // Way out: one strided copy of the fp32 state behind step n_valid.  Nothing else in the per-step loop changes.
 #include <algorithm>
 
 #include <string>
+#include <type_traits>
 
 #include "wgrad_launch.h"
 #include "gru_steps.h"
@@ -148,93 +148,75 @@ __global__ __launch_bounds__(256) void fc_read_rows_kernel(const T* __restrict__
     dst[i] = Elem<T>::from(src[(i / n) * np + (i % n)]);
 }
 
-// All T steps in one persistent launch (fcgru_seq.hip.h).  STREAM: from the seeded state (gru_seed_kernel has run), and --
-// inference plans -- with the snapshot behind step n_valid.
-template <bool SAVE, bool STREAM>
+// ---------------------------------------------------------------- persistent launches: bf16 or f32 by the plan's dtype
+// T -> the kernel templates and the name used in messages
+template <typename T> struct FcPersist;
+template <> struct FcPersist<bf16_t> {
+  static constexpr const char* seq_name = "fcgru_seq";
+  static constexpr const char* bptt_name = "fcgru_bptt";
+  template <int NF, bool SAVE, bool STREAM> static auto seq() { return fcgru_seq_kernel<NF, SAVE, STREAM>; }
+  template <int NF> static auto bptt() { return fcgru_bptt_kernel<NF>; }
+};
+template <> struct FcPersist<float> {
+  static constexpr const char* seq_name = "fcgru_seq_f32";
+  static constexpr const char* bptt_name = "fcgru_bptt_f32";
+  template <int NF, bool SAVE, bool STREAM> static auto seq() { return fcgru_seq_f32_kernel<NF, SAVE, STREAM>; }
+  template <int NF> static auto bptt() { return fcgru_bptt_f32_kernel<NF>; }
+};
+
+size_t fc_cnt_bytes(int n_steps) { return (size_t)2 * n_steps * FCS_SHARDS * FCS_CNT_STRIDE * 4; }   // [2 T][FCS_SHARDS][FCS_CNT_STRIDE]
+
+// One launch of all FCS_MEMBERS members on the parameter block p; kernel_of(NF) names the instantiation for
+// NF = (B + 15) / 16 row fragments
+template <typename P, typename K>
+int launch_members(const char* name, const P& p, K kernel_of, hipStream_t s) {
+  RGP_HIP(hipMemsetAsync(p.cnt, 0, fc_cnt_bytes(p.T), s));   // phase counters: zeroed EVERY call
+  void (*kern)(P) = nullptr;
+  switch ((p.B + 15) / 16) {
+    case 1: kern = kernel_of(std::integral_constant<int, 1>()); break;
+    case 2: kern = kernel_of(std::integral_constant<int, 2>()); break;
+    case 3: kern = kernel_of(std::integral_constant<int, 3>()); break;
+    case 4: kern = kernel_of(std::integral_constant<int, 4>()); break;
+    default: return set_err(RGP_EINVAL, "%s: batch %d", name, p.B);
+  }
+  PersistentLaunch guard(s);
+  RGP_TRY(guard.status());
+  kern<<<FCS_MEMBERS, SEQ_NT, 0, s>>>(p);
+  RGP_HIP(hipGetLastError());
+  return guard.commit();
+}
+
+// All T steps of the recurrence (fcgru_seq.hip.h / fcgru_seq_f32.hip.h).  STREAM: from the seeded state (gru_seed_kernel has
+// run), and -- inference plans -- with the snapshot behind step n_valid.
+template <typename T, bool SAVE, bool STREAM>
 int seq_persistent(rgp_fcgru* g, hipStream_t s) {
   char* ws = g->ws;
-  RGP_HIP(hipMemsetAsync(ws + g->seq_cnt, 0, (size_t)2 * g->T * FCS_SHARDS * FCS_CNT_STRIDE * 4, s));         // phase counters: zeroed EVERY call
-  typename FcSeqParamsOf<STREAM>::type p;
+  const char* name = FcPersist<T>::seq_name;
+  typename FcSeqParamsOf<T, STREAM>::type p;
   if constexpr (STREAM) {
-    p.seed = (const bf16_t*)(ws + (SAVE ? g->hp_all : g->hp));
-    p.seed_stride = (unsigned)((SAVE ? g->T + 1 : 1) * g->np * 2);
-    p.seed_bytes = (unsigned)g->B * p.seed_stride;       // (B <= 64, T <= 16384: below 2^32, as hbytes)
+    p.seed = (const T*)(ws + (SAVE ? g->hp_all : g->hp));
+    p.seed_stride = (unsigned)((SAVE ? g->T + 1 : 1) * FcExch<T>::ROW);
+    p.seed_bytes = (unsigned)g->B * p.seed_stride;       // (below 2^32, as hbytes: rgp_fcgru_create_flags)
     p.hsnap = SAVE ? nullptr : (float*)(ws + g->hsnap);
     p.n_valid = g->stream.n_valid;
   }
-  p.w_zr = (const bf16_t*)(ws + g->zr.w_off);
-  p.w_c = (const bf16_t*)(ws + g->c.w_off);
+  p.w_zr = (const T*)(ws + g->zr.w_off);
+  p.w_c = (const T*)(ws + g->c.w_off);
   p.xpre = (const float*)(ws + g->xpre);
-  p.hrows = (bf16_t*)(ws + g->hrows);
-  p.rh = (bf16_t*)(ws + (SAVE ? g->rh_all : g->rh));
+  p.hrows = (T*)(ws + g->hrows);
+  p.rh = (T*)(ws + (SAVE ? g->rh_all : g->rh));
   p.hall = (float*)(ws + (SAVE ? g->hall_t : g->hall));
   p.uall = SAVE ? (float*)(ws + g->uall) : nullptr;
   p.rall = SAVE ? (float*)(ws + g->rall) : nullptr;
   p.call = SAVE ? (float*)(ws + g->call) : nullptr;
-  p.hp_all = SAVE ? (bf16_t*)(ws + g->hp_all) : nullptr;
+  p.hp_all = SAVE ? (T*)(ws + g->hp_all) : nullptr;
   p.cnt = (unsigned*)(ws + g->seq_cnt);
   p.err = g->err.host;
   p.B = g->B; p.T = g->T;
   RGP_REQUIRE(g->np == FCS_NP && g->zr.K == FCS_NP && g->c.K == FCS_NP && g->zr.chunk_major == 0 && g->c.chunk_major == 0,
-              "fcgru_seq: unexpected filter packing");
-  void (*kern)(typename FcSeqParamsOf<STREAM>::type) = nullptr;
-  switch ((g->B + 15) / 16) {
-    case 1: kern = fcgru_seq_kernel<1, SAVE, STREAM>; break;
-    case 2: kern = fcgru_seq_kernel<2, SAVE, STREAM>; break;
-    case 3: kern = fcgru_seq_kernel<3, SAVE, STREAM>; break;
-    case 4: kern = fcgru_seq_kernel<4, SAVE, STREAM>; break;
-    default: return set_err(RGP_EINVAL, "fcgru_seq: batch %d", g->B);
-  }
-  PersistentLaunch guard(s);
-  RGP_TRY(guard.status());
-  kern<<<FCS_MEMBERS, SEQ_NT, 0, s>>>(p);
-  RGP_HIP(hipGetLastError());
-  return guard.commit();
+              "%s: unexpected filter packing", name);
+  return launch_members(name, p, [](auto nf) { return FcPersist<T>::template seq<decltype(nf)::value, SAVE, STREAM>(); }, s);
 }
-
-// The same for f32 plans (RGP_FCGRU_PERSISTENT_F32, fcgru_seq_f32.hip.h): the exchange rows are the plan's fp32 operand rows.
-template <bool SAVE, bool STREAM>
-int seq_persistent_f32(rgp_fcgru* g, hipStream_t s) {
-  char* ws = g->ws;
-  RGP_HIP(hipMemsetAsync(ws + g->seq_cnt, 0, (size_t)2 * g->T * FCS_SHARDS * FCS_CNT_STRIDE * 4, s));         // phase counters: zeroed EVERY call
-  typename FcSeq32ParamsOf<STREAM>::type p;
-  if constexpr (STREAM) {
-    p.seed = (const float*)(ws + (SAVE ? g->hp_all : g->hp));
-    p.seed_stride = (unsigned)((SAVE ? g->T + 1 : 1) * FCS32_ROW);
-    p.seed_bytes = (unsigned)g->B * p.seed_stride;       // (B <= 64, T <= 8192: below 2^32, as hbytes)
-    p.hsnap = SAVE ? nullptr : (float*)(ws + g->hsnap);
-    p.n_valid = g->stream.n_valid;
-  }
-  p.w_zr = (const float*)(ws + g->zr.w_off);
-  p.w_c = (const float*)(ws + g->c.w_off);
-  p.xpre = (const float*)(ws + g->xpre);
-  p.hrows = (float*)(ws + g->hrows);
-  p.rh = (float*)(ws + (SAVE ? g->rh_all : g->rh));
-  p.hall = (float*)(ws + (SAVE ? g->hall_t : g->hall));
-  p.uall = SAVE ? (float*)(ws + g->uall) : nullptr;
-  p.rall = SAVE ? (float*)(ws + g->rall) : nullptr;
-  p.call = SAVE ? (float*)(ws + g->call) : nullptr;
-  p.hp_all = SAVE ? (float*)(ws + g->hp_all) : nullptr;
-  p.cnt = (unsigned*)(ws + g->seq_cnt);
-  p.err = g->err.host;
-  p.B = g->B; p.T = g->T;
-  RGP_REQUIRE(g->np == FCS_NP && g->zr.K == FCS_NP && g->c.K == FCS_NP && g->zr.chunk_major == 0 && g->c.chunk_major == 0,
-              "fcgru_seq_f32: unexpected filter packing");
-  void (*kern)(typename FcSeq32ParamsOf<STREAM>::type) = nullptr;
-  switch ((g->B + 15) / 16) {
-    case 1: kern = fcgru_seq_f32_kernel<1, SAVE, STREAM>; break;
-    case 2: kern = fcgru_seq_f32_kernel<2, SAVE, STREAM>; break;
-    case 3: kern = fcgru_seq_f32_kernel<3, SAVE, STREAM>; break;
-    case 4: kern = fcgru_seq_f32_kernel<4, SAVE, STREAM>; break;
-    default: return set_err(RGP_EINVAL, "fcgru_seq_f32: batch %d", g->B);
-  }
-  PersistentLaunch guard(s);
-  RGP_TRY(guard.status());
-  kern<<<FCS_MEMBERS, SEQ_NT, 0, s>>>(p);
-  RGP_HIP(hipGetLastError());
-  return guard.commit();
-}
-
 template <typename T>
 int forward_impl(rgp_fcgru* g, const float* c3d_input, float* logits, float* probs, hipStream_t s) {
   char* ws = g->ws;
@@ -276,30 +258,15 @@ int forward_impl(rgp_fcgru* g, const float* c3d_input, float* logits, float* pro
   StreamCall& sc = g->stream;
   RGP_TRY(gru_seed_or_zero<T>(sc, sc.in, d, g->n, nullptr, save, s));
   const int n_valid = sc.on ? sc.n_valid : T_;
-  bool one_launch = false;
-  if constexpr (sizeof(T) == 2) {
-    if (g->persistent) {
-      // STREAM = false: zero state (and, inference plans, every step kept: the ping-pong then ends on h behind step T)
-      const bool stream_kernel = sc.carry() || (!save && n_valid < T_);
-      if (stream_kernel) RGP_TRY(save ? (seq_persistent<true, true>(g, s)) : (seq_persistent<false, true>(g, s)));
-      else RGP_TRY(save ? (seq_persistent<true, false>(g, s)) : (seq_persistent<false, false>(g, s)));
-      if (sc.on)
-        RGP_TRY(gru_state_out(save ? d.hall + (size_t)n_valid * st : stream_kernel ? (const float*)(ws + g->hsnap) : d.hall + (size_t)(T_ & 1) * st,
-                              sc.out, lin, d, g->n, s));
-      one_launch = true;
-    }
-  } else {
-    if (g->persistent) {                                   // RGP_FCGRU_PERSISTENT_F32: the same choice of kernel and of state source
-      const bool stream_kernel = sc.carry() || (!save && n_valid < T_);
-      if (stream_kernel) RGP_TRY(save ? (seq_persistent_f32<true, true>(g, s)) : (seq_persistent_f32<false, true>(g, s)));
-      else RGP_TRY(save ? (seq_persistent_f32<true, false>(g, s)) : (seq_persistent_f32<false, false>(g, s)));
-      if (sc.on)
-        RGP_TRY(gru_state_out(save ? d.hall + (size_t)n_valid * st : stream_kernel ? (const float*)(ws + g->hsnap) : d.hall + (size_t)(T_ & 1) * st,
-                              sc.out, lin, d, g->n, s));
-      one_launch = true;
-    }
-  }
-  if (!one_launch)
+  if (g->persistent) {                                     // (RGP_FCGRU_PERSISTENT / RGP_FCGRU_PERSISTENT_F32: the flag fixed the dtype)
+    // STREAM = false: zero state (and, inference plans, every step kept: the ping-pong then ends on h behind step T)
+    const bool stream_kernel = sc.carry() || (!save && n_valid < T_);
+    if (stream_kernel) RGP_TRY(save ? (seq_persistent<T, true, true>(g, s)) : (seq_persistent<T, false, true>(g, s)));
+    else RGP_TRY(save ? (seq_persistent<T, true, false>(g, s)) : (seq_persistent<T, false, false>(g, s)));
+    if (sc.on)
+      RGP_TRY(gru_state_out(save ? d.hall + (size_t)n_valid * st : stream_kernel ? (const float*)(ws + g->hsnap) : d.hall + (size_t)(T_ & 1) * st,
+                            sc.out, lin, d, g->n, s));
+  } else
     RGP_TRY((run_gru_steps<T, 1>(d, ws, s, [](int) { return RGP_OK; }, [&](int t, const float* h_next) -> int {
       return sc.on && t + 1 == n_valid ? gru_state_out(h_next, sc.out, lin, d, g->n, s) : RGP_OK;   // (the ring slot is rewritten two steps on)
     })));
@@ -436,72 +403,27 @@ __global__ __launch_bounds__(256) void fc_unpack_kernel(const float* __restrict_
   }
 }
 
-// Step 2 of backward_impl for all T steps in one persistent launch (fcgru_bptt.hip.h)
-int bptt_persistent_launch(rgp_fcgru* g, hipStream_t s) {
+// Step 2 of backward_impl for all T steps in one persistent launch (fcgru_bptt.hip.h / fcgru_bptt_f32.hip.h)
+template <typename T>
+int bptt_persistent(rgp_fcgru* g, hipStream_t s) {
   char* ws = g->ws;
-  RGP_HIP(hipMemsetAsync(ws + g->bptt_cnt, 0, (size_t)2 * g->T * FCS_SHARDS * FCS_CNT_STRIDE * 4, s));        // phase counters: zeroed EVERY call
-  FcBpttParams p;
-  p.b_c = (const bf16_t*)(ws + g->b_c.w_off);
-  p.b_zr = (const bf16_t*)(ws + g->b_zr.w_off);
+  const char* name = FcPersist<T>::bptt_name;
+  FcBpttParamsT<T> p;
+  p.b_c = (const T*)(ws + g->b_c.w_off);
+  p.b_zr = (const T*)(ws + g->b_zr.w_off);
   p.dh_head = (const float*)(ws + g->dh_head);
   p.hall = (const float*)(ws + g->hall_t);
   p.uall = (const float*)(ws + g->uall);
   p.rall = (const float*)(ws + g->rall);
   p.call = (const float*)(ws + g->call);
-  p.dxpre = (bf16_t*)(ws + g->dxpre);
+  p.dxpre = (T*)(ws + g->dxpre);
   p.carry = (float*)(ws + g->carry);
   p.cnt = (unsigned*)(ws + g->bptt_cnt);
   p.err = g->err.host;
   p.B = g->B; p.T = g->T;
   RGP_REQUIRE(g->np == FCS_NP && g->b_c.K == FCS_NP && g->b_zr.K == 2 * FCS_NP && g->b_c.chunk_major == 0 && g->b_zr.chunk_major == 0,
-              "fcgru_bptt: unexpected filter packing");
-  void (*kern)(FcBpttParams) = nullptr;
-  switch ((g->B + 15) / 16) {
-    case 1: kern = fcgru_bptt_kernel<1>; break;
-    case 2: kern = fcgru_bptt_kernel<2>; break;
-    case 3: kern = fcgru_bptt_kernel<3>; break;
-    case 4: kern = fcgru_bptt_kernel<4>; break;
-    default: return set_err(RGP_EINVAL, "fcgru_bptt: batch %d", g->B);
-  }
-  PersistentLaunch guard(s);
-  RGP_TRY(guard.status());
-  kern<<<FCS_MEMBERS, SEQ_NT, 0, s>>>(p);
-  RGP_HIP(hipGetLastError());
-  return guard.commit();
-}
-
-// The same for f32 plans (RGP_FCGRU_BPTT_PERSISTENT_F32, fcgru_bptt_f32.hip.h): the exchange rows are the plan's fp32 dxpre rows.
-int bptt_persistent_f32_launch(rgp_fcgru* g, hipStream_t s) {
-  char* ws = g->ws;
-  RGP_HIP(hipMemsetAsync(ws + g->bptt_cnt, 0, (size_t)2 * g->T * FCS_SHARDS * FCS_CNT_STRIDE * 4, s));        // phase counters: zeroed EVERY call
-  FcBptt32Params p;
-  p.b_c = (const float*)(ws + g->b_c.w_off);
-  p.b_zr = (const float*)(ws + g->b_zr.w_off);
-  p.dh_head = (const float*)(ws + g->dh_head);
-  p.hall = (const float*)(ws + g->hall_t);
-  p.uall = (const float*)(ws + g->uall);
-  p.rall = (const float*)(ws + g->rall);
-  p.call = (const float*)(ws + g->call);
-  p.dxpre = (float*)(ws + g->dxpre);
-  p.carry = (float*)(ws + g->carry);
-  p.cnt = (unsigned*)(ws + g->bptt_cnt);
-  p.err = g->err.host;
-  p.B = g->B; p.T = g->T;
-  RGP_REQUIRE(g->np == FCS_NP && g->b_c.K == FCS_NP && g->b_zr.K == 2 * FCS_NP && g->b_c.chunk_major == 0 && g->b_zr.chunk_major == 0,
-              "fcgru_bptt_f32: unexpected filter packing");
-  void (*kern)(FcBptt32Params) = nullptr;
-  switch ((g->B + 15) / 16) {
-    case 1: kern = fcgru_bptt_f32_kernel<1>; break;
-    case 2: kern = fcgru_bptt_f32_kernel<2>; break;
-    case 3: kern = fcgru_bptt_f32_kernel<3>; break;
-    case 4: kern = fcgru_bptt_f32_kernel<4>; break;
-    default: return set_err(RGP_EINVAL, "fcgru_bptt_f32: batch %d", g->B);
-  }
-  PersistentLaunch guard(s);
-  RGP_TRY(guard.status());
-  kern<<<FCS_MEMBERS, SEQ_NT, 0, s>>>(p);
-  RGP_HIP(hipGetLastError());
-  return guard.commit();
+              "%s: unexpected filter packing", name);
+  return launch_members(name, p, [](auto nf) { return FcPersist<T>::template bptt<decltype(nf)::value>(); }, s);
 }
 
 template <typename T>
@@ -540,19 +462,8 @@ int backward_impl(rgp_fcgru* g, const float* logits, const float* probs, const f
   }
   // 2. BPTT: one persistent launch (RGP_FCGRU_BPTT_PERSISTENT / RGP_FCGRU_BPTT_PERSISTENT_F32), or four launches per step
   const float* hall = Fp(g->hall_t);
-  bool one_launch = false;
-  if constexpr (sizeof(T) == 2) {
-    if (g->bptt_persistent) {
-      RGP_TRY(bptt_persistent_launch(g, s));
-      one_launch = true;
-    }
-  } else {
-    if (g->bptt_persistent) {
-      RGP_TRY(bptt_persistent_f32_launch(g, s));
-      one_launch = true;
-    }
-  }
-  for (int t = one_launch ? -1 : T_ - 1; t >= 0; --t) {
+  if (g->bptt_persistent) RGP_TRY(bptt_persistent<T>(g, s));
+  for (int t = g->bptt_persistent ? -1 : T_ - 1; t >= 0; --t) {
     const float* h_prev = hall + (size_t)t * st;
     fc_bwd1_kernel<T><<<nblk((long long)st), 256, 0, s>>>(Fp(g->dh_head), Fp(g->carry), h_prev, Fp(g->uall) + (size_t)t * st,
                                                          Fp(g->call) + (size_t)t * st, Tp(g->dxpre), Tp(g->dcp), B, T_, t, np, t == T_ - 1);
@@ -670,69 +581,50 @@ int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazem
   RGP_REQUIRE((gazemap_h == 49 && gazemap_w == 49) || (gazemap_h == 7 && gazemap_w == 7),
               "rgp_fcgru_create: gaze map %dx%d (reference uses 49x49 or 7x7)", gazemap_h, gazemap_w);
   RGP_REQUIRE(dtype == RGP_F32 || dtype == RGP_BF16, "rgp_fcgru_create: dtype %d", dtype);
-  if (flags & RGP_FCGRU_BPTT_PERSISTENT_F32) {
-    // the arguments (no device needed to refuse them); the device is asked below
-    RGP_REQUIRE(!(flags & RGP_FCGRU_BPTT_PERSISTENT),
-                "rgp_fcgru_create: flags name both persistent BPTT kernels (RGP_FCGRU_BPTT_PERSISTENT_F32 with RGP_FCGRU_BPTT_PERSISTENT)");
-    RGP_REQUIRE(flags & RGP_FCGRU_SAVE_FOR_BACKWARD, "rgp_fcgru_create: the persistent f32 BPTT kernel (flags) needs RGP_FCGRU_SAVE_FOR_BACKWARD");
-    RGP_REQUIRE(dtype == RGP_F32, "rgp_fcgru_create: the persistent f32 BPTT kernel (flags) takes f32 plans, dtype is %d", dtype);
-    RGP_REQUIRE(batch <= 64, "rgp_fcgru_create: the persistent f32 BPTT kernel (flags) takes at most 64 clips, batch is %d", batch);
-    // the kernel addresses the fp32 dxpre rows with 32-bit byte offsets, those of the rows >= B of the last 16-row fragment
-    // included (they have to land BEHIND the buffer to read zeros, not wrap): (B16 T + 1) rows of 3 * 1664 * 4 bytes must
-    // stay below 2^32 (B = 64: T <= 3360)
-    RGP_REQUIRE(((long long)((batch + 15) / 16 * 16) * n_steps + 1) * (long long)FCB32_ROW < (1LL << 32),
-                "rgp_fcgru_create: the persistent f32 BPTT kernel (flags) addresses (batch16 * n_steps + 1) * %u bytes with 32-bit offsets: "
-                "batch %d (rounded up to 16) x n_steps %d is past 2^32", FCB32_ROW, batch, n_steps);
+  RGP_REQUIRE((flags & (RGP_FCGRU_BPTT_PERSISTENT | RGP_FCGRU_BPTT_PERSISTENT_F32)) != (RGP_FCGRU_BPTT_PERSISTENT | RGP_FCGRU_BPTT_PERSISTENT_F32),
+              "rgp_fcgru_create: flags name both persistent BPTT kernels (RGP_FCGRU_BPTT_PERSISTENT_F32 with RGP_FCGRU_BPTT_PERSISTENT)");
+  // The four persistent kinds, in the order their arguments are refused (at most one BPTT kind and one forward kind get
+  // here).  No device is needed to refuse an argument; the device is asked once, behind all of them.
+  struct Kind { int flag; const char* noun; int dtype; const char* plans; bool training; int max_steps; };
+  // max_steps: the forward kernels address their exchange rows with 32-bit byte offsets, those of the up to 64 rows of the last
+  // row fragment included: 64 * T * np * 2 bytes below 2^32 is T < 20 165, 64 * T * np * 4 is T <= 10081, both rounded down
+  static const Kind kinds[] = {
+    {RGP_FCGRU_BPTT_PERSISTENT_F32, "persistent f32 BPTT kernel", RGP_F32, "f32", true, 0},
+    {RGP_FCGRU_BPTT_PERSISTENT, "persistent BPTT kernel", RGP_BF16, "bf16", true, 0},
+    {RGP_FCGRU_PERSISTENT, "persistent kernel", RGP_BF16, "bf16", false, 16384},
+    {RGP_FCGRU_PERSISTENT_F32, "persistent f32 kernel", RGP_F32, "f32", false, 8192},
+  };
+  const Kind* last = nullptr;
+  for (const Kind& k : kinds) {
+    if (!(flags & k.flag)) continue;
+    last = &k;
+    if (k.training) RGP_REQUIRE(flags & RGP_FCGRU_SAVE_FOR_BACKWARD, "rgp_fcgru_create: the %s (flags) needs RGP_FCGRU_SAVE_FOR_BACKWARD", k.noun);
+    RGP_REQUIRE(dtype == k.dtype, "rgp_fcgru_create: the %s (flags) takes %s plans, dtype is %d", k.noun, k.plans, dtype);
+    RGP_REQUIRE(batch <= 64, "rgp_fcgru_create: the %s (flags) takes at most 64 clips, batch is %d", k.noun, batch);
+    if (k.max_steps)
+      RGP_REQUIRE(n_steps <= k.max_steps, "rgp_fcgru_create: the %s (flags) takes at most %d steps, n_steps is %d", k.noun, k.max_steps, n_steps);
+    if (!k.training) continue;
+    // The BPTT kernels address the dxpre rows with 32-bit byte offsets, those of the rows >= B of the last 16-row fragment
+    // included (they have to land BEHIND the buffer to read zeros, not wrap): (B16 T + 1) rows of 3 * 1664 * 2 or 4 bytes must
+    // stay below 2^32 (B = 64: T <= 6721, f32 T <= 3360).  Written out: the bf16 kind words its two limits in its own way.
+    const long long rows16 = (long long)((batch + 15) / 16 * 16) * n_steps + 1;
+    if (k.dtype == RGP_F32) {
+      RGP_REQUIRE(rows16 * (long long)FCB32_ROW < (1LL << 32),
+                  "rgp_fcgru_create: the persistent f32 BPTT kernel (flags) addresses (batch16 * n_steps + 1) * %u bytes with 32-bit offsets: "
+                  "batch %d (rounded up to 16) x n_steps %d is past 2^32", FCB32_ROW, batch, n_steps);
+    } else {
+      RGP_REQUIRE(((long long)batch * n_steps + 1) * (long long)FCB_ROW < (1LL << 32),
+                  "rgp_fcgru_create: the persistent BPTT kernel (flags) addresses (batch * n_steps + 1) * %u bytes with 32-bit offsets: "
+                  "batch %d x n_steps %d is past 2^32", FCB_ROW, batch, n_steps);
+      RGP_REQUIRE(rows16 * (long long)FCB_ROW < (1LL << 32),
+                  "rgp_fcgru_create: the persistent BPTT kernel (flags) addresses whole 16-clip fragments with 32-bit offsets: "
+                  "batch %d (rounded up to 16) x n_steps %d is past 2^32", batch, n_steps);
+    }
   }
-  if (flags & RGP_FCGRU_BPTT_PERSISTENT) {
-    // the arguments (no device needed to refuse them); the device is asked below, behind the forward's argument checks
-    RGP_REQUIRE(flags & RGP_FCGRU_SAVE_FOR_BACKWARD, "rgp_fcgru_create: the persistent BPTT kernel (flags) needs RGP_FCGRU_SAVE_FOR_BACKWARD");
-    RGP_REQUIRE(dtype == RGP_BF16, "rgp_fcgru_create: the persistent BPTT kernel (flags) takes bf16 plans, dtype is %d", dtype);
-    RGP_REQUIRE(batch <= 64, "rgp_fcgru_create: the persistent BPTT kernel (flags) takes at most 64 clips, batch is %d", batch);
-    // the kernel addresses the dxpre rows with 32-bit byte offsets: (B T + 1) rows of 3 * 1664 * 2 bytes must stay below 2^32
-    // (B = 64: T <= 6721), and so must the offsets of the rows >= B of the last 16-row fragment, which have to land BEHIND the
-    // buffer to read zeros
-    RGP_REQUIRE(((long long)batch * n_steps + 1) * (long long)FCB_ROW < (1LL << 32),
-                "rgp_fcgru_create: the persistent BPTT kernel (flags) addresses (batch * n_steps + 1) * %u bytes with 32-bit offsets: "
-                "batch %d x n_steps %d is past 2^32", FCB_ROW, batch, n_steps);
-    RGP_REQUIRE(((long long)((batch + 15) / 16 * 16) * n_steps + 1) * (long long)FCB_ROW < (1LL << 32),
-                "rgp_fcgru_create: the persistent BPTT kernel (flags) addresses whole 16-clip fragments with 32-bit offsets: "
-                "batch %d (rounded up to 16) x n_steps %d is past 2^32", batch, n_steps);
-  }
-  if (flags & RGP_FCGRU_PERSISTENT) {
-    // the arguments first (no device needed to refuse them), then the device
-    RGP_REQUIRE(dtype == RGP_BF16, "rgp_fcgru_create: the persistent kernel (flags) takes bf16 plans, dtype is %d", dtype);
-    RGP_REQUIRE(batch <= 64, "rgp_fcgru_create: the persistent kernel (flags) takes at most 64 clips, batch is %d", batch);
-    // the kernel addresses its exchange rows with 32-bit byte offsets, those of the up to 64 rows of the last row fragment
-    // included: 64 * T * np * 2 bytes must stay below 2^32 (T < 20 165)
-    RGP_REQUIRE(n_steps <= 16384, "rgp_fcgru_create: the persistent kernel (flags) takes at most 16384 steps, n_steps is %d", n_steps);
+  if (last) {                                              // (a plan with both passes persistent: the message names the forward's kernel)
     int n_cu = 0;
     RGP_TRY(device_cu_count(&n_cu));
-    RGP_REQUIRE(n_cu >= FCS_MEMBERS, "rgp_fcgru_create: the persistent kernel (flags) needs %d CUs resident together, the device has %d",
-                FCS_MEMBERS, n_cu);
-  }
-  if (flags & RGP_FCGRU_PERSISTENT_F32) {
-    // the arguments first (no device needed to refuse them), then the device
-    RGP_REQUIRE(dtype == RGP_F32, "rgp_fcgru_create: the persistent f32 kernel (flags) takes f32 plans, dtype is %d", dtype);
-    RGP_REQUIRE(batch <= 64, "rgp_fcgru_create: the persistent f32 kernel (flags) takes at most 64 clips, batch is %d", batch);
-    // 32-bit byte offsets into the fp32 exchange rows, those of the up to 64 rows of the last row fragment included:
-    // 64 * T * np * 4 bytes must stay below 2^32 (T <= 10081), rounded down as the bf16 kernel's limit is
-    RGP_REQUIRE(n_steps <= 8192, "rgp_fcgru_create: the persistent f32 kernel (flags) takes at most 8192 steps, n_steps is %d", n_steps);
-    int n_cu = 0;
-    RGP_TRY(device_cu_count(&n_cu));
-    RGP_REQUIRE(n_cu >= FCS_MEMBERS, "rgp_fcgru_create: the persistent f32 kernel (flags) needs %d CUs resident together, the device has %d",
-                FCS_MEMBERS, n_cu);
-  }
-  if (flags & RGP_FCGRU_BPTT_PERSISTENT) {
-    int n_cu = 0;
-    RGP_TRY(device_cu_count(&n_cu));
-    RGP_REQUIRE(n_cu >= FCS_MEMBERS, "rgp_fcgru_create: the persistent BPTT kernel (flags) needs %d CUs resident together, the device has %d",
-                FCS_MEMBERS, n_cu);
-  }
-  if (flags & RGP_FCGRU_BPTT_PERSISTENT_F32) {
-    int n_cu = 0;
-    RGP_TRY(device_cu_count(&n_cu));
-    RGP_REQUIRE(n_cu >= FCS_MEMBERS, "rgp_fcgru_create: the persistent f32 BPTT kernel (flags) needs %d CUs resident together, the device has %d",
+    RGP_REQUIRE(n_cu >= FCS_MEMBERS, "rgp_fcgru_create: the %s (flags) needs %d CUs resident together, the device has %d", last->noun,
                 FCS_MEMBERS, n_cu);
   }
   rgp_fcgru* g = new rgp_fcgru();
@@ -765,7 +657,7 @@ int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazem
   g->xbias = a.take((size_t)3 * np * 4);
   g->ones = a.take((size_t)np * 4);
   g->zeros = a.take((size_t)np * 4);
-  if (g->persistent) g->seq_cnt = a.take((size_t)2 * n_steps * FCS_SHARDS * FCS_CNT_STRIDE * 4);
+  if (g->persistent) g->seq_cnt = a.take(fc_cnt_bytes(n_steps));
   if (g->persistent && !g->save) g->hsnap = a.take((size_t)batch * np * 4);
   if (g->save) {
     const size_t st = (size_t)batch * np;
@@ -791,7 +683,7 @@ int rgp_fcgru_create_flags(rgp_fcgru_t** plan, int batch, int n_steps, int gazem
     g->dwx = a.take((size_t)Kx * 3 * np * 4);
     g->dwh = a.take((size_t)np * 2 * np * 4);
     g->dwc = a.take((size_t)np * np * 4);
-    if (g->bptt_persistent) g->bptt_cnt = a.take((size_t)2 * n_steps * FCS_SHARDS * FCS_CNT_STRIDE * 4);
+    if (g->bptt_persistent) g->bptt_cnt = a.take(fc_cnt_bytes(n_steps));
   }
   g->ws_bytes = a.off;
   *plan = g;

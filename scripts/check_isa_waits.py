@@ -31,10 +31,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'recurrent_gaze_prediction_amd', 'csrc')
 
 
-def kernels(asm):
+def kernels_named(asm, prefix, contains=''):
+    """(symbol, body lines up to s_endpgm) of every kernel whose symbol starts with prefix (or one of a tuple) and contains `contains`."""
     lines = asm.split('\n')
     for st, l in enumerate(lines):
-        if (l.startswith('_ZN3rgp20igemm_stagger_kernel') or l.startswith('_ZN3rgp17igemm_wide_kernel')) and '@' in l:
+        if l.startswith(prefix) and contains in l and '@' in l:
             end = next(i for i in range(st, len(lines)) if 's_endpgm' in lines[i])
             yield l.split(':')[0], lines[st:end]
 
@@ -54,14 +55,6 @@ def stray_waits(body):
         else:
             i += 1
     return bad
-
-
-def wgrad_patch_kernels(asm):
-    lines = asm.split('\n')
-    for st, l in enumerate(lines):
-        if l.startswith('_ZN3rgpL23wgrad_patch_bf16_kernel') and '@' in l:
-            end = next(i for i in range(st, len(lines)) if 's_endpgm' in lines[i])
-            yield l.split(':')[0], lines[st:end]
 
 
 def wgrad_patch_faults(body):
@@ -85,14 +78,6 @@ def wgrad_patch_faults(body):
     return faults
 
 
-def patch_kernels(asm):
-    lines = asm.split('\n')
-    for st, l in enumerate(lines):
-        if l.startswith('_ZN3rgpL') and 'conv_patch' in l and '@' in l:
-            end = next(i for i in range(st, len(lines)) if 's_endpgm' in lines[i])
-            yield l.split(':')[0], lines[st:end]
-
-
 def patch_faults(name, body):
     """conv_patch*.hip.h: no scratch access between the first and the last MFMA (a reload there waits on vmcnt and with it
     on the LDS-DMA ring), and -- inference kernels (no arg-max codes) -- none behind the last MFMA either: the round-3
@@ -109,42 +94,30 @@ def patch_faults(name, body):
     return faults
 
 
-def fcgru_kernels(asm):
-    lines = asm.split('\n')
-    for st, l in enumerate(lines):
-        if l.startswith('_ZN3rgpL16fcgru_seq_kernel') and '@' in l:
-            end = next(i for i in range(st, len(lines)) if 's_endpgm' in lines[i])
-            yield l.split(':')[0], lines[st:end]
-
-
-def fcgru_faults(name, body):
-    """Runs of sc1 exchange loads and of MFMAs, in program order: exactly [13 NF loads, 13 NF MFMAs] twice."""
-    nf = int(name.split('fcgru_seq_kernelILi')[1][0])
-    runs = []
+def exchange_runs(body, mfma):
+    """Runs of sc1 sixteen-byte exchange loads ('L') and of `mfma` instructions ('M') in program order -> (runs, faults); the
+    faults are exchange loads narrower than 16 bytes and MFMAs of another kind."""
+    runs, faults = [], []
     for l in body:
-        k = 'L' if ('buffer_load_dwordx4' in l and 'sc1' in l) else 'M' if 'v_mfma' in l else None
+        k = 'L' if ('buffer_load_dwordx4' in l and 'sc1' in l) else 'M' if mfma in l else None
+        if k is None and 'buffer_load' in l and 'sc1' in l:
+            faults.append('exchange load narrower than 16 bytes: ' + l.strip())
+        if k is None and 'v_mfma' in l:
+            faults.append('an MFMA that is not %s: %s' % (mfma, l.strip()))
         if k and runs and runs[-1][0] == k:
             runs[-1][1] += 1
         elif k:
             runs.append([k, 1])
-    faults = []
-    if runs != [['L', 13 * nf], ['M', 13 * nf]] * 2:
-        faults.append('loads / MFMAs interleaved: ' + ' '.join('%s%d' % (k, n) for k, n in runs))
-    if any('scratch_' in l for l in body):
-        faults.append('scratch access')
-    return faults
+    return runs, faults
 
 
-def fcgru_f32_kernels(asm):
-    lines = asm.split('\n')
-    for st, l in enumerate(lines):
-        if l.startswith('_ZN3rgpL20fcgru_seq_f32_kernel') and '@' in l:
-            end = next(i for i in range(st, len(lines)) if 's_endpgm' in lines[i])
-            yield l.split(':')[0], lines[st:end]
+def bf16_phase(nf):
+    """fcs_gemm: all 13 NF loads of a phase in front of its 13 NF MFMAs."""
+    return [['L', 13 * nf], ['M', 13 * nf]]
 
 
-def fcgru_f32_expected(nf):
-    """Runs of one phase: the ring of two fragment buffers of fcs32_gemm."""
+def f32_phase(nf):
+    """fcs32_gemm: the ring of two fragment buffers."""
     if nf <= 2:
         return [['L', 26 * nf], ['M', 104 * nf]]
     runs = [['L', 52], ['M', 104]]
@@ -153,137 +126,55 @@ def fcgru_f32_expected(nf):
     return runs
 
 
-def fcgru_f32_faults(name, body):
-    """Runs of sc1 exchange loads and of MFMAs in program order against fcgru_f32_expected, twice (phase A, phase B)."""
-    nf = int(name.split('fcgru_seq_f32_kernelILi')[1][0])
-    runs = []
-    faults = []
-    for l in body:
-        k = 'L' if ('buffer_load_dwordx4' in l and 'sc1' in l) else 'M' if 'v_mfma_f32_16x16x4_f32' in l else None
-        if k is None and 'buffer_load' in l and 'sc1' in l:
-            faults.append('exchange load narrower than 16 bytes: ' + l.strip())
-        if k and runs and runs[-1][0] == k:
-            runs[-1][1] += 1
-        elif k:
-            runs.append([k, 1])
-    if runs != fcgru_f32_expected(nf) * 2:
-        faults.append('load groups not in front of their MFMAs: ' + ' '.join('%s%d' % (k, n) for k, n in runs))
+# (kernel, symbol prefix, instantiations, MFMA, runs of one phase, phases per kernel, what the summary line calls a fault)
+BF16_WHAT = 'with exchange loads not in front of their MFMAs, or spills'
+F32_WHAT = 'with a load group not in front of its MFMAs, narrow loads or spills'
+FCGRU_RULES = [
+    ('fcgru_seq', '_ZN3rgpL16fcgru_seq_kernel', 16, 'v_mfma_f32_16x16x32_bf16', bf16_phase, 2, BF16_WHAT),
+    ('fcgru_bptt', '_ZN3rgpL17fcgru_bptt_kernel', 4, 'v_mfma_f32_16x16x32_bf16', bf16_phase, 3, BF16_WHAT),
+    ('fcgru_seq_f32', '_ZN3rgpL20fcgru_seq_f32_kernel', 16, 'v_mfma_f32_16x16x4_f32', f32_phase, 2, F32_WHAT),
+    ('fcgru_bptt_f32', '_ZN3rgpL21fcgru_bptt_f32_kernel', 4, 'v_mfma_f32_16x16x4_f32', f32_phase, 3, F32_WHAT),
+]
+
+
+def fcgru_faults(name, body, kernel, mfma, phase, n_phases):
+    nf = int(name.split(kernel + '_kernelILi')[1][0])
+    runs, faults = exchange_runs(body, mfma)
+    if runs != phase(nf) * n_phases:
+        faults.append('loads not in front of their MFMAs: ' + ' '.join('%s%d' % (k, n) for k, n in runs))
     if any('scratch_' in l for l in body):
         faults.append('scratch access')
     return faults[:3]
 
 
-def fcgru_bptt_f32_kernels(asm):
-    lines = asm.split('\n')
-    for st, l in enumerate(lines):
-        if l.startswith('_ZN3rgpL21fcgru_bptt_f32_kernel') and '@' in l:
-            end = next(i for i in range(st, len(lines)) if 's_endpgm' in lines[i])
-            yield l.split(':')[0], lines[st:end]
-
-
-def fcgru_bptt_f32_faults(name, body):
-    """As fcgru_f32_faults, for the three fcs32_gemm passes of a BPTT step: the runs of fcgru_f32_expected three times."""
-    nf = int(name.split('fcgru_bptt_f32_kernelILi')[1][0])
-    runs = []
-    faults = []
-    for l in body:
-        k = 'L' if ('buffer_load_dwordx4' in l and 'sc1' in l) else 'M' if 'v_mfma_f32_16x16x4_f32' in l else None
-        if k is None and 'buffer_load' in l and 'sc1' in l:
-            faults.append('exchange load narrower than 16 bytes: ' + l.strip())
-        if k is None and 'v_mfma' in l:
-            faults.append('an MFMA that is not v_mfma_f32_16x16x4_f32: ' + l.strip())
-        if k and runs and runs[-1][0] == k:
-            runs[-1][1] += 1
-        elif k:
-            runs.append([k, 1])
-    if runs != fcgru_f32_expected(nf) * 3:
-        faults.append('load groups not in front of their MFMAs: ' + ' '.join('%s%d' % (k, n) for k, n in runs))
-    if any('scratch_' in l for l in body):
-        faults.append('scratch access')
-    return faults[:3]
-
-
-def fcgru_bptt_kernels(asm):
-    lines = asm.split('\n')
-    for st, l in enumerate(lines):
-        if l.startswith('_ZN3rgpL17fcgru_bptt_kernel') and '@' in l:
-            end = next(i for i in range(st, len(lines)) if 's_endpgm' in lines[i])
-            yield l.split(':')[0], lines[st:end]
-
-
-def fcgru_bptt_faults(name, body):
-    """As fcgru_faults, for the three fcs_gemm calls of a BPTT step: exactly [13 NF loads, 13 NF MFMAs] three times."""
-    nf = int(name.split('fcgru_bptt_kernelILi')[1][0])
-    runs = []
-    for l in body:
-        k = 'L' if ('buffer_load_dwordx4' in l and 'sc1' in l) else 'M' if 'v_mfma' in l else None
-        if k and runs and runs[-1][0] == k:
-            runs[-1][1] += 1
-        elif k:
-            runs.append([k, 1])
-    faults = []
-    if runs != [['L', 13 * nf], ['M', 13 * nf]] * 3:
-        faults.append('loads / MFMAs interleaved: ' + ' '.join('%s%d' % (k, n) for k, n in runs))
-    if any('scratch_' in l for l in body):
-        faults.append('scratch access')
-    return faults
+def compile_asm(tu):
+    with tempfile.NamedTemporaryFile(suffix='.s') as tf:
+        subprocess.run(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-I' + os.path.join(ROOT, 'include'),
+                        '-I' + CSRC, '-S', '--cuda-device-only', '-o', tf.name, os.path.join(CSRC, tu)], check=True,
+                       stderr=subprocess.DEVNULL)
+        return open(tf.name).read()
 
 
 def main():
     rc = 0
-    with tempfile.NamedTemporaryFile(suffix='.s') as tf:
-        subprocess.run(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-I' + os.path.join(ROOT, 'include'),
-                        '-I' + CSRC, '-S', '--cuda-device-only', '-o', tf.name, os.path.join(CSRC, 'rgp_fcgru.hip')], check=True,
-                       stderr=subprocess.DEVNULL)
-        asm = open(tf.name).read()
-    n = nbad = n_stream = 0
-    for name, body in fcgru_kernels(asm):
-        n += 1
-        # <NF, SAVE, STREAM>: the streaming instantiations (rgp_fcgru_forward_stream) run phase A of step 0 on the seeded rows
-        # through the same fcs_gemm call, so the same two [loads, MFMAs] runs are expected of them
-        n_stream += name.split('fcgru_seq_kernelILi')[1][1:].startswith('ELb0ELb1E') or \
-            name.split('fcgru_seq_kernelILi')[1][1:].startswith('ELb1ELb1E')
-        faults = fcgru_faults(name, body)
-        if faults:
-            nbad += 1
-            print('FCGRU_SEQ', name[:100], faults)
-    print('rgp_fcgru.hip: %d fcgru_seq kernels (%d streaming), %d with exchange loads not in front of their MFMAs, or spills' %
-          (n, n_stream, nbad))
-    rc |= nbad > 0 or n != 16 or n_stream != 8
+    asm = compile_asm('rgp_fcgru.hip')
+    for kernel, prefix, count, mfma, phase, n_phases, what in FCGRU_RULES:
+        n = nbad = n_stream = 0
+        for name, body in kernels_named(asm, prefix):
+            n += 1
+            # <NF, SAVE, STREAM>: the streaming instantiations (rgp_fcgru_forward_stream) run phase A of step 0 on the seeded rows
+            # through the same GEMM call, so the same runs are expected of them
+            n_stream += name.split('_kernelILi')[1][5:].startswith('ELb1E')
+            faults = fcgru_faults(name, body, kernel, mfma, phase, n_phases)
+            if faults:
+                nbad += 1
+                print(kernel.upper(), name[:100], faults)
+        streaming = ' (%d streaming)' % n_stream if kernel == 'fcgru_seq' else ''
+        print('rgp_fcgru.hip: %d %s kernels%s, %d %s' % (n, kernel, streaming, nbad, what))
+        rc |= nbad > 0 or n != count or (kernel == 'fcgru_seq' and n_stream != 8)
+    asm = compile_asm('rgp_conv_patch.hip')
     n = nbad = 0
-    for name, body in fcgru_bptt_kernels(asm):
-        n += 1
-        faults = fcgru_bptt_faults(name, body)
-        if faults:
-            nbad += 1
-            print('FCGRU_BPTT', name[:100], faults)
-    print('rgp_fcgru.hip: %d fcgru_bptt kernels, %d with exchange loads not in front of their MFMAs, or spills' % (n, nbad))
-    rc |= nbad > 0 or n != 4
-    n = nbad = 0
-    for name, body in fcgru_f32_kernels(asm):
-        n += 1
-        faults = fcgru_f32_faults(name, body)
-        if faults:
-            nbad += 1
-            print('FCGRU_SEQ_F32', name[:100], faults)
-    print('rgp_fcgru.hip: %d fcgru_seq_f32 kernels, %d with a load group not in front of its MFMAs, narrow loads or spills' % (n, nbad))
-    rc |= nbad > 0 or n != 16
-    n = nbad = 0
-    for name, body in fcgru_bptt_f32_kernels(asm):
-        n += 1
-        faults = fcgru_bptt_f32_faults(name, body)
-        if faults:
-            nbad += 1
-            print('FCGRU_BPTT_F32', name[:100], faults)
-    print('rgp_fcgru.hip: %d fcgru_bptt_f32 kernels, %d with a load group not in front of its MFMAs, narrow loads or spills' % (n, nbad))
-    rc |= nbad > 0 or n != 4
-    with tempfile.NamedTemporaryFile(suffix='.s') as tf:
-        subprocess.run(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-I' + os.path.join(ROOT, 'include'),
-                        '-I' + CSRC, '-S', '--cuda-device-only', '-o', tf.name, os.path.join(CSRC, 'rgp_conv_patch.hip')], check=True,
-                       stderr=subprocess.DEVNULL)
-        asm = open(tf.name).read()
-    n = nbad = 0
-    for name, body in patch_kernels(asm):
+    for name, body in kernels_named(asm, '_ZN3rgpL', 'conv_patch'):
         n += 1
         faults = patch_faults(name, body)
         if faults:
@@ -292,13 +183,9 @@ def main():
     print('rgp_conv_patch.hip: %d patch kernels, %d with scratch reloads in the K loop / an inference epilogue' % (n, nbad))
     rc |= nbad > 0
     for tu in ('rgp_c3d.hip', 'rgp_c3d_bwd.hip'):
-        with tempfile.NamedTemporaryFile(suffix='.s') as tf:
-            subprocess.run(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-I' + os.path.join(ROOT, 'include'),
-                            '-I' + CSRC, '-S', '--cuda-device-only', '-o', tf.name, os.path.join(CSRC, tu)], check=True,
-                           stderr=subprocess.DEVNULL)
-            asm = open(tf.name).read()
+        asm = compile_asm(tu)
         n = nbad = 0
-        for name, body in kernels(asm):
+        for name, body in kernels_named(asm, ('_ZN3rgp20igemm_stagger_kernel', '_ZN3rgp17igemm_wide_kernel')):
             n += 1
             bad = stray_waits(body)
             if bad:
@@ -307,7 +194,7 @@ def main():
         print('%s: %d staggered / wide kernels, %d with a compiler wait in front of the fragment reads' % (tu, n, nbad))
         rc |= nbad > 0
         nw = nwbad = 0
-        for name, body in wgrad_patch_kernels(asm):
+        for name, body in kernels_named(asm, '_ZN3rgpL23wgrad_patch_bf16_kernel'):
             nw += 1
             faults = wgrad_patch_faults(body)
             if faults:

@@ -45,6 +45,31 @@ def test_create_flags_refusals_name_the_argument(batch, dtype, flags, word, n_st
     assert rc == RGP_EINVAL and word in msg, (rc, msg)
 
 
+def test_refusals_of_the_four_persistent_kinds_come_in_one_order():
+    """The order of the refusals that rgp_fcgru_create_flags takes from its table of the four persistent kinds (flag, noun,
+    dtype, training plan or not): at batch 65, n_steps 2 every one of them is refused for an ARGUMENT, with RGP_EINVAL, before
+    the device is asked for its CU count (this runs without a device: a device error would be RGP_EHIP).  The two BPTT flags are
+    given with RGP_FCGRU_SAVE_FOR_BACKWARD, which they need ahead of everything else; without it that is what the message names."""
+    L = _lib
+    save = L.RGP_FCGRU_SAVE_FOR_BACKWARD
+    kinds = [(L.RGP_FCGRU_PERSISTENT, L.RGP_BF16, 0), (L.RGP_FCGRU_PERSISTENT_F32, L.RGP_F32, 0),
+             (L.RGP_FCGRU_BPTT_PERSISTENT, L.RGP_BF16, save), (L.RGP_FCGRU_BPTT_PERSISTENT_F32, L.RGP_F32, save)]
+    for flag, flag_dtype, needs in kinds:
+        for dtype in (L.RGP_BF16, L.RGP_F32):
+            lib, h, rc, msg = _create(65, dtype, flag | needs, 2)
+            # the right dtype: the batch; the wrong one: the dtype, which comes first
+            assert rc == RGP_EINVAL and ('batch' if dtype == flag_dtype else 'dtype') in msg, (flag, dtype, rc, msg)
+            assert ('batch' in msg) == (dtype == flag_dtype), (flag, dtype, msg)
+            if needs:
+                lib, h, rc, msg = _create(65, dtype, flag, 2)
+                assert rc == RGP_EINVAL and 'SAVE_FOR_BACKWARD' in msg and 'batch' not in msg, (flag, dtype, rc, msg)
+    # two flags for one pass: refused as naming both, whatever else is wrong with the call
+    for pair in (4 | 16, 2 | 16, 2 | 4, 8 | 32):
+        for dtype in (L.RGP_BF16, L.RGP_F32):
+            lib, h, rc, msg = _create(65, dtype, pair | save, 2)
+            assert rc == RGP_EINVAL and 'both' in msg, (pair, dtype, rc, msg)
+
+
 def test_per_step_plans_take_any_number_of_steps():
     lib, h, rc, msg = _create(1, _lib.RGP_BF16, _lib.RGP_FCGRU_PER_STEP, 16385)        # the limit is the persistent kernel's
     assert rc == 0, msg
