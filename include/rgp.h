@@ -385,12 +385,32 @@ size_t rgp_fcgru_buffer_elems(const rgp_fcgru_t* plan, const char* name);
  * rgp_fcgru_forward_stream(.., NULL, state_out, T, ..) computes exactly what rgp_fcgru_forward computes.  Argument errors
  * are RGP_EINVAL, name the argument, and come ahead of the bound / weights checks.  The dropout site behaves as in
  * rgp_fcgru_forward (it is frame-local).  A training plan accepts the call; rgp_fcgru_backward then returns RGP_ESTATE
- * (no truncated BPTT) until a plain forward has run.  A persistent launch that times out NaN-poisons state_out along with
+ * until a plain forward has run (it differentiates a recurrence from the zero state over all T steps), and
+ * rgp_fcgru_backward_stream below differentiates the call.  A persistent launch that times out NaN-poisons state_out along with
  * what it poisons anyway; state_in being read-only, the caller repeats the call.
  * rgp_fcgru_state_elems: B*1617, the fp32 elements of a state; host-only, works on an unbound plan. */
 size_t rgp_fcgru_state_elems(const rgp_fcgru_t* plan);
 int rgp_fcgru_forward_stream(rgp_fcgru_t* plan, const float* c3d_input, const float* state_in, float* state_out, int n_valid,
                              float* logits, float* probs, rgp_stream_t stream);
+/* Training across the carried state: the backward of the plan's LAST forward of either kind, on a training plan, either BPTT
+ * path.  Behind rgp_fcgru_forward_stream(.., state_in, .., n_valid, ..) it differentiates that call: the first n_valid steps, the
+ * recurrence started at state_in.  Behind rgp_fcgru_forward: all T steps from the zero state.
+ *   loss         that of rgp_fcgru_backward, summed over the frames of the valid steps and divided by loss_frames (> 0): the
+ *                caller's divisor, so that the gradients of a film's chunks add up to the gradient of a mean over the film.
+ *                logits, probs, labels are full size [B,T,G]; what lies behind n_valid reaches no output
+ *   d_state_out  fp32 [B][1617] dense, the gradient of whatever comes later w.r.t. the state_out the forward handed out;
+ *                NULL = zeros (truncated BPTT, or a film's last chunk); never written
+ *   d_state_in   fp32 [B][1617] dense, may be NULL, must not be d_state_out: d loss / d state_in, what "dh0" of
+ *                rgp_fcgru_read_buffer shows.  A persistent BPTT launch that times out poisons the gate-gradient rows of the
+ *                valid steps and this: NaN, never finite and wrong
+ *   grads        written, not accumulated, as rgp_fcgru_backward writes them
+ * c3d_input of the forward must be finite over all T steps, also behind n_valid: the gradient rows of those steps are zero, and
+ * the hoisted filter gradients multiply them with the rows the forward saved there.
+ * Argument errors are RGP_EINVAL, name the argument, and come ahead of the bound / weights checks; an inference plan, or a plan
+ * with no forward yet, is RGP_ESTATE.  rgp_fcgru_backward itself is unchanged. */
+int rgp_fcgru_backward_stream(rgp_fcgru_t* plan, const float* logits, const float* probs, const float* labels,
+                              const float* d_state_out, float* d_state_in, long long loss_frames,
+                              const rgp_fcgru_weights* grads, int loss_type, rgp_stream_t stream);
 /* ------------------------------------------------------------------ gaze_c3d_conv (the no-recurrence baseline) */
 typedef struct rgp_c3dconv rgp_c3dconv_t;
 

@@ -210,6 +210,8 @@ SIGNATURES = {
     'rgp_fcgru_buffer_elems': (c_size_t, [c_void_p, c_char_p]),
     'rgp_fcgru_state_elems': (c_size_t, [c_void_p]),
     'rgp_fcgru_forward_stream': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'rgp_fcgru_backward_stream': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong,
+                                          ctypes.POINTER(FcGruWeights), c_int, c_void_p]),
     'rgp_c3dconv_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int]),
     'rgp_c3dconv_destroy': (c_int, [c_void_p]),
     'rgp_c3dconv_workspace_bytes': (c_size_t, [c_void_p]),

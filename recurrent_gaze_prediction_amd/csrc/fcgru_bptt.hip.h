@@ -27,6 +27,14 @@
 // 2 T counters of its own; none behind the last phase.  Step 0 still runs GEMM ZR and stores the final carry (d loss / d h_{-1},
 // fp32 [B][np]) into g->carry, where the per-step path leaves the same quantity.
 //
+// Streaming (rgp_fcgru_backward_stream), template argument STREAM.  STREAM = false is what a call without a state gradient over
+// all T steps launches: the source and the parameter block it was measured with.  STREAM = true differentiates the first n_valid
+// steps of a streaming forward: the loop runs t = n_valid - 1 .. 0 on 2 n_valid counters (phase 2 (n_valid - 1 - t)), so a film's
+// one-step tail pays two rendezvous, not 2 T; thread b's carry starts from g->carry, where the host has seeded d loss / d state_out
+// (padded [B][np], zeros for a null gradient), instead of zero.  The rows keep the plan's T as their stride: no row is addressed
+// that STREAM = false does not address, and the host's 32-bit limits hold as they are.  Rows t >= n_valid of dxpre are neither
+// read nor written (the host has zeroed them); a launch that lost a member poisons the rows t < n_valid and the carry.
+//
 // Registers: 156 resident + 13 NF x 4 in flight; at NF = 4 that is 364 of the 512 a wave of a 4-wave workgroup may use, and
 // all four instantiations compile without scratch (profiles/fcgru_bptt_kernel_resources.txt): every phase issues its
 // 13 NF loads in ONE run at every NF.
@@ -51,9 +59,16 @@ struct FcBpttParamsT {
   unsigned* err;             // the plan's pinned error word
   int B, T;
 };
+// STREAM = true takes this on top (the STREAM = false instantiations keep the parameter block they were measured with)
+template <typename E>
+struct FcBpttStreamParamsT : FcBpttParamsT<E> {
+  int n_valid;               // steps of the streaming forward to differentiate, 1 .. T; carry holds the seed on entry
+};
+template <typename E, bool STREAM> struct FcBpttParamsOf { typedef FcBpttParamsT<E> type; };
+template <typename E> struct FcBpttParamsOf<E, true> { typedef FcBpttStreamParamsT<E> type; };
 
-template <int NF>
-static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_kernel(const FcBpttParamsT<bf16_t> p) {
+template <int NF, bool STREAM>
+static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_kernel(const typename FcBpttParamsOf<bf16_t, STREAM>::type p) {
   __shared__ __attribute__((aligned(16))) char red[4 * NF * 16 * FCS_PITCH];   // [K quarter][row][16 columns]
   __shared__ int s_timeout;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -61,6 +76,11 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_kernel(const FcBpttP
   const int frow = lane & 15, fk = lane >> 4;
   const int j = blockIdx.x, u0 = FCS_UNITS * j;          // member, its first unit
   const int np = FCS_NP, T_ = p.T, B = p.B;
+  // steps of this launch.  A reference: with STREAM = false every use below IS T_, and the kernel compiles to the code that was
+  // measured; as a variable of its own (equal to T_) the same kernel took another register allocation
+  int nv = 0;
+  if constexpr (STREAM) nv = p.n_valid;
+  const int& Tv = STREAM ? (const int&)nv : T_;
   const unsigned members = gridDim.x;
   if (tid == 0) s_timeout = 0;
 
@@ -104,11 +124,14 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_kernel(const FcBpttP
   FcbSlices cur, nxt;
 #pragma unroll
   for (int i = 0; i < 8; ++i) cur.dh[i] = cur.h[i] = cur.u[i] = cur.c[i] = cur.r[i] = nxt.dh[i] = nxt.h[i] = nxt.u[i] = nxt.c[i] = nxt.r[i] = 0.f;
-  if (own) load_step(T_ - 1, cur);
+  if constexpr (STREAM) {                                  // d loss / d state_out, seeded by the host (this thread alone stores there later)
+    if (own) load8(p.carry + coff, carry);
+  }
+  if (own) load_step(Tv - 1, cur);
 
-  for (int t = T_ - 1; t >= 0; --t) {
-    const int ph = 2 * (T_ - 1 - t);
-    // ---- 1. local math (carry = 0 at t = T - 1: dh = dh_head)
+  for (int t = Tv - 1; t >= 0; --t) {
+    const int ph = 2 * (Tv - 1 - t);
+    // ---- 1. local math (carry = 0 at t = T - 1: dh = dh_head; STREAM: the seed)
     if (own) {
       float dup[8], dcp[8];
 #pragma unroll
@@ -181,7 +204,7 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_kernel(const FcBpttP
       float fnan[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) fnan[i] = __builtin_nanf("");
-      for (int t = 0; t < T_; ++t)
+      for (int t = 0; t < Tv; ++t)
         for (int part = 0; part < 3; ++part) seq_st_sc1(p.dxpre, dxbytes, own_off(t, part), qnan);
       store8f(p.carry + coff, fnan);
     }

@@ -20,14 +20,15 @@
 // GEMM ZR (the longer GEMM phase), straight into the registers step t's slices have just left: at that point u, c and dh_head
 // are dead since the local math and h_prev and r since the r gate, so ONE set of 40 dwords is enough where fcgru_bptt.hip.h
 // holds two.  profiles/fcgru_f32_bptt_kernel_resources.txt: no scratch, no spill at NF = 1 .. 4.
+// Streaming: template argument STREAM, as fcgru_bptt.hip.h has it (the loop over n_valid steps, the seeded carry, the poisoning).
 #pragma once
 #include "fcgru_seq_f32.hip.h"
 #include "fcgru_bptt.hip.h"
 
 namespace rgp {
 
-template <int NF>
-static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_f32_kernel(const FcBpttParamsT<float> p) {
+template <int NF, bool STREAM>
+static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_f32_kernel(const typename FcBpttParamsOf<float, STREAM>::type p) {
   __shared__ __attribute__((aligned(16))) char red[4 * NF * 16 * FCS_PITCH];   // [K quarter][row][16 columns]
   __shared__ __attribute__((aligned(16))) char zw[2 * FCS_UNITS * FCS32_CPITCH];   // [u half | r half][unit][K]
   __shared__ int s_timeout;
@@ -36,6 +37,10 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_f32_kernel(const FcB
   const int frow = lane & 15, fk = lane >> 4;
   const int j = blockIdx.x, u0 = FCS_UNITS * j;          // member, its first unit
   const int np = FCS_NP, T_ = p.T, B = p.B;
+  // steps of this launch: a reference, so that STREAM = false reads T_ itself (fcgru_bptt.hip.h)
+  int nv = 0;
+  if constexpr (STREAM) nv = p.n_valid;
+  const int& Tv = STREAM ? (const int&)nv : T_;
   const unsigned members = gridDim.x;
   if (tid == 0) s_timeout = 0;
 
@@ -84,11 +89,14 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_f32_kernel(const FcB
   FcbSlices cur;
 #pragma unroll
   for (int i = 0; i < 8; ++i) carry[i] = cur.dh[i] = cur.h[i] = cur.u[i] = cur.c[i] = cur.r[i] = 0.f;
-  if (own) load_step(T_ - 1, cur);
+  if constexpr (STREAM) {                                  // d loss / d state_out, seeded by the host (this thread alone stores there later)
+    if (own) load8(p.carry + coff, carry);
+  }
+  if (own) load_step(Tv - 1, cur);
 
-  for (int t = T_ - 1; t >= 0; --t) {
-    const int ph = 2 * (T_ - 1 - t);
-    // ---- 1. local math (carry = 0 at t = T - 1: dh = dh_head)
+  for (int t = Tv - 1; t >= 0; --t) {
+    const int ph = 2 * (Tv - 1 - t);
+    // ---- 1. local math (carry = 0 at t = T - 1: dh = dh_head; STREAM: the seed)
     if (own) {
       float dup[8], dcp[8];
 #pragma unroll
@@ -159,7 +167,7 @@ static __global__ __launch_bounds__(SEQ_NT) void fcgru_bptt_f32_kernel(const FcB
       float fnan[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) fnan[i] = __builtin_nanf("");
-      for (int t = 0; t < T_; ++t)
+      for (int t = 0; t < Tv; ++t)
         for (int part = 0; part < 3; ++part) FcExch<float>::poison8(p.dxpre, dxbytes, own_off(t, part));
       store8f(p.carry + coff, fnan);
     }

@@ -27,8 +27,8 @@
 //
 // Time-out: a member whose wait passes the deadline stops waiting (its flag in LDS stays set) and, at the end of the launch,
 // sets the plan's error word and NaN-poisons its units of everything the launch hands on -- forward: every h row (all steps,
-// all clips), the fp32 states and hsnap, so the logits are NaN; BPTT: all three parts of every dxpre row and g->carry, so
-// every filter gradient and dE is NaN.  A launch that lost a member gives NaN, never finite and wrong.  No test runs this
+// all clips), the fp32 states and hsnap, so the logits are NaN; BPTT: all three parts of every dxpre row (streaming
+// instantiations: of the n_valid rows they wrote) and g->carry, so every filter gradient, dE and d_state_in is NaN.  A launch that lost a member gives NaN, never finite and wrong.  No test runs this
 // path, and none may.
 #pragma once
 #include "seq_group.hip.h"

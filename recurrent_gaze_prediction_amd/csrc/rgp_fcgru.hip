@@ -23,6 +23,9 @@
 // Streaming (rgp_fcgru_forward_stream): the same forward started from a caller's h_{-1} [B][1617] instead of zeros, on either
 // path and on inference and training plans.  Way in: gru_seed_or_zero (gru_steps.h), one launch in place of the two memsets.
 // Way out: one strided copy of the fp32 state behind step n_valid.  Nothing else in the per-step loop changes.
+// Training across the carried state (rgp_fcgru_backward_stream): the same backward on the first n_valid steps of the last
+// forward, d loss / d state_out seeded into the carry (the same seed kernel) and the final carry copied out as d loss / d state_in;
+// FcBwdStream holds what the call adds, and without it backward_impl enqueues what it always did.
 #include <algorithm>
 
 #include <string>
@@ -155,13 +158,13 @@ template <> struct FcPersist<bf16_t> {
   static constexpr const char* seq_name = "fcgru_seq";
   static constexpr const char* bptt_name = "fcgru_bptt";
   template <int NF, bool SAVE, bool STREAM> static auto seq() { return fcgru_seq_kernel<NF, SAVE, STREAM>; }
-  template <int NF> static auto bptt() { return fcgru_bptt_kernel<NF>; }
+  template <int NF, bool STREAM> static auto bptt() { return fcgru_bptt_kernel<NF, STREAM>; }
 };
 template <> struct FcPersist<float> {
   static constexpr const char* seq_name = "fcgru_seq_f32";
   static constexpr const char* bptt_name = "fcgru_bptt_f32";
   template <int NF, bool SAVE, bool STREAM> static auto seq() { return fcgru_seq_f32_kernel<NF, SAVE, STREAM>; }
-  template <int NF> static auto bptt() { return fcgru_bptt_f32_kernel<NF>; }
+  template <int NF, bool STREAM> static auto bptt() { return fcgru_bptt_f32_kernel<NF, STREAM>; }
 };
 
 size_t fc_cnt_bytes(int n_steps) { return (size_t)2 * n_steps * FCS_SHARDS * FCS_CNT_STRIDE * 4; }   // [2 T][FCS_SHARDS][FCS_CNT_STRIDE]
@@ -308,14 +311,17 @@ bool find_view(const rgp_fcgru* g, const char* name, FcView& v) {
 }
 
 // ---------------------------------------------------------------- backward kernels
-// d loss / d logits (gaze_rnn.py:363-408): xentropy (probs - labels) / F, l2 (logits - labels) / F
+// d loss / d logits (gaze_rnn.py:363-408): xentropy (probs - labels) scale, l2 (logits - labels) scale; scale = 1 / F, or the
+// streaming call's 1 / loss_frames.  Frames of the steps t >= n_valid are behind the call's last valid step: their rows are
+// written as zeros, whatever a and labels hold there (and whatever an earlier call left in the row).
 template <typename T>
 __global__ __launch_bounds__(256) void fc_dlogits_kernel(const float* __restrict__ a, const float* __restrict__ labels, float scale,
-                                                         T* __restrict__ dzo, int G, int Gp, long long total) {
+                                                         T* __restrict__ dzo, int G, int Gp, long long total, int T_, int n_valid) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int gcol = (int)(i % G);
     const long long f = i / G;
-    dzo[(f + 1) * Gp + gcol] = Elem<T>::to((a[i] - labels[i]) * scale);
+    const bool valid = (int)(f % T_) < n_valid;
+    dzo[(f + 1) * Gp + gcol] = Elem<T>::to(valid ? (a[i] - labels[i]) * scale : 0.f);
   }
 }
 
@@ -403,12 +409,14 @@ __global__ __launch_bounds__(256) void fc_unpack_kernel(const float* __restrict_
   }
 }
 
-// Step 2 of backward_impl for all T steps in one persistent launch (fcgru_bptt.hip.h / fcgru_bptt_f32.hip.h)
-template <typename T>
-int bptt_persistent(rgp_fcgru* g, hipStream_t s) {
+// Step 2 of backward_impl for all T steps in one persistent launch (fcgru_bptt.hip.h / fcgru_bptt_f32.hip.h).  STREAM: the
+// first n_valid steps, from the carry the host has seeded.
+template <typename T, bool STREAM>
+int bptt_persistent(rgp_fcgru* g, int n_valid, hipStream_t s) {
   char* ws = g->ws;
   const char* name = FcPersist<T>::bptt_name;
-  FcBpttParamsT<T> p;
+  typename FcBpttParamsOf<T, STREAM>::type p;
+  if constexpr (STREAM) p.n_valid = n_valid;
   p.b_c = (const T*)(ws + g->b_c.w_off);
   p.b_zr = (const T*)(ws + g->b_zr.w_off);
   p.dh_head = (const float*)(ws + g->dh_head);
@@ -423,12 +431,22 @@ int bptt_persistent(rgp_fcgru* g, hipStream_t s) {
   p.B = g->B; p.T = g->T;
   RGP_REQUIRE(g->np == FCS_NP && g->b_c.K == FCS_NP && g->b_zr.K == 2 * FCS_NP && g->b_c.chunk_major == 0 && g->b_zr.chunk_major == 0,
               "%s: unexpected filter packing", name);
-  return launch_members(name, p, [](auto nf) { return FcPersist<T>::template bptt<decltype(nf)::value>(); }, s);
+  return launch_members(name, p, [](auto nf) { return FcPersist<T>::template bptt<decltype(nf)::value, STREAM>(); }, s);
 }
+
+// What rgp_fcgru_backward_stream adds to a backward (the plain call: the defaults, and then every launch below is the one it
+// always was, in the same order).
+struct FcBwdStream {
+  bool on = false;
+  int n_valid = 0;                     // steps of the last forward to differentiate (plain: T)
+  long long loss_frames = 0;           // the loss's divisor (plain: F)
+  const float* d_state_out = nullptr;  // [B][n] dense, null = zeros
+  float* d_state_in = nullptr;         // [B][n] dense, null = not wanted
+};
 
 template <typename T>
 int backward_impl(rgp_fcgru* g, const float* logits, const float* probs, const float* labels, const rgp_fcgru_weights* gr,
-                  int loss_l2, hipStream_t s) {
+                  int loss_l2, const FcBwdStream& sb, hipStream_t s) {
   char* ws = g->ws;
   const int B = g->B, T_ = g->T, F = g->F, np = g->np, n = g->n, nx = g->nx, Kx = g->Kx, G = g->G, Gp = g->Gp;
   auto Tp = [&](size_t off) { return (T*)(ws + off); };
@@ -436,8 +454,9 @@ int backward_impl(rgp_fcgru* g, const float* logits, const float* probs, const f
   auto nblk = [](long long x) { return (int)std::min<long long>((x + 255) / 256, 8192); };
   const size_t st = (size_t)B * np;
   // 1. loss layer and output projection
-  fc_dlogits_kernel<T><<<nblk((long long)F * G), 256, 0, s>>>(loss_l2 ? logits : probs, labels, 1.0f / (float)F, Tp(g->dzo), G, Gp,
-                                                             (long long)F * G);
+  const int n_valid = sb.on ? sb.n_valid : T_;
+  fc_dlogits_kernel<T><<<nblk((long long)F * G), 256, 0, s>>>(loss_l2 ? logits : probs, labels, 1.0f / (float)(sb.on ? sb.loss_frames : F),
+                                                             Tp(g->dzo), G, Gp, (long long)F * G, T_, n_valid);
   fc_colsum_kernel<T><<<(G + 15) / 16, 256, 0, s>>>(Tp(g->dzo) + Gp, Gp, F, G, (float*)gr->proj_out_b);
   RGP_HIP(hipGetLastError());
   WgradParams wp;
@@ -462,11 +481,26 @@ int backward_impl(rgp_fcgru* g, const float* logits, const float* probs, const f
   }
   // 2. BPTT: one persistent launch (RGP_FCGRU_BPTT_PERSISTENT / RGP_FCGRU_BPTT_PERSISTENT_F32), or four launches per step
   const float* hall = Fp(g->hall_t);
-  if (g->bptt_persistent) RGP_TRY(bptt_persistent<T>(g, s));
-  for (int t = g->bptt_persistent ? -1 : T_ - 1; t >= 0; --t) {
+  // streaming call: the steps behind n_valid are not differentiated and the loop does not write their dxpre rows, which the
+  // hoisted launches of 3. and 4. read all the same: rows (b, t >= n_valid) are zeroed here, on both paths (a row of an earlier
+  // backward over more steps would stand there otherwise) -- per clip one run of T - n_valid rows, T rows apart
+  const size_t xrow = (size_t)3 * np * sizeof(T);
+  if (n_valid < T_)
+    RGP_HIP(hipMemset2DAsync(ws + g->dxpre + (size_t)(1 + n_valid) * xrow, (size_t)T_ * xrow, 0, (size_t)(T_ - n_valid) * xrow, B, s));
+  // d loss / d state_out -> g->carry, padded [B][np] with zero padding: the dense-row seed of the forward's state (its operand
+  // image lands in dcp, scratch of the per-step loop that fc_bwd1_kernel rewrites before anything reads it).  The persistent
+  // kernel's streaming instantiation always starts from the seeded carry (a null gradient: zeros).
+  const bool stream_kernel = g->bptt_persistent && (sb.d_state_out || n_valid < T_);
+  const bool seeded = sb.d_state_out || stream_kernel;
+  if (seeded) {
+    gru_seed_kernel<T><<<(int)std::min<size_t>((st + 255) / 256, 4096), 256, 0, s>>>(sb.d_state_out, Fp(g->carry), Tp(g->dcp), nullptr, np, B, 1, n, np);
+    RGP_HIP(hipGetLastError());
+  }
+  if (g->bptt_persistent) RGP_TRY(stream_kernel ? (bptt_persistent<T, true>(g, n_valid, s)) : (bptt_persistent<T, false>(g, n_valid, s)));
+  for (int t = g->bptt_persistent ? -1 : n_valid - 1; t >= 0; --t) {
     const float* h_prev = hall + (size_t)t * st;
     fc_bwd1_kernel<T><<<nblk((long long)st), 256, 0, s>>>(Fp(g->dh_head), Fp(g->carry), h_prev, Fp(g->uall) + (size_t)t * st,
-                                                         Fp(g->call) + (size_t)t * st, Tp(g->dxpre), Tp(g->dcp), B, T_, t, np, t == T_ - 1);
+                                                         Fp(g->call) + (size_t)t * st, Tp(g->dxpre), Tp(g->dcp), B, T_, t, np, t == n_valid - 1 && !seeded);
     RGP_HIP(hipGetLastError());
     {
       IgemmParams p = make_params(g->b_c, Tp(g->dcp), ws, B);
@@ -481,6 +515,11 @@ int backward_impl(rgp_fcgru* g, const float* logits, const float* probs, const f
       EpiParams e = make_epi(g->b_zr, Fp(g->carry), ws);
       RGP_TRY((launch_igemm<T, 1, 1, EpiAccumF32>(p, e, s)));
     }
+  }
+  if (sb.d_state_in) {                                          // the way out: d loss / d state_in, one strided copy of the final carry
+    GruSteps d;
+    d.B = B; d.rows = 1; d.S = np;
+    RGP_TRY(gru_state_out(Fp(g->carry), sb.d_state_in, (const int*)(ws + g->c.out_tab_off), d, n, s));
   }
   // 3. kernel gradients, hoisted over all steps (side stream: beside step 4)
   RGP_TRY(g->side.fork(s, 1, &sw));
@@ -753,6 +792,20 @@ int rgp_fcgru_forward_stream(rgp_fcgru_t* g, const float* c3d_input, const float
                               : forward_impl<float>(g, c3d_input, logits, probs, s);
 }
 
+namespace {
+// the launches of a backward behind its argument checks
+int backward_run(rgp_fcgru* g, const float* logits, const float* probs, const float* labels, const rgp_fcgru_weights* grads,
+                 int loss_type, const FcBwdStream& sb, hipStream_t s) {
+  if (g->bptt_persistent) RGP_TRY(fcgru_check_error(g));
+  RGP_TRY(g->dtype == RGP_BF16 ? backward_impl<bf16_t>(g, logits, probs, labels, grads, loss_type, sb, s)
+                               : backward_impl<float>(g, logits, probs, labels, grads, loss_type, sb, s));
+  fc_fold_bias_kernel<<<1, 64, 0, s>>>((const float*)(g->ws + g->dwc), (float*)grads->proj_c3d_b, g->Cp);
+  RGP_HIP(hipGetLastError());
+  g->bwd_done = true;
+  return RGP_OK;
+}
+}  // namespace
+
 int rgp_fcgru_backward(rgp_fcgru_t* g, const float* logits, const float* probs, const float* labels,
                        const rgp_fcgru_weights* grads, int loss_type, rgp_stream_t stream) {
   RGP_REQUIRE(g && logits && labels && grads, "rgp_fcgru_backward: null argument");
@@ -765,14 +818,35 @@ int rgp_fcgru_backward(rgp_fcgru_t* g, const float* logits, const float* probs, 
     RGP_REQUIRE(ptrs[i], "rgp_fcgru_backward: gradient pointer %zu is null", i);
   if (g->stream.streamed)
     return set_err(RGP_ESTATE, "rgp_fcgru_backward: the last forward was a streaming call (no truncated BPTT): run rgp_fcgru_forward first");
-  if (g->bptt_persistent) RGP_TRY(fcgru_check_error(g));
-  hipStream_t s = (hipStream_t)stream;
-  RGP_TRY(g->dtype == RGP_BF16 ? backward_impl<bf16_t>(g, logits, probs, labels, grads, loss_type, s)
-                               : backward_impl<float>(g, logits, probs, labels, grads, loss_type, s));
-  fc_fold_bias_kernel<<<1, 64, 0, s>>>((const float*)(g->ws + g->dwc), (float*)grads->proj_c3d_b, g->Cp);
-  RGP_HIP(hipGetLastError());
-  g->bwd_done = true;
-  return RGP_OK;
+  return backward_run(g, logits, probs, labels, grads, loss_type, FcBwdStream(), (hipStream_t)stream);
+}
+
+int rgp_fcgru_backward_stream(rgp_fcgru_t* g, const float* logits, const float* probs, const float* labels, const float* d_state_out,
+                              float* d_state_in, long long loss_frames, const rgp_fcgru_weights* grads, int loss_type,
+                              rgp_stream_t stream) {
+  const char* fn = "rgp_fcgru_backward_stream";
+  RGP_REQUIRE(g, "%s: null plan", fn);
+  RGP_REQUIRE(logits, "%s: null logits", fn);
+  RGP_REQUIRE(labels, "%s: null labels", fn);
+  RGP_REQUIRE(grads, "%s: null grads", fn);
+  const float* const* ptrs = (const float* const*)grads;
+  for (size_t i = 0; i < sizeof(rgp_fcgru_weights) / sizeof(float*); ++i)
+    RGP_REQUIRE(ptrs[i], "%s: gradient pointer %zu of grads is null", fn, i);
+  RGP_REQUIRE(loss_frames > 0, "%s: loss_frames=%lld must be positive", fn, loss_frames);
+  RGP_REQUIRE(loss_type == 0 || loss_type == 1, "%s: loss_type %d (0 xentropy, 1 l2)", fn, loss_type);
+  RGP_REQUIRE(loss_type == 1 || probs, "%s: null probs (xentropy needs the softmax maps)", fn);
+  RGP_REQUIRE(!d_state_in || d_state_in != d_state_out, "%s: d_state_in must not alias d_state_out", fn);
+  if (!g->save) return set_err(RGP_ESTATE, "%s: plan was created without save_for_backward", fn);
+  if (!g->ws) return set_err(RGP_EWORKSPACE, "rgp_fcgru: workspace not bound");
+  if (!g->weights_set) return set_err(RGP_ESTATE, "rgp_fcgru: weights not set");
+  if (!g->fwd_done) return set_err(RGP_ESTATE, "%s: no forward has run on this plan", fn);
+  FcBwdStream sb;
+  sb.on = true;
+  sb.n_valid = g->stream.streamed ? g->stream.last_n_valid : g->T;      // (a plain forward: every step, from the zero state)
+  sb.loss_frames = loss_frames;
+  sb.d_state_out = d_state_out;
+  sb.d_state_in = d_state_in;
+  return backward_run(g, logits, probs, labels, grads, loss_type, sb, (hipStream_t)stream);
 }
 
 int rgp_fcgru_status(rgp_fcgru_t* g, rgp_stream_t stream) {

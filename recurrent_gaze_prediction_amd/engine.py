@@ -835,6 +835,7 @@ class FcGruEngine(object):
         probs = torch.empty_like(logits) if want_probs else None
         with torch.cuda.device(self.device):
             _lib.check(self.lib.rgp_fcgru_forward(self._h, _ptr(x), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
+        self._last_n_valid = self.T
         return logits, probs
 
     STREAM_BN_PHASE = False     # this graph has no per-timestep batch-norm
@@ -844,19 +845,49 @@ class FcGruEngine(object):
         """fp32 elements of the recurrent state forward_stream carries (rgp_fcgru_state_elems): B * 1617, h per clip."""
         return int(self.lib.rgp_fcgru_state_elems(self._h))
 
-    def forward_stream(self, c3d_input, state=None, n_valid=None, want_probs=True):
+    def forward_stream(self, c3d_input, state=None, n_valid=None, want_probs=True, train=False):
         """One call of a stream (rgp_fcgru_forward_stream): the graph of forward() started from `state` instead of zeros, on
-        either recurrence path and on inference and training plans (backward() is refused behind it until a plain forward).
+        either recurrence path and on inference and training plans (backward() is refused behind it until a plain forward;
+        backward_stream() differentiates it).
         c3d_input [B,T,1024,7,7] fp32 at the full plan size; the recurrence is defined for the first n_valid (default T)
         steps, later outputs are unspecified.  state: fp32 device tensor of state_elems elements ([B, 1617], one slot of
-        read_buffer('h')) from an earlier call, or None = the zero state; never modified.  The dropout site is off.
+        read_buffer('h')) from an earlier call, or None = the zero state; never modified.  train: the dropout site, as
+        forward(train=...) arms it (the site is frame-local); off by default.
         Returns (logits, probs, new_state); new_state is a fresh tensor on every call: h behind step n_valid."""
-        self.dropout.off()
+        self.dropout.arm(train)
         logits = torch.empty(self.B, self.T, self.GH, self.GW, device=self.device)
         probs = torch.empty_like(logits) if want_probs else None
         new_state = _stream_call(self, self.lib.rgp_fcgru_forward_stream, self.B, self.T, c3d_input, state, n_valid,
                                  lambda si, so, nv: (_ptr(c3d_input), si, so, nv, _ptr(logits), _ptr(probs)))
+        self._last_n_valid = self.T if n_valid is None else int(n_valid)
         return logits, probs, new_state
+
+    def backward_stream(self, logits, probs, labels, d_state=None, loss_frames=None, loss_type='xentropy', want_d_state=True):
+        """The backward of the last forward of either kind (rgp_fcgru_backward_stream): behind forward_stream(state, n_valid) the
+        first n_valid steps of that call, the recurrence started at `state`; behind forward() all T steps from the zero state.
+        The loss is backward()'s, summed over the valid frames and divided by loss_frames (default B * n_valid of the last
+        forward THIS OBJECT ran: a Python-side copy of what the plan keeps, used for this default alone; name loss_frames when
+        the C entries are driven beside the engine), so the gradients of a film's chunks add up to the gradient of the mean over the film.  d_state: fp32
+        [B, 1617], the gradient w.r.t. the new_state the forward returned, or None = zeros (truncated BPTT, the last chunk);
+        never modified.  c3d_input of the forward must be finite over all T steps.
+        Returns (grads, d_state_in): {field: gradient view} (flat_grads, written, not accumulated) and a fresh tensor
+        [B, 1617] with d loss / d state (None with want_d_state=False)."""
+        assert self.save_for_backward, 'create the engine with save_for_backward=True'
+        assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
+        if d_state is not None:
+            assert d_state.is_cuda and d_state.dtype == torch.float32 and d_state.is_contiguous()
+            assert d_state.numel() == self.state_elems, (d_state.numel(), self.state_elems)
+        if loss_frames is None:
+            loss_frames = self.B * getattr(self, '_last_n_valid', self.T)
+        if self.flat_grads is None:
+            self.flat_grads, self.grads = self._flat(self.weights)
+        st = self._struct(self.grads)
+        d_in = torch.empty(self.B, 1617, dtype=torch.float32, device=self.device) if want_d_state else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rgp_fcgru_backward_stream(self._h, _ptr(logits), _ptr(probs), _ptr(labels), _ptr(d_state), _ptr(d_in),
+                                                          int(loss_frames), ctypes.byref(st),
+                                                          {'xentropy': 0, 'l2': 1}[loss_type], _stream_ptr(self.device)))
+        return self.grads, d_in
 
 
 class ShallowNetEngine(object):

@@ -245,6 +245,11 @@ class GazePredictionGRU(ModelBase):
                 raise err if err is not None else RuntimeError('a peer rank failed in its backward pass')
         elif err is not None:
             raise err
+        self._reduce_clip_step()
+
+    def _reduce_clip_step(self):
+        """The tail of a training step on the gradient in engine.flat_grads: all-reduce (data-parallel), clip by the global
+        norm, the configured optimizer, global_step + 1."""
         if self.reducer is not None:
             buckets = getattr(self.engine, 'grad_buckets', None)
             if callable(buckets):
@@ -322,6 +327,119 @@ class GazePredictionGRU(ModelBase):
             logits, probs, new_state = run()
             self._status_or_recover(final=True)
         return (probs if want_probs else logits), new_state
+
+    # ------------------------------------------------------------------ training across the carried state
+    def _chunk_loss_sum(self, logits, labels, n):
+        """The loss of the first n steps of one chunk, summed over its B * n frames (1-element device tensor)."""
+        from ..engine import l2_loss, softmax_xent
+        B, T = self.batch_size, self.n_lstm_steps
+        if self.config.loss_type == 'l2':
+            z = logits.clone()
+            z[:, n:] = 0                                   # (labels behind n are the zero padding)
+            return l2_loss(z, labels, 1)
+        return softmax_xent(logits, labels, want_probs=False)[1].view(B, T)[:, :n].sum().reshape(1)
+
+    def train_long_clip(self, c3d, gt_gazemap, mode='truncated', trace=None):
+        """Train on a film longer than the plan as ONE recurrence (fc-GRU models: gaze_rnn, gaze_rnn77).
+        c3d [B, S, 1024, 7, 7], any S; gt_gazemap [B, S, GH, GW] as single_step hands the maps to train_op (normalised for
+        xentropy).  The film is cut into chunks of the plan's T steps, the last one shorter and zero-padded.
+        mode='truncated': per chunk forward_stream(train=True) from the carried state, backward_stream without a state
+        gradient on the mean loss of the chunk's frames, one optimizer step -- truncated BPTT, S / T steps.
+        mode='exact': the states at the cuts and each chunk's dropout mask are kept in a first pass; in reverse order every
+        chunk is recomputed from its boundary state with its mask and differentiated with the state gradient chained back and
+        the divisor B * S; the chunk gradients are summed and ONE optimizer step is taken: the gradient of the mean loss over
+        the whole film, with the memory of one chunk.
+        A persistent launch that times out (RGP_ETIMEOUT): the model falls back to per-step launches as elsewhere; 'exact'
+        has not moved the parameters and is repeated as a whole, 'truncated' repeats the poisoned chunk (its state is read-only).
+        trace: a dict that receives 'states' (behind every chunk), 'logits' and, in exact mode, 'logits_recomputed'.
+        Returns the mean loss over the B * S frames (float)."""
+        from .. import engine as _engine
+        if not isinstance(self.engine, _engine.FcGruEngine):
+            raise NotImplementedError('train_long_clip: the fc-GRU models (gaze_rnn, gaze_rnn77) train across the carried state; '
+                                      'the engine of this %s has no backward_stream' % type(self).__name__)
+        if getattr(self, 'dist', None) is not None:
+            raise NotImplementedError('train_long_clip: data-parallel long-clip training is out of scope (a process group is attached)')
+        if self.config.loss_type == 'KLD':
+            raise NotImplementedError('train_long_clip: loss_type KLD')      # broken in the reference too (gaze_rnn.py:395-399)
+        if mode not in ('truncated', 'exact'):
+            raise ValueError("train_long_clip: mode %r (one of 'truncated', 'exact')" % (mode,))
+        dev, B, T = self.session.device, self.batch_size, self.n_lstm_steps
+        as_dev = lambda a: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, np.float32))).to(dev, torch.float32)
+        x_all = as_dev(c3d).reshape(B, -1, 1024, 7, 7)
+        S = x_all.shape[1]
+        g_all = as_dev(gt_gazemap).reshape(B, S, self.gazemap_height, self.gazemap_width)
+        assert S >= 1, 'train_long_clip: an empty film'
+        loss_type = 'l2' if self.config.loss_type == 'l2' else 'xentropy'
+        want_probs = loss_type == 'xentropy'
+        cuts = [(s, min(T, S - s)) for s in range(0, S, T)]
+
+        def chunk(a, s, n):                                 # steps [s, s + n) at the plan's size, zeros behind n
+            part = a[:, s:s + n]
+            if n < T:
+                part = torch.cat([part, part.new_zeros((B, T - n) + tuple(part.shape[2:]))], 1)
+            return part.contiguous()
+
+        def lost(final):                                    # True: the engine was replaced, repeat
+            return self._status_or_recover(final=final)
+
+        tr = trace if trace is not None else {}
+        tr.update(states=[], logits=[], logits_recomputed=[])
+
+        if mode == 'truncated':
+            state, total = None, 0.0
+            for s, n in cuts:
+                x, g = chunk(x_all, s, n), chunk(g_all, s, n)
+                for final in (False, True):
+                    logits, probs, new_state = self.engine.forward_stream(x, state=state, n_valid=n, want_probs=want_probs, train=True)
+                    self.engine.backward_stream(logits, probs, g, d_state=None, loss_frames=B * n, loss_type=loss_type,
+                                                want_d_state=False)
+                    if not lost(final):
+                        break
+                total += float(self._chunk_loss_sum(logits, g, n).item())
+                self._reduce_clip_step()
+                state = new_state
+                tr['states'].append(new_state)
+                tr['logits'].append(logits)
+            self.loss = total / (B * S)
+            return self.loss
+
+        def exact(final):
+            """-> the loss sum, the gradient of the film's mean loss in engine.flat_grads; None: the engine was replaced."""
+            eng = self.engine
+            drop = self._has_dropout() and eng.dropout.keep_prob < 1.0
+            tr.update(states=[], logits=[], logits_recomputed=[])
+            states, masks, total = [None], [], 0.0
+            for s, n in cuts:                               # pass 1: the states at the cuts, the masks, the loss
+                logits, _, new_state = eng.forward_stream(chunk(x_all, s, n), state=states[-1], n_valid=n, want_probs=False, train=True)
+                if lost(final):
+                    return None
+                masks.append(eng.dropout.mask.clone() if drop else None)
+                total += float(self._chunk_loss_sum(logits, chunk(g_all, s, n), n).item())
+                states.append(new_state)
+                tr['states'].append(new_state)
+                tr['logits'].append(logits)
+            acc, d_state = None, None
+            for i in reversed(range(len(cuts))):            # pass 2: recompute, differentiate, chain the state gradient
+                s, n = cuts[i]
+                if drop:
+                    eng.dropout.use(masks[i], eng.dropout.keep_prob)
+                logits, probs, _ = eng.forward_stream(chunk(x_all, s, n), state=states[i], n_valid=n, want_probs=want_probs,
+                                                      train='keep' if drop else False)
+                _, d_state = eng.backward_stream(logits, probs, chunk(g_all, s, n), d_state=d_state, loss_frames=B * S,
+                                                 loss_type=loss_type, want_d_state=i > 0)
+                if lost(final):
+                    return None
+                acc = eng.flat_grads.clone() if acc is None else acc.add_(eng.flat_grads)
+                tr['logits_recomputed'].insert(0, logits)
+            eng.flat_grads.copy_(acc)
+            return total
+
+        total = exact(False)
+        if total is None:                                   # the parameters have not moved: the whole call again, per step
+            total = exact(True)
+        self._reduce_clip_step()
+        self.loss = total / (B * S)
+        return self.loss
 
     def _status_or_recover(self, final=False):
         """"A TF session either returns or raises" (gaze_rnn.py:603-611).  Engines with persistent launches report a lost

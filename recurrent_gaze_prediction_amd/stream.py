@@ -154,6 +154,17 @@ def predict_long_clips(model, clips, frames=None):
     return [np.concatenate(o) if o else np.zeros((0,) + gh_gw, np.float32) for o in outs]
 
 
+def train_long_clips(model, clips, gazemaps, mode='truncated'):
+    """Training beside predict_long_clips (the fc-GRU models): B clips of ONE length S, C3D features [S, 1024, 7, 7] and gaze
+    maps [S, GH, GW] each, one per lane -> model.train_long_clip on the stacked film: every clip one recurrence from the zero
+    state, cut into the plan's T-step chunks.  Returns the mean loss."""
+    assert len(clips) == len(gazemaps) == model.batch_size, 'one clip and one map array per lane (%d)' % model.batch_size
+    x = np.stack([_host_f32(c).reshape(-1, 1024, 7, 7) for c in clips])
+    g = np.stack([_host_f32(m) for m in gazemaps])
+    assert x.shape[1] == g.shape[1], 'clips and gazemaps of one length, got %d and %d steps' % (x.shape[1], g.shape[1])
+    return model.train_long_clip(x, g, mode=mode)
+
+
 def predict_video(model, frames_u8, extractor, image_hw=98):
     """One uint8 clip [N, H, W, 3] -> maps [n_windows, GH, GW] (numpy) as ONE recurrence: frames.video_inputs makes the C3D
     features of the windows and the frame image paired with each on the device, predict_long_clips streams them and hands

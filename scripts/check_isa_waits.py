@@ -12,7 +12,8 @@ persistent fc-GRU kernel (fcgru_seq.hip.h): in each of its two phases all 13 x N
 must stand in front of the phase's first MFMA (the scheduler, left alone, sinks them between the MFMAs and re-uses 2 - 4
 registers: 2 - 3 loads in flight instead of the >= 8 the hand-off needs), and nothing may spill.  Sixteen instantiations
 <NF, SAVE, STREAM>: the eight STREAM = false ones as before, and the eight streaming ones (step 0 of phase A on the seeded rows).
-The persistent fc-GRU BPTT kernel (fcgru_bptt.hip.h), four instantiations <NF>: the same rule for each fcs_gemm call of its
+The persistent fc-GRU BPTT kernel (fcgru_bptt.hip.h), eight instantiations <NF, STREAM>, four of them streaming
+(rgp_fcgru_backward_stream: n_valid steps from the seeded carry, the same step body): the same rule for each fcs_gemm call of the
 step body -- GEMM C, the u half and the r half of GEMM ZR: three runs of exactly 13 x NF loads in front of 13 x NF MFMAs (no
 phase of any instantiation issues its loads in two runs), and no scratch access.
 The f32 persistent fc-GRU kernel (fcgru_seq_f32.hip.h), sixteen instantiations <NF, SAVE, STREAM>: a fragment's A operands are
@@ -21,7 +22,8 @@ each phase issues its loads in GROUPS: fragments 0 and 1 (26 min(NF, 2) loads) i
 fragment f + 2 behind the 104 MFMAs of fragment f.  Each group must stand in front of the MFMAs that consume it: the runs of a
 phase are exactly [L 26 min(NF, 2), M 104] + [L 26, M 104] x (NF - 3) + [L 26, M 208] (NF <= 2: [L 26 NF, M 104 NF]), twice per
 kernel, every exchange load 16 bytes wide, and no scratch access.
-The f32 persistent fc-GRU BPTT kernel (fcgru_bptt_f32.hip.h), four instantiations <NF>: a step is three fcs32_gemm passes --
+The f32 persistent fc-GRU BPTT kernel (fcgru_bptt_f32.hip.h), eight instantiations <NF, STREAM>, four of them streaming: a step
+is three fcs32_gemm passes --
 GEMM C (b_c from registers), the u half and the r half of GEMM ZR (both from LDS) -- so the runs of the f32 forward's phase are
 expected exactly THREE times per kernel, every exchange load 16 bytes wide, and no scratch access.
 """
@@ -126,14 +128,15 @@ def f32_phase(nf):
     return runs
 
 
-# (kernel, symbol prefix, instantiations, MFMA, runs of one phase, phases per kernel, what the summary line calls a fault)
+# (kernel, symbol prefix, instantiations, MFMA, runs of one phase, phases per kernel, what the summary line calls a fault, where
+# the STREAM argument stands behind '_kernelILi', streaming instantiations expected)
 BF16_WHAT = 'with exchange loads not in front of their MFMAs, or spills'
 F32_WHAT = 'with a load group not in front of its MFMAs, narrow loads or spills'
 FCGRU_RULES = [
-    ('fcgru_seq', '_ZN3rgpL16fcgru_seq_kernel', 16, 'v_mfma_f32_16x16x32_bf16', bf16_phase, 2, BF16_WHAT),
-    ('fcgru_bptt', '_ZN3rgpL17fcgru_bptt_kernel', 4, 'v_mfma_f32_16x16x32_bf16', bf16_phase, 3, BF16_WHAT),
-    ('fcgru_seq_f32', '_ZN3rgpL20fcgru_seq_f32_kernel', 16, 'v_mfma_f32_16x16x4_f32', f32_phase, 2, F32_WHAT),
-    ('fcgru_bptt_f32', '_ZN3rgpL21fcgru_bptt_f32_kernel', 4, 'v_mfma_f32_16x16x4_f32', f32_phase, 3, F32_WHAT),
+    ('fcgru_seq', '_ZN3rgpL16fcgru_seq_kernel', 16, 'v_mfma_f32_16x16x32_bf16', bf16_phase, 2, BF16_WHAT, 5, 8),
+    ('fcgru_bptt', '_ZN3rgpL17fcgru_bptt_kernel', 8, 'v_mfma_f32_16x16x32_bf16', bf16_phase, 3, BF16_WHAT, 1, 4),
+    ('fcgru_seq_f32', '_ZN3rgpL20fcgru_seq_f32_kernel', 16, 'v_mfma_f32_16x16x4_f32', f32_phase, 2, F32_WHAT, 5, 8),
+    ('fcgru_bptt_f32', '_ZN3rgpL21fcgru_bptt_f32_kernel', 8, 'v_mfma_f32_16x16x4_f32', f32_phase, 3, F32_WHAT, 1, 4),
 ]
 
 
@@ -158,20 +161,20 @@ def compile_asm(tu):
 def main():
     rc = 0
     asm = compile_asm('rgp_fcgru.hip')
-    for kernel, prefix, count, mfma, phase, n_phases, what in FCGRU_RULES:
+    for kernel, prefix, count, mfma, phase, n_phases, what, stream_at, count_stream in FCGRU_RULES:
         n = nbad = n_stream = 0
         for name, body in kernels_named(asm, prefix):
             n += 1
             # <NF, SAVE, STREAM>: the streaming instantiations (rgp_fcgru_forward_stream) run phase A of step 0 on the seeded rows
-            # through the same GEMM call, so the same runs are expected of them
-            n_stream += name.split('_kernelILi')[1][5:].startswith('ELb1E')
+            # through the same GEMM call, so the same runs are expected of them; <NF, STREAM> (rgp_fcgru_backward_stream): the same
+            # step body over n_valid steps
+            n_stream += name.split('_kernelILi')[1][stream_at:].startswith('ELb1E')
             faults = fcgru_faults(name, body, kernel, mfma, phase, n_phases)
             if faults:
                 nbad += 1
                 print(kernel.upper(), name[:100], faults)
-        streaming = ' (%d streaming)' % n_stream if kernel == 'fcgru_seq' else ''
-        print('rgp_fcgru.hip: %d %s kernels%s, %d %s' % (n, kernel, streaming, nbad, what))
-        rc |= nbad > 0 or n != count or (kernel == 'fcgru_seq' and n_stream != 8)
+        print('rgp_fcgru.hip: %d %s kernels (%d streaming), %d %s' % (n, kernel, n_stream, nbad, what))
+        rc |= nbad > 0 or n != count or n_stream != count_stream
     asm = compile_asm('rgp_conv_patch.hip')
     n = nbad = 0
     for name, body in kernels_named(asm, '_ZN3rgpL', 'conv_patch'):
