@@ -761,11 +761,16 @@ int rgp_c3d_create_ex(rgp_c3d_t** plan, int max_windows, int dtype, int flags);
  *  RGP_C3D_KERNELS_TILE128    with RGP_C3D_KERNELS_IGEMM: every implicit GEMM of the plan on the 128x128 tile loop.
  *  RGP_C3D_CONV2A_ROWWISE     inference plans on the patch kernels: conv2a + pool2 through conv_patch_bf16_kernel of
  *                             conv_patch.hip.h instead of conv_patch_slab_bf16_kernel of conv_patch_slab.hip.h (both
- *                             skip the halo-plane tap groups); bit-identical results (a cross-check and A/B switch). */
+ *                             skip the halo-plane tap groups); bit-identical results (a cross-check and A/B switch).
+ *  RGP_C3D_CONV3_TWOPLANE     inference plans on the patch kernels: conv3a and conv3b + pool3 through the body of
+ *                             conv_patch.hip.h whose block tile holds both output planes of a pooled plane (what every
+ *                             plan ran before, and what training plans run) instead of its plane-pure form;
+ *                             bit-identical results (a cross-check and A/B switch).  (Value 16 is not a flag.) */
 #define RGP_C3D_SAVE_FOR_BACKWARD 1
 #define RGP_C3D_KERNELS_IGEMM 2
 #define RGP_C3D_KERNELS_TILE128 4
 #define RGP_C3D_CONV2A_ROWWISE 8
+#define RGP_C3D_CONV3_TWOPLANE 32
 /* Name of the kernel instantiation the plan launches for layer i's forward at n_windows windows ("" if unknown):
  * what a profiler shows for the stage rgp_c3d_profile_read times as index i. */
 const char* rgp_c3d_layer_kernel_name(const rgp_c3d_t* plan, int layer, int n_windows);

@@ -19,6 +19,7 @@ RGP_F32, RGP_BF16 = 0, 1
 RGP_ETIMEOUT = -5
 RGP_GRCN_SAVE_FOR_BACKWARD, RGP_GRCN_PER_STEP, RGP_GRCN_UNFOLDED_HEAD = 1, 2, 4
 RGP_C3D_SAVE_FOR_BACKWARD, RGP_C3D_KERNELS_IGEMM, RGP_C3D_KERNELS_TILE128, RGP_C3D_CONV2A_ROWWISE = 1, 2, 4, 8
+RGP_C3D_CONV3_TWOPLANE = 32
 RGP_C3DCONV_SAVE_FOR_BACKWARD, RGP_C3DCONV_STAGED, RGP_C3DCONV_FUSED = 1, 2, 4
 RGP_LSTM_SAVE_FOR_BACKWARD, RGP_LSTM_PER_STEP, RGP_LSTM_PERSISTENT, RGP_LSTM_BPTT_PERSISTENT = 1, 2, 4, 8
 RGP_GRCN77_SAVE_FOR_BACKWARD, RGP_GRCN77_PER_STEP = 1, 2

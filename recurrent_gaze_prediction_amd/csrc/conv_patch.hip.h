@@ -3,6 +3,9 @@
 // their input gradients (conv3b's masked by the forward activation; conv2a's / conv3a's dense, for the un-pool kernel).
 // Spec: /root/reference/C3D/.../c3d_prototxt/feature_extration.prototxt:67-107 (conv2a, pool2), 108-173 (conv3a, conv3b,
 // pool3); the gradients are tf.gradients through them (base.py:278-281).  conv4a / conv4b: conv_patch14.hip.h.
+// Two bodies: conv_patch_body (this text; conv2a, every training forward, every input gradient, and conv3a / conv3b of plans
+// created with RGP_C3D_CONV3_TWOPLANE) and conv_patch_pure_body (the inference forward of conv3a / conv3b: a block tile of ONE
+// output plane of a pair of clip windows, two plane buffers, no half-empty K step; described in front of it, below).
 // The text below describes conv2a's forward; the other instances are the same kernel at 28 x 28 x 8 positions with
 // 4 / 8 channel sweeps of 32, tiles of 2 x 14 pooling windows x 256 channels (waves 2 (M) x 4 (N)), plane slabs of
 // 6 x 30 pixels and 16 KB filter slabs; the two dense input gradients have 64 / 128 output channels and use wave tiles
@@ -616,6 +619,371 @@ static __device__ __forceinline__ void conv_patch_body(const ConvPatchParams& p)
 template <int CIN, int NOUT, int HW, int DEPTH, bool POOL, bool ARGMAX = false, bool DGRAD = false, bool DENSE = false>
 static __global__ __launch_bounds__(512) void conv_patch_bf16_kernel(const ConvPatchParams p) {
   conv_patch_body<CIN, NOUT, HW, DEPTH, POOL, ARGMAX, DGRAD, DENSE>(p);
+}
+
+// ---- Plane-pure form: the inference forwards of conv3a (128 -> 256) and conv3b (256 -> 256) + pool3 on 28 x 28 x 8 ----
+// In the body above a block tile holds both output planes of a pooled plane, so a tap group that multiplies the zero halo
+// plane z = -1 / z = 8 can only leave out the MFMAs of one plane's fragments: its nine K steps stay, half empty (12 or 16
+// MFMAs per wave instead of 28), with a LOAD phase -- fragment reads, 16 KB filter slab, counted wait -- as long as a full
+// step's.  Here every filter slab multiplies ONE output plane, and such a tap group is left out as nine whole steps:
+//  * block tile = (pair of clip windows 2 q, 2 q + 1; output plane z; band of 4 rows yp) = 2 x 4 x 28 = 224 positions x 256
+//    channels.  M wave m (waves 4 m .. 4 m + 3, N waves as above) holds clip window 2 q + m: accumulator slot i = columns
+//    4 i .. 4 i + 3 of the band's four rows, in the row order of the fragments above (2 x 2 pooling windows x (dy, dx)).
+//    conv3b runs a tile as two passes, z = 2 zp and 2 zp + 1, conv3a one pass per tile.
+//  * K order of a pass: channel sweep x kz x (ky, kx), every accumulator receives its MFMAs in the order of the body above;
+//    a pass of plane 0 runs kz = 1, 2 only, a pass of plane 7 kz = 0, 1: 144 / 288 steps instead of 216 / 432, all of
+//    them 28 MFMAs per wave.  The halo planes are never fetched.
+//  * tap group kz of a pass reads input plane z + kz only, so TWO plane buffers suffice (four above): the executed tap
+//    groups alternate between them, and each one issues, in its first three LOAD phases, the fetch of the NEXT executed tap
+//    group's plane -- of this sweep, the next sweep, the next pass or the next tile -- into the buffer its predecessor
+//    has finished with (one instruction per wave and step: all three in the first step measured +0.04 ms on conv3a and
+//    +0.1 ms on conv3b per 1024 windows -- a LOAD phase is about as long as a COMPUTE phase, and a longer one is exposed).  A buffer is 12 rows of pitch 2080: rows 0 - 5 = the band's six input rows of window 2 q, rows 6 - 11
+//    of window 2 q + 1; 24 LDS-DMA instructions of 1 KB, three per wave, no dump instructions.  The fragment address is ONE
+//    register (M wave m reads at + 6 m rows) + immediates (256 bytes per slot, ky pitch + 64 kx per tap); the per-lane part
+//    is the one of the body above, so its bank argument holds (scripts/check_conv_patch_banks.py enumerates both).
+//  * filter ring: 4 slots, 3 steps ahead, as above.  The look-ahead of the last three steps of a tap group belongs to the
+//    next EXECUTED tap group -- the same one whose plane the group fetched.
+//  * pooling (conv3b): pass 1 stages bf16(relu(max4 + bias)) of the lane's pooling windows, pass 2 the maximum of its own
+//    such value and the staged one: adding one bias, ReLU and the rounding are monotone, so this is bf16(relu(max8 + bias)) bit
+//    for bit (finite inputs; the values are >= +0, so the bf16 maximum is an unsigned 16-bit one).  The same lane owns the
+//    same (window, channels) in both passes: no exchange between waves, and the groups stay staggered between the passes.
+//    conv3a stores un-pooled from registers and never levels the groups.
+//  * ragged pair (odd n_windows): the second window of the last pair reads the first one's planes and stores nothing.
+//  * tile order, conv3b: (chunk of RGP_CP_CHUNK28P pairs, zp, pair, yp) -- runs of equal-length tiles per XCD, as above.  A
+//    run of 16 pairs x 7 bands = 112 tiles is 3.5 lockstep rounds of an XCD's 32 CUs, so every CU gets 7 short tiles per
+//    two short runs (first + last pooled plane of a chunk); with chunks of 8 pairs (runs of 56) the CUs get 3 or 4 and wait
+//    for each other: measured +0.25 ms per 1024 windows, slower than the two-plane tile.
+//    conv3a: (pair, yp, z + rotation), the order of conv2a's inference forward above: the 8 planes of a band run side by side
+//    in a lockstep round, and plane z + kz of a sweep is fetched by the passes z - 1, z, z + 1 within 27 steps of each other
+//    -- one L2 fill serves them (a pass fetches 3 planes per output plane where the two-plane tile fetches 4 per 2) -- and
+//    the rotation deals every CU its two short passes per 8: -0.17 ms per 1024 windows against the chunk order.  For conv3b
+//    (4 pooled planes side by side share only their edge planes) the same order measured no different from chunks.
+#ifndef RGP_CP_CHUNK28P
+#define RGP_CP_CHUNK28P 16
+#endif
+
+template <int CIN, int NOUT, bool POOL> struct PatchPureCfg {
+  using B = PatchCfg<CIN, NOUT, 28, 8, POOL>;
+  static constexpr int LP = B::LP;                         // 2080
+  static constexpr int PPW = 3;                            // plane DMA instructions per wave: 12 rows x 2 / 8 waves
+  static constexpr int BUF_STRIDE = (12 * LP + 255) / 256 * 256;      // 25 088
+  static constexpr int BRING_OFF = 2 * BUF_STRIDE;         // 50 176
+  static constexpr int BPW = B::BPW, BSLOT = B::BSLOT, NSLOT = B::NSLOT, AHEAD = B::AHEAD;
+  static constexpr int STG_OFF = BRING_OFF + NSLOT * BSLOT;
+  static constexpr int STG_LD = NOUT + 8;
+  static constexpr int WIN = 56;                           // pooling windows of a tile: 2 clip windows x 2 rows x 14
+  static constexpr int BIAS_OFF = POOL ? STG_OFF + WIN * STG_LD * 2 : STG_OFF;
+  static constexpr int SMEM = BIAS_OFF + NOUT * 4;         // 146 304 (conv3b) / 116 736 (conv3a)
+  static constexpr int NCC = CIN / 32;
+  static constexpr int YT = 7;                             // bands per plane
+  static constexpr int ZT = POOL ? 4 : 8, NPASS = POOL ? 2 : 1;
+  static constexpr int TILES_PER_PAIR = ZT * YT;
+  static constexpr int CGN = NOUT / 8;
+  static_assert(B::NI == 4 && B::WNW == 4 && B::RPI == 2 && NOUT == 256, "wave tile 112 x 64, 2 (M) x 4 (N) waves");
+  static_assert(BRING_OFF % 1024 == 0 && SMEM <= 160 * 1024, "LDS budget");
+};
+
+template <int CIN, int NOUT, bool POOL>
+static __device__ __forceinline__ void conv_patch_pure_body(const ConvPatchParams& p) {
+  using C = PatchPureCfg<CIN, NOUT, POOL>;
+  using B = typename C::B;
+  constexpr int NI = 4;
+  extern __shared__ __attribute__((aligned(16))) char cp_smem[];
+  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)cp_smem;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 2, wn = wave & 3;                   // M wave = clip window of the pair = stagger group
+  const bool group_b = wave >= 4;
+  const int frow = lane & 15, fk = lane >> 4;
+
+  const int npair = (p.n_windows + 1) >> 1;
+  const int nt = npair * C::TILES_PER_PAIR;
+  auto tile_of = [&](int t) {                                // as above: XCD x owns a contiguous range of tiles
+    const int q = nt >> 3, r = nt & 7, x = t & 7, y = t >> 3;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
+  };
+  int t_seq = blockIdx.x;
+  if (t_seq >= nt) return;
+  // tile -> (pair, zt = pooled plane (conv3b) or plane (conv3a), band); the two orders: header
+  auto decode = [&](int tile, int& q, int& zt, int& yp) {
+    constexpr int NPC = RGP_CP_CHUNK28P, TPP = C::TILES_PER_PAIR;
+    if constexpr (!POOL) {
+      q = tile / TPP;
+      const int r = tile - q * TPP;
+      yp = r / C::ZT;
+      zt = ((r % C::ZT) + (tile >> 5)) & (C::ZT - 1);
+      return;
+    }
+    const int c = tile / (NPC * TPP), r = tile - c * (NPC * TPP);
+    const int cp = min(NPC, npair - c * NPC);                // pairs of this chunk (the last one may be short)
+    zt = r / (cp * C::YT);
+    const int r2 = r - zt * (cp * C::YT);
+    const int w = r2 / C::YT;
+    q = c * NPC + w;
+    yp = r2 - w * C::YT;
+  };
+
+  // plane z + kz (halo-padded index) of (pair q, band yp), channel sweep cc: this wave's half -- waves 0 - 3 fetch the six
+  // rows of window 2 q, waves 4 - 7 those of window 2 q + 1 (ragged pair: of window 2 q again)
+  auto plane_src = [&](int q, int z, int yp, int cc, int kz) -> const char* {
+    int w = 2 * q + wm;
+    if (w >= p.n_windows) w = 2 * q;
+    return (const char*)(p.in + (long long)w * B::IN_IMG + (long long)(z + kz) * B::IN_PLANE + (4 * yp) * B::IN_ROW + cc * 32);
+  };
+  // this wave's three of a plane's 24 DMA instructions: job j = (buffer row j / 2, 16-pixel part j % 2)
+  const unsigned dlane = (unsigned)((lane >> 2) * (CIN * 2) + (lane & 3) * 16);
+  auto dma_plane = [&](const char* src, int buf, bool last_touch, int u0, int u1) {
+#pragma unroll
+    for (int u = u0; u < u1; ++u) {
+      const int j = wave * C::PPW + u;
+      const int r = j >> 1, part = j & 1;
+      const char* g = src + (long long)(r - 6 * wm) * (B::IN_ROW * 2) + part * 16 * (CIN * 2) + dlane;
+      char* l = cp_smem + buf * C::BUF_STRIDE + r * C::LP + part * 1024;
+      if (last_touch)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, 2 /* nt */);
+      else
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, RGP_PLANE_AUX);
+    }
+  };
+  // filter slabs: as above
+  const int brow = lane >> 2;
+  const int bchk = (lane & 3) ^ ((-(brow >> 2)) & 3);
+  auto b_row = [&](int blk) { return (blk / NI) * (16 * NI) + brow * NI + (blk % NI); };
+  unsigned b_off[C::BPW];
+#pragma unroll
+  for (int u = 0; u < C::BPW; ++u) b_off[u] = (unsigned)(b_row(wave * C::BPW + u) * (B::K * 2) + bchk * 16);
+  auto dma_b = [&](int slot, int cc, int tap) {
+    const int koff = (((cc >> 1) * 27 + tap) * 64 + (cc & 1) * 32) * 2;
+    const char* base = (const char*)p.wp + koff;
+#pragma unroll
+    for (int u = 0; u < C::BPW; ++u)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + b_off[u]),
+                                       (__attribute__((address_space(3))) void*)(cp_smem + C::BRING_OFF + slot * C::BSLOT + (wave * C::BPW + u) * 1024),
+                                       16, 0, 0);
+  };
+
+  // fragment row frow: pooling window frow >> 2 of the slot's 2 x 2 -- (row pair, column pair) = (0, 0), (1, 0), (1, 1), (0, 1) --
+  // and (dy, dx) = ((frow >> 1) & 1, frow & 1); K chunk fk
+  const int r_w = frow >> 2, r_ypl = (r_w == 1 || r_w == 2) ? 1 : 0, r_xo = r_w >> 1;
+  const int r_dy = (frow >> 1) & 1, r_dx = frow & 1;
+  const unsigned ra0 = lds0 + (6 * wm + 2 * r_ypl + r_dy) * C::LP + (2 * r_xo + r_dx) * 64 + fk * 16;
+  const unsigned b_addr = lds0 + C::BRING_OFF + (wn * NI) * 1024 + frow * 64 + ((fk ^ ((-(frow >> 2)) & 3)) << 4);
+
+  if (tid < NOUT) ((float*)(cp_smem + C::BIAS_OFF))[tid] = p.bias[tid];
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+
+  int q, zt, yp;
+  decode(tile_of(t_seq), q, zt, yp);
+  // ---- prologue (once): the plane of the first executed tap group into buffer 0, the filter slabs of steps 0 .. 2 ----
+  {
+    const int z0 = POOL ? 2 * zt : zt, k0 = z0 == 0 ? 1 : 0;
+    dma_plane(plane_src(q, z0, yp, 0, k0), 0, false, 0, C::PPW);
+    dma_b(0, 0, k0 * 9);
+    dma_b(1, 0, k0 * 9 + 1);
+    dma_b(2, 0, k0 * 9 + 2);
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * C::BPW) : "memory");   // the plane and slab 0 landed
+    __builtin_amdgcn_s_barrier();
+  }
+  int slot = 0;
+  int buf = 0;                                               // plane buffer of the current tap group
+  unsigned ra = ra0;
+  if (group_b) __builtin_amdgcn_s_barrier();                 // run one half-step behind group A
+  while (true) {
+    const int t_next = t_seq + gridDim.x;
+    const bool has_next = t_next < nt;
+    // the tile after this one (after the last one: this tile again -- its fetches land in buffers nobody reads any more)
+    int qn, ztn, ypn;
+    decode(tile_of(has_next ? t_next : t_seq), qn, ztn, ypn);
+#pragma clang loop unroll(disable)
+    for (int ps = 0; ps < C::NPASS; ++ps) {
+      const int z = POOL ? 2 * zt + ps : zt;
+      const int k0 = z == 0 ? 1 : 0, k1 = z == 7 ? 1 : 2;   // executed tap groups of this pass
+      // the pass after this one
+      const bool same_tile = ps + 1 < C::NPASS;
+      const int jq = same_tile ? q : qn, jyp = same_tile ? yp : ypn;
+      const int jz = same_tile ? z + 1 : (POOL ? 2 * ztn : ztn);
+      const int jk0 = jz == 0 ? 1 : 0;
+
+      f32x4 acc[7][NI];
+#pragma unroll
+      for (int i = 0; i < 7; ++i)
+#pragma unroll
+        for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+#pragma clang loop unroll(disable)
+      for (int cc = 0; cc < C::NCC; ++cc) {
+#pragma clang loop unroll(disable)
+        for (int kz = k0; kz <= k1; ++kz) {
+          // the next executed tap group (ncc, nkz): its plane is fetched by this one, and the filter look-ahead of this
+          // group's last three steps are its first three slabs
+          int ncc, nkz;
+          const char* npl;
+          if (kz < k1) { ncc = cc; nkz = kz + 1; npl = plane_src(q, z, yp, ncc, nkz); }
+          else if (cc + 1 < C::NCC) { ncc = cc + 1; nkz = k0; npl = plane_src(q, z, yp, ncc, nkz); }
+          else { ncc = 0; nkz = jk0; npl = plane_src(jq, jz, jyp, ncc, nkz); }
+          // odd sweeps read the second half of the 128-byte lines their predecessor brought in: `nt`, as above (conv3b only)
+          const bool lt = CIN != 128 && (ncc & 1) != 0;
+#pragma unroll
+          for (int t9 = 0; t9 < 9; ++t9) {
+            // ---------------- LOAD ----------------
+            f32x4 af[7], bf[NI];
+            const unsigned bb = b_addr + slot * C::BSLOT;
+            auto reads = [&](auto T9) {
+              constexpr int t = decltype(T9)::value;
+              constexpr int imm = (t / 3) * C::LP + (t % 3) * 64;
+              af[0] = cp_lds_read128<imm>(ra);
+              af[1] = cp_lds_read128<imm + 256>(ra);
+              af[2] = cp_lds_read128<imm + 512>(ra);
+              af[3] = cp_lds_read128<imm + 768>(ra);
+              af[4] = cp_lds_read128<imm + 1024>(ra);
+              af[5] = cp_lds_read128<imm + 1280>(ra);
+              af[6] = cp_lds_read128<imm + 1536>(ra);
+            };
+            switch (t9) {
+              case 0: reads(std::integral_constant<int, 0>{}); break;
+              case 1: reads(std::integral_constant<int, 1>{}); break;
+              case 2: reads(std::integral_constant<int, 2>{}); break;
+              case 3: reads(std::integral_constant<int, 3>{}); break;
+              case 4: reads(std::integral_constant<int, 4>{}); break;
+              case 5: reads(std::integral_constant<int, 5>{}); break;
+              case 6: reads(std::integral_constant<int, 6>{}); break;
+              case 7: reads(std::integral_constant<int, 7>{}); break;
+              default: reads(std::integral_constant<int, 8>{}); break;
+            }
+            bf[0] = cp_lds_read128<0>(bb);
+            bf[1] = cp_lds_read128<1024>(bb);
+            bf[2] = cp_lds_read128<2048>(bb);
+            bf[3] = cp_lds_read128<3072>(bb);
+            __builtin_amdgcn_sched_barrier(0);
+            auto issue_b = [&]() {
+              // filter slab three executed steps ahead
+              int slot3 = slot + C::AHEAD;
+              if (slot3 >= C::NSLOT) slot3 -= C::NSLOT;
+              if (t9 < 6) dma_b(slot3, cc, kz * 9 + t9 + 3);
+              else dma_b(slot3, ncc, nkz * 9 + t9 - 6);
+            };
+            // the plane of the next executed tap group: one of the wave's three instructions in each of the steps 0 .. 2
+            if (t9 < 3) dma_plane(npl, buf ^ 1, lt, t9, t9 + 1);
+            issue_b();
+            __builtin_amdgcn_sched_barrier(0);
+            // slab s+1 landed: younger are slabs s+2, s+3, this step's plane instruction and the previous step's (the last
+            // one has landed by the wait of step 4)
+            if (t9 == 1 || t9 == 2) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * C::BPW + 2) : "memory");
+            else if (t9 == 0 || t9 == 3) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * C::BPW + 1) : "memory");
+            else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * C::BPW) : "memory");
+#pragma unroll
+            for (int i = 0; i < 7; ++i) asm volatile("" : "+v"(af[i]));
+#pragma unroll
+            for (int j = 0; j < NI; ++j) asm volatile("" : "+v"(bf[j]));
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            // ---------------- COMPUTE ----------------
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int j = 0; j < NI; ++j) {
+#pragma unroll
+              for (int i = 0; i < 7; ++i) {
+                const int ii = RGP_MMA_ORDER == 2 && (j & 1) ? 6 - i : i;
+                Mma<bf16_t>::step(acc[ii][j], af[ii], bf[j]);
+              }
+            }
+            __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            slot = slot + 1 == C::NSLOT ? 0 : slot + 1;
+          }
+          buf ^= 1;
+          ra = ra0 + buf * C::BUF_STRIDE;
+        }
+      }
+
+      // epilogue-only lane values: re-derived per pass from opaque copies of the lane ids (see the body above)
+      int e_fk = fk, e_frow = frow, e_tid = tid;
+      asm volatile("" : "+v"(e_fk), "+v"(e_frow), "+v"(e_tid));
+      const int e_ypl = (e_fk == 1 || e_fk == 2) ? 1 : 0;    // this lane's pooling window of slot i: row pair e_ypl, column pair 2 i + (e_fk >> 1)
+      float b4[NI];
+#pragma unroll
+      for (int j = 0; j < NI; ++j) b4[j] = ((const float*)(cp_smem + C::BIAS_OFF))[wn * 64 + e_frow * 4 + j];
+      if constexpr (POOL) {
+        // ---- pass epilogue: max over (dy, dx) = the four registers of an accumulator, bias + ReLU, bf16; pass 2: maximum with
+        // the value this lane staged in pass 1 ----
+        typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+        bf16_t* stg = (bf16_t*)(cp_smem + C::STG_OFF);
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+          unsigned short pv[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const f32x4 c = acc[i][j];
+            pv[j] = f2bf(cp_relu(cp_max(cp_max3(c[0], c[1], c[2]), c[3]) + b4[j]));
+          }
+          u16x2 o0 = {pv[0], pv[1]}, o1 = {pv[2], pv[3]};
+          bf16_t* sp = stg + ((2 * wm + e_ypl) * 14 + 2 * i + (e_fk >> 1)) * C::STG_LD + wn * 64 + 4 * e_frow;
+          if (ps == 1) {
+            const uint2 prev = *(const uint2*)sp;
+            o0 = __builtin_elementwise_max(o0, __builtin_bit_cast(u16x2, prev.x));
+            o1 = __builtin_elementwise_max(o1, __builtin_bit_cast(u16x2, prev.y));
+          }
+          uint2 o;
+          o.x = __builtin_bit_cast(unsigned, o0);
+          o.y = __builtin_bit_cast(unsigned, o1);
+          *(uint2*)sp = o;
+        }
+        if (ps == 1) {
+          // ---- tile epilogue: level the groups, 16-byte stores of the staged 56 pooling windows x 256 channels ----
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // raw barriers: __syncthreads() would also drain the look-ahead DMA
+          if (!group_b) __builtin_amdgcn_s_barrier();
+          __builtin_amdgcn_s_barrier();
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const int item = e_tid + 512 * k;
+            const int w = item / C::CGN, cg = item % C::CGN;  // pooling window of the tile, 8-channel group
+            const int cw = w / 28, wr = w - 28 * cw, ypl = wr / 14, xp = wr - 14 * ypl;
+            if (w < C::WIN && 2 * q + cw < p.n_windows)
+              *(u32x4*)(p.out + (long long)(2 * q + cw) * B::OUT_IMG + (zt + 1) * B::OUT_PLANE + (2 * yp + ypl + 1) * B::OUT_ROW + (xp + 1) * NOUT + cg * 8) =
+                  *(const u32x4*)(stg + w * C::STG_LD + cg * 8);
+          }
+          if (has_next && group_b) __builtin_amdgcn_s_barrier();   // staggered again
+        }
+      } else {
+        // ---- epilogue: bias + ReLU, 8-byte stores from registers (slot i, register e: dy = e >> 1, dx = e & 1) ----
+        if (2 * q + wm < p.n_windows) {
+#pragma unroll
+          for (int i = 0; i < 7; ++i) {
+            const long long ow = (long long)(2 * q + wm) * B::OUT_IMG + (z + 1) * B::OUT_PLANE + (4 * yp + 2 * e_ypl + 1) * B::OUT_ROW +
+                                 (2 * (2 * i + (e_fk >> 1)) + 1) * NOUT + wn * 64 + e_frow * 4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const long long oe = ow + (e >> 1) * B::OUT_ROW + (e & 1) * NOUT;
+              float v[NI];
+#pragma unroll
+              for (int j = 0; j < NI; ++j) v[j] = fmaxf(acc[i][j][e] + b4[j], 0.f);
+              uint2 o;
+              o.x = (unsigned)f2bf(v[0]) | ((unsigned)f2bf(v[1]) << 16);
+              o.y = (unsigned)f2bf(v[2]) | ((unsigned)f2bf(v[3]) << 16);
+              *(uint2*)(p.out + oe) = o;
+            }
+          }
+        }
+      }
+    }
+    if (!has_next) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the look-ahead DMA lands before the LDS is released
+      if constexpr (!POOL) { if (!group_b) __builtin_amdgcn_s_barrier(); }   // every wave has met the same number of barriers
+      break;
+    }
+    t_seq = t_next;
+    q = qn; zt = ztn; yp = ypn;
+  }
+}
+
+// (a kernel name of its own; rgp_c3d_layer_kernel_name reports a layer by its shape, whichever body runs it)
+template <int CIN, int NOUT, bool POOL>
+static __global__ __launch_bounds__(512) void conv_patch_pure_bf16_kernel(const ConvPatchParams p) {
+  conv_patch_pure_body<CIN, NOUT, POOL>(p);
 }
 
 }  // namespace rgp

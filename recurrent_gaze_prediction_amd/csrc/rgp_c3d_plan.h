@@ -37,6 +37,9 @@ struct rgp_c3d {
   // operands, bit-identical results; switched off per plan by RGP_C3D_CONV2A_ROWWISE.  Training plans (arg-max codes
   // recorded) run conv_patch_bf16_kernel<..., ARGMAX>.
   bool conv2a_slab() const { return use_patch() && !save && !(kernels & RGP_C3D_CONV2A_ROWWISE) && rgp::dev_knob("RGP_C2A_SLAB", 1) != 0; }
+  // conv3a's / conv3b's INFERENCE forward on the plane-pure form of the patch kernel (conv_patch_pure_bf16_kernel,
+  // conv_patch.hip.h): same operands, bit-identical results; switched off per plan by RGP_C3D_CONV3_TWOPLANE
+  bool conv3_pure() const { return use_patch() && !save && !(kernels & RGP_C3D_CONV3_TWOPLANE); }
   rgp::ConvDesc L[8];
   size_t act_off[9] = {0};       // act[i] = halo-padded input of layer i; act[8] = conv5b rows
   long long act_stride[9] = {0}; // elements per window

@@ -52,6 +52,28 @@ static int run_conv2a_slab(rgp_c3d* c, int n, hipStream_t s) {
   return RGP_OK;
 }
 
+// conv3a / conv3b + pool3, inference plans: the plane-pure form (conv_patch.hip.h)
+template <int CIN, bool POOL>
+static int run_conv_patch_pure(rgp_c3d* c, int layer, int n, hipStream_t s) {
+  using Cfg = PatchPureCfg<CIN, 256, POOL>;
+  ConvPatchParams p;
+  p.in = (const bf16_t*)(c->ws + c->act_off[layer]);
+  p.wp = (const bf16_t*)(c->ws + c->L[layer].w_off);
+  p.bias = c->bias[layer];
+  p.out = (bf16_t*)(c->ws + c->act_off[layer + 1]);
+  p.argmax = nullptr;
+  p.mask = nullptr;
+  p.n_windows = n;
+  p.ablate = 0;
+  int n_cu = 0;
+  RGP_TRY(device_cu_count(&n_cu));
+  auto kern = conv_patch_pure_bf16_kernel<CIN, 256, POOL>;
+  RGP_TRY(ensure_dyn_smem((const void*)kern, Cfg::SMEM));
+  kern<<<n_cu, 512, Cfg::SMEM, s>>>(p);
+  RGP_HIP(hipGetLastError());
+  return RGP_OK;
+}
+
 template <int CIN, bool POOL, bool ARGMAX>
 static int run_conv_patch14(rgp_c3d* c, int layer, int n, hipStream_t s) {
   using Cfg = Patch14Cfg<CIN, POOL>;
@@ -101,6 +123,8 @@ int run_conv_patch_bf16(rgp_c3d* c, int layer, int n, hipStream_t s) {
   if (layer == 5) return c->save ? run_conv_patch14<512, true, true>(c, layer, n, s) : run_conv_patch14<512, true, false>(c, layer, n, s);
   if (layer == 1 && c->conv2a_slab()) return run_conv2a_slab(c, n, s);
   if (layer == 1) return c->save ? run_conv_patch<64, 128, 56, 16, true, true>(c, layer, n, s) : run_conv_patch<64, 128, 56, 16, true, false>(c, layer, n, s);
+  if (layer == 2 && c->conv3_pure()) return run_conv_patch_pure<128, false>(c, layer, n, s);
+  if (layer == 3 && c->conv3_pure()) return run_conv_patch_pure<256, true>(c, layer, n, s);
   if (layer == 2) return run_conv_patch<128, 256, 28, 8, false, false>(c, layer, n, s);
   if (layer == 3) return c->save ? run_conv_patch<256, 256, 28, 8, true, true>(c, layer, n, s) : run_conv_patch<256, 256, 28, 8, true, false>(c, layer, n, s);
   return set_err(RGP_EINVAL, "conv_patch: no kernel for layer %d", layer);

@@ -1115,13 +1115,15 @@ class C3DEngine(object):
 
     KERNELS = {'patch': 0, 'igemm': _lib.RGP_C3D_KERNELS_IGEMM,
                'igemm128': _lib.RGP_C3D_KERNELS_IGEMM | _lib.RGP_C3D_KERNELS_TILE128,
-               'patch-rowwise': _lib.RGP_C3D_CONV2A_ROWWISE}
+               'patch-rowwise': _lib.RGP_C3D_CONV2A_ROWWISE, 'patch-twoplane': _lib.RGP_C3D_CONV3_TWOPLANE}
 
     def __init__(self, max_windows, dtype='bf16', device='cuda:0', save_for_backward=False, kernels='patch'):
         """kernels: 'patch' (default: the layer-specific kernels for conv2a..conv4b), 'igemm' (the general
         implicit-GEMM / filter-gradient kernels for every layer, tile by problem size) or 'igemm128' (the same on
         the 128x128 tile loop only), 'patch-rowwise' (the patch kernels with conv2a's inference forward on
-        conv_patch_bf16_kernel instead of conv_patch_slab_bf16_kernel: RGP_C3D_CONV2A_ROWWISE) -- rgp_c3d_create_ex flags; the alternatives exist
+        conv_patch_bf16_kernel instead of conv_patch_slab_bf16_kernel: RGP_C3D_CONV2A_ROWWISE),
+        'patch-twoplane' (the patch kernels with conv3a's / conv3b's inference forward on the two-plane block tile
+        instead of the plane-pure one: RGP_C3D_CONV3_TWOPLANE) -- rgp_c3d_create_ex flags; the alternatives exist
         for cross-checks."""
         self.lib = _lib.load()
         self.device = _require_gpu(device)
