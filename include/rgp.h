@@ -132,14 +132,38 @@ int rgp_grcn_forward_rows(rgp_grcn_t* plan, const void* c3d_rows, float* logits,
  *              position mod T gets results that do not depend on where the stream was cut; with cuts at multiples of T
  *              this is the reference's chunked evaluation plus a carried state.
  * rgp_grcn_forward_stream(.., NULL, state_out, T, 0, ..) computes what rgp_grcn_forward computes.  Argument errors are
- * RGP_EINVAL and are reported ahead of the plan's bound / weights state.  A training plan accepts the call, but a
- * following rgp_grcn_backward / _from_states returns RGP_ESTATE (no truncated BPTT) until a plain forward has run.
+ * RGP_EINVAL and are reported ahead of the plan's bound / weights state.  A training plan accepts the call; a following
+ * rgp_grcn_backward / _from_states returns RGP_ESTATE until a plain forward has run (they differentiate a recurrence from the
+ * zero state over all T steps with batch-norm slot t), and rgp_grcn_backward_stream below differentiates the call.
  * A persistent launch that times out (rgp_grcn_status) NaN-poisons state_out of its clips along with the maps; state_in
  * being read-only, the caller repeats the call.
  * rgp_grcn_state_elems: B*49*S, the fp32 elements of a state; host-only, works on an unbound plan. */
 size_t rgp_grcn_state_elems(const rgp_grcn_t* plan);
 int rgp_grcn_forward_stream(rgp_grcn_t* plan, const float* c3d_input, const void* c3d_rows, const float* state_in, float* state_out,
                             int n_valid, int bn_phase, float* logits, float* probs, rgp_stream_t stream);
+/* Training across the carried state: the backward of the plan's LAST forward of either kind, on a training plan, either BPTT
+ * path.  Behind rgp_grcn_forward_stream(.., state_in, .., n_valid, bn_phase, ..) it differentiates that call: steps
+ * 0 .. n_valid-1, the recurrence started at state_in, step t through batch-norm slot (bn_phase + t) % T (its gamma is read and
+ * its gradient slot written; the slots of the steps behind n_valid receive zeros).  Behind rgp_grcn_forward / _forward_rows:
+ * all T steps from the zero state, slot t.
+ *   loss         that of rgp_grcn_backward, summed over the frames of the valid steps and divided by loss_frames (> 0): the
+ *                caller's divisor, so that the gradients of a film's chunks add up to the gradient of a mean over the film.
+ *                logits, probs, labels are full size [B,T,49,49]; what lies behind n_valid reaches no output
+ *   d_state_out  fp32 [B][49][S], 16-byte aligned: the gradient of whatever comes later w.r.t. the state_out the forward handed
+ *                out (the state behind step n_valid); NULL = zeros (truncated BPTT, or a film's last chunk); never written
+ *   d_state_in   fp32 [B][49][S], 16-byte aligned, may be NULL, must not be d_state_out: receives d loss / d state_in.  A
+ *                persistent BPTT launch that times out poisons the gate-gradient rows of the valid steps and this: NaN, never
+ *                finite and wrong
+ *   grads        written, not accumulated, as rgp_grcn_backward writes them; rgp_grcn_wait_grads works as behind it
+ * The inputs of the forward must be finite over all T steps, also behind n_valid: the gradient rows of those steps are zero,
+ * and the hoisted filter gradients multiply them with what the forward saved there.
+ * rgp_grcn_backward_input behind this call returns d_rows with the rows of the steps >= n_valid exactly zero.
+ * Argument errors are RGP_EINVAL, name the argument, and come ahead of the bound / weights checks; an inference plan, or a plan
+ * with no forward yet, is RGP_ESTATE.  rgp_grcn_backward and rgp_grcn_backward_from_states are unchanged and keep refusing
+ * behind a streaming forward.  Not captured into HIP graphs (not tested). */
+int rgp_grcn_backward_stream(rgp_grcn_t* plan, const float* logits, const float* probs, const float* labels,
+                             const float* d_state_out, float* d_state_in, long long loss_frames,
+                             const rgp_grcn_weights* grads, int loss_type, rgp_stream_t stream);
 
 /* Stages of the same graph on the plan's workspace (for tests / profiling):
  * rgp_proj_fwd          transpose + xw_plus_b                  gaze_grcn.py:225-254
@@ -154,7 +178,9 @@ int rgp_head_fwd(rgp_grcn_t* plan, float* logits, rgp_stream_t stream);
 /* Copies an intermediate, un-padded and widened to fp32, into dst:
  * "c3d_embedded" [B,T,7,7,P]   "xpre" [B,T,7,7,3S] (z|r|c pre-activations of W*x)
  * "rcn_outputs" [B,T,7,7,S] (h_t)   "bn" [B,T,7,7,S]   "d1" [B*T,23,23,64]   "d2" [B*T,49,49,32]
- * "u" / "r" / "c" [T,B,7,7,S] (r,c only with save_for_backward). */
+ * "u" / "r" / "c" [T,B,7,7,S] (r,c only with save_for_backward).
+ * Of the last backward of a save_for_backward plan (read-only, for tests): "dxpre" [B,T,7,7,3S] (gradients of the z|r|c
+ * pre-activations)   "dh_head" [T,B,7,7,S] (gradient reaching h_t from the head, behind the batch-norm backward). */
 int rgp_grcn_read_buffer(rgp_grcn_t* plan, const char* name, float* dst, rgp_stream_t stream);
 /* Number of fp32 elements rgp_grcn_read_buffer writes for name (0 if unknown). */
 size_t rgp_grcn_buffer_elems(const rgp_grcn_t* plan, const char* name);

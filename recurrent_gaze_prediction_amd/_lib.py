@@ -186,6 +186,8 @@ SIGNATURES = {
     'rgp_grcn_forward_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'rgp_grcn_state_elems': (c_size_t, [c_void_p]),
     'rgp_grcn_forward_stream': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'rgp_grcn_backward_stream': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong,
+                                         ctypes.POINTER(GrcnWeights), c_int, c_void_p]),
     'rgp_proj_fwd': (c_int, [c_void_p, c_void_p, c_void_p]),
     'rgp_convgru_xconv_fwd': (c_int, [c_void_p, c_void_p]),
     'rgp_convgru_seq_fwd': (c_int, [c_void_p, c_void_p]),

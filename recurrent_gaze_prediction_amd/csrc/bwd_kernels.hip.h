@@ -31,6 +31,34 @@ static __global__ __launch_bounds__(256) void dlogits_kernel(const float* __rest
   if (threadIdx.x == 0) frame_sum[row] = acc;
 }
 
+// The same for a streaming call's backward (rgp_grcn_backward_stream): frame = b T + t; the frames of the steps t >= n_valid
+// lie behind the call's last valid step: their dz rows and sums are written as zeros, whatever the operands hold there (and
+// whatever an earlier call left in the row).  A sibling: the plain backward keeps the kernel it was measured with.
+static __global__ __launch_bounds__(256) void dlogits_stream_kernel(const float* __restrict__ probs_or_logits,
+                                                             const float* __restrict__ labels, float* __restrict__ dz,
+                                                             float* __restrict__ frame_sum, int n, float scale, int l2, int T_,
+                                                             int n_valid) {
+  __shared__ float sh[4];
+  const long long row = blockIdx.x;
+  if ((int)(row % T_) >= n_valid) {
+    for (int j = threadIdx.x; j < n; j += 256) dz[row * n + j] = 0.f;
+    if (threadIdx.x == 0) frame_sum[row] = 0.f;
+    return;
+  }
+  float gs = 0.f;
+  for (int j = threadIdx.x; j < n; j += 256) gs += labels[row * n + j];
+  gs = block_reduce(gs, sh, false);
+  float acc = 0.f;
+  for (int j = threadIdx.x; j < n; j += 256) {
+    const float p = probs_or_logits[row * n + j], g = labels[row * n + j];
+    const float d = (l2 ? (p - g) : (p * gs - g)) * scale;
+    dz[row * n + j] = d;
+    acc += d;
+  }
+  acc = block_reduce(acc, sh, false);
+  if (threadIdx.x == 0) frame_sum[row] = acc;
+}
+
 // out[0] (+)= scale * sum(x[0..n))   (single block, deterministic order)
 static __global__ __launch_bounds__(256) void sum_kernel(const float* __restrict__ x, float* __restrict__ out, long long n,
                                                   float scale) {
@@ -212,9 +240,12 @@ static __global__ __launch_bounds__(256) void head_unfold_grads_kernel(const flo
 static __global__ __launch_bounds__(256) void bn_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ hall,
                                                      const float* __restrict__ gamma, float* __restrict__ dgamma,
                                                      float* __restrict__ dbeta, float* __restrict__ dh_head, int B,
-                                                     int T_, int S, float inv, int t0) {
+                                                     int T_, int S, float inv, int t0, int phase) {
   __shared__ float sh[4];
   const int t = blockIdx.y + t0, c0 = blockIdx.x * 8;      // (grid.y = T, t0 = 0: every step; grid.y = 1: step t0)
+  // the batch-norm layer step t went through: slot t, or (phase + t) % T of a streaming call (a bijection over t: every slot
+  // of dgamma / dbeta is written by exactly one block row)
+  const int slot = (phase + t) % T_;
   float sg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const int rows = B * 49;
   for (int r = threadIdx.x; r < rows; r += 256) {
@@ -226,7 +257,7 @@ static __global__ __launch_bounds__(256) void bn_bwd_kernel(const float* __restr
     for (int i = 0; i < 8; ++i) {
       sg[i] += d[i] * h[i];
       sb[i] += d[i];
-      o[i] = d[i] * gamma[(long long)t * S + c0 + i] * inv;
+      o[i] = d[i] * gamma[(long long)slot * S + c0 + i] * inv;
     }
   }
 #pragma unroll
@@ -234,8 +265,8 @@ static __global__ __launch_bounds__(256) void bn_bwd_kernel(const float* __restr
     const float a = block_reduce(sg[i], sh, false);
     const float b2 = block_reduce(sb[i], sh, false);
     if (threadIdx.x == 0) {
-      dgamma[(long long)t * S + c0 + i] = a * inv;
-      dbeta[(long long)t * S + c0 + i] = b2;
+      dgamma[(long long)slot * S + c0 + i] = a * inv;
+      dbeta[(long long)slot * S + c0 + i] = b2;
     }
   }
 }

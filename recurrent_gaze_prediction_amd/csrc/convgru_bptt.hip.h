@@ -13,6 +13,15 @@
 // (K = 1152 and 2304: 27 k-steps per wave and K-quarter = 108 VGPRs) stay in registers for the whole sequence, the carry
 // of a tile in the registers of the wave that finalises it.  dc_pre, then dz_pre | dr_pre (bf16 operand images) are
 // exchanged between the members twice per step.
+//
+// Streaming (rgp_grcn_backward_stream), template argument STREAM.  STREAM = false is what a backward over all T steps from the
+// zero state launches: the source and the parameter block it was measured with.  STREAM = true differentiates the first n_valid
+// steps of a streaming forward: the loop runs t = n_valid - 1 .. 0 on phase counters 2 (n_valid - 1 - t), so a film's one-step
+// tail pays two rendezvous, not 2 T; the carry registers start from d loss / d state_out (null: zeros); step 0 runs its second
+// half as well when d loss / d state_in is wanted, and the wave that owns a tile stores the finished carry there.  Rows keep the
+// plan's T as their stride: rows t >= n_valid of dxpre are neither read nor written (the host has zeroed them), and no row is
+// addressed that STREAM = false does not address.  A launch that lost a member poisons the dxpre rows t < n_valid -- the bound
+// of the poison loop is the bound of the step loop -- and d_state_in.
 #pragma once
 #include "seq_group.hip.h"
 
@@ -33,6 +42,23 @@ struct BpttParams {
   SeqGroupArgs g;            // 2 T phase counters per group
   int T;
 };
+// STREAM = true takes this on top (the STREAM = false instantiations keep the parameter block they were measured with)
+struct BpttStreamParams : BpttParams {
+  int n_valid;               // steps of the streaming forward to differentiate, 1 .. T
+  const float* d_state_out;  // [B][49][128] fp32 gradient reaching the state behind step n_valid, or null = zeros
+  float* d_state_in;         // [B][49][128] fp32 d loss / d state_in, or null = not wanted
+};
+// The streaming arguments that only the prologue and the epilogue need (the two state pointers, the poison loop's bound) are read
+// from the kernel's argument block again where they are used, behind an opaque barrier the compiler cannot hoist the load over:
+// held in SGPRs across the step loop they were spilled to VGPR lanes (the <7> kernel has no scalar register to spare).  The block
+// is the kernel's only argument: it starts at the kernarg segment.
+__device__ __forceinline__ const BpttStreamParams* bptt_stream_args() {
+  auto k = __builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return (const BpttStreamParams*)k;
+}
+template <bool STREAM> struct BpttParamsOf { typedef BpttParams type; };
+template <> struct BpttParamsOf<true> { typedef BpttStreamParams type; };
 
 // LDS, the forward kernel's layout and size: two operand images, 4 x NF partial tiles of 1 KiB (in 56 KiB), staging, flag
 constexpr int BPTT_RED_OFF = 2 * SEQ_IMG;
@@ -41,8 +67,8 @@ constexpr int BPTT_FLAG_OFF = BPTT_STAGE_OFF + 4 * 512;
 constexpr int BPTT_SMEM = BPTT_FLAG_OFF + 16;
 static_assert(BPTT_SMEM <= 160 * 1024, "LDS budget");
 
-template <int NF>
-static __global__ __launch_bounds__(SEQ_NT) void convgru_bptt_kernel(const BpttParams p) {
+template <int NF, bool STREAM>
+static __global__ __launch_bounds__(SEQ_NT) void convgru_bptt_kernel(const typename BpttParamsOf<STREAM>::type p) {
   extern __shared__ __attribute__((aligned(16))) char sq_smem[];
   char* img_a = sq_smem;                 // dc_pre, later dz_pre
   char* img_b = sq_smem + SEQ_IMG;       // dr_pre
@@ -51,6 +77,11 @@ static __global__ __launch_bounds__(SEQ_NT) void convgru_bptt_kernel(const BpttP
   if (!g.init(sq_smem, 2 * SEQ_IMG, BPTT_STAGE_OFF, BPTT_FLAG_OFF, p.g, 2 * p.T)) return;
   const int kq = g.kq, ch = g.ch, clip0 = g.clip0;
   const int S = 128, T_ = p.T;
+  // steps of this launch.  A reference: with STREAM = false every use below IS T_, and the kernel compiles to the code that was
+  // measured (as a variable of its own, equal to T_, such a kernel took another register allocation)
+  int nv = 0;
+  if constexpr (STREAM) nv = p.n_valid;
+  const int& Tv = STREAM ? (const int&)nv : T_;
   const long long st = (long long)p.g.B * 49 * S;
   const unsigned xbytes = (unsigned)p.g.ngroups * 98u * 256u;
 
@@ -73,9 +104,19 @@ static __global__ __launch_bounds__(SEQ_NT) void convgru_bptt_kernel(const BpttP
       ovalid[o][r] = g.own_valid(o, r);
     }
   float carry[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  if constexpr (STREAM) {                                // d loss / d state_out: this lane's rows, its own channel
+    const float* seed = bptt_stream_args()->d_state_out;
+    if (seed) {
+#pragma unroll
+      for (int o = 0; o < 2; ++o)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (ovalid[o][r]) carry[o][r] = seed[((long long)(clip0 * 49 + orow[o][r])) * S + ch];
+    }
+  }
   __syncthreads();                                       // images zeroed, flag cleared (init)
 
-  for (int t = T_ - 1; t >= 0; --t) {
+  for (int t = Tv - 1; t >= 0; --t) {
     // saved forward quantities of this lane's rows (own channels)
     float hp[2][4], uu[2][4], rr[2][4], cc[2][4], dh[2][4];
 #pragma unroll
@@ -102,8 +143,8 @@ static __global__ __launch_bounds__(SEQ_NT) void convgru_bptt_kernel(const BpttP
 #pragma unroll
     for (int o = 0; o < 2; ++o)
       if (kq + 4 * o < NF) g.publish_tile(p.xch_c, xbytes, g.group, kq + 4 * o, dcp[o]);
-    g.arrive(2 * (T_ - 1 - t));
-    g.wait(2 * (T_ - 1 - t));
+    g.arrive(2 * (Tv - 1 - t));
+    g.wait(2 * (Tv - 1 - t));
     __syncthreads();
     g.load_image(p.xch_c, xbytes, g.group, img_a);
     __syncthreads();
@@ -156,16 +197,21 @@ static __global__ __launch_bounds__(SEQ_NT) void convgru_bptt_kernel(const BpttP
             p.dxpre[(((long long)(clip0 + c) * T_ + t) * 49 + r49) * (3 * S) + S + ch] = drp[o][r];
           }
     };
-    // (the last step's carry is not needed by anybody: the recurrence starts from h_0 = 0, gaze_grcn.py:262)
-    if (t == 0) { store_drp(); break; }
+    // (the last step's carry is not needed by anybody: the recurrence starts from h_0 = 0, gaze_grcn.py:262 -- unless a
+    // streaming call asks for it: d loss / d state_in)
+    bool last = t == 0;
+    if constexpr (STREAM) {
+      if (last) last = !bptt_stream_args()->d_state_in;
+    }
+    if (last) { store_drp(); break; }
 #pragma unroll
     for (int o = 0; o < 2; ++o)
       if (kq + 4 * o < NF) {
         g.publish_tile(p.xch_z, xbytes, g.group, kq + 4 * o, dzp[o]);
         g.publish_tile(p.xch_r, xbytes, g.group, kq + 4 * o, drp[o]);
       }
-    g.arrive(2 * (T_ - 1 - t) + 1);                       // (the hand-off's barriers also order the partial-tile reads above)
-    g.wait(2 * (T_ - 1 - t) + 1);
+    g.arrive(2 * (Tv - 1 - t) + 1);                       // (the hand-off's barriers also order the partial-tile reads above)
+    g.wait(2 * (Tv - 1 - t) + 1);
     __syncthreads();
     g.load_image(p.xch_z, xbytes, g.group, img_a);
     g.load_image(p.xch_r, xbytes, g.group, img_b);
@@ -198,16 +244,40 @@ static __global__ __launch_bounds__(SEQ_NT) void convgru_bptt_kernel(const BpttP
     }
     __syncthreads();                                      // partial tiles read before the next step overwrites them
   }
+  if constexpr (STREAM) {                                // the finished carry = d loss / d state_in
+    float* out = bptt_stream_args()->d_state_in;
+    if (out) {
+#pragma unroll
+      for (int o = 0; o < 2; ++o)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (ovalid[o][r]) out[((long long)(clip0 * 49 + orow[o][r])) * S + ch] = carry[o][r];
+    }
+  }
   // a group that timed out must not look like a result
   if (g.timed_out()) {
+    if constexpr (STREAM) {
+      float* out = bptt_stream_args()->d_state_in;
+      for (int t = 0; t < Tv; ++t)
 #pragma unroll
-    for (int o = 0; o < 2; ++o)
+        for (int o = 0; o < 2; ++o)
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (ovalid[o][r]) {
-          const int c = orow[o][r] / 49, r49 = orow[o][r] - c * 49;
-          p.dxpre[(((long long)(clip0 + c) * T_) * 49 + r49) * (3 * S) + ch] = __builtin_nanf("");
-        }
+          for (int r = 0; r < 4; ++r)
+            if (ovalid[o][r]) {
+              const int c = orow[o][r] / 49, r49 = orow[o][r] - c * 49;
+              p.dxpre[(((long long)(clip0 + c) * T_ + t) * 49 + r49) * (3 * S) + ch] = __builtin_nanf("");
+              if (t == 0 && out) out[((long long)(clip0 * 49 + orow[o][r])) * S + ch] = __builtin_nanf("");
+            }
+    } else {
+#pragma unroll
+      for (int o = 0; o < 2; ++o)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (ovalid[o][r]) {
+            const int c = orow[o][r] / 49, r49 = orow[o][r] - c * 49;
+            p.dxpre[(((long long)(clip0 + c) * T_) * 49 + r49) * (3 * S) + ch] = __builtin_nanf("");
+          }
+    }
   }
 }
 

@@ -314,9 +314,17 @@ struct FoldedHeadBwd {
   template <typename T>
   int pack(PackBatch<T>& pk, const float* kf) { return pk.add(b_hf, kf, b_hf.N, 0); }
   // d loss / d logits -> dz, d out_b
-  int loss_grad(char* ws, const float* logits, const float* probs, const float* labels, int loss_l2, int F, float* d_out_b, hipStream_t s) {
-    dlogits_kernel<<<F, 256, 0, s>>>(loss_l2 ? logits : probs, labels, (float*)(ws + dz.off), (float*)(ws + frame_sum.off), 2401,
-                                     1.0f / (float)F, loss_l2);
+  // loss_frames > 0 (a streaming call's backward): the divisor is the caller's, frames are (b, t) of T_ steps, and the dz rows
+  // of the frames t >= n_valid are written as zeros -- everything above the recurrence then contributes nothing for them
+  int loss_grad(char* ws, const float* logits, const float* probs, const float* labels, int loss_l2, int F, float* d_out_b, hipStream_t s,
+                long long loss_frames = 0, int T_ = 0, int n_valid = 0) {
+    if (loss_frames > 0) {
+      dlogits_stream_kernel<<<F, 256, 0, s>>>(loss_l2 ? logits : probs, labels, (float*)(ws + dz.off), (float*)(ws + frame_sum.off),
+                                              2401, 1.0f / (float)loss_frames, loss_l2, T_, n_valid);
+    } else {
+      dlogits_kernel<<<F, 256, 0, s>>>(loss_l2 ? logits : probs, labels, (float*)(ws + dz.off), (float*)(ws + frame_sum.off), 2401,
+                                       1.0f / (float)F, loss_l2);
+    }
     sum_kernel<<<1, 256, 0, s>>>((const float*)(ws + frame_sum.off), d_out_b, F, 1.0f);
     RGP_HIP(hipGetLastError());
     return RGP_OK;

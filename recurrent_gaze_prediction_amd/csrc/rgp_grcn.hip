@@ -431,6 +431,7 @@ int rgp_grcn_bind_workspace(rgp_grcn_t* g, void* workspace, size_t bytes, rgp_st
   RGP_TRY(g->sg.alloc_err());
   g->ws = (char*)workspace;
   g->weights_set = false;
+  g->fwd_done = false;
   // zero everything once: halos of E / Hp / RHp / Hbn / D1 / D2 stay zero because
   // epilogues only ever write interiors.
   RGP_HIP(hipMemsetAsync(g->ws, 0, g->ws_bytes, s));
@@ -515,19 +516,27 @@ static int grcn_tail(rgp_grcn_t* g, float* logits, float* probs, rgp_stream_t st
   return RGP_OK;
 }
 
+// fwd_done (what rgp_grcn_backward_stream asks for) is cleared when a public forward begins and set when it has enqueued
+// everything: a forward that fails half-way, or a stage run on its own, does not arm the streaming backward.
 int rgp_grcn_forward(rgp_grcn_t* g, const float* c3d_input, float* logits, float* probs, rgp_stream_t stream) {
+  if (g) g->fwd_done = false;
   RGP_TRY(rgp_proj_fwd(g, c3d_input, stream));
-  return grcn_tail(g, logits, probs, stream);
+  RGP_TRY(grcn_tail(g, logits, probs, stream));
+  g->fwd_done = true;
+  return RGP_OK;
 }
 
 int rgp_grcn_forward_rows(rgp_grcn_t* g, const void* c3d_rows, float* logits, float* probs, rgp_stream_t stream) {
+  if (g) g->fwd_done = false;
   RGP_TRY(check_ready(g));
   RGP_REQUIRE(c3d_rows && logits, "rgp_grcn_forward_rows: null argument");
   hipStream_t s = (hipStream_t)stream;
   const int pid = g->prof.begin(0, s);
   RGP_TRY(RGP_BY_DTYPE(g->dtype, proj_impl, g, nullptr, c3d_rows, s));
   g->prof.end(pid, s);
-  return grcn_tail(g, logits, probs, stream);
+  RGP_TRY(grcn_tail(g, logits, probs, stream));
+  g->fwd_done = true;
+  return RGP_OK;
 }
 
 size_t rgp_grcn_state_elems(const rgp_grcn_t* g) { return g ? (size_t)g->B * 49 * g->S : 0; }
@@ -535,13 +544,16 @@ size_t rgp_grcn_state_elems(const rgp_grcn_t* g) { return g ? (size_t)g->B * 49 
 int rgp_grcn_forward_stream(rgp_grcn_t* g, const float* c3d_input, const void* c3d_rows, const float* state_in, float* state_out,
                             int n_valid, int bn_phase, float* logits, float* probs, rgp_stream_t stream) {
   RGP_REQUIRE(g, "rgp_grcn_forward_stream: null plan");
+  g->fwd_done = false;
   RGP_TRY(check_stream_args("rgp_grcn_forward_stream", g->T, c3d_input, c3d_rows, state_in, state_out, n_valid, bn_phase, logits));
   RGP_TRY(check_ready(g));
   hipStream_t s = (hipStream_t)stream;
   StreamScope call(g->stream, state_in, state_out, n_valid, bn_phase);
   RGP_TRY(c3d_input ? rgp_proj_fwd(g, c3d_input, stream) : grcn_proj_rows_fwd(g, c3d_rows, s));
   RGP_TRY(grcn_tail(g, logits, probs, stream));
-  return grcn_state_out(g, s);
+  RGP_TRY(grcn_state_out(g, s));
+  g->fwd_done = true;
+  return RGP_OK;
 }
 
 }  // extern "C"
@@ -586,7 +598,12 @@ static bool find_view(const rgp_grcn* g, const char* name, BufView& v) {
   else if (n == "r" && g->save) v = {g->rall.off, g->o_lin49_S, 49, S, 49LL * S, (long long)g->T * g->B, true};
   else if (n == "c" && g->save) v = {g->call.off, g->o_lin49_S, 49, S, 49LL * S, (long long)g->T * g->B, true};
   else if (n == "h_all") v = {g->hall.off + (size_t)g->B * 49 * S * 4, g->o_lin49_S, 49, S, 49LL * S, (long long)g->T * g->B, true};
-  else return false;
+  else {                                                                  // a training plan's gradient buffers (read-only, for tests)
+    size_t off = 0;
+    if (!g->save || !grcn_bwd_view(g, name, &off)) return false;
+    if (n == "dxpre") v = {off, g->o_lin49_3S, 49, 3 * S, 49LL * 3 * S, g->F, true};                    // [B,T,7,7,3S]
+    else v = {off, g->o_lin49_S, 49, S, 49LL * S, (long long)g->T * g->B, true};                       // dh_head [T,B,7,7,S]
+  }
   return true;
 }
 

@@ -11,6 +11,7 @@
 // so BPTT itself is 2 dgrad convs + 2 element-wise kernels per step.
 #include <algorithm>
 #include <cstring>
+#include <string>
 
 #include "rgp_grcn_plan.h"
 #include "wgrad_launch.h"
@@ -110,15 +111,30 @@ __global__ __launch_bounds__(256) void dense_colsum_kernel(const T* __restrict__
   }
 }
 
+// What rgp_grcn_backward_stream adds to a backward (the plain calls: the defaults, and then every launch below is the one it
+// always was, in the same order).  Independent of where the gradient w.r.t. the states comes from (loss or ext_dy).
+struct GrcnBwdStream {
+  bool on = false;
+  int n_valid = 0;                     // steps of the last forward to differentiate (plain: T)
+  int bn_phase = 0;                    // batch-norm slot of step 0 in that forward
+  long long loss_frames = 0;           // the loss's divisor (plain: F)
+  const float* d_state_out = nullptr;  // [B][49][S] fp32, null = zeros
+  float* d_state_in = nullptr;         // [B][49][S] fp32, null = not wanted
+};
+
 template <typename T>
 int backward_impl(rgp_grcn* g, const float* probs, const float* logits, const float* labels,
-                  const rgp_grcn_weights* gr, int loss_l2, hipStream_t s, const float* ext_dy = nullptr) {
+                  const rgp_grcn_weights* gr, int loss_l2, hipStream_t s, const float* ext_dy = nullptr,
+                  const GrcnBwdStream& sb = GrcnBwdStream()) {
   GrcnBwd* b = g->bwd;
   char* ws = g->ws;
   const int B = g->B, T_ = g->T, S = g->S, P = g->P, F = g->F;
   const long long M = b->M, M2 = b->M2;
   auto wg_params = []() { WgradParams p; memset(&p, 0, sizeof(p)); return p; };
   const size_t st = (size_t)B * 49 * S;
+  const int n_valid = sb.on ? sb.n_valid : T_;
+  // the persistent kernel's streaming instantiation: only where the call differs from a backward over all T steps from zero
+  const bool stream_kernel = sb.on && (sb.d_state_out || sb.d_state_in || n_valid < T_);
   auto I = [&](size_t off) { return (const int*)(ws + off); };
   auto Fp = [&](const Buf& x) { return (float*)(ws + x.off); };
   auto Tp = [&](const Buf& x) { return (T*)(ws + x.off); };
@@ -185,7 +201,8 @@ int backward_impl(rgp_grcn* g, const float* probs, const float* logits, const fl
     if (!stepwise) RGP_HIP(hipMemcpyAsync(Fp(b->dy), ext_dy, (size_t)M * S * 4, hipMemcpyDeviceToDevice, s));
   } else {
   // 1. d loss / d logits, d out_b
-  RGP_TRY(b->hb.loss_grad(ws, logits, probs, labels, loss_l2, F, (float*)gr->out_b, s));
+  if (sb.on) RGP_TRY(b->hb.loss_grad(ws, logits, probs, labels, loss_l2, F, (float*)gr->out_b, s, sb.loss_frames, T_, n_valid));
+  else RGP_TRY(b->hb.loss_grad(ws, logits, probs, labels, loss_l2, F, (float*)gr->out_b, s));
   if (g->fold_head) {
     // 2'-4'. the folded head (head_fold.hip.h): patches of dz -> dK (one wgrad launch: rows = the 7x7 positions, X = the
     // patches, dY = the padded BN(h) image, as deconv1's filter gradient) -> chain rule through the fold -> dy = Pm x K
@@ -271,7 +288,17 @@ int backward_impl(rgp_grcn* g, const float* probs, const float* logits, const fl
   const float inv = 1.0f / sqrtf(1.0f + 1e-3f);
   if (!stepwise)
     bn_bwd_kernel<<<dim3(S / 8, T_), 256, 0, s>>>(Fp(b->dy), Fp(g->hall), b->w.bn_gamma, (float*)gr->bn_gamma,
-                                                    (float*)gr->bn_beta, Fp(b->dh_head), B, T_, S, inv, 0);
+                                                    (float*)gr->bn_beta, Fp(b->dh_head), B, T_, S, inv, 0, sb.bn_phase);
+  // streaming call: the steps behind n_valid are not differentiated and neither BPTT path writes their dxpre rows, which the
+  // hoisted launches of 7. - 9. read all the same: rows (b, t >= n_valid) are zeroed here (a row of an earlier backward over
+  // more steps would stand there otherwise) -- per clip one run of T - n_valid frames, T frames apart
+  if (n_valid < T_) {
+    const size_t xrow = (size_t)49 * 3 * S * 4;
+    RGP_HIP(hipMemset2DAsync(ws + b->dxpre.off + (size_t)n_valid * xrow, (size_t)T_ * xrow, 0, (size_t)(T_ - n_valid) * xrow, B, s));
+  }
+  // per-step path: d loss / d state_out seeds the carry
+  const bool seeded = sb.d_state_out && !persistent;
+  if (seeded) RGP_HIP(hipMemcpyAsync(Fp(b->dh_carry), sb.d_state_out, st * 4, hipMemcpyDeviceToDevice, s));
   // 6. BPTT: t = T-1 .. 0 -- one persistent launch where the plan allows it (bf16, the reference cell, <= 64 clips)
   const int ew_blocks = (int)std::min<size_t>((st + 255) / 256, 4096);
   // bn_gamma/beta, up_weight1..3, out_W, out_b are final here.  Their event lets the host start the group's all-reduce on
@@ -314,7 +341,14 @@ int backward_impl(rgp_grcn* g, const float* probs, const float* logits, const fl
     q.g = g->sg.args(B, (unsigned*)(ws + b->bptt_cnt.off), RGP_FAULT_BPTT_LOST_MEMBER);
     q.T = T_;
     RGP_REQUIRE(b->b_c.K == 9 * S && b->b_zr.K == 18 * S, "convgru_bptt: unexpected filter packing");
-    RGP_TRY(launch_seq_group(g->sg, convgru_bptt_kernel<4>, convgru_bptt_kernel<7>, q, BPTT_SMEM, s));
+    if (stream_kernel) {
+      BpttStreamParams qs;
+      (BpttParams&)qs = q;
+      qs.n_valid = n_valid; qs.d_state_out = sb.d_state_out; qs.d_state_in = sb.d_state_in;
+      RGP_TRY(launch_seq_group(g->sg, convgru_bptt_kernel<4, true>, convgru_bptt_kernel<7, true>, qs, BPTT_SMEM, s));
+    } else {
+      RGP_TRY(launch_seq_group(g->sg, convgru_bptt_kernel<4, false>, convgru_bptt_kernel<7, false>, q, BPTT_SMEM, s));
+    }
   }
   if (fork) RGP_HIP(hipStreamWaitEvent(s, b->ev_join, 0));              // the chain has ended (it had the whole BPTT launch to do so)
   if (mark && !top_early && !stepwise) RGP_HIP(hipEventRecord(b->grad_ev[0], s));     // full-chip launch: the TOP group leaves behind it
@@ -326,12 +360,12 @@ int backward_impl(rgp_grcn* g, const float* probs, const float* logits, const fl
   // (3,3) 9.68, (3,6) 10.2 ms per cascade forward + backward, profiles/r05_ab_cascade.txt)
   const int ks_c = std::max(1, std::min(8, dev_knob("RGP_BPTT_KSPLIT_C", b->b_c.nk >= 16 ? 2 : 1)));
   const int ks_zr = std::max(1, std::min(8, dev_knob("RGP_BPTT_KSPLIT_ZR", b->b_zr.nk >= 48 ? 3 : b->b_zr.nk >= 16 ? 2 : 1)));
-  for (int t = T_ - 1; t >= 0 && !persistent; --t) {
+  for (int t = n_valid - 1; t >= 0 && !persistent; --t) {
     const float* h_prev = Fp(g->hall) + (size_t)t * st;
     if (stepwise) RGP_HIP(hipStreamWaitEvent(s, g->bwd_step_ev[t], 0));      // frame (b, t) of ext_dy is complete
     gru_bwd1_kernel<T><<<ew_blocks, 256, 0, s>>>(Fp(b->dh_head) + (size_t)t * st, Fp(b->dh_carry), h_prev,
                                                   Fp(g->uall) + (size_t)t * st, Fp(g->call) + (size_t)t * st, Fp(b->dxpre),
-                                                  Tp(b->dcp_pad), I(g->o_pad9_S), B, T_, t, S, t == T_ - 1,
+                                                  Tp(b->dcp_pad), I(g->o_pad9_S), B, T_, t, S, t == n_valid - 1 && !seeded,
                                                   ks_c > 1 ? Fp(b->drh) : nullptr, stepwise ? ext_dy : nullptr,
                                                   b->w.bn_gamma + (size_t)t * S, inv);
     RGP_HIP(hipGetLastError());
@@ -351,9 +385,11 @@ int backward_impl(rgp_grcn* g, const float* probs, const float* logits, const fl
       else RGP_TRY((launch_igemm<T, 1, 1, EpiAccumF32>(p, e, s)));
     }
   }
+  // the way out: d loss / d state_in is the carry the loop leaves (the persistent kernel has stored it itself)
+  if (sb.d_state_in && !persistent) RGP_HIP(hipMemcpyAsync(sb.d_state_in, Fp(b->dh_carry), st * 4, hipMemcpyDeviceToDevice, s));
   if (stepwise) {                                                         // the batch-norm's own gradients, off the step chain
     bn_bwd_kernel<<<dim3(S / 8, T_), 256, 0, s>>>(ext_dy, Fp(g->hall), b->w.bn_gamma, (float*)gr->bn_gamma, (float*)gr->bn_beta,
-                                                    Fp(b->dh_head), B, T_, S, inv, 0);
+                                                    Fp(b->dh_head), B, T_, S, inv, 0, 0);
     if (mark) RGP_HIP(hipEventRecord(b->grad_ev[0], s));
   }
   // 7. hoisted input convs: the padded gradient image both branches below read
@@ -614,6 +650,15 @@ void grcn_bwd_destroy(rgp_grcn* g) {
   g->bwd = nullptr;
 }
 
+bool grcn_bwd_view(const rgp_grcn* g, const char* name, size_t* off) {
+  if (!g->bwd || !name) return false;
+  const std::string n(name);
+  if (n == "dxpre") *off = g->bwd->dxpre.off;
+  else if (n == "dh_head") *off = g->bwd->dh_head.off;
+  else return false;
+  return true;
+}
+
 extern "C" {
 
 int rgp_grcn_backward(rgp_grcn_t* g, const float* logits, const float* probs, const float* labels,
@@ -637,6 +682,35 @@ int rgp_grcn_backward_from_states(rgp_grcn_t* g, const float* d_states, const rg
   if (g->stream.streamed) return set_err(RGP_ESTATE, "rgp_grcn_backward_from_states: the last forward was a streaming call (no truncated BPTT)");
   RGP_TRY(require_pointers(grads, "rgp_grcn_backward_from_states", "gradient"));
   return RGP_BY_DTYPE(g->dtype, backward_impl, g, nullptr, nullptr, nullptr, grads, 0, (hipStream_t)stream, d_states);
+}
+
+int rgp_grcn_backward_stream(rgp_grcn_t* g, const float* logits, const float* probs, const float* labels, const float* d_state_out,
+                             float* d_state_in, long long loss_frames, const rgp_grcn_weights* grads, int loss_type,
+                             rgp_stream_t stream) {
+  const char* fn = "rgp_grcn_backward_stream";
+  RGP_REQUIRE(g, "%s: null plan", fn);
+  RGP_REQUIRE(logits, "%s: null logits", fn);
+  RGP_REQUIRE(labels, "%s: null labels", fn);
+  RGP_REQUIRE(grads, "%s: null grads", fn);
+  RGP_TRY(require_pointers(grads, fn, "gradient"));
+  RGP_REQUIRE(loss_frames > 0, "%s: loss_frames=%lld must be positive", fn, loss_frames);
+  RGP_REQUIRE(loss_type == 0 || loss_type == 1, "%s: loss_type %d (0 xentropy, 1 l2)", fn, loss_type);
+  RGP_REQUIRE(loss_type == 1 || probs, "%s: null probs (xentropy needs the softmax maps)", fn);
+  RGP_REQUIRE(!d_state_in || d_state_in != d_state_out, "%s: d_state_in must not alias d_state_out", fn);
+  RGP_REQUIRE((((size_t)d_state_out | (size_t)d_state_in) & 15) == 0, "%s: d_state_out and d_state_in must be 16-byte aligned", fn);
+  if (!g->save || !g->bwd) return set_err(RGP_ESTATE, "%s: plan was created without save_for_backward", fn);
+  if (!g->ws) return set_err(RGP_EWORKSPACE, "rgp_grcn: workspace not bound");
+  if (!g->weights_set) return set_err(RGP_ESTATE, "rgp_grcn: weights not set");
+  if (!g->fwd_done) return set_err(RGP_ESTATE, "%s: no forward has run on this plan", fn);
+  RGP_TRY(grcn_check_error(g));
+  GrcnBwdStream sb;
+  sb.on = true;
+  sb.n_valid = g->stream.streamed ? g->stream.last_n_valid : g->T;      // (a plain forward: every step, from the zero state, slot 0)
+  sb.bn_phase = g->stream.streamed ? g->stream.last_bn_phase : 0;
+  sb.loss_frames = loss_frames;
+  sb.d_state_out = d_state_out;
+  sb.d_state_in = d_state_in;
+  return RGP_BY_DTYPE(g->dtype, backward_impl, g, probs, logits, labels, grads, loss_type, (hipStream_t)stream, (const float*)nullptr, sb);
 }
 
 int rgp_grcn_persistent_workgroups(const rgp_grcn_t* g) {

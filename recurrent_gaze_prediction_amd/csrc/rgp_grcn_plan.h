@@ -30,6 +30,7 @@ struct rgp_grcn {
   size_t ws_bytes = 0;
   char* ws = nullptr;
   bool weights_set = false;
+  bool fwd_done = false;           // the last public forward of either kind enqueued all its stages (rgp_grcn_backward_stream)
   const float *bn_gamma = nullptr, *bn_beta = nullptr, *proj_b = nullptr, *out_b = nullptr;
   rgp::StageProfiler prof;
   rgp::StreamCall stream;   // rgp_grcn_forward_stream, or the call of the plan that owns this one (rgp_grcn77, rgp_cascade)
@@ -53,3 +54,5 @@ int grcn_bwd_pack(rgp_grcn* g, const rgp_grcn_weights* w, hipStream_t s, hipStre
 int grcn_bwd_fork_fold(rgp_grcn* g, hipStream_t s, hipStream_t* sc);
 int grcn_bwd_join_fold(rgp_grcn* g, hipStream_t s);
 void grcn_bwd_destroy(rgp_grcn* g);
+// workspace offset of a backward buffer rgp_grcn_read_buffer shows ("dxpre", "dh_head"); false = no such buffer
+bool grcn_bwd_view(const rgp_grcn* g, const char* name, size_t* off);

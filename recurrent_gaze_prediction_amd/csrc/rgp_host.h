@@ -170,7 +170,8 @@ struct StreamCall {
   bool seeded = false;             // slot 0 of the plan's state buffers holds a caller's state, not the zeros of the bind
   bool streamed = false;           // the saved activations are a streaming call's: they do not start at h_0 = 0 with batch-norm
                                    // slot 0, which is what the plain backward differentiates -> RGP_ESTATE there
-  int last_n_valid = 0;            // n_valid of the last streaming call: what a backward behind it differentiates (fc-GRU)
+  int last_n_valid = 0;            // n_valid of the last streaming call: what a backward behind it differentiates (fc-GRU, gaze_grcn)
+  int last_bn_phase = 0;           // ... and its bn_phase: the batch-norm slots that call used (gaze_grcn)
   bool carry() const { return on && in; }
   // The re-zero rule.  Slot 0 is zero from the bind on and no plain forward writes it, so only two kinds of call run a seed
   // launch: one with a state to put there, and the first zero-state call behind one, which puts the zeros back (a null source).
@@ -187,10 +188,10 @@ struct StreamCall {
 struct StreamScope {
   StreamCall& c;
   StreamScope(StreamCall& c_, const float* in, float* out, int n_valid, int bn_phase = 0) : c(c_) {
-    c.on = c.streamed = true; c.in = in; c.out = out; c.n_valid = c.last_n_valid = n_valid; c.bn_phase = bn_phase;
+    c.on = c.streamed = true; c.in = in; c.out = out; c.n_valid = c.last_n_valid = n_valid; c.bn_phase = c.last_bn_phase = bn_phase;
   }
   StreamScope(StreamCall& sub, const StreamCall& outer) : c(sub) {
-    if (outer.on) { c.on = c.streamed = true; c.in = outer.in; c.out = outer.out; c.n_valid = c.last_n_valid = outer.n_valid; }
+    if (outer.on) { c.on = c.streamed = true; c.in = outer.in; c.out = outer.out; c.n_valid = c.last_n_valid = outer.n_valid; c.last_bn_phase = 0; }
   }
   ~StreamScope() { c.on = false; c.in = nullptr; c.out = nullptr; c.n_valid = c.bn_phase = 0; }
 };

@@ -537,6 +537,51 @@ class GrcnEngine(_PersistentEngine):
         self.repack()
         return self._gnorm
 
+    # ---- training across the carried state (rgp_grcn_backward_stream)
+    def forward(self, *args, **kw):
+        out = super(GrcnEngine, self).forward(*args, **kw)
+        self._last_n_valid = self.T
+        return out
+
+    def forward_rows(self, *args, **kw):
+        out = super(GrcnEngine, self).forward_rows(*args, **kw)
+        self._last_n_valid = self.T
+        return out
+
+    def forward_stream(self, c3d_input=None, rows=None, state=None, n_valid=None, bn_phase=0, want_probs=True):
+        out = super(GrcnEngine, self).forward_stream(c3d_input, rows, state, n_valid, bn_phase, want_probs)
+        self._last_n_valid = self.T if n_valid is None else int(n_valid)
+        return out
+    forward_stream.__doc__ = _PersistentEngine.forward_stream.__doc__
+
+    def backward_stream(self, logits, probs, labels, d_state=None, loss_frames=None, loss_type='xentropy', want_d_state=True):
+        """The backward of the last forward of either kind (rgp_grcn_backward_stream): behind forward_stream(state, n_valid,
+        bn_phase) the first n_valid steps of that call, the recurrence started at `state`, step t through batch-norm slot
+        (bn_phase + t) % T; behind forward() / forward_rows() all T steps from the zero state.
+        The loss is backward()'s, summed over the valid frames and divided by loss_frames (default B * n_valid of the last
+        forward THIS OBJECT ran: a Python-side copy of what the plan keeps, used for this default alone), so the gradients of a
+        film's chunks add up to the gradient of the mean over the film.  d_state: fp32, state_elems elements ([B, 7, 7, S]), the
+        gradient w.r.t. the new_state the forward returned, or None = zeros (truncated BPTT, the last chunk); never modified.
+        The inputs of the forward must be finite over all T steps.
+        Returns (grads, d_state_in): {variable: gradient view} (flat_grads, written, not accumulated) and a fresh tensor
+        [B, 7, 7, S] with d loss / d state (None with want_d_state=False)."""
+        assert self.save_for_backward, 'create the engine with save_for_backward=True'
+        assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
+        if d_state is not None:
+            assert d_state.is_cuda and d_state.dtype == torch.float32 and d_state.is_contiguous()
+            assert d_state.numel() == self.state_elems, (d_state.numel(), self.state_elems)
+        if loss_frames is None:
+            loss_frames = self.B * getattr(self, '_last_n_valid', self.T)
+        if self.grads is None:
+            self.flat_grads, self.grads = _flat_views(self.PARAM_TO_FIELD, self.weights, self.device, self.UNTRAINED)
+        st = _struct(self.WEIGHTS, self.PARAM_TO_FIELD, self.grads)
+        d_in = torch.empty(self.B, 7, 7, self.S, dtype=torch.float32, device=self.device) if want_d_state else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['backward_stream'](self._h, _ptr(logits), _ptr(probs), _ptr(labels), _ptr(d_state), _ptr(d_in),
+                                                  int(loss_frames), ctypes.byref(st), {'xentropy': 0, 'l2': 1}[loss_type],
+                                                  _stream_ptr(self.device)))
+        return self.grads, d_in
+
     @property
     def grads_top_early(self):
         """Whether the first gradient bucket (grad_buckets()[0]) is released before the BPTT launch (include/rgp.h: only

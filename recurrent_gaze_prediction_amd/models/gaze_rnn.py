@@ -340,7 +340,7 @@ class GazePredictionGRU(ModelBase):
         return softmax_xent(logits, labels, want_probs=False)[1].view(B, T)[:, :n].sum().reshape(1)
 
     def train_long_clip(self, c3d, gt_gazemap, mode='truncated', trace=None):
-        """Train on a film longer than the plan as ONE recurrence (fc-GRU models: gaze_rnn, gaze_rnn77).
+        """Train on a film longer than the plan as ONE recurrence (fc-GRU models: gaze_rnn, gaze_rnn77; gaze_grcn).
         c3d [B, S, 1024, 7, 7], any S; gt_gazemap [B, S, GH, GW] as single_step hands the maps to train_op (normalised for
         xentropy).  The film is cut into chunks of the plan's T steps, the last one shorter and zero-padded.
         mode='truncated': per chunk forward_stream(train=True) from the carried state, backward_stream without a state
@@ -349,14 +349,16 @@ class GazePredictionGRU(ModelBase):
         chunk is recomputed from its boundary state with its mask and differentiated with the state gradient chained back and
         the divisor B * S; the chunk gradients are summed and ONE optimizer step is taken: the gradient of the mean loss over
         the whole film, with the memory of one chunk.
+        gaze_grcn: chunk i runs with batch-norm phase (its stream position) % T, as predict_stream runs it; the graph has no live
+        dropout site, so there is no mask to keep.
         A persistent launch that times out (RGP_ETIMEOUT): the model falls back to per-step launches as elsewhere; 'exact'
         has not moved the parameters and is repeated as a whole, 'truncated' repeats the poisoned chunk (its state is read-only).
         trace: a dict that receives 'states' (behind every chunk), 'logits' and, in exact mode, 'logits_recomputed'.
         Returns the mean loss over the B * S frames (float)."""
         from .. import engine as _engine
-        if not isinstance(self.engine, _engine.FcGruEngine):
-            raise NotImplementedError('train_long_clip: the fc-GRU models (gaze_rnn, gaze_rnn77) train across the carried state; '
-                                      'the engine of this %s has no backward_stream' % type(self).__name__)
+        if not isinstance(self.engine, (_engine.FcGruEngine, _engine.GrcnEngine)):
+            raise NotImplementedError('train_long_clip: the fc-GRU models (gaze_rnn, gaze_rnn77) and gaze_grcn train across the '
+                                      'carried state; the engine of this %s has no backward_stream' % type(self).__name__)
         if getattr(self, 'dist', None) is not None:
             raise NotImplementedError('train_long_clip: data-parallel long-clip training is out of scope (a process group is attached)')
         if self.config.loss_type == 'KLD':
@@ -382,6 +384,11 @@ class GazePredictionGRU(ModelBase):
         def lost(final):                                    # True: the engine was replaced, repeat
             return self._status_or_recover(final=final)
 
+        def forward(eng, x, state, s, n, probs, train):     # one chunk, film steps [s, s + n), from `state`
+            if isinstance(eng, _engine.GrcnEngine):         # (no live dropout site; the batch-norm slot of step 0: the position mod T)
+                return eng.forward_stream(x, state=state, n_valid=n, bn_phase=s % T, want_probs=probs)
+            return eng.forward_stream(x, state=state, n_valid=n, want_probs=probs, train=train)
+
         tr = trace if trace is not None else {}
         tr.update(states=[], logits=[], logits_recomputed=[])
 
@@ -390,7 +397,7 @@ class GazePredictionGRU(ModelBase):
             for s, n in cuts:
                 x, g = chunk(x_all, s, n), chunk(g_all, s, n)
                 for final in (False, True):
-                    logits, probs, new_state = self.engine.forward_stream(x, state=state, n_valid=n, want_probs=want_probs, train=True)
+                    logits, probs, new_state = forward(self.engine, x, state, s, n, want_probs, True)
                     self.engine.backward_stream(logits, probs, g, d_state=None, loss_frames=B * n, loss_type=loss_type,
                                                 want_d_state=False)
                     if not lost(final):
@@ -410,7 +417,7 @@ class GazePredictionGRU(ModelBase):
             tr.update(states=[], logits=[], logits_recomputed=[])
             states, masks, total = [None], [], 0.0
             for s, n in cuts:                               # pass 1: the states at the cuts, the masks, the loss
-                logits, _, new_state = eng.forward_stream(chunk(x_all, s, n), state=states[-1], n_valid=n, want_probs=False, train=True)
+                logits, _, new_state = forward(eng, chunk(x_all, s, n), states[-1], s, n, False, True)
                 if lost(final):
                     return None
                 masks.append(eng.dropout.mask.clone() if drop else None)
@@ -423,8 +430,7 @@ class GazePredictionGRU(ModelBase):
                 s, n = cuts[i]
                 if drop:
                     eng.dropout.use(masks[i], eng.dropout.keep_prob)
-                logits, probs, _ = eng.forward_stream(chunk(x_all, s, n), state=states[i], n_valid=n, want_probs=want_probs,
-                                                      train='keep' if drop else False)
+                logits, probs, _ = forward(eng, chunk(x_all, s, n), states[i], s, n, want_probs, 'keep' if drop else False)
                 _, d_state = eng.backward_stream(logits, probs, chunk(g_all, s, n), d_state=d_state, loss_frames=B * S,
                                                  loss_type=loss_type, want_d_state=i > 0)
                 if lost(final):

@@ -155,7 +155,7 @@ def predict_long_clips(model, clips, frames=None):
 
 
 def train_long_clips(model, clips, gazemaps, mode='truncated'):
-    """Training beside predict_long_clips (the fc-GRU models): B clips of ONE length S, C3D features [S, 1024, 7, 7] and gaze
+    """Training beside predict_long_clips (the fc-GRU models and gaze_grcn): B clips of ONE length S, C3D features [S, 1024, 7, 7] and gaze
     maps [S, GH, GW] each, one per lane -> model.train_long_clip on the stacked film: every clip one recurrence from the zero
     state, cut into the plan's T-step chunks.  Returns the mean loss."""
     assert len(clips) == len(gazemaps) == model.batch_size, 'one clip and one map array per lane (%d)' % model.batch_size
