@@ -3,6 +3,14 @@
 PyTorch is plumbing only here (device memory, streams); all arithmetic happens in
 the HIP kernels behind the C ABI (include/rgp.h).  These classes play the role of
 the reference's ``tf.Session`` + graph for the gaze path (models/gaze_rnn.py:523-531).
+
+Layout: every engine class stands on _PlanEngine, the plan owner (library, device, the family's resolved entry points
+``_f``, handle, workspace, destroy; the flat fp32 master buffer with its per-variable views, the lazily created gradient
+buffer, the weights struct, adam_step).  What only some families' C ABI has lives in one mixin each, and a class lists
+exactly those its family exports (tests/test_engine_tables_cpu.py holds the classes to _lib.SIGNATURES): _Buffers
+(buffer_elems), _Streaming (state_elems, forward_stream), _Persistent (status, persistent_workgroups), _BpttPersistent,
+_FaultHook (inject_fault), _StreamBackward (backward_stream).  The models probe engines with hasattr / getattr, so a
+member an ABI lacks must stay absent.  DESIGN.md section 37.
 """
 import ctypes
 
@@ -72,6 +80,20 @@ def load_optimizer_state(engine, state):
     for k, v in (state or {}).items():
         if k in OPT_STATE_KEYS:
             setattr(engine, k, torch.as_tensor(v).to(engine.device, torch.float32).contiguous().clone())
+
+
+def move_training_state(old, new):
+    """What a model's fallback engine takes over from the one it replaces (the models' _recover_from_timeout): the master
+    weights, the optimizer slots that exist and, where both engines have a dropout site, the site's key AND its draw
+    counter: the mask sequence goes on where it was (the recomputed batch draws the mask after the one the poisoned forward
+    used), it does not start again from the seed."""
+    new.set_weights(old.weights)
+    for k in OPT_STATE_KEYS:
+        if getattr(old, k, None) is not None:
+            setattr(new, k, getattr(old, k).clone())
+    if getattr(old, 'dropout', None) is not None and getattr(new, 'dropout', None) is not None:
+        new.dropout.configure(old.dropout.keep_prob, seed=old.dropout.seed)
+        new.dropout.draws = old.dropout.draws
 
 
 def clip_step_multi(engines, step, lr, max_grad_norm=10.0, method='adam', beta1=0.9, beta2=0.999, eps=1e-8,
@@ -245,27 +267,6 @@ class DropoutSite(object):
         _lib.check(self._set(ctypes.c_float(self.keep_prob), _ptr(self.mask)))
 
 
-def _stream_call(eng, fn, B, T, c3d_input, state, n_valid, args, rows=None):
-    """What the forward_stream methods share: c3d_input (or rows, as forward_rows takes them) and state are checked, n_valid
-    defaults to T, new_state is allocated and fn(plan, *args(state, new_state, n_valid), stream) is called and checked.
-    Returns new_state."""
-    x = c3d_input
-    if x is not None:
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
-        assert tuple(x.shape) == (B, T, 1024, 7, 7), tuple(x.shape)
-    if rows is not None:
-        assert rows.is_cuda and rows.dtype == eng.torch_dtype and rows.is_contiguous()
-        assert rows.numel() == B * T * 49 * 1024
-    n_valid = T if n_valid is None else int(n_valid)
-    if state is not None:
-        assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous()
-        assert state.numel() == eng.state_elems, (state.numel(), eng.state_elems)
-    new_state = torch.empty(eng.state_elems, dtype=torch.float32, device=eng.device)
-    with torch.cuda.device(eng.device):
-        _lib.check(fn(eng._h, *(args(_ptr(state), _ptr(new_state), n_valid) + (_stream_ptr(eng.device),))))
-    return new_state
-
-
 def _flat_layout(names, shapes, untrained=()):
     """[(name, offset, numel)] of a flat fp32 buffer holding `names` in order, those in `untrained` left out."""
     out, off = [], 0
@@ -299,27 +300,28 @@ def _struct(struct_cls, fields, views):
     return st
 
 
-class _GazeEngine(object):
-    """What the three gaze-family engines share: the owner of one rgp_<family>_ plan, its workspace and the flat fp32
-    master buffers.  A subclass names the C prefix, the parameter -> field map, the weights struct and the variables
-    kept out of the flat buffers, and creates the plan with _create()."""
-    PREFIX = PARAM_TO_FIELD = WEIGHTS = None
+class _PlanEngine(object):
+    """The plan owner under every engine class: one rgp_<family>_ plan, its workspace, and the flat fp32 master buffers.
+
+    A subclass names PREFIX (the family's C prefix), CREATE (its create entry behind the prefix), WEIGHTS (the struct of
+    set_weights / backward), PARAM_TO_FIELD ({variable name: field of WEIGHTS} in the flat buffer's order; None = every
+    field of WEIGHTS under its own name) and UNTRAINED (variables kept out of the flat buffers), and calls _create_plan()
+    from its __init__.  Hooks for what is a family's own: _param_fields, _check_shapes, _struct_of."""
+    PREFIX = WEIGHTS = PARAM_TO_FIELD = None
+    CREATE = 'create'
     UNTRAINED = ()
 
-    def _create(self, batch, n_steps, dtype, save_for_backward, device, *create_args):
-        """Common part of __init__; create_args: the arguments of rgp_<family>_create behind the plan pointer."""
+    def _create_plan(self, device, *create_args):
+        """create_args: the arguments of the create entry behind the plan pointer."""
         self.lib = _lib.load()
         self.device = _require_gpu(device)
-        self.B, self.T = int(batch), int(n_steps)
-        self.dtype = dtype
-        self.save_for_backward = bool(save_for_backward)
-        self.torch_dtype = torch.bfloat16 if _lib.DTYPES[dtype] == _lib.RGP_BF16 else torch.float32
-        self.flat_params = self.flat_grads = self.grads = self.weights = None
+        self.flat_params = self.flat_grads = self.grads = self.weights = self.adam_m = self.adam_v = None
+        self._fields = self._param_fields()
         # the family's entry points by their name behind the prefix (resolved once: the training step is host-bound)
         self._f = {k[len(self.PREFIX):]: getattr(self.lib, k) for k in _lib.SIGNATURES if k.startswith(self.PREFIX)}
         self._h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(self._f['create'](ctypes.byref(self._h), *create_args))
+            _lib.check(self._f[self.CREATE](ctypes.byref(self._h), *create_args))
             nbytes = self._f['workspace_bytes'](self._h)
             self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             _lib.check(self._f['bind_workspace'](self._h, _ptr(self.workspace), nbytes, _stream_ptr(self.device)))
@@ -329,25 +331,197 @@ class _GazeEngine(object):
         if h:
             self._f['destroy'](h)
 
+    def _call(self, entry, *args):
+        """rgp_<family>_<entry>(plan, *args, stream) on the current stream of the plan's device, checked."""
+        with torch.cuda.device(self.device):
+            _lib.check(self._f[entry](self._h, *(args + (_stream_ptr(self.device),))))
+
+    def _forward(self, entry, n_valid, *args):
+        """_call for the forward entries.  The one place that notes how many steps the last forward of this object defined
+        (backward_stream's default divisor)."""
+        self._call(entry, *args)
+        self._last_n_valid = n_valid
+
+    def _dropout_site(self, n_elems):
+        """The tf.nn.dropout site of a plan with a set_dropout entry; off until a training step draws a mask."""
+        return DropoutSite(self.lib, self.device, n_elems, lambda keep, mask: self._f['set_dropout'](self._h, keep, mask))
+
+    def _param_fields(self):
+        """Hook: {variable name: field of WEIGHTS} of THIS plan, in the order of the flat buffers."""
+        return self.PARAM_TO_FIELD or {k: k for k in self.WEIGHTS.FIELDS}
+
     def _check_shapes(self, src):
         """Hook: assert what the plan's geometry fixes about the parameters' shapes."""
 
-    def set_weights(self, params):
-        """params: dict keyed by the reference's TF variable names (scope stripped) -> array/tensor (fp32).
-        The values are copied into the engine's flat fp32 master buffer, then packed / folded (repack)."""
-        src = {k: _as_dev_f32(params[k], self.device) for k in self.PARAM_TO_FIELD}
+    def _struct_of(self, views):
+        """Hook: WEIGHTS with the device pointers of views (the master weights or the gradients)."""
+        return _struct(self.WEIGHTS, self._fields, views)
+
+    def _copy_in(self, values):
+        """{variable: array/tensor} -> the flat fp32 master buffer (created on the first call) through its views."""
+        src = {k: _as_dev_f32(values[k], self.device) for k in self._fields}
         self._check_shapes(src)
         if self.weights is None:
-            self.flat_params, self.weights = _flat_views(self.PARAM_TO_FIELD, src, self.device, self.UNTRAINED)
-        for k in self.PARAM_TO_FIELD:
+            self.flat_params, self.weights = _flat_views(self._fields, src, self.device, self.UNTRAINED)
+        for k in self._fields:
             self.weights[k].copy_(src[k])
+
+    def set_weights(self, params):
+        """params: dict keyed by the variables' names (the reference's TF names, scope stripped) -> array/tensor (fp32).
+        The values are copied into the engine's flat fp32 master buffer, then packed / folded (repack)."""
+        self._copy_in(params)
         self.repack()
 
     def repack(self):
         """Re-pack the master weights into MFMA operand form (after set_weights / an optimizer step)."""
-        st = _struct(self.WEIGHTS, self.PARAM_TO_FIELD, self.weights)   # the plan keeps raw pointers to biases / BN: views stay alive
+        st = self._struct_of(self.weights)      # the plan keeps raw pointers to biases / BN: views stay alive
+        self._call('set_weights', ctypes.byref(st))
+
+    def _grad_struct(self):
+        """WEIGHTS over the gradient views; flat_grads / grads are created by the first backward and reused."""
+        if self.grads is None:
+            self.flat_grads, self.grads = _flat_views(self._fields, self.weights, self.device, self.UNTRAINED)
+        return self._struct_of(self.grads)
+
+    def adam_step(self, step, lr, max_grad_norm=10.0, method='adam'):
+        """clip_by_global_norm + the chosen optimizer of base.py:268-273 on the flat buffers (the trained variables
+        only), then repack."""
+        return clip_step_multi([self], step, lr, max_grad_norm, method)
+
+
+class _Buffers(object):
+    """rgp_<family>_buffer_elems / _read_buffer: the intermediates of a plan by name, flat fp32."""
+
+    def read_buffer_elems(self, name):
+        """fp32 elements read_buffer(name) returns; 0 = this plan has no such intermediate."""
+        return int(self._f['buffer_elems'](self._h, name.encode()))
+
+    def read_buffer(self, name):
+        n = self.read_buffer_elems(name)
+        if n == 0:
+            raise _lib.RgpError('unknown intermediate %r' % name)
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._call('read_buffer', name.encode(), _ptr(out))
+        return out
+
+
+class _Streaming(object):
+    """rgp_<family>_state_elems / _forward_stream: a recurrent state carried across calls."""
+    STREAM_BN_PHASE = False     # the family's forward_stream takes a batch-norm phase (gaze_grcn: one BN layer per timestep)
+
+    @property
+    def state_elems(self):
+        """fp32 elements of the recurrent state forward_stream carries (rgp_<family>_state_elems; the fc-GRU: B * 1617, h per
+        clip; the cascade: per clip the bottom state 49*256, then the top state 49*49*3, each part [B, ...])."""
+        return int(self._f['state_elems'](self._h))
+
+    def _stream_call(self, B, T, c3d_input, state, n_valid, args, rows=None):
+        """What the forward_stream methods share: c3d_input (or rows, as forward_rows takes them) and state are checked,
+        n_valid defaults to T, new_state is allocated and rgp_<family>_forward_stream(plan, *args(state, new_state,
+        n_valid), stream) is called and checked.  Returns new_state."""
+        x = c3d_input
+        if x is not None:
+            assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+            assert tuple(x.shape) == (B, T, 1024, 7, 7), tuple(x.shape)
+        if rows is not None:
+            assert rows.is_cuda and rows.dtype == self.torch_dtype and rows.is_contiguous()
+            assert rows.numel() == B * T * 49 * 1024
+        n_valid = T if n_valid is None else int(n_valid)
+        if state is not None:
+            assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous()
+            assert state.numel() == self.state_elems, (state.numel(), self.state_elems)
+        new_state = torch.empty(self.state_elems, dtype=torch.float32, device=self.device)
+        self._forward('forward_stream', n_valid, *args(_ptr(state), _ptr(new_state), n_valid))
+        return new_state
+
+
+class _Persistent(_Streaming):
+    """... and rgp_<family>_status / _persistent_workgroups: a recurrence that may run as one persistent launch (gaze_grcn,
+    gaze_grcn77, gaze_lstm, the fc-GRU; gaze_c3d_conv has none, and the models ask an engine for `status` / `persistent` with
+    getattr)."""
+
+    def status(self):
+        """Wait for the current stream and raise RgpError (RGP_ETIMEOUT) if a persistent launch of this plan lost a
+        group member since the last check (its outputs are NaN)."""
+        self._call('status')
+
+    @property
+    def persistent_workgroups(self):
+        """CUs a persistent sequence launch of this plan occupies (0: the recurrence runs as per-timestep launches)."""
         with torch.cuda.device(self.device):
-            _lib.check(self._f['set_weights'](self._h, ctypes.byref(st), _stream_ptr(self.device)))
+            return int(self._f['persistent_workgroups'](self._h))
+
+    @property
+    def persistent(self):
+        return self.persistent_workgroups > 0
+
+
+class _BpttPersistent(object):
+    """rgp_<family>_bptt_persistent_workgroups (gaze_lstm, the fc-GRU)."""
+
+    @property
+    def bptt_persistent_workgroups(self):
+        """CUs the persistent BPTT launch of this plan's backward occupies (0: per-timestep launches)."""
+        with torch.cuda.device(self.device):
+            return int(self._f['bptt_persistent_workgroups'](self._h))
+
+    @property
+    def bptt_persistent(self):
+        return self.bptt_persistent_workgroups > 0
+
+
+class _FaultHook(object):
+    """rgp_<family>_inject_fault (gaze_grcn, gaze_lstm)."""
+
+    def inject_fault(self, kind='seq'):
+        """Test hook (rgp_<family>_inject_fault): the next persistent launch of the forward ('seq') or of the BPTT
+        ('bptt') loses a group member."""
+        with torch.cuda.device(self.device):
+            _lib.check(self._f['inject_fault'](self._h, {'seq': _lib.RGP_FAULT_SEQ_LOST_MEMBER,
+                                                         'bptt': _lib.RGP_FAULT_BPTT_LOST_MEMBER}[kind]))
+
+
+class _StreamBackward(object):
+    """rgp_<family>_backward_stream (gaze_grcn, the fc-GRU): training across the carried state.  A class says what shape its
+    d_state_in has (_state_shape)."""
+
+    def backward_stream(self, logits, probs, labels, d_state=None, loss_frames=None, loss_type='xentropy', want_d_state=True):
+        """The backward of the last forward of either kind (rgp_<family>_backward_stream): behind forward_stream(state,
+        n_valid[, bn_phase]) the first n_valid steps of that call, the recurrence started at `state` (gaze_grcn: step t
+        through batch-norm slot (bn_phase + t) % T); behind forward() / forward_rows() all T steps from the zero state.
+        The loss is backward()'s, summed over the valid frames and divided by loss_frames (default B * n_valid of the last
+        forward THIS OBJECT ran: a Python-side copy of what the plan keeps, used for this default alone; name loss_frames
+        when the C entries are driven beside the engine), so the gradients of a film's chunks add up to the gradient of the
+        mean over the film.  d_state: fp32, state_elems elements (gaze_grcn [B, 7, 7, S], the fc-GRU [B, 1617]), the gradient
+        w.r.t. the new_state the forward returned, or None = zeros (truncated BPTT, the last chunk); never modified.
+        The inputs of the forward must be finite over all T steps.
+        Returns (grads, d_state_in): {variable: gradient view} (flat_grads, written, not accumulated) and a fresh tensor
+        shaped like the state with d loss / d state (None with want_d_state=False)."""
+        assert self.save_for_backward, 'create the engine with save_for_backward=True'
+        assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
+        if d_state is not None:
+            assert d_state.is_cuda and d_state.dtype == torch.float32 and d_state.is_contiguous()
+            assert d_state.numel() == self.state_elems, (d_state.numel(), self.state_elems)
+        if loss_frames is None:
+            loss_frames = self.B * getattr(self, '_last_n_valid', self.T)
+        st = self._grad_struct()
+        d_in = torch.empty(self._state_shape(), dtype=torch.float32, device=self.device) if want_d_state else None
+        self._call('backward_stream', _ptr(logits), _ptr(probs), _ptr(labels), _ptr(d_state), _ptr(d_in), int(loss_frames),
+                   ctypes.byref(st), {'xentropy': 0, 'l2': 1}[loss_type])
+        return self.grads, d_in
+
+
+class _GazeEngine(_Buffers, _PlanEngine):
+    """What the gaze-family engines on conv5b rows share (gaze_grcn, gaze_c3d_conv, gaze_lstm, gaze_grcn77): plans at fixed
+    (B, T, dtype), forward from features or rows, the reference loss's backward."""
+
+    def _create(self, batch, n_steps, dtype, save_for_backward, device, *create_args):
+        """Common part of __init__; create_args: the arguments of rgp_<family>_create behind the plan pointer."""
+        self.B, self.T = int(batch), int(n_steps)
+        self.dtype = dtype
+        self.save_for_backward = bool(save_for_backward)
+        self.torch_dtype = torch.bfloat16 if _lib.DTYPES[dtype] == _lib.RGP_BF16 else torch.float32
+        self._create_plan(device, *create_args)
 
     def backward(self, logits, probs, labels, loss_type='xentropy'):
         """Gradients of the reference loss (gaze_rnn.py:363-408) w.r.t. every variable, after a
@@ -356,12 +530,8 @@ class _GazeEngine(object):
         # (GrcnEngine used to leave this check, and the contiguity of forward_rows' rows, to the library: no caller relied on it)
         assert self.save_for_backward, 'create the engine with save_for_backward=True'
         assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
-        if self.grads is None:
-            self.flat_grads, self.grads = _flat_views(self.PARAM_TO_FIELD, self.weights, self.device, self.UNTRAINED)
-        st = _struct(self.WEIGHTS, self.PARAM_TO_FIELD, self.grads)
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['backward'](self._h, _ptr(logits), _ptr(probs), _ptr(labels), ctypes.byref(st),
-                                           {'xentropy': 0, 'l2': 1}[loss_type], _stream_ptr(self.device)))
+        st = self._grad_struct()
+        self._call('backward', _ptr(logits), _ptr(probs), _ptr(labels), ctypes.byref(st), {'xentropy': 0, 'l2': 1}[loss_type])
         return self.grads
 
     def grad_buckets(self):
@@ -372,14 +542,8 @@ class _GazeEngine(object):
         """After backward(): d loss / d input as conv5b rows [B*T*49, 1024] fp32 (column d*512+c), the
         gradient C3DEngine.backward(d_rows=...) consumes when the conv stack is fine-tuned."""
         d = out if out is not None else torch.empty(self.B * self.T * 49, 1024, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['backward_input'](self._h, _ptr(d), _stream_ptr(self.device)))
+        self._call('backward_input', _ptr(d))
         return d
-
-    def adam_step(self, step, lr, max_grad_norm=10.0, method='adam'):
-        """clip_by_global_norm + the chosen optimizer of base.py:268-273 on the flat buffers (the trained variables
-        only), then repack."""
-        return clip_step_multi([self], step, lr, max_grad_norm, method)
 
     def _outputs(self, want_probs, out_logits, out_probs):
         logits = out_logits if out_logits is not None else torch.empty(self.B, self.T, 49, 49, device=self.device)
@@ -394,8 +558,7 @@ class _GazeEngine(object):
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
         assert tuple(x.shape) == (self.B, self.T, 1024, 7, 7), tuple(x.shape)
         logits, probs = self._outputs(want_probs, out_logits, out_probs)
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['forward'](self._h, _ptr(x), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
+        self._forward('forward', self.T, _ptr(x), _ptr(logits), _ptr(probs))
         return logits, probs
 
     def forward_rows(self, rows, want_probs=True, out_logits=None, out_probs=None):
@@ -403,50 +566,13 @@ class _GazeEngine(object):
         assert rows.is_cuda and rows.dtype == self.torch_dtype and rows.is_contiguous()
         assert rows.numel() == self.B * self.T * 49 * 1024
         logits, probs = self._outputs(want_probs, out_logits, out_probs)
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['forward_rows'](self._h, _ptr(rows), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
+        self._forward('forward_rows', self.T, _ptr(rows), _ptr(logits), _ptr(probs))
         return logits, probs
 
-    def read_buffer_elems(self, name):
-        """fp32 elements read_buffer(name) returns; 0 = this plan has no such intermediate."""
-        return int(self._f['buffer_elems'](self._h, name.encode()))
 
-    def read_buffer(self, name):
-        n = self.read_buffer_elems(name)
-        if n == 0:
-            raise _lib.RgpError('unknown intermediate %r' % name)
-        out = torch.empty(n, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['read_buffer'](self._h, name.encode(), _ptr(out), _stream_ptr(self.device)))
-        return out
-
-
-class _PersistentEngine(_GazeEngine):
-    """... with a recurrence that may run as a persistent launch (gaze_grcn, gaze_lstm; gaze_c3d_conv has none, and the
-    models ask an engine for `status` / `persistent` with getattr)."""
-
-    def status(self):
-        """Wait for the current stream and raise RgpError (RGP_ETIMEOUT) if a persistent launch of this plan lost a
-        group member since the last check (its outputs are NaN)."""
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['status'](self._h, _stream_ptr(self.device)))
-
-    @property
-    def persistent_workgroups(self):
-        """CUs a persistent sequence launch of this plan occupies (0: the recurrence runs as per-timestep launches)."""
-        with torch.cuda.device(self.device):
-            return int(self._f['persistent_workgroups'](self._h))
-
-    @property
-    def persistent(self):
-        return self.persistent_workgroups > 0
-
-    STREAM_BN_PHASE = False     # the family's forward_stream takes a batch-norm phase (gaze_grcn: one BN layer per timestep)
-
-    @property
-    def state_elems(self):
-        """fp32 elements of the recurrent state forward_stream carries (rgp_<family>_state_elems)."""
-        return int(self._f['state_elems'](self._h))
+class _PersistentEngine(_Persistent, _GazeEngine):
+    """... with a ConvGRU / ConvLSTM recurrence that streams and may run as a persistent launch (gaze_grcn, gaze_grcn77,
+    gaze_lstm)."""
 
     def forward_stream(self, c3d_input=None, rows=None, state=None, n_valid=None, bn_phase=0, want_probs=True):
         """One call of a stream (rgp_<family>_forward_stream): the graph of forward() / forward_rows() started from
@@ -459,19 +585,12 @@ class _PersistentEngine(_GazeEngine):
         assert self.STREAM_BN_PHASE or bn_phase == 0, 'this family has no per-timestep batch-norm'
         logits, probs = self._outputs(want_probs, None, None)
         phase = (int(bn_phase),) if self.STREAM_BN_PHASE else ()
-        new_state = _stream_call(self, self._f['forward_stream'], self.B, self.T, c3d_input, state, n_valid, lambda si, so, nv: (
+        new_state = self._stream_call(self.B, self.T, c3d_input, state, n_valid, lambda si, so, nv: (
             _ptr(c3d_input), _ptr(rows), si, so, nv) + phase + (_ptr(logits), _ptr(probs)), rows=rows)
         return logits, probs, new_state
 
-    def inject_fault(self, kind='seq'):
-        """Test hook (rgp_<family>_inject_fault): the next persistent launch of the forward ('seq') or of the BPTT
-        ('bptt') loses a group member."""
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['inject_fault'](self._h, {'seq': _lib.RGP_FAULT_SEQ_LOST_MEMBER,
-                                                         'bptt': _lib.RGP_FAULT_BPTT_LOST_MEMBER}[kind]))
 
-
-class GrcnEngine(_PersistentEngine):
+class GrcnEngine(_StreamBackward, _FaultHook, _PersistentEngine):
     """gaze_grcn graph (models/gaze_grcn.py:173-376) at fixed (B, T, P, S, dtype)."""
     PREFIX, PARAM_TO_FIELD, WEIGHTS = 'rgp_grcn_', GRCN_PARAM_TO_FIELD, _lib.GrcnWeights
     STREAM_BN_PHASE = True
@@ -537,50 +656,8 @@ class GrcnEngine(_PersistentEngine):
         self.repack()
         return self._gnorm
 
-    # ---- training across the carried state (rgp_grcn_backward_stream)
-    def forward(self, *args, **kw):
-        out = super(GrcnEngine, self).forward(*args, **kw)
-        self._last_n_valid = self.T
-        return out
-
-    def forward_rows(self, *args, **kw):
-        out = super(GrcnEngine, self).forward_rows(*args, **kw)
-        self._last_n_valid = self.T
-        return out
-
-    def forward_stream(self, c3d_input=None, rows=None, state=None, n_valid=None, bn_phase=0, want_probs=True):
-        out = super(GrcnEngine, self).forward_stream(c3d_input, rows, state, n_valid, bn_phase, want_probs)
-        self._last_n_valid = self.T if n_valid is None else int(n_valid)
-        return out
-    forward_stream.__doc__ = _PersistentEngine.forward_stream.__doc__
-
-    def backward_stream(self, logits, probs, labels, d_state=None, loss_frames=None, loss_type='xentropy', want_d_state=True):
-        """The backward of the last forward of either kind (rgp_grcn_backward_stream): behind forward_stream(state, n_valid,
-        bn_phase) the first n_valid steps of that call, the recurrence started at `state`, step t through batch-norm slot
-        (bn_phase + t) % T; behind forward() / forward_rows() all T steps from the zero state.
-        The loss is backward()'s, summed over the valid frames and divided by loss_frames (default B * n_valid of the last
-        forward THIS OBJECT ran: a Python-side copy of what the plan keeps, used for this default alone), so the gradients of a
-        film's chunks add up to the gradient of the mean over the film.  d_state: fp32, state_elems elements ([B, 7, 7, S]), the
-        gradient w.r.t. the new_state the forward returned, or None = zeros (truncated BPTT, the last chunk); never modified.
-        The inputs of the forward must be finite over all T steps.
-        Returns (grads, d_state_in): {variable: gradient view} (flat_grads, written, not accumulated) and a fresh tensor
-        [B, 7, 7, S] with d loss / d state (None with want_d_state=False)."""
-        assert self.save_for_backward, 'create the engine with save_for_backward=True'
-        assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
-        if d_state is not None:
-            assert d_state.is_cuda and d_state.dtype == torch.float32 and d_state.is_contiguous()
-            assert d_state.numel() == self.state_elems, (d_state.numel(), self.state_elems)
-        if loss_frames is None:
-            loss_frames = self.B * getattr(self, '_last_n_valid', self.T)
-        if self.grads is None:
-            self.flat_grads, self.grads = _flat_views(self.PARAM_TO_FIELD, self.weights, self.device, self.UNTRAINED)
-        st = _struct(self.WEIGHTS, self.PARAM_TO_FIELD, self.grads)
-        d_in = torch.empty(self.B, 7, 7, self.S, dtype=torch.float32, device=self.device) if want_d_state else None
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['backward_stream'](self._h, _ptr(logits), _ptr(probs), _ptr(labels), _ptr(d_state), _ptr(d_in),
-                                                  int(loss_frames), ctypes.byref(st), {'xentropy': 0, 'l2': 1}[loss_type],
-                                                  _stream_ptr(self.device)))
-        return self.grads, d_in
+    def _state_shape(self):
+        return (self.B, 7, 7, self.S)
 
     @property
     def grads_top_early(self):
@@ -648,7 +725,7 @@ def lstm_flat_layout(shapes):
     return _flat_layout(LSTM_PARAM_TO_FIELD, shapes, LSTM_UNTRAINED)
 
 
-class LstmEngine(_PersistentEngine):
+class LstmEngine(_BpttPersistent, _FaultHook, _PersistentEngine):
     """gaze_lstm graph (models/gaze_lstm.py:178-353) at fixed (B, T, dtype): projection, ConvLSTM, up-sampling head.
 
     per_step=True: the recurrence as one launch per timestep (RGP_LSTM_PER_STEP), the library's second implementation;
@@ -671,15 +748,6 @@ class LstmEngine(_PersistentEngine):
 
     def _check_shapes(self, src):
         assert tuple(src['ConvLSTM_Wxi'].shape) == (3, 3, self.P, self.S) and tuple(src['ConvLSTM_Wci'].shape) == (7, 7, self.S)
-
-    @property
-    def bptt_persistent_workgroups(self):
-        with torch.cuda.device(self.device):
-            return int(self.lib.rgp_lstm_bptt_persistent_workgroups(self._h))
-
-    @property
-    def bptt_persistent(self):
-        return self.bptt_persistent_workgroups > 0
 
 
 GRCN77_PARAM_TO_FIELD = {   # TF variable name (scope RCNBottom/ stripped, gaze_grcn77.py:152-153,174-184) -> rgp_grcn77_weights field
@@ -720,8 +788,7 @@ class Grcn77Engine(_PersistentEngine):
             assert states.is_cuda and states.dtype == torch.float32 and states.is_contiguous()
             assert tuple(states.shape) == (self.B, self.T, 7, 7, self.S), tuple(states.shape)
         logits, probs = self._outputs(want_probs, None, None)
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['head_fwd'](self._h, _ptr(states), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
+        self._call('head_fwd', _ptr(states), _ptr(logits), _ptr(probs))
         return logits, probs
 
     def inject_fault(self, kind='seq'):
@@ -747,7 +814,7 @@ def softmax_xent(logits, labels=None, want_probs=True):
     return probs, frame_loss, loss
 
 
-class FcGruEngine(object):
+class FcGruEngine(_StreamBackward, _BpttPersistent, _Persistent, _PlanEngine):
     """fc-GRU gaze model (models/gaze_rnn.py:211-360, BASELINE config 2) at fixed (B, T, GH, GW).
 
     per_step=True names the per-timestep recurrence (RGP_FCGRU_PER_STEP: two launches per step), persistent=True the
@@ -768,95 +835,33 @@ class FcGruEngine(object):
                      'r': lambda B, T: (T, B, 1617), 'c': lambda B, T: (T, B, 1617), 'hp': lambda B, T: (B, T + 1, 1617),
                      'rh': lambda B, T: (B, T, 1617), 'dxpre': lambda B, T: (B, T, 3, 1617), 'dh_head': lambda B, T: (B, T, 1617),
                      'dh0': lambda B, T: (B, 1617)}
+    PREFIX, CREATE, WEIGHTS = 'rgp_fcgru_', 'create_flags', _lib.FcGruWeights
 
     def __init__(self, batch, n_steps, gazemap_hw=(49, 49), dtype='f32', device='cuda:0', save_for_backward=False,
                  per_step=False, persistent=False, bptt_persistent=False, bptt_persistent_f32=False):
-        self.lib = _lib.load()
-        self.device = _require_gpu(device)
         self.B, self.T, self.GH, self.GW = int(batch), int(n_steps), int(gazemap_hw[0]), int(gazemap_hw[1])
         self.dtype = dtype
         self.save_for_backward = bool(save_for_backward)
         self.per_step = bool(per_step)
-        self.flat_params = self.flat_grads = self.grads = self.adam_m = self.adam_v = None
-        self._h = ctypes.c_void_p()
         flags = (_lib.RGP_FCGRU_SAVE_FOR_BACKWARD if save_for_backward else 0) | (_lib.RGP_FCGRU_PER_STEP if per_step else 0) | \
             ((_lib.RGP_FCGRU_PERSISTENT_F32 if dtype == 'f32' else _lib.RGP_FCGRU_PERSISTENT) if persistent else 0) | \
             (_lib.RGP_FCGRU_BPTT_PERSISTENT if bptt_persistent else 0) | \
             (_lib.RGP_FCGRU_BPTT_PERSISTENT_F32 if bptt_persistent_f32 else 0)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_fcgru_create_flags(ctypes.byref(self._h), self.B, self.T, self.GH, self.GW,
-                                                       _lib.DTYPES[dtype], flags))
-            nbytes = self.lib.rgp_fcgru_workspace_bytes(self._h)
-            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.rgp_fcgru_bind_workspace(self._h, _ptr(self.workspace), nbytes, _stream_ptr(self.device)))
-        self.weights = None
+        self._create_plan(device, self.B, self.T, self.GH, self.GW, _lib.DTYPES[dtype], flags)
         # tf.nn.dropout on c3d_embedded [B*T*49, 32] (gaze_rnn.py:302-303): off until a training step draws a mask
-        self.dropout = DropoutSite(self.lib, self.device, self.B * self.T * 49 * 32,
-                                   lambda keep, mask: self.lib.rgp_fcgru_set_dropout(self._h, keep, mask))
+        self.dropout = self._dropout_site(self.B * self.T * 49 * 32)
 
-    def __del__(self):
-        h, self._h = getattr(self, '_h', None), None
-        if h:
-            self.lib.rgp_fcgru_destroy(h)
-
-    def _flat(self, like):
-        return _flat_views(_lib.FcGruWeights.FIELDS, like, self.device)
-
-    def _struct(self, views):
-        return _struct(_lib.FcGruWeights, {k: k for k in _lib.FcGruWeights.FIELDS}, views)
-
-    def set_weights(self, params):
-        src = {k: _as_dev_f32(params[k], self.device) for k in _lib.FcGruWeights.FIELDS}
-        if self.flat_params is None:
-            self.flat_params, self.weights = self._flat(src)
-        for k in _lib.FcGruWeights.FIELDS:
-            self.weights[k].copy_(src[k])
-        self.repack()
-
-    def repack(self):
-        st = self._struct(self.weights)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_fcgru_set_weights(self._h, ctypes.byref(st), _stream_ptr(self.device)))
+    def _state_shape(self):
+        return (self.B, 1617)
 
     def backward(self, logits, probs, labels, loss_type='xentropy'):
         """Gradients of the loss of gaze_rnn.py:363-408 w.r.t. the 8 variables after forward() on the same
         inputs; returns {field: gradient view}, the flat buffer is flat_grads."""
         assert self.save_for_backward, 'create the engine with save_for_backward=True'
         assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
-        if self.flat_grads is None:
-            self.flat_grads, self.grads = self._flat(self.weights)
-        st = self._struct(self.grads)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_fcgru_backward(self._h, _ptr(logits), _ptr(probs), _ptr(labels), ctypes.byref(st),
-                                                   {'xentropy': 0, 'l2': 1}[loss_type], _stream_ptr(self.device)))
+        st = self._grad_struct()
+        self._call('backward', _ptr(logits), _ptr(probs), _ptr(labels), ctypes.byref(st), {'xentropy': 0, 'l2': 1}[loss_type])
         return self.grads
-
-    def adam_step(self, step, lr, max_grad_norm=10.0, method='adam'):
-        return clip_step_multi([self], step, lr, max_grad_norm, method)
-
-    def status(self):
-        """Wait for the current stream and raise RgpError (RGP_ETIMEOUT) if a persistent launch of this plan lost a
-        member since the last check (its outputs are NaN)."""
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_fcgru_status(self._h, _stream_ptr(self.device)))
-
-    @property
-    def persistent_workgroups(self):
-        """CUs the persistent recurrence launch of this plan occupies (0: per-timestep launches)."""
-        return int(self.lib.rgp_fcgru_persistent_workgroups(self._h))
-
-    @property
-    def persistent(self):
-        return self.persistent_workgroups > 0
-
-    @property
-    def bptt_persistent_workgroups(self):
-        """CUs the persistent BPTT launch of this plan's backward occupies (0: four launches per timestep)."""
-        return int(self.lib.rgp_fcgru_bptt_persistent_workgroups(self._h))
-
-    @property
-    def bptt_persistent(self):
-        return self.bptt_persistent_workgroups > 0
 
     def read_buffer(self, name):
         """An intermediate of the last forward (or backward) of a training plan (rgp_fcgru_read_buffer), fp32, shaped as the class
@@ -865,8 +870,7 @@ class FcGruEngine(object):
             raise _lib.RgpError('unknown intermediate %r' % name)
         shape = self.BUFFER_SHAPES[name](self.B, self.T)
         out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_fcgru_read_buffer(self._h, name.encode(), _ptr(out), _stream_ptr(self.device)))
+        self._call('read_buffer', name.encode(), _ptr(out))
         return out
 
     def forward(self, c3d_input, want_probs=True, train=False):
@@ -878,17 +882,8 @@ class FcGruEngine(object):
         self.dropout.arm(train)
         logits = torch.empty(self.B, self.T, self.GH, self.GW, device=self.device)
         probs = torch.empty_like(logits) if want_probs else None
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_fcgru_forward(self._h, _ptr(x), _ptr(logits), _ptr(probs), _stream_ptr(self.device)))
-        self._last_n_valid = self.T
+        self._forward('forward', self.T, _ptr(x), _ptr(logits), _ptr(probs))
         return logits, probs
-
-    STREAM_BN_PHASE = False     # this graph has no per-timestep batch-norm
-
-    @property
-    def state_elems(self):
-        """fp32 elements of the recurrent state forward_stream carries (rgp_fcgru_state_elems): B * 1617, h per clip."""
-        return int(self.lib.rgp_fcgru_state_elems(self._h))
 
     def forward_stream(self, c3d_input, state=None, n_valid=None, want_probs=True, train=False):
         """One call of a stream (rgp_fcgru_forward_stream): the graph of forward() started from `state` instead of zeros, on
@@ -902,85 +897,23 @@ class FcGruEngine(object):
         self.dropout.arm(train)
         logits = torch.empty(self.B, self.T, self.GH, self.GW, device=self.device)
         probs = torch.empty_like(logits) if want_probs else None
-        new_state = _stream_call(self, self.lib.rgp_fcgru_forward_stream, self.B, self.T, c3d_input, state, n_valid,
-                                 lambda si, so, nv: (_ptr(c3d_input), si, so, nv, _ptr(logits), _ptr(probs)))
-        self._last_n_valid = self.T if n_valid is None else int(n_valid)
+        new_state = self._stream_call(self.B, self.T, c3d_input, state, n_valid,
+                                      lambda si, so, nv: (_ptr(c3d_input), si, so, nv, _ptr(logits), _ptr(probs)))
         return logits, probs, new_state
 
-    def backward_stream(self, logits, probs, labels, d_state=None, loss_frames=None, loss_type='xentropy', want_d_state=True):
-        """The backward of the last forward of either kind (rgp_fcgru_backward_stream): behind forward_stream(state, n_valid) the
-        first n_valid steps of that call, the recurrence started at `state`; behind forward() all T steps from the zero state.
-        The loss is backward()'s, summed over the valid frames and divided by loss_frames (default B * n_valid of the last
-        forward THIS OBJECT ran: a Python-side copy of what the plan keeps, used for this default alone; name loss_frames when
-        the C entries are driven beside the engine), so the gradients of a film's chunks add up to the gradient of the mean over the film.  d_state: fp32
-        [B, 1617], the gradient w.r.t. the new_state the forward returned, or None = zeros (truncated BPTT, the last chunk);
-        never modified.  c3d_input of the forward must be finite over all T steps.
-        Returns (grads, d_state_in): {field: gradient view} (flat_grads, written, not accumulated) and a fresh tensor
-        [B, 1617] with d loss / d state (None with want_d_state=False)."""
-        assert self.save_for_backward, 'create the engine with save_for_backward=True'
-        assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
-        if d_state is not None:
-            assert d_state.is_cuda and d_state.dtype == torch.float32 and d_state.is_contiguous()
-            assert d_state.numel() == self.state_elems, (d_state.numel(), self.state_elems)
-        if loss_frames is None:
-            loss_frames = self.B * getattr(self, '_last_n_valid', self.T)
-        if self.flat_grads is None:
-            self.flat_grads, self.grads = self._flat(self.weights)
-        st = self._struct(self.grads)
-        d_in = torch.empty(self.B, 1617, dtype=torch.float32, device=self.device) if want_d_state else None
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_fcgru_backward_stream(self._h, _ptr(logits), _ptr(probs), _ptr(labels), _ptr(d_state), _ptr(d_in),
-                                                          int(loss_frames), ctypes.byref(st),
-                                                          {'xentropy': 0, 'l2': 1}[loss_type], _stream_ptr(self.device)))
-        return self.grads, d_in
 
-
-class ShallowNetEngine(object):
+class ShallowNetEngine(_Buffers, _PlanEngine):
     """Frame-wise ShallowNet (models/saliency_shallownet.py:74-216, BASELINE config 1)."""
 
+    PREFIX, CREATE, WEIGHTS = 'rgp_shallownet_', 'create_ex', _lib.ShallowNetWeights
+
     def __init__(self, max_frames, image_hw=98, dtype='f32', device='cuda:0', save_for_backward=False, dropout=False):
-        self.lib = _lib.load()
-        self.device = _require_gpu(device)
         self.max_frames, self.image_hw, self.dtype = int(max_frames), int(image_hw), dtype
         self.save_for_backward = bool(save_for_backward)
-        self.flat_params = self.flat_grads = self.grads = self.adam_m = self.adam_v = None
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_shallownet_create_ex(ctypes.byref(self._h), self.max_frames, self.image_hw,
-                                                         _lib.DTYPES[dtype], int(self.save_for_backward)))
-            nbytes = self.lib.rgp_shallownet_workspace_bytes(self._h)
-            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.rgp_shallownet_bind_workspace(self._h, _ptr(self.workspace), nbytes,
-                                                              _stream_ptr(self.device)))
-        self.weights = None
+        self._create_plan(device, self.max_frames, self.image_hw, _lib.DTYPES[dtype], int(self.save_for_backward))
         # tf.nn.dropout on relu(fc1) [n, 4802] before the maxout (saliency_shallownet.py:152-158): only SaliencyModel has
         # the site; the gaze models build the net with dropout off, and their checkpoints hold no site for it
-        self.dropout = DropoutSite(self.lib, self.device, self.max_frames * 4802,
-                                   lambda keep, mask: self.lib.rgp_shallownet_set_dropout(self._h, keep, mask)) if dropout else None
-
-    def __del__(self):
-        h, self._h = getattr(self, '_h', None), None
-        if h:
-            self.lib.rgp_shallownet_destroy(h)
-
-    def _flat(self, like):
-        return _flat_views(_lib.ShallowNetWeights.FIELDS, like, self.device)
-
-    def _struct(self, views):
-        return _struct(_lib.ShallowNetWeights, {k: k for k in _lib.ShallowNetWeights.FIELDS}, views)
-
-    def set_weights(self, params):
-        src = {k: _as_dev_f32(params[k], self.device) for k in _lib.ShallowNetWeights.FIELDS}
-        if self.flat_params is None:
-            self.flat_params, self.weights = self._flat(src)
-        for k in _lib.ShallowNetWeights.FIELDS:
-            self.weights[k].copy_(src[k])
-        self.repack()
-
-    def repack(self):
-        st = self._struct(self.weights)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_shallownet_set_weights(self._h, ctypes.byref(st), _stream_ptr(self.device)))
+        self.dropout = self._dropout_site(self.max_frames * 4802) if dropout else None
 
     def backward(self, d_saliency):
         """d loss / d saliency [n,49,49] fp32 (frames of the last forward) -> {field: gradient view} for all ten
@@ -988,27 +921,16 @@ class ShallowNetEngine(object):
         assert self.save_for_backward, 'create the engine with save_for_backward=True'
         d = d_saliency
         assert d.is_cuda and d.dtype == torch.float32 and d.is_contiguous() and tuple(d.shape[1:]) == (49, 49)
-        if self.flat_grads is None:
-            self.flat_grads, self.grads = self._flat(self.weights)
-        st = self._struct(self.grads)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_shallownet_backward(self._h, d.shape[0], _ptr(d), ctypes.byref(st), _stream_ptr(self.device)))
+        st = self._grad_struct()
+        self._call('backward', d.shape[0], _ptr(d), ctypes.byref(st))
         return self.grads
-
-    def adam_step(self, step, lr, max_grad_norm=10.0, method='adam'):
-        return clip_step_multi([self], step, lr, max_grad_norm, method)
-
-    def read_buffer_elems(self, name):
-        """fp32 elements read_buffer(name) returns for the frames of the last forward; 0 = this plan has no such buffer."""
-        return int(self.lib.rgp_shallownet_buffer_elems(self._h, name.encode()))
 
     def read_buffer(self, name):
         """Flat fp32 copy of an intermediate of the last forward / backward (names and layouts: rgp_shallownet_read_buffer,
         include/rgp.h).  Raises RgpError for an unknown name (RGP_EINVAL) and for a buffer this plan does not hold yet
         (RGP_ESTATE: a training-plan buffer of an inference plan, a gradient before a backward)."""
         out = torch.empty(max(self.read_buffer_elems(name), 1), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_shallownet_read_buffer(self._h, name.encode(), _ptr(out), _stream_ptr(self.device)))
+        self._call('read_buffer', name.encode(), _ptr(out))
         return out
 
     def forward(self, frames, want_7x7=False, train=False):
@@ -1024,13 +946,11 @@ class ShallowNetEngine(object):
             self.dropout.arm(train)
         sal = torch.empty(n, 49, 49, device=self.device)
         sal7 = torch.empty(n, 7, 7, device=self.device) if want_7x7 else None
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_shallownet_forward(self._h, _ptr(frames), n, _ptr(sal), _ptr(sal7),
-                                                       _stream_ptr(self.device)))
+        self._call('forward', _ptr(frames), n, _ptr(sal), _ptr(sal7))
         return sal, sal7
 
 
-class CascadeEngine(object):
+class CascadeEngine(_Streaming, _PlanEngine):
     """Two-level cascade (models/gaze_grcn_cascade.py:188-423, BASELINE config 5), forward."""
 
     # rgp_cascade_weights field -> key of the parameter dictionary (TF variable names)
@@ -1045,35 +965,17 @@ class CascadeEngine(object):
             ('fc1_w', 'LastProjection/fc1_w'), ('fc1_b', 'LastProjection/fc1_b'),
             ('fc2_w', 'LastProjection/fc2_w'), ('fc2_b', 'LastProjection/fc2_b'))
 
+    PREFIX, CREATE, WEIGHTS = 'rgp_cascade_', 'create_ex', _lib.CascadeWeights
+
     def __init__(self, batch, n_steps, image_hw=98, dtype='bf16', device='cuda:0', save_for_backward=False):
-        self.lib = _lib.load()
-        self.device = _require_gpu(device)
         self.batch, self.n_steps, self.image_hw, self.dtype = int(batch), int(n_steps), int(image_hw), dtype
         self.save_for_backward = bool(save_for_backward)
-        self.flat_params = self.flat_grads = self.grads = self.adam_m = self.adam_v = None
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_cascade_create_ex(ctypes.byref(self._h), self.batch, self.n_steps, self.image_hw,
-                                                      _lib.DTYPES[dtype], int(self.save_for_backward)))
-            nbytes = self.lib.rgp_cascade_workspace_bytes(self._h)
-            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.rgp_cascade_bind_workspace(self._h, _ptr(self.workspace), nbytes,
-                                                           _stream_ptr(self.device)))
-        self.weights = None
+        self._create_plan(device, self.batch, self.n_steps, self.image_hw, _lib.DTYPES[dtype], int(self.save_for_backward))
         # tf.nn.dropout on relu(fc1) [B*T, 4802] before the maxout (gaze_grcn_cascade.py:401-402)
-        self.dropout = DropoutSite(self.lib, self.device, self.batch * self.n_steps * 4802,
-                                   lambda keep, mask: self.lib.rgp_cascade_set_dropout(self._h, keep, mask))
+        self.dropout = self._dropout_site(self.batch * self.n_steps * 4802)
 
-    def __del__(self):
-        h, self._h = getattr(self, '_h', None), None
-        if h:
-            self.lib.rgp_cascade_destroy(h)
-
-    def _flat(self, like):
-        return _flat_views([f for f, _ in self.KEYS], like, self.device)
-
-    def _struct(self, views):
-        st = _struct(_lib.CascadeWeights, {f: f for f, _ in self.KEYS}, views)
+    def _struct_of(self, views):
+        st = _struct(self.WEIGHTS, self._fields, views)
         for k in _lib.ShallowNetWeights.FIELDS:                 # frozen (learning rate 0, base.py:264-265)
             setattr(st.shallownet, k, self.weights['shallownet.' + k].data_ptr())
         return st
@@ -1081,32 +983,19 @@ class CascadeEngine(object):
     def set_weights(self, params):
         """The 19 trainable arrays live in one flat fp32 master buffer (one all-reduce bucket, one Adam launch);
         the ShallowNet's arrays are separate and frozen."""
-        src = {field: _as_dev_f32(params[key], self.device) for field, key in self.KEYS}
-        if self.flat_params is None:
-            self.flat_params, self.weights = self._flat(src)
-        for f, _ in self.KEYS:
-            self.weights[f].copy_(src[f])
+        self._copy_in({field: params[key] for field, key in self.KEYS})
         for k in _lib.ShallowNetWeights.FIELDS:
             self.weights['shallownet.' + k] = _as_dev_f32(params['ShallowNet'][k], self.device)
         self.repack()
-
-    def repack(self):
-        st = self._struct(self.weights)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_cascade_set_weights(self._h, ctypes.byref(st), _stream_ptr(self.device)))
 
     def backward(self, maps, gt, want_d_rows=False):
         """Gradients of the l2 loss (gaze_grcn_cascade.py:428-441) after forward() on the same inputs.
         Returns ({rgp_cascade_weights field: gradient view}, d_rows or None); the flat buffer is flat_grads."""
         assert self.save_for_backward, 'create the engine with save_for_backward=True'
         assert gt.is_cuda and gt.dtype == torch.float32 and gt.is_contiguous() and gt.numel() == maps.numel()
-        if self.flat_grads is None:
-            self.flat_grads, self.grads = self._flat(self.weights)
-        st = self._struct(self.grads)
+        st = self._grad_struct()
         d_rows = torch.empty(self.batch * self.n_steps * 49, 1024, device=self.device) if want_d_rows else None
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_cascade_backward(self._h, _ptr(maps), _ptr(gt), ctypes.byref(st), _ptr(d_rows),
-                                                     _stream_ptr(self.device)))
+        self._call('backward', _ptr(maps), _ptr(gt), ctypes.byref(st), _ptr(d_rows))
         return self.grads, d_rows
 
     def forward(self, frame_images, c3d_input, train=False):
@@ -1119,16 +1008,8 @@ class CascadeEngine(object):
         assert tuple(frame_images.shape) == (B, T, self.image_hw, self.image_hw, 3), tuple(frame_images.shape)
         assert tuple(c3d_input.shape) == (B, T, 1024, 7, 7), tuple(c3d_input.shape)
         maps = torch.empty(B, T, 49, 49, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_cascade_forward(self._h, _ptr(frame_images), _ptr(c3d_input), _ptr(maps),
-                                                    _stream_ptr(self.device)))
+        self._call('forward', _ptr(frame_images), _ptr(c3d_input), _ptr(maps))
         return maps
-
-    @property
-    def state_elems(self):
-        """fp32 elements of the state forward_stream carries (rgp_cascade_state_elems): per clip the bottom state 49*256,
-        then the top state 49*49*3, each part [B, ...]."""
-        return int(self.lib.rgp_cascade_state_elems(self._h))
 
     def forward_stream(self, frame_images, c3d_input, state=None, n_valid=None, train=False):
         """One call of a stream (rgp_cascade_forward_stream): the graph of forward() with both recurrent states started
@@ -1141,8 +1022,8 @@ class CascadeEngine(object):
         assert frame_images.is_cuda and frame_images.dtype == torch.float32 and frame_images.is_contiguous()
         assert tuple(frame_images.shape) == (B, T, self.image_hw, self.image_hw, 3), tuple(frame_images.shape)
         maps = torch.empty(B, T, 49, 49, device=self.device)
-        new_state = _stream_call(self, self.lib.rgp_cascade_forward_stream, B, T, c3d_input, state, n_valid,
-                                 lambda si, so, nv: (_ptr(frame_images), _ptr(c3d_input), si, so, nv, _ptr(maps)))
+        new_state = self._stream_call(B, T, c3d_input, state, n_valid,
+                                      lambda si, so, nv: (_ptr(frame_images), _ptr(c3d_input), si, so, nv, _ptr(maps)))
         return maps, new_state
 
     BUFFERS = {'frm_sal': lambda B, T: (B, T, 49, 49), 'rcn_outputs': lambda B, T: (B, T, 7, 7, 256),
@@ -1150,13 +1031,13 @@ class CascadeEngine(object):
 
     def read_buffer(self, name):
         out = torch.empty(self.BUFFERS[name](self.batch, self.n_steps), device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_cascade_read_buffer(self._h, name.encode(), _ptr(out), _stream_ptr(self.device)))
+        self._call('read_buffer', name.encode(), _ptr(out))
         return out
 
 
-class C3DEngine(object):
+class C3DEngine(_PlanEngine):
     """C3D conv1a..conv5b (prototxt:22-342) for up to max_windows windows per launch chain."""
+    PREFIX, CREATE, WEIGHTS = 'rgp_c3d_', 'create_ex', _lib.C3DWeights
 
     KERNELS = {'patch': 0, 'igemm': _lib.RGP_C3D_KERNELS_IGEMM,
                'igemm128': _lib.RGP_C3D_KERNELS_IGEMM | _lib.RGP_C3D_KERNELS_TILE128,
@@ -1170,47 +1051,35 @@ class C3DEngine(object):
         'patch-twoplane' (the patch kernels with conv3a's / conv3b's inference forward on the two-plane block tile
         instead of the plane-pure one: RGP_C3D_CONV3_TWOPLANE) -- rgp_c3d_create_ex flags; the alternatives exist
         for cross-checks."""
-        self.lib = _lib.load()
-        self.device = _require_gpu(device)
         self.max_windows = int(max_windows)
         self.dtype = dtype
         self.kernels = kernels
         self.save_for_backward = bool(save_for_backward)
         self.torch_dtype = torch.bfloat16 if _lib.DTYPES[dtype] == _lib.RGP_BF16 else torch.float32
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rgp_c3d_create_ex(ctypes.byref(self._h), self.max_windows, _lib.DTYPES[dtype],
-                                                  int(self.save_for_backward) | self.KERNELS[kernels]))
-            nbytes = self.lib.rgp_c3d_workspace_bytes(self._h)
-            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.rgp_c3d_bind_workspace(self._h, _ptr(self.workspace), nbytes, _stream_ptr(self.device)))
+        self._create_plan(device, self.max_windows, _lib.DTYPES[dtype], int(self.save_for_backward) | self.KERNELS[kernels])
         # fp32 master parameters in one flat vector, layout w[0], b[0], w[1], b[1], ... (= rgp_c3d_backward's grads)
         n = self.lib.rgp_c3d_param_elems(self._h)
         self.flat_params = torch.zeros(n, device=self.device)
         self.flat_grads = torch.zeros(n, device=self.device) if self.save_for_backward else None
-        self.adam_m = self.adam_v = None
-        self.weights = {}
-        for i, name in enumerate(C3D_LAYER_NAMES):
-            cin, cout = C3D_CHANNELS[i]
-            ow, ob = self.lib.rgp_c3d_param_offset(self._h, i, 0), self.lib.rgp_c3d_param_offset(self._h, i, 1)
-            self.weights[name + '_w'] = self.flat_params[ow:ow + 27 * cin * cout].view(3, 3, 3, cin, cout)
-            self.weights[name + '_b'] = self.flat_params[ob:ob + cout]
+        self.weights = self._views(self.flat_params)
         self.weights_set = False
 
-    def __del__(self):
-        h, self._h = getattr(self, '_h', None), None
-        if h:
-            self.lib.rgp_c3d_destroy(h)
+    def _param_fields(self):
+        return None         # the master layout is the library's (rgp_c3d_param_offset), not a struct of named fields
 
-    def grad_views(self):
-        """{name: view into flat_grads} with the shapes of the parameters."""
+    def _views(self, flat):
+        """{name: view into flat} with the shapes of the parameters, at the library's offsets."""
         out = {}
         for i, name in enumerate(C3D_LAYER_NAMES):
             cin, cout = C3D_CHANNELS[i]
             ow, ob = self.lib.rgp_c3d_param_offset(self._h, i, 0), self.lib.rgp_c3d_param_offset(self._h, i, 1)
-            out[name + '_w'] = self.flat_grads[ow:ow + 27 * cin * cout].view(3, 3, 3, cin, cout)
-            out[name + '_b'] = self.flat_grads[ob:ob + cout]
+            out[name + '_w'] = flat[ow:ow + 27 * cin * cout].view(3, 3, 3, cin, cout)
+            out[name + '_b'] = flat[ob:ob + cout]
         return out
+
+    def grad_views(self):
+        """{name: view into flat_grads} with the shapes of the parameters."""
+        return self._views(self.flat_grads)
 
     def set_weights(self, params):
         """params: {'conv1a_w': [3,3,3,Cin,Cout], 'conv1a_b': [Cout], ...} fp32 -> master copy + packed operands."""
@@ -1343,68 +1212,45 @@ def action_learning_rate(step, lr0=0.002, decay=0.96, decay_steps=10):
     return float(lr0) * float(decay) ** (float(step) / float(decay_steps))
 
 
-class ActionEngine(object):
+class ActionEngine(_Buffers, _PlanEngine):
     """Owner of one rgp_action_ plan (action_classification.py:210-292), its workspace, the flat fp32 master buffer
     (W1 first, then Wg / b1 / W2 / b2 / W3 / b3: the small variables lie back to back, one optimizer launch) and, for NN
-    training plans, Adam's slots adam_m / adam_v in the same layout.  A training step updates flat_params in place."""
+    training plans, Adam's slots adam_m / adam_v in the same layout.  A training step (train_step: the plan's own fused
+    optimizer, no flat_grads) updates flat_params in place.  set_weights takes {name: array} (synthetic.action_params /
+    checkpoint.import_action_*_variables) and leaves Adam's slots as they are (zero on first use)."""
+
+    PREFIX, WEIGHTS = 'rgp_action_', _lib.ActionWeights
+    PARAM_TO_FIELD = ACTION_PARAM_TO_FIELD['NN']       # every variable of the struct; a plan's own list: _param_fields
 
     def __init__(self, batch, dim_feat=1024, mode='NN', use_gazemap=False, dtype='bf16', save_for_backward=False,
                  device='cuda:0', unfused=False):
-        self.lib = _lib.load()
-        self.device = _require_gpu(device)
         self.B, self.C, self.K = int(batch), int(dim_feat), 49 * int(dim_feat)
         self.mode, self.use_gazemap, self.dtype = mode, bool(use_gazemap), dtype
         self.N = 256 if mode == 'NN' else 13
         self.save_for_backward, self.unfused = bool(save_for_backward), bool(unfused)
         self.torch_dtype = torch.bfloat16 if _lib.DTYPES[dtype] == _lib.RGP_BF16 else torch.float32
         self.names = tuple(k for k in ACTION_PARAM_TO_FIELD[mode] if k != 'Wg' or self.use_gazemap)
-        self.flat_params = self.weights = self.adam_m = self.adam_v = None
         flags = (_lib.RGP_ACTION_USE_GAZEMAP if use_gazemap else 0) | (_lib.RGP_ACTION_SAVE_FOR_BACKWARD if save_for_backward else 0) \
             | (_lib.RGP_ACTION_UNFUSED if unfused else 0)
-        self._f = {k[len('rgp_action_'):]: getattr(self.lib, k) for k in _lib.SIGNATURES if k.startswith('rgp_action_')}
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['create'](ctypes.byref(self._h), self.B, self.C, {'NN': _lib.RGP_ACTION_NN, 'SVM': _lib.RGP_ACTION_SVM}[mode],
-                                         _lib.DTYPES[dtype], flags))
-            nbytes = self._f['workspace_bytes'](self._h)
-            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(self._f['bind_workspace'](self._h, _ptr(self.workspace), nbytes, _stream_ptr(self.device)))
+        self._create_plan(device, self.B, self.C, {'NN': _lib.RGP_ACTION_NN, 'SVM': _lib.RGP_ACTION_SVM}[mode],
+                          _lib.DTYPES[dtype], flags)
 
-    def __del__(self):
-        h, self._h = getattr(self, '_h', None), None
-        if h:
-            self._f['destroy'](h)
-
-    def _st(self, views):
-        return _struct(_lib.ActionWeights, {k: ACTION_PARAM_TO_FIELD[self.mode][k] for k in self.names}, views)
+    def _param_fields(self):
+        return {k: ACTION_PARAM_TO_FIELD[self.mode][k] for k in self.names}
 
     def shapes(self):
         s = {'W1': (self.K, self.N), 'Wg': (2401, 49), 'b1': (self.N,), 'W2': (256, 256), 'b2': (256,), 'W3': (256, 13), 'b3': (13,)}
         return {k: s[k] for k in self.names}
 
-    def set_weights(self, params):
-        """params: {name: array} (synthetic.action_params / checkpoint.import_action_*_variables) -> the flat master
-        buffer and the operand copy of W1.  Adam's slots are left as they are (zero on first use)."""
-        src = {k: _as_dev_f32(params[k], self.device) for k in self.names}
+    def _check_shapes(self, src):
         for k, shp in self.shapes().items():
             assert tuple(src[k].shape) == shp, (k, tuple(src[k].shape), shp)
-        if self.weights is None:
-            self.flat_params, self.weights = _flat_views(self.names, src, self.device)
-        for k in self.names:
-            self.weights[k].copy_(src[k])
-        self.repack()
-
-    def repack(self):
-        st = self._st(self.weights)
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['set_weights'](self._h, ctypes.byref(st), _stream_ptr(self.device)))
 
     def get_weights(self):
         """{name: device tensor}: copies made by the library (rgp_action_get_weights)."""
         flat, views = _flat_views(self.names, self.weights, self.device)
-        st = self._st(views)
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['get_weights'](self._h, ctypes.byref(st), _stream_ptr(self.device)))
+        st = self._struct_of(views)
+        self._call('get_weights', ctypes.byref(st))
         return views
 
     def slots(self):
@@ -1414,7 +1260,7 @@ class ActionEngine(object):
         if getattr(self, '_bound_m', None) is not self.adam_m or self._bound_v is not self.adam_v:   # (load_optimizer_state swaps them)
             layout = _flat_layout(self.names, self.shapes())
             self._mv = tuple({k: buf[off:off + n].view(self.shapes()[k]) for k, off, n in layout} for buf in (self.adam_m, self.adam_v))
-            _lib.check(self._f['bind_slots'](self._h, ctypes.byref(self._st(self._mv[0])), ctypes.byref(self._st(self._mv[1]))))
+            _lib.check(self._f['bind_slots'](self._h, ctypes.byref(self._struct_of(self._mv[0])), ctypes.byref(self._struct_of(self._mv[1]))))
             self._bound_m, self._bound_v = self.adam_m, self.adam_v
         return self._mv
 
@@ -1434,8 +1280,7 @@ class ActionEngine(object):
         self._check_inputs(c3d, gazemap)
         logits = torch.empty(self.B, 13, device=self.device)
         y_pred = torch.empty_like(logits)
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['forward'](self._h, _ptr(c3d), self._gm(gazemap), _ptr(logits), _ptr(y_pred), _stream_ptr(self.device)))
+        self._call('forward', _ptr(c3d), self._gm(gazemap), _ptr(logits), _ptr(y_pred))
         return logits, y_pred
 
     def forward_rows(self, rows, gazemap=None):
@@ -1443,16 +1288,14 @@ class ActionEngine(object):
         assert rows.is_cuda and rows.dtype == self.torch_dtype and rows.is_contiguous() and rows.numel() == self.B * 49 * 1024
         logits = torch.empty(self.B, 13, device=self.device)
         y_pred = torch.empty_like(logits)
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['forward_rows'](self._h, _ptr(rows), self._gm(gazemap), _ptr(logits), _ptr(y_pred), _stream_ptr(self.device)))
+        self._call('forward_rows', _ptr(rows), self._gm(gazemap), _ptr(logits), _ptr(y_pred))
         return logits, y_pred
 
     def loss(self, labels):
         """The loss of the last forward's batch -> 1-element device tensor."""
         assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous() and labels.numel() == self.B * 13
         out = torch.empty(1, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['loss'](self._h, _ptr(labels), _ptr(out), _stream_ptr(self.device)))
+        self._call('loss', _ptr(labels), _ptr(out))
         return out
 
     def train_step(self, c3d, gazemap, labels, step, lr=None):
@@ -1464,37 +1307,20 @@ class ActionEngine(object):
         if self.mode == 'NN':
             self.slots()
         out = torch.empty(1, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['train_step'](self._h, _ptr(c3d), self._gm(gazemap), _ptr(labels), int(step), float(lr), _ptr(out),
-                                             _stream_ptr(self.device)))
+        self._call('train_step', _ptr(c3d), self._gm(gazemap), _ptr(labels), int(step), float(lr), _ptr(out))
         return out
 
     # ---- the stages of a step (tests)
     def fc1_fwd(self, c3d, gazemap=None):
         self._check_inputs(c3d, gazemap)
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['fc1_fwd'](self._h, _ptr(c3d), self._gm(gazemap), _stream_ptr(self.device)))
+        self._call('fc1_fwd', _ptr(c3d), self._gm(gazemap))
 
     def tail(self, labels=None):
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['tail'](self._h, _ptr(labels), _stream_ptr(self.device)))
+        self._call('tail', _ptr(labels))
 
     def fc1_update(self, c3d, gazemap, d_h1, step, lr):
         self._check_inputs(c3d, gazemap)
         assert d_h1.is_cuda and d_h1.dtype == torch.float32 and d_h1.is_contiguous() and d_h1.numel() == self.B * self.N
         if self.mode == 'NN':
             self.slots()
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['fc1_update'](self._h, _ptr(c3d), self._gm(gazemap), _ptr(d_h1), int(step), float(lr), _stream_ptr(self.device)))
-
-    def read_buffer_elems(self, name):
-        return int(self._f['buffer_elems'](self._h, name.encode()))
-
-    def read_buffer(self, name):
-        n = self.read_buffer_elems(name)
-        if n == 0:
-            raise _lib.RgpError('unknown intermediate %r' % name)
-        out = torch.empty(n, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._f['read_buffer'](self._h, name.encode(), _ptr(out), _stream_ptr(self.device)))
-        return out
+        self._call('fc1_update', _ptr(c3d), self._gm(gazemap), _ptr(d_h1), int(step), float(lr))

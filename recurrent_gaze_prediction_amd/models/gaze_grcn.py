@@ -70,8 +70,8 @@ class GazePredictionGRCN(GazePredictionGRU):
         """A persistent ConvGRU launch lost a group member (another process on the device took its CUs; include/rgp.h):
         continue on a plan that runs the recurrence and its BPTT as per-timestep launches (RGP_GRCN_PER_STEP), which need no
         co-residency.  A NEW engine object in this process (never a re-exec): master weights and optimizer slots move
-        over device to device; the poisoned outputs are recomputed by the caller.  Logged once."""
-        from ..engine import OPT_STATE_KEYS
+        over device to device (engine.move_training_state); the poisoned outputs are recomputed by the caller.  Logged once."""
+        from ..engine import move_training_state
         old = self.engine
         if getattr(old, 'per_step', False):
             return False                                          # already the fallback: the error is something else
@@ -79,10 +79,7 @@ class GazePredictionGRCN(GazePredictionGRU):
         log.warning('persistent ConvGRU launch timed out (RGP_ETIMEOUT): switching this model to per-timestep launches')
         new = GrcnEngine(old.B, old.T, old.P, old.S, dtype=old.dtype, save_for_backward=old.save_for_backward,
                          device=old.device, per_step=True)
-        new.set_weights(old.weights)
-        for k in OPT_STATE_KEYS:
-            if getattr(old, k, None) is not None:
-                setattr(new, k, getattr(old, k).clone())
+        move_training_state(old, new)
         self.engine = new
         self.config.convgru_per_step = True
         return True

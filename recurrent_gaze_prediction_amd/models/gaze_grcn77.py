@@ -53,9 +53,9 @@ class GazePredictionGRCN(GazePredictionGRU):
     def _recover_from_timeout(self):
         """A persistent ConvGRU launch lost a group member (include/rgp.h): continue on a plan that runs the recurrence
         and its BPTT as per-timestep launches (RGP_GRCN77_PER_STEP).  A new engine object in this process; master
-        weights and optimizer slots move over device to device; the caller recomputes the poisoned batch.
-        (models/gaze_grcn.py does the same.)"""
-        from ..engine import OPT_STATE_KEYS
+        weights and optimizer slots move over device to device (engine.move_training_state); the caller recomputes the
+        poisoned batch."""
+        from ..engine import move_training_state
         old = self.engine
         if getattr(old, 'per_step', False):
             return False
@@ -63,10 +63,7 @@ class GazePredictionGRCN(GazePredictionGRU):
         log.warning('persistent ConvGRU launch timed out (RGP_ETIMEOUT): switching this model to per-timestep launches')
         new = Grcn77Engine(old.B, old.T, dtype=old.dtype, save_for_backward=old.save_for_backward, device=old.device,
                            per_step=True)
-        new.set_weights(old.weights)
-        for k in OPT_STATE_KEYS:
-            if getattr(old, k, None) is not None:
-                setattr(new, k, getattr(old, k).clone())
+        move_training_state(old, new)
         self.engine = new
         self.config.convgru_per_step = True
         return True

@@ -88,9 +88,10 @@ class GazePredictionLSTM(GazePredictionGRU):
 
     def _recover_from_timeout(self):
         """A persistent ConvLSTM launch (forward or BPTT) lost a group member (include/rgp.h): continue on a plan that runs
-        the recurrence and its BPTT as per-timestep launches (RGP_LSTM_PER_STEP, no RGP_LSTM_BPTT_PERSISTENT).  A new engine object in this process; master weights and optimizer
-        slots move over device to device; the caller recomputes the poisoned batch.  (models/gaze_grcn.py does the same.)"""
-        from ..engine import OPT_STATE_KEYS
+        the recurrence and its BPTT as per-timestep launches (RGP_LSTM_PER_STEP, no RGP_LSTM_BPTT_PERSISTENT).  A new engine
+        object in this process; master weights and optimizer slots move over device to device (engine.move_training_state);
+        the caller recomputes the poisoned batch."""
+        from ..engine import move_training_state
         old = self.engine
         if getattr(old, 'per_step', False) and not getattr(old, 'bptt_persistent', False):
             return False
@@ -98,10 +99,7 @@ class GazePredictionLSTM(GazePredictionGRU):
         log.warning('persistent ConvLSTM launch timed out (RGP_ETIMEOUT): switching this model to per-timestep launches')
         new = LstmEngine(old.B, old.T, dtype=old.dtype, save_for_backward=old.save_for_backward, device=old.device, per_step=True,
                          bptt_persistent=False)
-        new.set_weights(old.weights)
-        for k in OPT_STATE_KEYS:
-            if getattr(old, k, None) is not None:
-                setattr(new, k, getattr(old, k).clone())
+        move_training_state(old, new)
         self.engine = new
         self.config.convlstm_path = 'per_step'
         self.config.convlstm_bptt_path = 'per_step'

@@ -355,8 +355,7 @@ class GazePredictionGRU(ModelBase):
         has not moved the parameters and is repeated as a whole, 'truncated' repeats the poisoned chunk (its state is read-only).
         trace: a dict that receives 'states' (behind every chunk), 'logits' and, in exact mode, 'logits_recomputed'.
         Returns the mean loss over the B * S frames (float)."""
-        from .. import engine as _engine
-        if not isinstance(self.engine, (_engine.FcGruEngine, _engine.GrcnEngine)):
+        if not callable(getattr(self.engine, 'backward_stream', None)):
             raise NotImplementedError('train_long_clip: the fc-GRU models (gaze_rnn, gaze_rnn77) and gaze_grcn train across the '
                                       'carried state; the engine of this %s has no backward_stream' % type(self).__name__)
         if getattr(self, 'dist', None) is not None:
@@ -385,9 +384,10 @@ class GazePredictionGRU(ModelBase):
             return self._status_or_recover(final=final)
 
         def forward(eng, x, state, s, n, probs, train):     # one chunk, film steps [s, s + n), from `state`
-            if isinstance(eng, _engine.GrcnEngine):         # (no live dropout site; the batch-norm slot of step 0: the position mod T)
-                return eng.forward_stream(x, state=state, n_valid=n, bn_phase=s % T, want_probs=probs)
-            return eng.forward_stream(x, state=state, n_valid=n, want_probs=probs, train=train)
+            kw = {'bn_phase': s % T} if eng.STREAM_BN_PHASE else {}       # the batch-norm slot of step 0: the position mod T
+            if self._has_dropout():                                       # a live dropout site takes the training feed
+                kw['train'] = train
+            return eng.forward_stream(x, state=state, n_valid=n, want_probs=probs, **kw)
 
         tr = trace if trace is not None else {}
         tr.update(states=[], logits=[], logits_recomputed=[])
@@ -470,9 +470,9 @@ class GazePredictionGRU(ModelBase):
     def _recover_from_timeout(self):
         """The fc-GRU model (this class, gaze_rnn77): a persistent recurrence or BPTT launch lost a member (include/rgp.h) --
         continue on a plan that runs the recurrence as per-timestep launches (RGP_FCGRU_PER_STEP) and its BPTT per step too.
-        A new engine object in this process; master weights, optimizer slots and the dropout site move over; the caller recomputes the poisoned
-        batch.  Same shape as models/gaze_lstm.py.  The models of the other families override this; one that does not,
-        and whose engine is not the fc-GRU's, has no fallback (False)."""
+        A new engine object in this process; master weights, optimizer slots and the dropout site move over
+        (engine.move_training_state); the caller recomputes the poisoned batch.  The models of the other families override
+        this; one that does not, and whose engine is not the fc-GRU's, has no fallback (False)."""
         from .. import engine as _engine
         old = self.engine
         if not isinstance(old, _engine.FcGruEngine):
@@ -482,15 +482,7 @@ class GazePredictionGRU(ModelBase):
         log.warning('persistent fc-GRU launch timed out (RGP_ETIMEOUT): switching this model to per-timestep launches')
         new = self._new_fcgru_engine(old.B, old.T, (old.GH, old.GW), dtype=old.dtype, device=old.device,
                                      save_for_backward=old.save_for_backward, per_step=True)
-        new.set_weights(old.weights)
-        for k in _engine.OPT_STATE_KEYS:
-            if getattr(old, k, None) is not None:
-                setattr(new, k, getattr(old, k).clone())
-        if getattr(old, 'dropout', None) is not None and getattr(new, 'dropout', None) is not None:
-            # the site's key AND its draw counter: the mask sequence goes on where it was (the recomputed batch draws the
-            # mask after the one the poisoned forward used), it does not start again from the seed
-            new.dropout.configure(old.dropout.keep_prob, seed=old.dropout.seed)
-            new.dropout.draws = old.dropout.draws
+        _engine.move_training_state(old, new)
         self.engine = new
         self.config.fcgru_path = 'per_step'
         self.config.fcgru_bptt_path = 'per_step'
